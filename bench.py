@@ -2,7 +2,11 @@
 """Headline benchmark (BASELINE.json): mel-frames/sec of a Glow-TTS training step (forward incl. log-prior + MAS +
 losses, backward, gradient all-reduce when N > 1) on LJSpeech-shaped synthetic batches, plus MAS us/utterance.
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5]
+    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5] [--full] [--dump-outputs DIR]
+A plain run sets up, warms up, times exactly K steps and prints the headline line (`value`, `ms_per_step`).  `--full` adds everything else
+this script measures: the extra timed windows (median / spread), the forward+backward-only step, the MAS timings, the roofline, the long-form
+inverse-flow leg of config 5, the CPU baseline with the oracle parity sample, and the `f32` key.  `--dump-outputs DIR` writes what the last
+timed step computed (loss, sampled parameters and gradients, per-tensor norms) as DIR/<name>.npy, so that two builds can be compared.
 For N > 1 it runs one rank per GPU over RCCL: launched through torch.distributed.run (WORLD_SIZE set) it joins that job, launched plainly
 (`python bench.py --gpus N`) it spawns the N ranks itself and refuses when the node has fewer GPUs.  Prints ONE JSON line on rank 0.
 
@@ -571,6 +575,26 @@ def inverse_flow_leg(model, hp, dev, B, seed):
             "utterances": B, "tokens": Tt, "mel_frames_per_utterance": round(frames / B, 1), "launch_mode": "hipgraph (2 graphs per call)"}
 
 
+def dump_outputs(out_dir, model, loss, n_sample=1 << 20, seed=2024):
+    """--dump-outputs: what the last timed Train_Step computed, as its caller receives it - the loss (MLE + duration) and the model's
+    parameters and gradients after the update.  The flat parameter / gradient vectors (named_parameters order, fp32) are sampled at a fixed
+    seeded set of indices; every tensor is also covered by its L2 norm (fp64).  About 8 MB in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for _, p in model.named_parameters()]
+    grads = [p.grad if p.grad is not None else torch.zeros_like(p) for p in params]
+    flat_p = torch.cat([p.detach().float().reshape(-1) for p in params])
+    flat_g = torch.cat([g.detach().float().reshape(-1) for g in grads])
+    idx = torch.randint(0, flat_p.numel(), (min(n_sample, flat_p.numel()),), generator=torch.Generator().manual_seed(seed)).sort().values
+    idx = idx.to(flat_p.device)
+    arrays = {"loss": loss.detach().float().reshape(1).cpu().numpy(),
+              "params_sample": flat_p[idx].cpu().numpy(), "grads_sample": flat_g[idx].cpu().numpy(),
+              "param_norms": torch.stack([p.detach().double().norm() for p in params]).cpu().numpy(),
+              "grad_norms": torch.stack([g.detach().double().norm() for g in grads]).cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -580,7 +604,11 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="utterances per GPU (default: the config's per-GPU share)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--ragged", action="store_true", help="Set V (ragged lengths) instead of Set F (fixed)")
-    ap.add_argument("--windows", type=int, default=10, help="extra timed windows of --steps steps after the reported one (median / spread keys)")
+    ap.add_argument("--full", action="store_true", help="also run every measurement beside the headline figure (extra windows, forward+backward-only "
+                    "step, MAS timings, roofline, config 5's inverse-flow leg, CPU baseline + parity sample, f32 key)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy")
+    ap.add_argument("--windows", type=int, default=None, help="extra timed windows of --steps steps after the reported one (median / spread keys; "
+                    "default 10 with --full, else 0)")
     ap.add_argument("--tokens", type=int, default=120, help="padded token length (experiments)")
     ap.add_argument("--frames", type=int, default=800, help="padded mel length (experiments; the metric is quoted on 800)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -607,6 +635,8 @@ def main():
                     "captured hipGraph of the step (default: graph replay; at B = 32 the eager step is bound by host launch work)")
     ap.set_defaults(graph=True)
     args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 10 if args.full else 0
     cfg = CONFIGS[args.config]
 
     if not torch.cuda.is_available():
@@ -849,6 +879,8 @@ def main():
     one_step()
     elapsed, loss = timed_window()                              # the reported window: exactly --steps steps
     own_elapsed = own[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss)
     if args.sync_each and rank == 0:
         print(f"[sync-each] host time of one step's enqueue (replay call): median {sorted(host_replay)[len(host_replay) // 2] * 1e6:.0f} us", file=sys.stderr)
     extra = [timed_window()[0] for _ in range(max(0, args.windows))]
@@ -889,7 +921,7 @@ def main():
                 raise SystemExit(f"[bench] rank {rank}: {len(names)} parameter tensors differ between ranks after the optimizer steps, e.g. {names[:4]} .. {names[-2:]}; "
                                  f"largest relative difference of the sums {((hi - lo).abs() / (lo.abs() + 1e-9)).max().item():.2e}")
     fwd_bwd_only = None
-    if opt is not None and not dp and graph is not None and args.windows > 0:      # (--windows 0 = profiling runs: every traced step is a full Train_Step)
+    if args.full and opt is not None and not dp and graph is not None and args.windows > 0:      # (--windows 0 = profiling runs: every traced step is a full Train_Step)
         # round 1's definition of the step (forward + losses + backward, no update), for continuity: a second graph of the same model
         try:
             def fwd_bwd_noopt():
@@ -935,7 +967,7 @@ def main():
         _gd._collective(dist.all_reduce, hi_t, op=dist.ReduceOp.MAX)
         dist_check = {"rccl_ranks_seen": int(ones.item()), "world_size": dist.get_world_size(), "backend": dist.get_backend(),
                       "ms_per_step_rank_min": round(1e3 * float(lo_t) / args.steps, 3), "ms_per_step_rank_max": round(1e3 * float(hi_t) / args.steps, 3)}
-    inv = inverse_flow_leg(model, hp, dev, B, 99 + rank) if (args.config == 5 and rank == 0 and not args.profile_run) else None      # (kernel-trace runs: the step's launches only)
+    inv = inverse_flow_leg(model, hp, dev, B, 99 + rank) if (args.full and args.config == 5 and rank == 0 and not args.profile_run) else None      # (kernel-trace runs: the step's launches only)
     if rank == 0:
         value = frames * args.steps / elapsed
         ms = [1e3 * e / args.steps for e in [elapsed] + extra]
@@ -955,7 +987,7 @@ def main():
                         "ms_per_step_min": round(min(ms), 3), "ms_per_step_max": round(max(ms), 3)},
             "model_tflops": round(tflops, 2),
         }
-        if not args.profile_run:                              # (kernel-trace runs: only the step's own launches, so calls per step come out as integers)
+        if args.full and not args.profile_run:                # (kernel-trace runs: only the step's own launches, so calls per step come out as integers)
             out["mas_us_per_utt"] = round(mas_us_per_utt(B, Tt, Tm), 3)
             out["mas"] = mas_keys(B, Tt, Tm)
             out["roofline"] = roofline(args.precision, B, Tm // 2, tflops / world)
@@ -966,13 +998,13 @@ def main():
             out["inverse_flow"] = inv
         if dist_check is not None:
             out["distributed"] = dist_check
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
             try:
                 out["parity_sample"] = parity_sample(model, cfg, batch, cond)
             except Exception as exc:                            # noqa: BLE001 - a reported extra, never fatal for the timing line
                 out["parity_sample"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if args.precision == "bf16" and not dp and not args.no_f32_key and args.config == 2 and opt is not None:
+        if args.full and args.precision == "bf16" and not dp and not args.no_f32_key and args.config == 2 and opt is not None:
             out["f32"] = f32_key(args)
     # The JSON line must be the LAST line of the job's stdout.  RCCL writes a banner ("Librccl path : ...") through C stdio, which a pipe
     # buffers until exit, i.e. behind Python's own output: every rank flushes its C buffers, the ranks meet once more, then rank 0 prints.

@@ -229,8 +229,25 @@ def make_mas_cases():
     print(f"wrote mas_cases.npz: {os.path.getsize(os.path.join(HERE, 'mas_cases.npz')) / 1024:.0f} KiB")
 
 
+def make_mas_build_check_case():
+    """The random batch of tests/test_oracle_golden.py::test_mas_oracle_matches_reference_build_if_present through the reference's
+    compiled core.pyx (oracle/_ref): stored, so that the test needs no reference build."""
+    core = mas_ref.reference_core()
+    rng = np.random.default_rng(7)
+    v = rng.normal(-100, 30, (3, 17, 41)).astype(np.float32)
+    tx = np.array([17, 5, 9], np.int32); ty = np.array([41, 30, 9], np.int32)
+    mask = (np.arange(17)[None, :, None] < tx[:, None, None]) & (np.arange(41)[None, None, :] < ty[:, None, None])
+    v = (v * mask).astype(np.float32)
+    path = np.zeros(v.shape, dtype=np.int32)
+    core.maximum_path_c(path, v.copy(), tx, ty)
+    assert np.array_equal(mas_ref.maximum_path_c(v, tx, ty), path)
+    np.savez_compressed(os.path.join(HERE, "mas_build_check.npz"), value=v, t_x=tx, t_y=ty, path=path.astype(np.int8))
+    print("wrote mas_build_check.npz: oracle C == reference core.pyx")
+
+
 if __name__ == "__main__":
     make_mas_cases()
+    make_mas_build_check_case()
     if "--mas-only" in sys.argv:
         sys.exit(0)
     make_model_case("Vanilla", 1234, "tiny_vanilla.npz")

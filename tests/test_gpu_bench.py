@@ -34,7 +34,7 @@ def test_bench_refuses_more_gpus_than_the_node_has():
 
 
 def test_bench_gpus_2_spawns_two_ranks():
-    out = _run(["--gpus", "2", "--one-device", "--backend", "gloo"] + FAST)
+    out = _run(["--gpus", "2", "--one-device", "--backend", "gloo", "--full"] + FAST)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _json_line(out)
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "dp2" and d["config"]["global_batch"] == 64
@@ -46,6 +46,24 @@ def test_bench_force_dist_runs_rccl_with_one_rank():
     assert out.returncode == 0, out.stderr[-3000:]
     d = _json_line(out)
     assert d["n_gpus"] == 1 and d["launch_mode"] == "hipgraph" and "RCCL" in d["config"]["workload"]
+
+
+def test_bench_plain_run_is_the_headline_only_and_dumps_outputs(tmp_path):
+    """A plain run times exactly --steps steps and prints the headline keys without the --full legs; --dump-outputs writes what the last
+    timed step computed (loss, parameter / gradient samples, per-tensor norms) as float32 / float64 .npy files, 64 MB at most."""
+    import numpy as np
+    out = _run(["--steps", "3", "--warmup", "2", "--dump-outputs", str(tmp_path)], timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    d = _json_line(out)
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["launch_mode"] == "hipgraph"
+    assert d["metric"] == "mel-frames/sec (train fwd+bwd)" and d["unit"] == "mel-frames/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert not {"roofline", "mas", "mas_us_per_utt", "cpu_baseline", "parity_sample", "f32", "fwd_bwd_only"} & set(d), sorted(d)
+    names = ("loss", "params_sample", "grads_sample", "param_norms", "grad_norms")
+    assert sorted(os.listdir(tmp_path)) == sorted(f"{n}.npy" for n in names)
+    arrays = {n: np.load(tmp_path / f"{n}.npy") for n in names}
+    assert all(a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert abs(float(arrays["loss"][0]) - d["loss"]) < 1e-3 and arrays["grad_norms"].max() > 0
 
 
 def test_bench_world_size_must_match_gpus():

@@ -35,19 +35,18 @@ def test_python_mas_twin_matches_core_pyx_vectors(name, golden_dir):
     assert np.array_equal(path, d[f"{name}/path"].astype(np.int32))
 
 
-def test_mas_oracle_matches_reference_build_if_present():
-    core = mas_ref.reference_core()
-    if core is None:
-        pytest.skip("oracle/_ref not built (reference absent)")
-    rng = np.random.default_rng(7)
-    v = rng.normal(-100, 30, (3, 17, 41)).astype(np.float32)
-    tx = np.array([17, 5, 9], np.int32); ty = np.array([41, 30, 9], np.int32)
-    mask = (np.arange(17)[None, :, None] < tx[:, None, None]) & (np.arange(41)[None, None, :] < ty[:, None, None])
-    v = (v * mask).astype(np.float32)
+def test_mas_oracle_matches_reference_build_if_present(golden_dir):
+    """oracle/mas_ref.c against the path the reference's compiled core.pyx gave on a random batch (tests/golden/mas_build_check.npz,
+    written by tests/golden/make_golden.py); when oracle/_ref is built, against the live core.pyx as well."""
+    d = np.load(f"{golden_dir}/mas_build_check.npz")
+    v, tx, ty = d["value"], d["t_x"], d["t_y"]
     p = mas_ref.maximum_path_c(v, tx, ty)
-    p2 = np.zeros_like(p); v2 = v.copy()
-    core.maximum_path_c(p2, v2, tx, ty)
-    assert np.array_equal(p, p2)
+    assert np.array_equal(p, d["path"].astype(np.int32))
+    core = mas_ref.reference_core()
+    if core is not None:
+        p2 = np.zeros_like(p); v2 = v.copy()
+        core.maximum_path_c(p2, v2, tx, ty)
+        assert np.array_equal(p, p2)
 
 
 @pytest.mark.parametrize("mode,fname", [("Vanilla", "tiny_vanilla.npz"), ("SE", "tiny_se.npz"), ("PE", "tiny_pe.npz"), ("GR", "tiny_gr.npz")])

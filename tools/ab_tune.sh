@@ -7,7 +7,7 @@ targs=""; for kv in $B; do targs="$targs --tune $kv"; done
 for i in $(seq 1 $N); do
   for arm in A B; do
     if [ $arm = A ]; then extra=""; else extra="$targs"; fi
-    python $REPO/bench.py --no-cpu-baseline --no-f32-key --windows 4 $extra 2>/dev/null | python -c "
+    python $REPO/bench.py --full --no-cpu-baseline --no-f32-key --windows 4 $extra 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$arm', '$extra', 'ms/step', d['ms_per_step'], 'median', d.get('ms_per_step_median'), 'fwd_bwd_only', (d.get('fwd_bwd_only') or {}).get('ms_per_step'))"
   done
