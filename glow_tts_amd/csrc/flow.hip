@@ -169,6 +169,27 @@ extern "C" int glowtts_flow_forward(const glowtts_flow_dims* d, const glowtts_fl
     return coupling_net(c, a->xmid, a->xout, false, true);
 }
 
+extern "C" int glowtts_flow_encode(const glowtts_flow_dims* d, const glowtts_flow_params* p, const glowtts_flow_acts* a, void* stream)
+{
+    // glowtts_flow_forward's arithmetic under glowtts_flow_inverse's scratch contract (voice conversion, mel -> z): nothing is kept
+    CHECK(check_dims(d));
+    if (d->drop_p != 0.f) return GLOWTTS_E_ARG;             // an eval pass
+    if (!p || !a || !a->xin || !a->xmid || !a->xout || !a->rowmask) return GLOWTTS_E_ARG;
+    if (!p->wn_img) {                            // scratch of the per-conv launches (the fused kernel keeps all of it on chip)
+        if (!a->skip || !a->hs[0] || !a->hs[1] || !a->gates[0]) return GLOWTTS_E_ARG;
+        if (d->act_bf16 && !a->acts[0]) return GLOWTTS_E_ARG;
+    }
+    if (a->next_xmid) {                          // the next flow's ActNorm + 1x1 in the fused launch's epilogue (glowtts_flow_acts.next_*)
+        if (!p->wn_img || !a->next_an_logs || !a->next_an_bias || !a->next_winfo || !a->next_xout) return GLOWTTS_E_ARG;
+        // the launch reads xmid with a halo across its 64-row windows: no buffer it writes may be one it reads
+        if (a->next_xmid == a->xmid || a->next_xout == a->xmid || a->xout == a->xmid || a->next_xmid == a->xout) return GLOWTTS_E_ARG;
+    }
+    const Ctx c = make_ctx(d, p, a, stream);
+    if (!a->actnorm_done)
+        CHECK(glowtts_actnorm_inv1x1_pass_bf(a->xin, a->xmid, a->xout, a->xa_bf, p->an_logs, p->an_bias, p->winfo, a->rowmask, c.R, d->C, stream));
+    return coupling_net(c, a->xmid, a->xout, false, false);
+}
+
 extern "C" int glowtts_flow_inverse(const glowtts_flow_dims* d, const glowtts_flow_params* p, const glowtts_flow_acts* a, void* stream)
 {
     CHECK(check_dims(d));

@@ -77,6 +77,7 @@ def _L():
         L.glowtts_actnorm_inv1x1.argtypes = [c_void_p] * 6 + [c_i64, c_int, c_int, c_void_p]
         L.glowtts_flow_forward.argtypes = [c_void_p] * 4
         L.glowtts_flow_inverse.argtypes = [c_void_p] * 4
+        L.glowtts_flow_encode.argtypes = [c_void_p] * 4
         L.glowtts_flow_backward.argtypes = [c_void_p] * 5
         L.glowtts_wgrad_grouped.argtypes = [c_void_p] + [c_int] * 9 + [c_void_p]
         L.glowtts_wgrad_grouped_io.argtypes = [c_void_p] + [c_int] * 10 + [c_void_p]
@@ -717,6 +718,13 @@ class _Prepared:
             if t is not None:
                 t.record_stream(cs)
 
+    def release_sources(self):
+        """Eval passes only (need_bwd False): drop the stacked fp32 conv weights the images were packed from - no launch reads them again (the
+        per-flow structs point into the packed images; biases and ActNorm parameters stay).  Voice conversion's peak allocation: the fp32 weights
+        of a full-width decoder are 84 MB, 6.5 KiB per squeezed row at B = 32 x 800 frames."""
+        for k in ("w_start", "w_in", "w_rs", "w_rs_last", "w_end"):
+            self.keep.pop(k, None)
+
     def set_cond(self, cond):
         """Attach the per-call conditioning [B, F, L, 2H] (None: unconditioned) to the per-flow parameter structs."""
         F_, H, Lw = len(self.params), self._H, self._Lw
@@ -873,44 +881,134 @@ def _run_forward(cfg, prep, mels, lengths, drop_p=0.0, seed=None, pitch=None):
     return z, logdet, buf, rowmask, T, prow
 
 
+class _RowScratch:
+    """Row buffers of the eval passes (decoder_inverse / decoder_encode_rows / decoder_convert), reused by every flow: a second flow-variable
+    buffer, the coupling input xmid (two when the forward chains the next flow's ActNorm + 1x1 into the fused launch) and, when some flow runs
+    the per-conv launches, their WaveNet scratch (the fused kernel keeps it on chip)."""
+
+    def __init__(self, cfg, prep, x, mids=1):
+        R, dev = x.shape[0], x.device
+        self.other = torch.empty_like(x)
+        self.xmid = [torch.empty_like(x) for _ in range(mids)]
+        self.hs = self.gates = self.actp = self.skipb = self.skip = None
+        if not all(p.wn_img for p in prep.params):
+            self.hs = torch.empty(2, R, cfg.H, device=dev, dtype=cfg.act_dtype)
+            self.gates = torch.empty(R, 2 * cfg.H, device=dev, dtype=cfg.act_dtype)
+            self.actp = torch.empty(R, cfg.H, device=dev, dtype=torch.bfloat16) if cfg.act_bf16 else None
+            self.skipb = torch.empty(R, cfg.H, device=dev, dtype=torch.bfloat16) if cfg.act_bf16 else None
+            self.skip = torch.empty(R, cfg.H, device=dev)
+
+    def add_mid(self):
+        if len(self.xmid) < 2:
+            self.xmid.append(torch.empty_like(self.xmid[0]))
+
+    def acts(self, xin, xmid, xout, rowmask):
+        a = FlowActs()
+        a.xin, a.xmid, a.xout = xin.data_ptr(), xmid.data_ptr(), xout.data_ptr()
+        if self.hs is not None:
+            a.hs[0], a.hs[1] = self.hs[0].data_ptr(), self.hs[1].data_ptr()
+            a.gates[0], a.skip = self.gates.data_ptr(), self.skip.data_ptr()
+            if self.actp is not None:
+                a.acts[0], a.skip_bf = self.actp.data_ptr(), self.skipb.data_ptr()
+        a.outs, a.rowmask = None, rowmask.data_ptr()
+        return a
+
+
+def decoder_inverse_rows(cfg, prep, x, rowmask, T, B, pitch=None, scratch=None):
+    """Flows F-1 .. 0 inverted (Modules.py:664) on squeezed rows x [B*(T+4), C], with the conditioning already attached to `prep`.  x is used as
+    scratch; returns the rows tensor that holds the result (x or one of the scratch buffers).  pitch: None or (pitch rows [R, ns] from
+    pitch_rows, pitch_w [F, L, 2H, ns], pitch_b [F, L, 2H]) - GR mode."""
+    L = _L()
+    sc = scratch if scratch is not None else _RowScratch(cfg, prep, x)
+    assert sc.other is not x
+    dims = _dims(cfg, B, T)
+    cur, nxt = x, sc.other
+    for f in range(cfg.F - 1, -1, -1):
+        if pitch is not None:
+            cr = _cond_rows(cfg, prep, f, pitch[0], pitch[1], pitch[2], T + 2 * ROW_PAD)
+            prep.set_cond_rows(f, cr)
+        a = sc.acts(nxt, sc.xmid[0], cur, rowmask)
+        _lib.check(L.glowtts_flow_inverse(ctypes.byref(dims), ctypes.byref(prep.params[f]), ctypes.byref(a), _lib.stream()),
+                   "glowtts_flow_inverse")
+        cur, nxt = nxt, cur
+    return cur
+
+
+def decoder_encode_rows(cfg, prep, rows, rowmask, T, B, pitch=None, scratch=None):
+    """Decoder.forward(reverse=False) in eval mode (Modules.py:298-309) without the log-determinants: flows 0 .. F-1 through glowtts_flow_encode on
+    squeezed rows [B*(T+4), C], keeping nothing, with the conditioning already attached to `prep`.  `rows` is used as scratch; returns the rows
+    tensor that holds z.  Where _run_forward chains the next flow's ActNorm + 1x1 into a flow's fused launch, so does this - the same launches
+    and arithmetic as the training forward.  Buffer plan: the flow variable ping-pongs between `rows` and scratch.other (flow f reads cur, writes
+    nxt); xmid alternates between two buffers when chained, so that a launch, which reads its xmid with a halo across 64-row windows, never
+    writes a buffer it reads (it writes nxt's x_b half, the next flow's xmid and cur's x_a half - the next flow's output).  pitch: as in
+    decoder_inverse_rows."""
+    L = _L()
+    sc = scratch if scratch is not None else _RowScratch(cfg, prep, rows)
+    assert sc.other is not rows
+    if TUNE["chain_actnorm"] and pitch is None and any(p.wn_img for p in prep.params[:-1]):
+        sc.add_mid()
+    dims = _dims(cfg, B, T)
+    cur, nxt = rows, sc.other
+    chained = False
+    for f in range(cfg.F):
+        if pitch is not None:
+            cr = _cond_rows(cfg, prep, f, pitch[0], pitch[1], pitch[2], T + 2 * ROW_PAD)
+            prep.set_cond_rows(f, cr)
+        a = sc.acts(cur, sc.xmid[f % len(sc.xmid)], nxt, rowmask)
+        a.actnorm_done = int(chained)
+        chained = bool(TUNE["chain_actnorm"]) and f + 1 < cfg.F and bool(prep.params[f].wn_img) and pitch is None
+        if chained:
+            pn = prep.params[f + 1]
+            a.next_an_logs, a.next_an_bias, a.next_winfo = pn.an_logs, pn.an_bias, pn.winfo
+            a.next_xmid, a.next_xout = sc.xmid[(f + 1) % 2].data_ptr(), cur.data_ptr()
+        _lib.check(L.glowtts_flow_encode(ctypes.byref(dims), ctypes.byref(prep.params[f]), ctypes.byref(a), _lib.stream()),
+                   "glowtts_flow_encode")
+        cur, nxt = nxt, cur
+    if pitch is not None:
+        prep.set_cond(prep.cond)
+    return cur
+
+
 def decoder_inverse(cfg, W, z, lengths, cond=None, fill=None, prep=None, pitch=None):
     """Decoder.forward(reverse=True) (Modules.py:298-309): z [B,Cm,Tm] -> mels [B,Cm,ns*(Tm//ns)].
     prep: a _Prepared built earlier from the same weights (then W is not read; `cond`, which varies per call, is attached here).
     pitch: None or (pitches [B, Tm], pitch_w [F, L, 2H, ns], pitch_b [F, L, 2H]) - GR mode."""
-    L = _L()
     if prep is None:
         prep = _Prepared(cfg, W, need_bwd=False, cond=cond)
     elif cond is not None or prep.cond is not None:
         prep.set_cond(cond)
     B, _, Tm = z.shape
     x, rowmask, T = squeeze_rows(cfg, z, lengths)
-    R = x.shape[0]
-    dev = z.device
-    other = torch.empty_like(x)
-    xmid = torch.empty_like(x)
-    hs = torch.empty(2, R, cfg.H, device=dev, dtype=cfg.act_dtype)
-    gates = torch.empty(R, 2 * cfg.H, device=dev, dtype=cfg.act_dtype)
-    actp = torch.empty(R, cfg.H, device=dev, dtype=torch.bfloat16) if cfg.act_bf16 else None
-    skipb = torch.empty(R, cfg.H, device=dev, dtype=torch.bfloat16) if cfg.act_bf16 else None
-    skip = torch.empty(R, cfg.H, device=dev)
-    dims = _dims(cfg, B, T)
-    cur, nxt = x, other
-    prow = pitch_rows(cfg, pitch[0], rowmask, B, T) if pitch is not None else None
-    for f in range(cfg.F - 1, -1, -1):
-        if pitch is not None:
-            cr = _cond_rows(cfg, prep, f, prow, pitch[1], pitch[2], T + 2 * ROW_PAD)
-            prep.set_cond_rows(f, cr)
-        a = FlowActs()
-        a.xout, a.xmid, a.xin = cur.data_ptr(), xmid.data_ptr(), nxt.data_ptr()
-        a.hs[0], a.hs[1] = hs[0].data_ptr(), hs[1].data_ptr()
-        a.gates[0], a.skip, a.rowmask = gates.data_ptr(), skip.data_ptr(), rowmask.data_ptr()
-        if actp is not None:
-            a.acts[0], a.skip_bf = actp.data_ptr(), skipb.data_ptr()
-        a.outs = None
-        _lib.check(L.glowtts_flow_inverse(ctypes.byref(dims), ctypes.byref(prep.params[f]), ctypes.byref(a), _lib.stream()),
-                   "glowtts_flow_inverse")
-        cur, nxt = nxt, cur
-    return unsqueeze_rows(cfg, cur, lengths, B, (Tm // cfg.ns) * cfg.ns, fill=fill)
+    prow = (pitch_rows(cfg, pitch[0], rowmask, B, T), pitch[1], pitch[2]) if pitch is not None else None
+    out = decoder_inverse_rows(cfg, prep, x, rowmask, T, B, prow)
+    return unsqueeze_rows(cfg, out, lengths, B, (Tm // cfg.ns) * cfg.ns, fill=fill)
+
+
+def decoder_convert(cfg, W_or_prep, mels, lengths, cond_src, cond_tgt, fill, pitch=None, encode_only=False):
+    """Voice conversion through the invertible decoder (Glow-TTS, section 3.4): mels [B, Cm, Tm] -> z with the flows run forward under the
+    source's conditioning cond_src [B, F, L, 2H] (or None), then z -> mels through the inverse flows under cond_tgt.  One squeeze, one
+    unsqueeze, the weight images packed once (W_or_prep: the stacked weights, or a _Prepared of them).  lengths are cut to whole squeeze
+    groups (the reference's squeeze mask mask[:, :, ns-1::ns]); returns (mels [B, Cm, ns*(Tm//ns)] with `fill` beyond each utterance, the cut
+    lengths).  pitch: None or (pitches [B, Tm] of the source frames, pitch_w, pitch_b) - GR mode, the same track in both directions.
+    encode_only: return (z [B, Cm, ns*(Tm//ns)] zero beyond each utterance, the cut lengths) instead."""
+    prep = W_or_prep if isinstance(W_or_prep, _Prepared) else _Prepared(cfg, dict(W_or_prep), need_bwd=False, cond=None)
+    B, _, Tm = mels.shape
+    Tc = (Tm // cfg.ns) * cfg.ns
+    lengths = (lengths // cfg.ns) * cfg.ns
+    x, rowmask, T = squeeze_rows(cfg, mels, lengths)
+    prow = (pitch_rows(cfg, pitch[0], rowmask, B, T), pitch[1], pitch[2]) if pitch is not None else None
+    sc = _RowScratch(cfg, prep, x)
+    prep.set_cond(cond_src)
+    z = decoder_encode_rows(cfg, prep, x, rowmask, T, B, prow, scratch=sc)
+    if z is sc.other:                       # (odd flow count: the input rows are the free buffer now)
+        sc.other = x
+    if encode_only:
+        prep.set_cond(None)
+        return unsqueeze_rows(cfg, z, lengths, B, Tc), lengths
+    prep.set_cond(cond_tgt)
+    out = decoder_inverse_rows(cfg, prep, z, rowmask, T, B, prow, scratch=sc)
+    prep.set_cond(None)
+    return unsqueeze_rows(cfg, out, lengths, B, Tc, fill=fill), lengths
 
 
 def actnorm_data_init(cfg, W, mels, lengths, cond=None, allreduce=None, pitch=None):

@@ -111,6 +111,88 @@ class Inferencer:
         return files
 
 
+    def _pad_mels(self, mp):
+        """[(mel [T, Mel], pitch [T] or None)] -> (mels [B, Mel, Tmax] padded with -Max_Abs_Mel, lengths, pitches [B, Tmax] or None)"""
+        hp = self.hp
+        lengths = torch.tensor([m.shape[0] for m, _ in mp], dtype=torch.int64)
+        mels = torch.full((len(mp), hp.Sound.Mel_Dim, int(lengths.max())), -float(hp.Sound.Max_Abs_Mel))
+        for b, (m, _) in enumerate(mp):
+            mels[b, :, :m.shape[0]] = torch.from_numpy(m.T)
+        pitches = None
+        if all(p is not None for _, p in mp):
+            pitches = torch.zeros(len(mp), int(lengths.max()))
+            for b, (_, p) in enumerate(mp):
+                n = min(p.shape[0], mels.shape[2])
+                pitches[b, :n] = torch.from_numpy(p[:n])
+        return mels, lengths, pitches
+
+    def Voice_Conversion(self, labels, sources, source_speakers=None, target_speakers=None, target_references=None, inference_path="./inference"):
+        """Voice conversion through the invertible decoder (GlowTTS.voice_conversion): `sources` - recorded mels as .npy files / arrays [T, Mel]
+        or wav files (GR: a wav also gives the YIN pitch track the flows read; (mel, pitch) pairs are taken as they are) - go through the flows
+        forward under their own conditioning and back under the target's.  SE-LUT: speaker indices; SE-GE2E: d-vectors [E]; PE / GR:
+        `target_references` (same formats as `sources`) give the target prosody vector (GR: plus the target speaker).  A None target takes
+        the source's value.  Batches of Inference_Batch_Size; one NPY/<label>.npy [T, Mel] per utterance; returns the written files."""
+        logging.info("Start voice conversion.")
+        hp = self.hp
+        model = self.model_Dict["GlowTTS"]
+        mode = hp.Mode.upper()
+        lut = "LUT" in model.layer_Dict
+        bs = hp.Inference_Batch_Size or hp.Train.Batch_Size
+        n = len(sources)
+        source_speakers = source_speakers or [None] * n
+        target_speakers = target_speakers or [None] * n
+        target_references = target_references or [None] * n
+        os.makedirs(os.path.join(inference_path, "NPY").replace("\\", "/"), exist_ok=True)
+        dev = self.device
+
+        def speakers_of(vals):
+            if any(v is None for v in vals):
+                return None
+            if lut:
+                return torch.tensor([int(v) for v in vals], dtype=torch.int64, device=dev)
+            return torch.from_numpy(np.stack([np.asarray(v, np.float32) for v in vals])).to(dev)      # GE2E: d-vectors
+
+        files = []
+        for s in range(0, n, bs):
+            sl = slice(s, s + bs)
+            mels, lengths, pitches = self._pad_mels([self._reference(r) for r in sources[sl]])
+            spk, tspk = speakers_of(source_speakers[sl]), speakers_of(target_speakers[sl])
+            kw = {}
+            if mode in ("SE", "GR") and lut:
+                kw.update(speakers=spk, target_speakers=tspk)
+            elif mode in ("SE", "GR"):
+                kw.update(mels_for_ge2e=spk, target_mels_for_ge2e=tspk)
+            refs = target_references[sl]
+            if mode in ("PE", "GR") and not any(r is None for r in refs):
+                tm, tl, _ = self._pad_mels([self._reference(r) for r in refs])
+                kw.update(target_mels_for_prosody=tm.to(dev), target_mel_lengths_for_prosody=tl.to(dev))
+            out, out_lengths = model.voice_conversion(mels.to(dev), lengths.to(dev), pitches=None if pitches is None else pitches.to(dev), **kw)
+            for label, mel, m in zip(labels[sl], out.cpu().numpy(), out_lengths.cpu().tolist()):
+                path = os.path.join(inference_path, "NPY", "{}.npy".format(label)).replace("\\", "/")
+                np.save(path, mel[:, :m].T, allow_pickle=False)                   # [T, Mel], like Inference_Step
+                files.append(path)
+        return files
+
+
+def read_convert_list(path):
+    """The --convert TSV: label, source path, source speaker, target speaker and, optionally, a target reference path, tab-separated; an
+    optional header line whose first column is `Label`.  Empty speaker / reference columns are None."""
+    out = []
+    with open(path, "r", encoding="utf-8") as f:
+        for i, line in enumerate(f.read().splitlines()):
+            if not line.strip():
+                continue
+            cols = [x.strip() for x in line.split("\t")]
+            if i == 0 and cols[0].lower() == "label":
+                continue
+            if len(cols) < 4:
+                raise ValueError("{}:{}: expected label, source, source speaker, target speaker[, target reference]".format(path, i + 1))
+            spk = lambda x: int(x) if x else None
+            out.append({"label": cols[0], "source": cols[1], "source_speaker": spk(cols[2]), "target_speaker": spk(cols[3]),
+                        "target_reference": (cols[4] or None) if len(cols) > 4 else None})
+    return out
+
+
 def main(argv=None):
     import argparse
     logging.basicConfig(level=logging.INFO)
@@ -118,8 +200,15 @@ def main(argv=None):
     ap.add_argument("-c", "--checkpoint", required=True)
     ap.add_argument("-t", "--prompts", default=None, help="inference prompt TSV (Datasets.py:137-144); default: the reference's two example sentences")
     ap.add_argument("-o", "--out", default="./inference")
+    ap.add_argument("--convert", default=None, metavar="LIST.tsv",
+                    help="voice conversion instead of text-to-mel: label, source mel (.npy [T, Mel] or wav), source speaker, target speaker[, target reference]")
     args = ap.parse_args(argv)
     inf = Inferencer(checkpoint_path=args.checkpoint)
+    if args.convert:
+        recs = read_convert_list(args.convert)
+        print("\n".join(inf.Voice_Conversion([r["label"] for r in recs], [r["source"] for r in recs], [r["source_speaker"] for r in recs],
+                                              [r["target_speaker"] for r in recs], [r["target_reference"] for r in recs], args.out)))
+        return
     if args.prompts:
         recs = [r for r in data.read_inference_prompts(args.prompts) if r["text"] is not None]
         labels, texts, scales, speakers = [r["label"] for r in recs], [r["text"] for r in recs], [r["length_scale"] for r in recs], [r["speaker"] for r in recs]

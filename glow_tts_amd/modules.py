@@ -494,6 +494,55 @@ class GlowTTS(torch.nn.Module):
                                        pitch=pitch)   # :198-202
         return mels, mel_lengths, attn
 
+    # ---------------------------------------------------------------- voice conversion through the invertible decoder
+    def _decoder_pass_inputs(self, mels, mel_lengths, pitches):
+        """Checks shared by encode_mels / voice_conversion; -> (P, stacks, the packed decoder weights, pitch or None)."""
+        if not mels.is_cuda:
+            raise RuntimeError("glow_tts_amd runs on the GPU only (no CPU fallback)")
+        if not all(f.layers[0].initialized for f in self._flows()):
+            # (an inference call must not data-initialise parameters the way the first training forward does, Modules.py:685-687)
+            raise RuntimeError("ActNorm is not initialised: load a trained checkpoint (or run one training forward) before encoding mels")
+        P = self._params()
+        stacks = self._stacks(P)
+        pw, pb = stacks.pitch_weights()
+        if pw is not None and pitches is None:
+            raise ValueError("GR mode needs `pitches` [Batch, Mel_t] of the source mels (Modules.py:58, 867-869)")
+        prep = decoder._Prepared(self.dec_cfg, dict(zip(decoder.WEIGHT_KEYS, [w.contiguous() for w in stacks.weights()])), need_bwd=False, cond=None)
+        prep.release_sources()                # (the fp32 weights go before the row buffers are allocated)
+        return P, stacks, prep, ((pitches, pw, pb) if pw is not None else None)
+
+    @torch.no_grad()
+    def encode_mels(self, mels, mel_lengths, speakers=None, mels_for_ge2e=None, pitches=None):
+        """The decoder's forward in eval mode (Modules.py:50-100, 298-309) without the log-determinants or anything of the text side:
+        mels [B, Mel, Tm] -> (z [B, Mel, T'], z_lengths) with T' = Num_Squeeze * (Tm // Num_Squeeze) and
+        z_lengths = Num_Squeeze * (mel_lengths // Num_Squeeze) (lengths need not be multiples of Num_Squeeze); z is zero beyond each
+        utterance.  The conditioning is what `forward` computes from the same arguments (PE / GR: the prosody vector of `mels` itself).
+        Runs at dec_cfg.precision and keeps no activation."""
+        P, stacks, prep, pitch = self._decoder_pass_inputs(mels, mel_lengths, pitches)
+        spk, pro = self._conditioning(P, speakers, mels_for_ge2e, mels, mel_lengths)
+        cond = stacks.conditioning(spk, pro)
+        return decoder.decoder_convert(self.dec_cfg, prep, mels.contiguous(), mel_lengths, cond, None, None, pitch, encode_only=True)
+
+    @torch.no_grad()
+    def voice_conversion(self, mels, mel_lengths, speakers=None, mels_for_ge2e=None, pitches=None, target_speakers=None, target_mels_for_ge2e=None,
+                         target_mels_for_prosody=None, target_mel_lengths_for_prosody=None):
+        """Voice conversion through the invertible decoder (Glow-TTS, section 3.4): the recorded mels go through the flows forward under their
+        own conditioning (what `forward` computes from mels / speakers / mels_for_ge2e / pitches), z comes back through the inverse flows under
+        the target's: SE-LUT `target_speakers` indices, SE-GE2E `target_mels_for_ge2e` d-vectors [B, E], PE / GR a prosody vector of
+        `target_mels_for_prosody` (GR: with the target speaker and the source's pitch track).  A target argument left None takes the source's
+        value (the identity conversion).  -> (mels [B, Mel, T'], mel_lengths): T' = Num_Squeeze * (Tm // Num_Squeeze), lengths cut to whole
+        squeeze groups, frames beyond an utterance = -Max_Abs_Mel (as `inference` fills them).  Runs at dec_cfg.precision."""
+        if self.hp.Mode.upper() == "VANILLA":
+            raise ValueError("voice conversion needs a conditioned model (Mode SE, PE or GR): a Vanilla decoder has nothing to convert between")
+        P, stacks, prep, pitch = self._decoder_pass_inputs(mels, mel_lengths, pitches)
+        spk, pro = self._conditioning(P, speakers, mels_for_ge2e, mels, mel_lengths)
+        tspk, tpro = self._conditioning(P, target_speakers if target_speakers is not None else speakers,
+                                        target_mels_for_ge2e if target_mels_for_ge2e is not None else mels_for_ge2e,
+                                        target_mels_for_prosody, target_mel_lengths_for_prosody,
+                                        prosodies=pro if target_mels_for_prosody is None else None)
+        cond_src, cond_tgt = stacks.conditioning(spk, pro), stacks.conditioning(tspk, tpro)
+        return decoder.decoder_convert(self.dec_cfg, prep, mels.contiguous(), mel_lengths, cond_src, cond_tgt, -float(self.hp.Sound.Max_Abs_Mel), pitch)
+
     def prepared_decoder_weights(self):
         """Packed weight images of the decoder for the CURRENT parameter values (inference with static weights: pack once, not per call)."""
         with torch.no_grad():

@@ -485,6 +485,10 @@ typedef struct glowtts_flow_grads {       /* backward outputs; weight grads are 
 int glowtts_flow_forward(const glowtts_flow_dims *d, const glowtts_flow_params *p, const glowtts_flow_acts *a, void *stream);
 /* inference inverse: xout(in) -> xin(out).  Uses hs[0], hs[1], gates[0], skip as scratch; xmid as scratch. */
 int glowtts_flow_inverse(const glowtts_flow_dims *d, const glowtts_flow_params *p, const glowtts_flow_acts *a, void *stream);
+/* ABI 7 (additive): glowtts_flow_forward's arithmetic in eval mode (drop_p must be 0) under glowtts_flow_inverse's scratch contract: xin -> xout,
+ * reading hs[0], hs[1], gates[0], skip, acts[0] (act_bf16) and xmid as scratch and keeping nothing (outs, xa_bf may be NULL).  Honours actnorm_done
+ * and, on the fused coupling network, the next_* chaining fields; a launch's reads (xmid) must not alias its writes (xout, next_xmid, next_xout). */
+int glowtts_flow_encode(const glowtts_flow_dims *d, const glowtts_flow_params *p, const glowtts_flow_acts *a, void *stream);
 /* backward of glowtts_flow_forward */
 int glowtts_flow_backward(const glowtts_flow_dims *d, const glowtts_flow_params *p, const glowtts_flow_acts *a,
                           const glowtts_flow_grads *g, void *stream);
