@@ -42,6 +42,7 @@ def _L():
         L.glowtts_embedding_fwd.argtypes = [c_p] * 4 + [c_int] * 3 + [c_f, c_p]
         L.glowtts_embedding_bwd.argtypes = [c_p] * 4 + [c_int] * 4 + [c_f, c_p]
         L.glowtts_rpr_attention_fwd_prec.argtypes = [c_p] * 6 + [c_int] * 5 + [c_f, c_u32, c_p, c_int, c_p]
+        L.glowtts_rpr_attention_fwd_eval.argtypes = [c_p] * 5 + [c_int] * 6 + [c_p]
         L.glowtts_rpr_attention_scratch_floats.argtypes = [c_int] * 5
         L.glowtts_rpr_attention_scratch_floats.restype = c_i64
         L.glowtts_rpr_attention_bwd_prec.argtypes = [c_p] * 11 + [c_int] * 5 + [c_f, c_u32, c_p, c_int, c_p]
@@ -552,9 +553,32 @@ class EmbeddingRows(torch.autograd.Function):
         return None, dt, None, None
 
 
+# Longest padded utterance the training kernels (glowtts_rpr_attention_fwd_prec / _bwd: a [queries][Tp] probability tile in LDS) take
+ATTN_TRAIN_MAX_TP = 256
+
+
+def rpr_attention_eval(qkv, relk, relv, rowmask, B, Tp, H, win, precision=0):
+    """The attention core without dropout, probability matrix or autograd (glowtts_rpr_attention_fwd_eval): any Tp, for inference."""
+    qkv = qkv.contiguous()
+    D = qkv.shape[1] // (3 * H)
+    out = torch.empty(B * Tp, H * D, device=qkv.device)
+    rk, rv = relk.detach().contiguous(), relv.detach().contiguous()
+    _lib.check(_L().glowtts_rpr_attention_fwd_eval(qkv.data_ptr(), rk.data_ptr(), rv.data_ptr(), rowmask.data_ptr(), out.data_ptr(),
+                                                   B, Tp, H, D, win, int(precision), _lib.stream()), "glowtts_rpr_attention_fwd_eval")
+    return out
+
+
 class RPRAttention(torch.autograd.Function):
     """Attention core of RPR_MHA.py:95-128 on fused QKV rows [B*Tp, 3*H*D] -> [B*Tp, H*D].  precision: ops.F32 / ops.BF16 (bf16 MFMA
-    contractions for Tp <= 128, fp32 softmax; see glowtts_rpr_attention_fwd_prec)."""
+    contractions for Tp <= 128, fp32 softmax; see glowtts_rpr_attention_fwd_prec).  Tp > 256 without dropout and with nothing to
+    differentiate (inference on long texts) takes `rpr_attention_eval` instead: no [B, H, Tp, Tp] probability matrix, no autograd node."""
+
+    @classmethod
+    def apply(cls, qkv, relk, relv, rowmask, B, Tp, H, win, drop_p, seed, seed_t, precision=0):
+        if Tp > ATTN_TRAIN_MAX_TP and float(drop_p) == 0.0 and \
+                not (torch.is_grad_enabled() and any(t.requires_grad for t in (qkv, relk, relv))):
+            return rpr_attention_eval(qkv, relk, relv, rowmask, B, Tp, H, win, precision)
+        return super().apply(qkv, relk, relv, rowmask, B, Tp, H, win, drop_p, seed, seed_t, precision)
 
     @staticmethod
     def forward(ctx, qkv, relk, relv, rowmask, B, Tp, H, win, drop_p, seed, seed_t, precision=0):

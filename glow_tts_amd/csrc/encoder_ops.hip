@@ -1603,3 +1603,276 @@ extern "C" int glowtts_rpr_attention_bwd(const float* qkv, const float* relk, co
     return glowtts_rpr_attention_bwd_prec(qkv, relk, relv, rowmask, P, dout, dS, dqkv, drelk, drelv, scratch, B, Tp, H, D, win, drop_p, seed, seed_ptr,
                                           GLOWTTS_F32, stream);
 }
+
+// ------------------------------------------------------------------------------------------------
+// Eval-mode attention core for any Tp (inference on long texts): the same arithmetic as glowtts_rpr_attention_fwd_prec without
+// dropout and without the [B][H][Tp][Tp] probability matrix.  Keys stream through LDS in blocks of 32 with an online softmax (a
+// running max m and sum l per query), so LDS use does not depend on Tp.
+//   MFMA path (D in {64, 96}, 2 win + 1 <= 32): one wave per 32 queries, NW = 2 or 4 waves per workgroup sharing the staged K / V block.
+//   The scores are computed transposed, S^T = K Q^T (key on the accumulator rows, query on the lane), so that
+//     - the softmax statistics of a query are lane-local: 16 registers plus one swap between the two lane halves;
+//     - the probabilities P^T are already the B operand of O^T += V^T P^T (key = the accumulator row): no trip through LDS;
+//     - O^T keeps the query on the lane, so the per-block rescale by exp(m_old - m_new) is one multiply per register.
+//   The relative-position terms: q_i . relK[dd] is one product per wave before the key loop (kept in LDS, [query][dd]); the band's
+//   scores s_{i, i+dd-w} are kept in LDS as they pass, and sum_dd exp(s - m) relV[dd] is one product after the loop, at the final max
+//   (the same rescaled accumulator: O_i = sum_j exp(s_ij - m) (v_j + [band] relV[j-i+w]), divided by l at the end).
+//   Q^T stays in registers (D / KSTEP fragments).  BF: the two contractions (and the two relative terms) on bf16 MFMAs.
+//   General path (any other D <= 128): fp32 VALU, one wave per 4 queries of a 16-query workgroup, lanes over 64-key blocks.
+// ------------------------------------------------------------------------------------------------
+constexpr int AE_KB = 32;       // keys per block (MFMA path)
+constexpr int AE_LR = 33;       // row stride of the per-wave [32 queries][32 dd] tiles
+
+template <int ND, bool BF, int NW>
+__global__ __launch_bounds__(64 * NW) void attn_fwd_eval_mfma_kernel(const float* __restrict__ qkv, const float* __restrict__ relk,
+                                                                     const float* __restrict__ relv, const float* __restrict__ rowmask,
+                                                                     float* __restrict__ out, int Tp, int H, int win)
+{
+    constexpr int D = ND * 32, LD = D + 1;
+    constexpr int KSTEP = AtOp<BF>::KSTEP, NQS = D / KSTEP;
+    constexpr int EPS = BF ? 8 : 1;                          // accumulator registers per k-step when P^T is the B operand
+    typedef typename AtOp<BF>::T Frag;
+    __shared__ float Ks[AE_KB * LD], Vs[AE_KB * LD], Ms[AE_KB];
+    __shared__ float RB[NW][2][32 * AE_LR];                  // per wave: q_i . relK[dd], then the band scores s_{i, i+dd-w}
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
+    const int h = blockIdx.y, b = blockIdx.z;
+    const int q0 = (blockIdx.x * NW + wave) * 32, i = q0 + l31;          // this lane's query (both lane halves)
+    const int C = H * D, ld = 3 * C, nw = 2 * win + 1;
+    const float* base = qkv + (long)b * Tp * ld + (long)h * D;
+    const float* rm = rowmask + (long)b * Tp;
+    float* myR = RB[wave][0];
+    float* myS = RB[wave][1];
+    const int koff = BF ? 8 * lhi : lhi;
+
+    // Q^T fragments, the B operand of every score product (B[k][col = query])
+    Frag qf[NQS];
+    {
+        const bool qv = i < Tp;
+        const float* qr = base + (long)(qv ? i : 0) * ld;
+#pragma unroll
+        for (int s = 0; s < NQS; ++s) qf[s] = at_frag<BF>([&](int e) { return qv ? qr[s * KSTEP + koff + e] : 0.f; });
+    }
+    {   // R^T = relK Q^T: R[reg] = relK[dd = acc_row(reg, lhi)] . q_i
+        f32x16 R;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) R[r] = 0.f;
+        const bool rv = l31 < nw;
+        const float* kr = relk + (long)(rv ? l31 : 0) * D;
+#pragma unroll
+        for (int s = 0; s < NQS; ++s) R = at_mma<BF>(at_frag<BF>([&](int e) { return rv ? kr[s * KSTEP + koff + e] : 0.f; }), qf[s], R);
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) myR[l31 * AE_LR + acc_row(reg, lhi)] = R[reg];
+        for (int t = lane; t < 32 * AE_LR; t += 64) myS[t] = -3.0e38f;              // band keys outside [0, Tp) contribute nothing
+    }
+    const float mi = i < Tp ? rm[i] : 0.f;
+    const float isd = rsqrtf((float)D);
+    float m = -3.0e38f, l = 0.f;
+    f32x16 O[ND];
+#pragma unroll
+    for (int nd = 0; nd < ND; ++nd)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) O[nd][r] = 0.f;
+
+#pragma unroll 1
+    for (int kb = 0; kb < Tp; kb += AE_KB) {
+        __syncthreads();                                     // every wave is done with the previous block
+        stage_rows<D, LD, AE_KB, 64 * NW>(Ks, base + C + (long)kb * ld, ld, Tp - kb, tid);
+        stage_rows<D, LD, AE_KB, 64 * NW>(Vs, base + 2 * C + (long)kb * ld, ld, Tp - kb, tid);
+        if (tid < AE_KB) Ms[tid] = kb + tid < Tp ? rm[kb + tid] : 0.f;
+        __syncthreads();
+        f32x16 S;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) S[r] = 0.f;
+#pragma unroll
+        for (int s = 0; s < NQS; ++s) S = at_mma<BF>(at_frag<BF>([&](int e) { return Ks[l31 * LD + s * KSTEP + koff + e]; }), qf[s], S);
+        const bool band = kb <= q0 + 31 + win && kb + AE_KB - 1 >= q0 - win;      // (wave-uniform) the block meets a query's window
+        float bm = -3.0e38f;
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int jl = acc_row(reg, lhi), j = kb + jl, dd = j - i + win;
+            const bool inb = band && dd >= 0 && dd < nw;
+            float v = S[reg];
+            if (inb) v += myR[l31 * AE_LR + dd];
+            v *= isd;
+            if (mi * Ms[jl] == 0.f) v = -1e4f;                                    // RPR_MHA.py:117
+            if (j >= Tp) v = -3.0e38f;
+            else if (inb) myS[l31 * AE_LR + dd] = v;
+            S[reg] = v; bm = fmaxf(bm, v);
+        }
+        bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+        const float mn = fmaxf(m, bm), alpha = __expf(m - mn);
+        float ps = 0.f;
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) { const float p = kb + acc_row(reg, lhi) < Tp ? __expf(S[reg] - mn) : 0.f; S[reg] = p; ps += p; }
+        ps += __shfl_xor(ps, 32, 64);
+        l = l * alpha + ps;
+        m = mn;
+#pragma unroll
+        for (int nd = 0; nd < ND; ++nd)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) O[nd][r] *= alpha;
+        // O^T += V^T P^T: the k-step s takes accumulator registers [EPS s, EPS s + EPS) of S as its B fragment, so A's k order follows acc_row
+#pragma unroll
+        for (int s = 0; s < 16 / EPS; ++s) {
+            const Frag pf = at_frag<BF>([&](int e) { return S[s * EPS + e]; });
+#pragma unroll
+            for (int nd = 0; nd < ND; ++nd)
+                O[nd] = at_mma<BF>(at_frag<BF>([&](int e) { return Vs[acc_row(s * EPS + e, lhi) * LD + 32 * nd + l31]; }), pf, O[nd]);
+        }
+    }
+    __syncthreads();                                         // myS complete (written by both lane halves)
+    // O^T += relV^T Pband^T at the final max: Pband[i][dd] = exp(s_{i, i+dd-w} - m)
+    for (int s = 0; s * KSTEP < nw; ++s) {
+        const Frag pf = at_frag<BF>([&](int e) { const int dd = s * KSTEP + koff + e; return dd < nw ? __expf(myS[l31 * AE_LR + dd] - m) : 0.f; });
+#pragma unroll
+        for (int nd = 0; nd < ND; ++nd)
+            O[nd] = at_mma<BF>(at_frag<BF>([&](int e) { const int dd = s * KSTEP + koff + e; return dd < nw ? relv[(long)dd * D + 32 * nd + l31] : 0.f; }),
+                               pf, O[nd]);
+    }
+    // O^T holds the query on the lane: each 32 x 32 block goes through the wave's q . relK tile (idle since the key loop) so that a store writes 32
+    // consecutive floats of one output row instead of 32 rows C floats apart.  (l > 0 on every lane, padded queries included: key 0 is in range.)
+    const float il = 1.f / l;
+    float* T = myR;
+#pragma unroll
+    for (int nd = 0; nd < ND; ++nd) {
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) T[l31 * AE_LR + acc_row(reg, lhi)] = O[nd][reg] * il;
+        __syncthreads();                                     // (uniform: every wave runs the same epilogue)
+#pragma unroll
+        for (int q = lhi; q < 32; q += 2) {
+            const int iq = q0 + q;
+            if (iq < Tp) out[((long)b * Tp + iq) * C + (long)h * D + 32 * nd + l31] = T[q * AE_LR + l31];
+        }
+        __syncthreads();                                     // T is rewritten by the next block
+    }
+}
+
+constexpr int AEG_Q = 16, AEG_KB = 64;          // general path: queries per workgroup (4 per wave), keys per block
+
+__global__ __launch_bounds__(256) void attn_fwd_eval_kernel(const float* __restrict__ qkv, const float* __restrict__ relk, const float* __restrict__ relv,
+                                                            const float* __restrict__ rowmask, float* __restrict__ out, int Tp, int H, int D, int win)
+{
+    extern __shared__ float sm[];
+    const int ldk = D + 1;
+    float* Ks = sm;                                          // [64][D+1]
+    float* Vs = Ks + AEG_KB * ldk;                           // [64][D+1]
+    float* Qs = Vs + AEG_KB * ldk;                           // [16][D]
+    float* Ps = Qs + AEG_Q * D;                              // [4 waves][64]
+    float* Ms = Ps + 4 * AEG_KB;                             // [64]
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int q0 = blockIdx.x * AEG_Q, h = blockIdx.y, b = blockIdx.z;
+    const int C = H * D, ld = 3 * C, nw = 2 * win + 1;
+    const float* base = qkv + (long)b * Tp * ld + (long)h * D;
+    const float* rm = rowmask + (long)b * Tp;
+    for (int t = tid; t < AEG_Q * D; t += 256) { const int qi = t / D, d = t - qi * D, i = q0 + qi; Qs[t] = i < Tp ? base[(long)i * ld + d] : 0.f; }
+    float m[4], l[4], o[4][2], mi[4];
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) {
+        const int i = q0 + wave * 4 + qq;
+        m[qq] = -3.0e38f; l[qq] = 0.f; o[qq][0] = 0.f; o[qq][1] = 0.f; mi[qq] = i < Tp ? rm[i] : 0.f;
+    }
+    const float isd = rsqrtf((float)D);
+    float* pw = Ps + wave * AEG_KB;
+#pragma unroll 1
+    for (int kb = 0; kb < Tp; kb += AEG_KB) {
+        __syncthreads();
+        for (int t = tid; t < AEG_KB * D; t += 256) {
+            const int jj = t / D, d = t - jj * D, j = kb + jj;
+            const bool ok = j < Tp;
+            Ks[jj * ldk + d] = ok ? base[(long)j * ld + C + d] : 0.f;
+            Vs[jj * ldk + d] = ok ? base[(long)j * ld + 2 * C + d] : 0.f;
+        }
+        if (tid < AEG_KB) Ms[tid] = kb + tid < Tp ? rm[kb + tid] : 0.f;
+        __syncthreads();
+        const int jn = min(AEG_KB, Tp - kb);
+#pragma unroll
+        for (int qq = 0; qq < 4; ++qq) {                     // (queries past Tp run along - the barriers are uniform - and are not written)
+            const int i = q0 + wave * 4 + qq, j = kb + lane, dd = j - i + win;
+            const float* q = Qs + (wave * 4 + qq) * D;
+            const float* kr = Ks + lane * ldk;
+            float acc = 0.f;
+            if (dd >= 0 && dd < nw) { const float* rr = relk + (long)dd * D; for (int d = 0; d < D; ++d) acc += q[d] * (kr[d] + rr[d]); }
+            else                    { for (int d = 0; d < D; ++d) acc += q[d] * kr[d]; }
+            float s = acc * isd;
+            if (mi[qq] * Ms[lane] == 0.f) s = -1e4f;         // RPR_MHA.py:117
+            const bool valid = j < Tp;
+            const float mn = fmaxf(m[qq], wave_max(valid ? s : -3.0e38f)), alpha = __expf(m[qq] - mn);
+            const float p = valid ? __expf(s - mn) : 0.f;
+            l[qq] = l[qq] * alpha + wave_sum(p);
+            m[qq] = mn;
+            pw[lane] = p;
+            __syncthreads();
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const int d = lane + 64 * c;
+                if (d < D) {
+                    float a2 = 0.f;
+                    for (int jj = 0; jj < jn; ++jj) a2 += pw[jj] * Vs[jj * ldk + d];
+                    for (int e = 0; e < nw; ++e) { const int jb = i + e - win - kb; if (jb >= 0 && jb < jn) a2 += pw[jb] * relv[(long)e * D + d]; }
+                    o[qq][c] = o[qq][c] * alpha + a2;
+                }
+            }
+            __syncthreads();                                 // pw is rewritten by the next query
+        }
+    }
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) {
+        const int i = q0 + wave * 4 + qq;
+        if (i >= Tp) continue;
+        float* op = out + ((long)b * Tp + i) * C + (long)h * D;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) { const int d = lane + 64 * c; if (d < D) op[d] = o[qq][c] / l[qq]; }
+    }
+}
+
+template <int ND, bool BF, int NW>
+static void launch_attn_fwd_eval_mfma(hipStream_t st, const float* qkv, const float* relk, const float* relv, const float* rowmask, float* out,
+                                      int B, int Tp, int H, int win)
+{
+    GLOWTTS_NOTE_STATIC("attn_fwd_eval_mfma<%d,%s,%d>", ND * 32, BF ? "bf16" : "f32", NW);
+    hipLaunchKernelGGL((attn_fwd_eval_mfma_kernel<ND, BF, NW>), dim3((Tp + 32 * NW - 1) / (32 * NW), H, B), dim3(64 * NW), 0, st,
+                       qkv, relk, relv, rowmask, out, Tp, H, win);
+}
+template <int ND, bool BF>
+static void launch_attn_fwd_eval_nw(int nwv, hipStream_t st, const float* qkv, const float* relk, const float* relv, const float* rowmask, float* out,
+                                    int B, int Tp, int H, int win)
+{
+    if (nwv == 4) launch_attn_fwd_eval_mfma<ND, BF, 4>(st, qkv, relk, relv, rowmask, out, B, Tp, H, win);
+    else          launch_attn_fwd_eval_mfma<ND, BF, 2>(st, qkv, relk, relv, rowmask, out, B, Tp, H, win);
+}
+
+// waves (32-query tiles) per workgroup of the MFMA path, i.e. queries per staged key block.  Measured (tools/bench_long_text.py, DESIGN.md "Long
+// texts"; H = 2, D = 96): one-wave workgroups are never the fastest, even at B = 1 (64 tiles at Tp = 1024: 203 us against 187 with 2 or 4 waves);
+// 4 waves beat 2 by 2-4 % at 512-1024 tiles and by 1.35-1.8x from 2048 tiles (B = 32, Tp >= 1024); below 512 tiles 2 is within 3 % of 4 or better.
+static int attn_eval_waves(int B, int Tp, int H)
+{
+    const int forced = GLOWTTS_TUNABLE("GLOWTTS_ATTN_EVAL_WAVES", 0);
+    if (forced == 2 || forced == 4) return forced;
+    const long tiles = (long)B * H * ((Tp + 31) / 32);
+    return tiles >= 512 ? 4 : 2;
+}
+
+extern "C" int glowtts_rpr_attention_fwd_eval(const float* qkv, const float* relk, const float* relv, const float* rowmask, float* out,
+                                              int B, int Tp, int H, int D, int win, int precision, void* stream)
+{
+    if (!qkv || !relk || !relv || !rowmask || !out || B < 1 || B > 65535 || Tp < 1 || H < 1 || H > 65535 || D < 1 || D > 128 || win < 0)
+        return GLOWTTS_E_ARG;
+    if (precision != GLOWTTS_F32 && precision != GLOWTTS_BF16) return GLOWTTS_E_ARG;
+    const bool bf = precision == GLOWTTS_BF16;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if ((D == 64 || D == 96) && 2 * win + 1 <= 32 && GLOWTTS_TUNABLE("GLOWTTS_ATTN_EVAL_MFMA", 1) != 0) {
+        const int nwv = attn_eval_waves(B, Tp, H);
+        if (D == 96) {
+            if (bf) launch_attn_fwd_eval_nw<3, true>(nwv, st, qkv, relk, relv, rowmask, out, B, Tp, H, win);
+            else    launch_attn_fwd_eval_nw<3, false>(nwv, st, qkv, relk, relv, rowmask, out, B, Tp, H, win);
+        } else {
+            if (bf) launch_attn_fwd_eval_nw<2, true>(nwv, st, qkv, relk, relv, rowmask, out, B, Tp, H, win);
+            else    launch_attn_fwd_eval_nw<2, false>(nwv, st, qkv, relk, relv, rowmask, out, B, Tp, H, win);
+        }
+        RET_LAUNCH();
+    }
+    const size_t lds = ((size_t)2 * AEG_KB * (D + 1) + (size_t)AEG_Q * D + 5 * AEG_KB) * sizeof(float);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_eval_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    GLOWTTS_NOTE_STATIC("attn_fwd_eval_gen");
+    hipLaunchKernelGGL(attn_fwd_eval_kernel, dim3((Tp + AEG_Q - 1) / AEG_Q, H, B), dim3(256), lds, st, qkv, relk, relv, rowmask, out, Tp, H, D, win);
+    RET_LAUNCH();
+}

@@ -7,7 +7,8 @@ size (host-bound).  Here a call is
     graph B  (per token shape x bucket)   alignment expansion, prior sample, 12 inverse flows, unsqueeze
 with the decoder's weight images packed once (`GlowTTS.prepared_decoder_weights`): serving weights are static.  Frames beyond an
 utterance's length are masked exactly as the reference masks the batch padding, so the valid part of the result does not depend on the
-bucket.  Call `refresh()` after the parameters changed.  Vanilla / LUT / pre-computed d-vector conditioning are tensor inputs of fixed shape;
+bucket.  A call whose longest utterance exceeds the largest bucket runs graph B's work eagerly (same packed weights, nothing captured).
+Call `refresh()` after the parameters changed.  Vanilla / LUT / pre-computed d-vector conditioning are tensor inputs of fixed shape;
 PE mode: the GST prosody encoder, whose reference mels vary in length, runs eagerly before graph A and hands it the [B, Size] vector."""
 import bisect
 
@@ -82,8 +83,11 @@ class GraphedInference:
         mel_lengths = front[3]
         tmax = int(mel_lengths.max())                                  # the one device -> host read of the call
         i = bisect.bisect_left(self.buckets, tmax)
-        if i == len(self.buckets):
-            raise ValueError(f"{tmax} frames exceed the largest mel bucket {self.buckets[-1]}")
+        ns = int(m.hp.Decoder.Num_Squeeze)
+        T = (tmax // ns) * ns
+        if i == len(self.buckets):                                     # longer than the largest bucket: the back half eagerly, nothing captured
+            mels, lengths, attn = m.inference_back(front, None, noise_scale, noises, prep=self.prep)
+            return mels[:, :, :T], lengths, attn[:, :, :tmax]
         Tb = self.buckets[i]
         bkey = (key, Tb, noises is not None)
         if bkey not in self.back:
@@ -99,6 +103,4 @@ class GraphedInference:
             n = min(Tb, noises.shape[2])
             nz[:, :, :n].copy_(noises[:, :, :n], non_blocking=True)
         g2.replay()
-        ns = int(m.hp.Decoder.Num_Squeeze)
-        T = (tmax // ns) * ns
         return mels[:, :, :T], lengths, attn[:, :, :tmax]

@@ -687,6 +687,13 @@ int glowtts_rpr_attention_fwd_prec(const float *qkv, const float *relk, const fl
 /* rows of per-workgroup partial sums of (d relK | d relV) [rows][2 (2 win + 1) D] that glowtts_rpr_attention_bwd* leaves at the head of `scratch`; with
  * drelk == drelv == NULL (round 5) the call stops there and the caller sums them itself (glowtts_colsum_batched over several layers at once). */
 int64_t glowtts_rpr_attention_bwd_partial_rows(int B, int Tp, int H, int D, int win);
+/* Eval-mode attention core (RPR_MHA.py:95-128) for any Tp >= 1 (long-text inference): what glowtts_rpr_attention_fwd_prec computes on valid
+ * rows, without dropout and without the probability matrix - keys stream through LDS in blocks with an online softmax, so neither LDS nor
+ * device memory grows with Tp^2 and no scratch is needed.  Same qkv / out / rowmask layouts; rows of padded queries are finite.
+ * D <= 128.  D in {64, 96} with win <= 15: MFMA path (GLOWTTS_F32: v_mfma_f32_32x32x2_f32, exact fp32; GLOWTTS_BF16: bf16 operands on
+ * v_mfma_f32_32x32x16_bf16, fp32 softmax and accumulate); any other D or window: fp32 VALU path in either mode. */
+int glowtts_rpr_attention_fwd_eval(const float *qkv, const float *relk, const float *relv, const float *rowmask, float *out,
+                                   int B, int Tp, int H, int D, int win, int precision, void *stream);
 int glowtts_rpr_attention_bwd_prec(const float *qkv, const float *relk, const float *relv, const float *rowmask, const float *P, const float *dout,
                                    float *dS, float *dqkv, float *drelk, float *drelv, float *scratch,
                                    int B, int Tp, int H, int D, int win, float drop_p, uint32_t seed, const uint32_t *seed_ptr, int precision, void *stream);
