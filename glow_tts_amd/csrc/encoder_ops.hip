@@ -1506,9 +1506,11 @@ extern "C" int glowtts_rpr_attention_fwd_prec(const float* qkv, const float* rel
         const dim3 grid((Tp + 63) / 64, H, B);
         if (D == 96) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_long_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
+            GLOWTTS_NOTE_STATIC("attn_fwd_long<96>");
             hipLaunchKernelGGL(attn_fwd_long_kernel<3>, grid, dim3(128), l2, st, qkv, relk, relv, rowmask, out, P, B, Tp, H, win, drop_p, seed, seed_ptr);
         } else {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_long_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
+            GLOWTTS_NOTE_STATIC("attn_fwd_long<64>");
             hipLaunchKernelGGL(attn_fwd_long_kernel<2>, grid, dim3(128), l2, st, qkv, relk, relv, rowmask, out, P, B, Tp, H, win, drop_p, seed, seed_ptr);
         }
         RET_LAUNCH();
@@ -1516,6 +1518,7 @@ extern "C" int glowtts_rpr_attention_fwd_prec(const float* qkv, const float* rel
     const size_t lds = attn_lds_bytes(Tp, D, win, false);
     if (lds > 160 * 1024) return GLOWTTS_E_ARG;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    GLOWTTS_NOTE_STATIC("attn_fwd_gen");
     hipLaunchKernelGGL(attn_fwd_kernel, dim3((Tp + ATT_QT - 1) / ATT_QT, H, B), dim3(256), lds, static_cast<hipStream_t>(stream),
                        qkv, relk, relv, rowmask, out, P, B, Tp, H, D, win, drop_p, seed, seed_ptr);
     RET_LAUNCH();
@@ -1567,11 +1570,13 @@ extern "C" int glowtts_rpr_attention_bwd_prec(const float* qkv, const float* rel
         if (D == 96) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_long_q_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_long_kv_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3);
+            GLOWTTS_NOTE_STATIC("attn_bwd_long<96>");
             hipLaunchKernelGGL(attn_bwd_long_q_kernel<3>, grid, dim3(128), l2, st, qkv, relk, relv, rowmask, P, dout, dS, dqkv, scratch, B, Tp, H, win, drop_p, seed, seed_ptr);
             hipLaunchKernelGGL(attn_bwd_long_kv_kernel<3>, grid, dim3(128), l3, st, qkv, P, dS, dout, dqkv, B, Tp, H, drop_p, seed, seed_ptr);
         } else {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_long_q_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_long_kv_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3);
+            GLOWTTS_NOTE_STATIC("attn_bwd_long<64>");
             hipLaunchKernelGGL(attn_bwd_long_q_kernel<2>, grid, dim3(128), l2, st, qkv, relk, relv, rowmask, P, dout, dS, dqkv, scratch, B, Tp, H, win, drop_p, seed, seed_ptr);
             hipLaunchKernelGGL(attn_bwd_long_kv_kernel<2>, grid, dim3(128), l3, st, qkv, P, dS, dout, dqkv, B, Tp, H, drop_p, seed, seed_ptr);
         }
@@ -1580,6 +1585,7 @@ extern "C" int glowtts_rpr_attention_bwd_prec(const float* qkv, const float* rel
         const size_t lds = attn_lds_bytes(Tp, D, win, true);
         if (lds > 160 * 1024) return GLOWTTS_E_ARG;
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_a_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        GLOWTTS_NOTE_STATIC("attn_bwd_gen");
         hipLaunchKernelGGL(attn_bwd_a_kernel, dim3((Tp + ATT_QT - 1) / ATT_QT, H, B), dim3(256), lds, st, qkv, relk, relv, rowmask, P, dout, dS, dqkv, B, Tp, H, D, win, drop_p);
         hipLaunchKernelGGL(attn_bwd_b_kernel, dim3((Tp + 3) / 4, H, B), dim3(256), 0, st, qkv, P, dS, dout, dqkv, B, Tp, H, D);
         hipLaunchKernelGGL(attn_bwd_rel_kernel, dim3(nw, B * H), dim3(128), 0, st, qkv, P, dS, dout, scratch, B, Tp, H, D, win);

@@ -20,6 +20,11 @@ from .conv_fn import AttentionBlock, EmbeddingRows, FFNBlock, ParamGate, RPRAtte
 
 ROW_PAD = 2
 
+# Test hook: when a list, every dropout site of a training-mode `encoder_forward` appends (site name, kind "linear" | "attention", site seed, rate,
+# shape of the tensor the element ids run over) in launch order - what a parity test needs to restate the masks (the step's seed word is added on
+# the device).  No effect when None.
+DROP_LOG = None
+
 
 def _with_bf16(y, yb):
     """Attaches the bf16 copy of fp32 rows (see conv_fn.bf16_of)."""
@@ -186,6 +191,10 @@ def encoder_forward(P, hp, tokens, mask, speakers=None, prosodies=None, training
         counter[0] += 7919
         return counter[0]
 
+    def log_site(site, kind, seed, p_, shape):
+        if DROP_LOG is not None and training and site is not None:
+            DROP_LOG.append((site, kind, int(seed), float(p_), tuple(int(v) for v in shape)))
+
     # Conv parameters pass through one ParamGate: the convs' weight gradients are then deferred to a few grouped launches at the end
     # of the encoder's backward (conv_fn.WgradTape).  QKV: one fused [3C, C, 1] weight per layer (views of a flat tensor with `cache`).
     Pc = dict(P)
@@ -252,17 +261,21 @@ def encoder_forward(P, hp, tokens, mask, speakers=None, prosodies=None, training
     # operands - the LDS-DMA kernel instead of the register-staged one (fp32 -> bf16 in the loop); see conv_fn.ConvRows
     bf_rows = precision == ops.BF16 and C % 32 == 0
 
-    def conv(xr, name, relu=False, mask_out=False, residual=None, drop=0.0, out_bf16=False, xb=None):
+    def conv(xr, name, relu=False, mask_out=False, residual=None, drop=0.0, out_bf16=False, xb=None, site=None):
         p_ = float(drop) if training else 0.0
+        seed = nseed()
+        log_site(site, "linear", seed, p_, (xr.shape[0], Pc[name + ".weight"].shape[0]))
         xb = (xb if xb is not None else bf16_of(xr)) if bf_rows else None
         out_bf16 = out_bf16 and (xb is not None or xr.dtype == torch.bfloat16)
         return conv_rows(xr, Pc[name + ".weight"], Pc.get(name + ".bias"), rmf, relu=relu, mask_out=mask_out, residual=residual,
-                         precision=precision, drop_p=p_, seed=nseed(), seed_t=seed_t, tape=tape,
+                         precision=precision, drop_p=p_, seed=seed, seed_t=seed_t, tape=tape,
                          packs=packset.get(name) if packset is not None else None, xb=xb, out_bf16=out_bf16)
 
-    def ln(a, b, name, relu=False, drop=0.0):
+    def ln(a, b, name, relu=False, drop=0.0, site=None):
         p_ = float(drop) if training else 0.0
-        return layernorm_rows(a, b, P[name + ".weight"], P[name + ".bias"], rmf, relu=relu, drop_p=p_, seed=nseed(), seed_t=seed_t,
+        seed = nseed()
+        log_site(site, "linear", seed, p_, a.shape)
+        return layernorm_rows(a, b, P[name + ".weight"], P[name + ".bias"], rmf, relu=relu, drop_p=p_, seed=seed, seed_t=seed_t,
                               want_bf16=bf_rows)
 
     from .decoder import stamp
@@ -272,7 +285,7 @@ def encoder_forward(P, hp, tokens, mask, speakers=None, prosodies=None, training
     res = x
     for i in range(e.Prenet.Stacks):
         q = f"{prefix}.layer_Dict.Prenet.layer_Dict.CLRD_{i}.layer_Dict"
-        x = ln(conv(x, q + ".Conv"), None, q + ".LayerNorm", relu=True, drop=e.Prenet.Dropout_Rate)
+        x = ln(conv(x, q + ".Conv"), None, q + ".LayerNorm", relu=True, drop=e.Prenet.Dropout_Rate, site=f"Prenet.CLRD_{i}")
     x = conv(x, prefix + ".layer_Dict.Prenet.layer_Dict.Conv1x1", mask_out=True, residual=res)
     if pack_join is not None:
         pack_join()                                                    # the second launch's images are needed from here on
@@ -291,9 +304,14 @@ def encoder_forward(P, hp, tokens, mask, speakers=None, prosodies=None, training
         if blocks:
             # bf16-stored rows, training: two autograd nodes per layer whose backward chains are hand-ordered (conv_fn.AttentionBlock / FFNBlock)
             pdr = float(dr) if training else 0.0
+            sa, sf = (nseed(), nseed()), (nseed(), nseed())
+            log_site(f"ANCRDCN_{i}.Attention", "attention", sa[0], pdr, (B, H, Tp, Tp))
+            log_site(f"ANCRDCN_{i}.Projection", "linear", sa[1], pdr, (B * Tp, C))
+            log_site(f"ANCRDCN_{i}.Conv_0", "linear", sf[0], pdr, (B * Tp, e.Transformer.Conv.Calc_Channels))
+            log_site(f"ANCRDCN_{i}.Conv_1", "linear", sf[1], pdr, (B * Tp, C))
             x = _with_bf16(*AttentionBlock.apply(x, bf16_of(x), Pc[a + ".QKV.weight"], Pc[a + ".QKV.bias"], Pc[a + ".weight_K"], Pc[a + ".weight_V"],
                                                  Pc[a + ".layer_Dict.Projection.weight"], Pc[a + ".layer_Dict.Projection.bias"],
-                                                 Pc[q + ".LayerNorm_0.weight"], Pc[q + ".LayerNorm_0.bias"], rmf, B, Tp, H, win, pdr, (nseed(), nseed()), seed_t,
+                                                 Pc[q + ".LayerNorm_0.weight"], Pc[q + ".LayerNorm_0.bias"], rmf, B, Tp, H, win, pdr, sa, seed_t,
                                                  tape, packset.get(a + ".QKV"), packset.get(a + ".layer_Dict.Projection"), qkv_pre, rel_gated))
             # the block's closing LayerNorm also computes the NEXT block's fused Q / K / V conv (one launch less on the forward chain per block)
             nxt = None
@@ -301,17 +319,19 @@ def encoder_forward(P, hp, tokens, mask, speakers=None, prosodies=None, training
                 an = f"{prefix}.layer_Dict.Transformer.layer_Dict.ANCRDCN_{i + 1}.layer_Dict.Attention"
                 nxt = (packset.get(an + ".QKV")[0], Pc[an + ".QKV.bias"])
             out = FFNBlock.apply(x, bf16_of(x), Pc[q + ".Conv_0.weight"], Pc[q + ".Conv_0.bias"], Pc[q + ".Conv_1.weight"], Pc[q + ".Conv_1.bias"],
-                                 Pc[q + ".LayerNorm_1.weight"], Pc[q + ".LayerNorm_1.bias"], rmf, pdr, (nseed(), nseed()), seed_t, tape,
+                                 Pc[q + ".LayerNorm_1.weight"], Pc[q + ".LayerNorm_1.bias"], rmf, pdr, sf, seed_t, tape,
                                  packset.get(q + ".Conv_0"), packset.get(q + ".Conv_1"), nxt)
             x, qkv_pre = _with_bf16(out[0], out[1]), (out[2] if nxt is not None else None)
             continue
         qkv = conv(x, a + ".QKV")                                                                            # RPR_MHA.py:82-84 (one fused 1x1 conv)
+        aseed = nseed()
+        log_site(f"ANCRDCN_{i}.Attention", "attention", aseed, float(dr) if training else 0.0, (B, H, Tp, Tp))
         att = RPRAttention.apply(qkv, P[a + ".weight_K"], P[a + ".weight_V"], rmf, B, Tp, H, win,
-                                 float(dr) if training else 0.0, nseed(), seed_t, precision)                 # RPR_MHA.py:95-128
-        att = conv(att, a + ".layer_Dict.Projection", drop=dr)                                               # :93 + Dropout :561
+                                 float(dr) if training else 0.0, aseed, seed_t, precision)                   # RPR_MHA.py:95-128
+        att = conv(att, a + ".layer_Dict.Projection", drop=dr, site=f"ANCRDCN_{i}.Projection")               # :93 + Dropout :561
         x = ln(att, x, q + ".LayerNorm_0")                                                                   # :562
-        h = conv(x, q + ".Conv_0", relu=True, mask_out=True, drop=dr, out_bf16=True)                         # :565-567 (only Conv_1 reads it)
-        h = conv(h, q + ".Conv_1", mask_out=True, drop=dr)                                                   # :568-569 (x*mask at :571)
+        h = conv(x, q + ".Conv_0", relu=True, mask_out=True, drop=dr, out_bf16=True, site=f"ANCRDCN_{i}.Conv_0")   # :565-567 (only Conv_1 reads it)
+        h = conv(h, q + ".Conv_1", mask_out=True, drop=dr, site=f"ANCRDCN_{i}.Conv_1")                       # :568-569 (x*mask at :571)
         x = ln(h, x, q + ".LayerNorm_1")                                                                     # :571
     proj = conv(x, prefix + ".layer_Dict.Project", mask_out=True)
     stamp("enc_fwd_project")
@@ -336,7 +356,8 @@ def encoder_forward(P, hp, tokens, mask, speakers=None, prosodies=None, training
     dp = e.Duration_Predictor
     for i in range(dp.Stacks):
         q = f"{prefix}.layer_Dict.Duration_Predictor.layer_Dict.CRND_{i}.layer_Dict.Conv"
-        d = conv(d, q, relu=True, mask_out=True, drop=dp.Dropout_Rate, xb=db if i == 0 else None, out_bf16=i + 1 < dp.Stacks)
+        d = conv(d, q, relu=True, mask_out=True, drop=dp.Dropout_Rate, xb=db if i == 0 else None, out_bf16=i + 1 < dp.Stacks,
+                 site=f"CRND_{i}")
     # Projection to one channel: N = 1 is not a GEMM; a masked dot product per frame (multiply + row reduction: rocBLAS' gemv took
     # 82 us for these 3.5k x 256 rows, 5x the two elementwise kernels)
     wq = prefix + ".layer_Dict.Duration_Predictor.layer_Dict.Projection"

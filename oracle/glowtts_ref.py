@@ -107,11 +107,21 @@ def ln_ch(sd, p, x):
 
 
 # --------------------------------------------------------------------------- encoder
-def rpr_attention(sd, p, x, mask, cfg):
+def _site(p):
+    """Stable name of a dropout site from its parameter prefix: the last block name (`CLRD_1`, `ANCRDCN_3`, `CRND_0`), with the
+    owning sub-network for the prenet (`Prenet.CLRD_1`)."""
+    parts = p.split(".")
+    blk = [q for q in parts if q.startswith(("CLRD_", "ANCRDCN_", "CRND_"))][-1]
+    return "Prenet." + blk if blk.startswith("CLRD_") else blk
+
+
+def rpr_attention(sd, p, x, mask, cfg, drop=None):
     """RPR_MHA.py:69-128 self-attention with Shaw relative positions, restated in banded form:
     only offsets d = j - i in [-w, w] contribute and row d + w of weight_K / weight_V is the
     embedding of offset d (Get_Relative_Embedding :131-140 zero-pads the rest).
-    x [B,C,T]; mask [B,1,T] float.  Returns [B,C,T]."""
+    x [B,C,T]; mask [B,1,T] float.  Returns [B,C,T].
+    drop (test hook; eval mode when None): callable(site, x) -> x after the dropout the reference applies at that site - here
+    `ANCRDCN_i.Attention` on the probabilities [B,H,T,T] (:120), ahead of BOTH of their uses (:121 and :124-126)."""
     B, C, T = x.shape
     H, w = cfg.heads, cfg.window
     D = C // H
@@ -131,6 +141,8 @@ def rpr_attention(sd, p, x, mask, cfg):
     amask = (mask.transpose(1, 2) * mask).unsqueeze(1)                           # [B,1,T,T]  Modules.py:558
     scores = scores.masked_fill(amask == 0, -1e4)                                # (:117)
     pr = torch.softmax(scores, dim=-1)                                           # (:119) dropout is identity in eval
+    if drop is not None:
+        pr = drop(_site(p) + ".Attention", pr)                                   # (:120)
     out = pr @ v                                                                 # (:121)
     # relative-V term: sum_d P[i, i+d] * relV[d+w]                               # (:124-126)
     pb = torch.zeros(B, H, T, 2 * w + 1, dtype=x.dtype)
@@ -144,46 +156,59 @@ def rpr_attention(sd, p, x, mask, cfg):
     return conv(sd, p + ".layer_Dict.Projection", out)                           # (:93)
 
 
-def prenet(sd, p, x, mask, cfg):
-    """Modules.py:438-489: stacks x [Conv k5 on x*mask -> LN -> ReLU -> Dropout] -> 1x1 + residual -> *mask."""
+def prenet(sd, p, x, mask, cfg, drop=None):
+    """Modules.py:438-489: stacks x [Conv k5 on x*mask -> LN -> ReLU -> Dropout] -> 1x1 + residual -> *mask.
+    drop: see `rpr_attention`; sites `Prenet.CLRD_i` (:487)."""
     res = x
     for i in range(cfg.prenet_stacks):
         q = f"{p}.layer_Dict.CLRD_{i}.layer_Dict"
         x = conv(sd, q + ".Conv", x * mask, pad=(cfg.prenet_kernel - 1) // 2)
         x = torch.relu(ln_ch(sd, q + ".LayerNorm", x))
+        if drop is not None:
+            x = drop(_site(q), x)                                                # :487
     return (conv(sd, p + ".layer_Dict.Conv1x1", x) + res) * mask
 
 
-def transformer(sd, p, x, mask, cfg):
-    """Modules.py:492-573 (ANCRDCN x stacks, final *mask)."""
+def transformer(sd, p, x, mask, cfg, drop=None):
+    """Modules.py:492-573 (ANCRDCN x stacks, final *mask).  drop: see `rpr_attention`; sites `ANCRDCN_i.Attention` (RPR_MHA.py:120),
+    `ANCRDCN_i.Projection` (:561), `ANCRDCN_i.Conv_0` (:567, after the ReLU), `ANCRDCN_i.Conv_1` (:569, ahead of the mask and the residual)."""
     pad = (cfg.ffn_kernel - 1) // 2
     for i in range(cfg.enc_stacks):
         q = f"{p}.layer_Dict.ANCRDCN_{i}.layer_Dict"
         x = x * mask                                                             # :554 (in place in the reference)
         res = x
-        a = rpr_attention(sd, q + ".Attention", x, mask, cfg)                    # :556-559
+        a = rpr_attention(sd, q + ".Attention", x, mask, cfg, drop)              # :556-559
+        if drop is not None:
+            a = drop(_site(q) + ".Projection", a)                                # :561
         x = ln_ch(sd, q + ".LayerNorm_0", a + res)                               # :562
         res = x
         h = torch.relu(conv(sd, q + ".Conv_0", x * mask, pad))                   # :565-566
+        if drop is not None:
+            h = drop(_site(q) + ".Conv_0", h)                                    # :567
         h = conv(sd, q + ".Conv_1", h * mask, pad)                               # :568
+        if drop is not None:
+            h = drop(_site(q) + ".Conv_1", h)                                    # :569
         x = ln_ch(sd, q + ".LayerNorm_1", h * mask + res)                        # :571
     return x * mask                                                              # :507
 
 
-def duration_predictor(sd, p, x, mask, cond, cfg):
-    """Modules.py:576-648.  cond = speakers + prosodies ([B,256]) or None."""
+def duration_predictor(sd, p, x, mask, cond, cfg, drop=None):
+    """Modules.py:576-648.  cond = speakers + prosodies ([B,256]) or None.  drop: see `rpr_attention`; sites `CRND_i` (:646)."""
     if cond is not None:
         x = torch.cat([x, cond.unsqueeze(2).expand(-1, -1, x.shape[2])], dim=1)  # :606-612
     for i in range(cfg.dp_stacks):
         x = torch.relu(conv(sd, f"{p}.layer_Dict.CRND_{i}.layer_Dict.Conv", x * mask, (cfg.dp_kernel - 1) // 2))
+        if drop is not None:
+            x = drop(f"CRND_{i}", x)                                             # :646
     return conv(sd, p + ".layer_Dict.Projection", x * mask) * mask               # :616-618
 
 
-def encoder(sd, tokens, mask, cfg, speakers=None, prosodies=None, p="layer_Dict.Encoder"):
-    """Modules.py:262-284 -> mean [B,mel,T], log_std [B,mel,T], log_dur [B,1,T]."""
+def encoder(sd, tokens, mask, cfg, speakers=None, prosodies=None, p="layer_Dict.Encoder", drop=None):
+    """Modules.py:262-284 -> mean [B,mel,T], log_std [B,mel,T], log_dur [B,1,T].  drop (test hook; eval mode when None): callable(site, x) ->
+    x after the dropout of that site (see `prenet`, `transformer`, `duration_predictor`) - a parity test injects the keep masks the HIP path drew."""
     x = F.embedding(tokens, sd[p + ".layer_Dict.Embedding.weight"]).transpose(1, 2) * math.sqrt(cfg.enc_channels)
-    x = prenet(sd, p + ".layer_Dict.Prenet", x, mask, cfg)
-    x = transformer(sd, p + ".layer_Dict.Transformer", x, mask, cfg)
+    x = prenet(sd, p + ".layer_Dict.Prenet", x, mask, cfg, drop)
+    x = transformer(sd, p + ".layer_Dict.Transformer", x, mask, cfg, drop)
     proj = conv(sd, p + ".layer_Dict.Project", x) * mask
     mean, log_std = proj[:, :cfg.mel_dim], proj[:, cfg.mel_dim:]
     cond = None
@@ -193,7 +218,7 @@ def encoder(sd, tokens, mask, cfg, speakers=None, prosodies=None, p="layer_Dict.
             cond = cond + speakers.detach()                                     # :277-280
         if prosodies is not None:
             cond = cond + prosodies.detach()
-    log_dur = duration_predictor(sd, p + ".layer_Dict.Duration_Predictor", x.detach(), mask, cond, cfg)
+    log_dur = duration_predictor(sd, p + ".layer_Dict.Duration_Predictor", x.detach(), mask, cond, cfg, drop)
     return mean, log_std, log_dur
 
 
@@ -399,12 +424,14 @@ def mas(value, mask, max_neg_val=-1e9):
     return torch.from_numpy(path).to(dtype=value.dtype)
 
 
-def forward_train(sd, cfg, tokens, token_lengths, mels, mel_lengths, speakers=None, prosodies=None, pitches=None, attn=None):
+def forward_train(sd, cfg, tokens, token_lengths, mels, mel_lengths, speakers=None, prosodies=None, pitches=None, attn=None,
+                  enc_drop=None, wn_drop=None):
     """Modules.py:50-126 GlowTTS.forward, every Mode: Vanilla / SE (LUT ids or pre-computed d-vectors) / PE (GST prosody encoder on the
     target mels, :81-82) / GR (LUT + prosody encoder + adversarial speaker classifier :84-87 + per-frame pitch conditioning :89-90, 300-301).
     `speakers`: int64 ids (LUT) or float [B,256] vectors (GE2E d-vectors are an input); `prosodies`: pre-computed vectors
     override the prosody encoder.  `attn` (test hook, not in the reference): use this alignment instead of searching one - lets a parity test
-    compare gradients on EQUAL alignments when the search sits on near-ties."""
+    compare gradients on EQUAL alignments when the search sits on near-ties.  `enc_drop` / `wn_drop` (test hooks; eval mode when None): the dropout
+    hooks of `encoder` and `wavenet` - train mode with injected keep masks."""
     mode = cfg.mode.upper()
     attn_given = attn
     if speakers is not None and speakers.dtype == torch.long:
@@ -418,8 +445,8 @@ def forward_train(sd, cfg, tokens, token_lengths, mels, mel_lengths, speakers=No
         pitches = None                                                           # :89-90
     tmask = mask_from_lengths(token_lengths, tokens.shape[1])
     mmask = mask_from_lengths(mel_lengths, mels.shape[2])
-    mean, log_std, log_dur = encoder(sd, tokens, tmask, cfg, speakers, prosodies)
-    z, log_dets, mmask2 = decoder(sd, mels, mmask, cfg, False, speakers, prosodies, pitches)
+    mean, log_std, log_dur = encoder(sd, tokens, tmask, cfg, speakers, prosodies, drop=enc_drop)
+    z, log_dets, mmask2 = decoder(sd, mels, mmask, cfg, False, speakers, prosodies, pitches, drop=wn_drop)
     amask = (tmask.unsqueeze(-1) * mmask2.unsqueeze(2)).squeeze(1)               # :102-103
     with torch.no_grad():
         logp = log_prior(mean, log_std, z)

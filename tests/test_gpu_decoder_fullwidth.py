@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from oracle import glowtts_ref as O
+from dropout_masks import hip_keep_multipliers as _hip_keep_multipliers
 from helpers import full_width_state, launch_counts, launch_reset
 
 pytestmark = pytest.mark.gpu
@@ -179,28 +180,6 @@ def test_full_width_dropout_masks_agree_between_forward_backward_and_precisions(
     if ds32 is not None:
         a, b = ds16.flatten().double(), ds32.flatten().double()
         assert (a @ b / (a.norm() * b.norm())).item() >= 0.98
-
-
-def _hip_keep_multipliers(seed_word, flow, layer, B, T, H, p):
-    """The WaveNet dropout multipliers the HIP epilogues draw (csrc/device_common.h: drop_rowkey / drop_colkey / drop_draw), restated with
-    numpy uint32 arithmetic: [B, 2H, T] for gate pre-activation channel (tanh j | sigmoid H + j) of squeezed frame t of utterance b.
-    Row index = position in the rows layout [B][T + 4] (two pad rows in front of every utterance)."""
-    import numpy as np
-    u = lambda v: np.asarray(v, dtype=np.uint64) & 0xFFFFFFFF
-    thr = int(p * 65536.0 + 0.5)
-    ik = np.float32(65536.0) / np.float32(65536.0 - thr)
-    seed = (1000003 * flow + int(seed_word) + layer) & 0xFFFFFFFF
-    rows = (np.arange(B)[:, None] * (T + 4) + 2 + np.arange(T)[None, :]).astype(np.uint64)            # [B, T]
-    x = u(rows * 0x9E3779B1 + seed)
-    x ^= x >> 16
-    x = u(x * 0x85EBCA6B)
-    x ^= x >> 13
-    ck = u((np.arange(H, dtype=np.uint64) + 1) * 0x27D4EB2F)                                          # [H]
-    d = u((x[:, None, :] ^ ck[None, :, None]) * 0xC2B2AE35)                                           # [B, H, T]
-    d ^= d >> 16
-    keep_t, keep_s = (d & 0xFFFF) >= thr, (d >> 16) >= thr
-    m = np.concatenate([keep_t, keep_s], 1).astype(np.float32) * ik
-    return torch.from_numpy(m)
 
 
 def test_full_width_backward_f32_in_train_mode_with_the_same_dropout_masks():

@@ -7,8 +7,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-def attention_core_ref(qkv, relk, relv, rowmask, B, Tp, H, win):
-    """RPR_MHA.py:95-128 on fused rows [B*Tp, 3*H*D] (Q | K | V), every row a position, rowmask 0 on padding."""
+def attention_core_ref(qkv, relk, relv, rowmask, B, Tp, H, win, keep=None):
+    """RPR_MHA.py:95-128 on fused rows [B*Tp, 3*H*D] (Q | K | V), every row a position, rowmask 0 on padding.
+    keep [B,H,Tp,Tp]: dropout multipliers on the probabilities (:120), ahead of BOTH of their uses (:121, :124-126)."""
     C3 = qkv.shape[1]
     D = C3 // (3 * H)
     x = qkv.view(B, Tp, 3, H, D)
@@ -24,6 +25,8 @@ def attention_core_ref(qkv, relk, relv, rowmask, B, Tp, H, win):
     m = rowmask.view(B, Tp)
     scores = scores.masked_fill((m[:, :, None] * m[:, None, :]).unsqueeze(1) == 0, -1e4)
     pr = torch.softmax(scores, dim=-1)
+    if keep is not None:
+        pr = pr * keep
     out = pr @ v
     pb = torch.zeros(B, H, Tp, 2 * win + 1, device=qkv.device, dtype=qkv.dtype)
     for d in range(-win, win + 1):

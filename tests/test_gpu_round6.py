@@ -88,6 +88,106 @@ def _prior_case(B=3, C=80, Tx=37, Ty=96, seed=0):
     return tl, ml, idx, mean, ls, z, ld
 
 
+def _prior_reference(tl, ml, idx, mean, ls, z, ld, ns=2, mel_dim=80, scale=1.0):
+    """Modules.py:120-122 and :1020-1029 as float64 torch expressions, gradients by autograd: the expansion of (mean, log_std) by the alignment index
+    (a gather), the duration targets log(count + 1e-7) on valid tokens, the MLE sum over sum(len // ns) * ns * mel_dim - the independent third party of
+    the fused / unfused comparisons below.  -> [mel_mean, mel_log_std, targets [B, Tx], loss, d mean, d log_std, d z, d log_dets] (of loss * scale)."""
+    import math
+    Tx = mean.shape[2]
+    m, l, zz, dd = (t.double().requires_grad_(True) for t in (mean, ls, z, ld))
+    onehot = (idx[:, None, :] == torch.arange(Tx)[None, :, None]).double()          # [B, Tx, Ty]; frames without a token (-1) own nothing
+    mm, ms = m @ onehot, l @ onehot                                                  # :120-121
+    tmask = (torch.arange(Tx)[None] < tl[:, None]).double()
+    tg = torch.log(onehot.sum(-1) + 1e-7) * tmask                                    # :122
+    loss = ms.sum() + 0.5 * (torch.exp(-2 * ms) * (zz - mm) ** 2).sum() - dd.sum()   # :1023-1026
+    loss = loss / ((ml // ns).sum() * ns * mel_dim) + 0.5 * math.log(2 * math.pi)    # :1027-1029
+    (loss * scale).backward()
+    return [mm.detach(), ms.detach(), tg.detach(), loss.detach(), m.grad, l.grad, zz.grad, dd.grad]
+
+
+def _assert_prior_against_reference(got, ref):
+    """got / ref: [mel_mean, mel_log_std, targets, loss, d mean, d log_std, d z, d log_dets].  The expansions are gathers: equal; the log-duration
+    targets within 1e-5 (the suite's log_dur_target bar); sums within 1e-5 of the tensor's largest entry (test_expand_prior_forward_backward's bar)."""
+    names = ("mel_mean", "mel_log_std", "targets", "loss", "d mean", "d log_std", "d z", "d log_dets")
+    for name, a, b in zip(names, got, ref):
+        a = a.double().reshape(b.shape)
+        if name in ("mel_mean", "mel_log_std"):
+            assert torch.equal(a, b), name
+        elif name == "targets":
+            assert (a - b).abs().max() <= 1e-5, (name, (a - b).abs().max().item())
+        else:
+            assert (a - b).abs().max() <= 1e-5 * b.abs().max(), (name, (a - b).abs().max().item(), b.abs().max().item())
+
+
+def _case_from_durations(durs, Tx, Ty, seed, C=80):
+    """Alignment given as frames per token of every utterance -> the tensors of `_prior_case`."""
+    g = torch.Generator().manual_seed(seed)
+    B = len(durs)
+    tl, ml = torch.tensor([len(d) for d in durs]), torch.tensor([sum(d) for d in durs])
+    assert int(tl.max()) <= Tx and int(ml.max()) <= Ty and all(n >= 1 for d in durs for n in d)
+    idx = torch.full((B, Ty), -1, dtype=torch.int32)
+    for b, d in enumerate(durs):
+        idx[b, :sum(d)] = torch.repeat_interleave(torch.arange(len(d), dtype=torch.int32), torch.tensor(d))
+    mean, ls = torch.randn(B, C, Tx, generator=g), torch.randn(B, C, Tx, generator=g) * 0.3
+    mmask = (torch.arange(Ty)[None] < ml[:, None]).float()
+    z = torch.randn(B, C, Ty, generator=g) * mmask[:, None]
+    ld = torch.randn(B, generator=g)
+    return tl, ml, idx, mean, ls, z, ld
+
+
+def _rand_durs(n_tok, total, g):
+    cuts = torch.sort(torch.randperm(total - 1, generator=g)[:n_tok - 1] + 1).values.tolist() if n_tok > 1 else []
+    b = [0] + cuts + [total]
+    return [b[i + 1] - b[i] for i in range(n_tok)]
+
+
+def _edge_alignments():
+    g = torch.Generator().manual_seed(64)
+    return {
+        # runs around the 64-frame boundary of the wave-wide segmented scan (csrc/loss_ops.hip expand_bwd_kernel / prior_bwd_block): a run that ends exactly at
+        # frame 63 (40..63, and 0..63), runs that straddle 63 / 64 (50..69, and 1..126)
+        "frame_63_64": ([[10, 30, 24, 1, 20, 43], [50, 20, 2, 24], [64, 64], [1, 126, 1]], 8, 128),
+        # one token owns every frame of an utterance: Tx = 1 ...
+        "one_token_tx1": ([[70], [64], [2]], 1, 70),
+        # ... and Tx > 1 with every other token at its minimum of one frame (owner first, last, in the middle)
+        "one_owner": ([[95, 1, 1, 1, 1, 1], [1, 1, 1, 1, 1, 59], [1, 1, 94, 1, 1], [1, 1, 6]], 6, 100),
+        # Ty below, and not a multiple of, 64
+        "ty_4": ([[2, 1, 1], [1, 1], [2]], 3, 4),
+        "ty_60": ([_rand_durs(17, 60, g), _rand_durs(5, 44, g), _rand_durs(30, 58, g)], 30, 60),
+        "ty_68": ([_rand_durs(9, 68, g), _rand_durs(33, 66, g), [1, 1]], 33, 68),
+    }
+
+
+@pytest.mark.parametrize("name", ["base", "frame_63_64", "one_token_tx1", "one_owner", "ty_4", "ty_60", "ty_68"])
+def test_expand_pair_and_prior_loss_against_float64(name):
+    """The fused loss launches (`ExpandPair`, `PriorLoss`) AND the launches they replaced (`ExpandPrior`, `duration_targets`, `MLELoss`) against
+    `_prior_reference` - the bit-for-bit comparison of the two HIP paths (test_expand_pair_and_prior_loss_equal_the_separate_launches) held no independent
+    value.  On `_prior_case` and on alignments aimed at the segmented scan of the backward kernels (see `_edge_alignments`)."""
+    from glow_tts_amd import alignment as A
+    if name == "base":
+        case = _prior_case()
+    else:
+        durs, Tx, Ty = _edge_alignments()[name]
+        case = _case_from_durations(durs, Tx, Ty, seed=len(name))
+    tl, ml, idx, mean, ls, z, ld = case
+    ref = _prior_reference(*case, scale=1.7)
+    dev = lambda t: t.cuda()
+    for fused in (False, True):
+        m, l, zz, dd = (dev(t).requires_grad_(True) for t in (mean, ls, z, ld))
+        if fused:
+            mm, ms, tg, _ = A.ExpandPair.apply(m, l, dev(idx), dev(tl), None, True)
+            A.tag_prior(mm, ms, m, l, dev(idx))
+            loss = A.mle_loss(zz, mm, ms, dd, dev(ml), 2, 80)
+            assert type(loss.grad_fn).__name__.startswith("PriorLoss")
+        else:
+            mm, ms = A.ExpandPrior.apply(m, dev(idx)), A.ExpandPrior.apply(l, dev(idx))
+            tg = A.duration_targets(dev(idx), dev(tl), mean.shape[2]).squeeze(1)
+            loss = A.mle_loss(zz, mm, ms, dd, dev(ml), 2, 80)
+        (loss * 1.7).backward()
+        torch.cuda.synchronize()
+        _assert_prior_against_reference([t.detach().cpu() for t in (mm, ms, tg, loss, m.grad, l.grad, zz.grad, dd.grad)], ref)
+
+
 def test_expand_pair_and_prior_loss_equal_the_separate_launches():
     """Round 6 fusions of Modules.py:120-122 and of the MLE backward through them: `ExpandPair` (one launch) == two `ExpandPrior` + `duration_targets`, and
     `PriorLoss` (one backward launch: d z + token-space segment sums) == `MLELoss` behind `ExpandPrior` - bit for bit, values and all four gradients; and
@@ -115,6 +215,7 @@ def test_expand_pair_and_prior_loss_equal_the_separate_launches():
         res.append([t.detach().cpu() for t in (mm, ms, tg, loss, m.grad, l.grad, zz.grad, dd.grad)])
     for a, b in zip(*res):
         assert torch.equal(a, b)
+    _assert_prior_against_reference(res[0], _prior_reference(tl, ml, idx, mean, ls, z, ld, scale=1.7))     # ... and an independent value
     # the tagged outputs used anywhere else still get the general backward
     m, l = dev(mean).requires_grad_(True), dev(ls).requires_grad_(True)
     mm, ms, _, none = A.ExpandPair.apply(m, l, dev(idx), dev(tl), None)
@@ -163,6 +264,13 @@ def test_seeded_losses_write_their_gradients_in_the_forward_launch():
     plain, seeded, foreign = run("plain"), run("seeded"), run("foreign")
     for x, y, w in zip(plain, seeded, foreign):
         assert torch.equal(x, y) and torch.equal(x, w)
+    # ... and an independent value: float64 expressions of the two losses (Modules.py:1020-1029, Train.py:206 MSELoss) and autograd
+    ref = _prior_reference(tl, ml, idx, mean, ls, z, ld)
+    a64, t64 = a0.double().requires_grad_(True), t0.double()
+    len64 = torch.nn.functional.mse_loss(a64, t64)
+    len64.backward()
+    for name, got, want in zip(("mle", "length", "d mean", "d log_std", "d z", "d log_dets", "d log_dur"), seeded, [ref[3], len64.detach()] + ref[4:] + [a64.grad]):
+        assert (got.double().reshape(want.shape) - want).abs().max() <= 1e-5 * want.abs().max(), name
     # weighted terms (data parallel): seeds are device scalars the forward launches read
     wm, wr = torch.tensor(0.37).cuda(), torch.tensor(0.5).cuda()
     m, l, zz, dd, a = (dev(t).requires_grad_(True) for t in (mean, ls, z, ld, a0))

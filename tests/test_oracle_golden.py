@@ -80,6 +80,77 @@ def test_model_oracle_matches_reference_vectors(mode, fname):
     assert np.array_equal(a.numpy().astype(np.int8), r["inf_attn"])
 
 
+TRAIN_SITES = {"Attention": (".layer_Dict.Attention.layer_Dict.Dropout", 0), "Projection": (".layer_Dict.Dropout", 0),
+               "Conv_0": (".layer_Dict.Dropout", 1), "Conv_1": (".layer_Dict.Dropout", 2)}
+
+
+def _stored_mask(d, name, call, shape):
+    """-> keep multiplier mask / (1 - p) of the reference's Dropout module `name`, call `call` (tests/golden/make_train_golden.py)."""
+    want = tuple(int(v) for v in d[f"shape/{name}/{call}"])
+    assert want == tuple(shape), (name, call, want, tuple(shape))
+    n = int(np.prod(want))
+    keep = np.unpackbits(d[f"mask/{name}/{call}"])[:n].reshape(want).astype(np.float32)
+    return torch.from_numpy(keep) / (1.0 - float(d[f"p/{name}/{call}"]))
+
+
+@pytest.mark.parametrize("mode,fname,tname", [("Vanilla", "tiny_vanilla.npz", "tiny_train_vanilla.npz"), ("SE", "tiny_se.npz", "tiny_train_se.npz")])
+def test_model_oracle_matches_reference_in_train_mode(mode, fname, tname, golden_dir):
+    """Train mode: the oracle's `drop` hooks sit where the reference calls its Dropout modules (Modules.py:487, 561, 567, 569, 646, 862,
+    RPR_MHA.py:120).  The fixture holds the keep masks the unmodified reference was run with in train() (one per module and call), its outputs,
+    losses and parameter gradients; the oracle fed the same masks must reproduce them at the bars of the eval pin in make_golden.py
+    (2e-5 relative on outputs, alignment exact, 2e-3 on gradients)."""
+    sd, _, r = load_case(fname)
+    d = np.load(f"{golden_dir}/{tname}")
+    cfg = tiny_cfg(mode)
+    t = lambda k: torch.from_numpy(r[k])
+    spk = t("speakers") if "speakers" in r else None
+    enc = "layer_Dict.Encoder.layer_Dict."
+    used = set()
+
+    def enc_drop(site, x):
+        if site.startswith("Prenet."):
+            name, call = enc + "Prenet.layer_Dict." + site[len("Prenet."):] + ".layer_Dict.Dropout", 0
+        elif site.startswith("CRND_"):
+            name, call = enc + "Duration_Predictor.layer_Dict." + site + ".layer_Dict.Dropout", 0
+        else:
+            blk, what = site.split(".")
+            name, call = enc + "Transformer.layer_Dict." + blk + TRAIN_SITES[what][0], TRAIN_SITES[what][1]
+        assert (name, call) not in used, site
+        used.add((name, call))
+        return x * _stored_mask(d, name, call, x.shape)
+
+    def wn_drop(pfx, layer, ins):
+        used.add((pfx + ".layer_Dict.Dropout", layer))
+        return ins * _stored_mask(d, pfx + ".layer_Dict.Dropout", layer, ins.shape)
+
+    sdg = {k: v.clone().requires_grad_(v.is_floating_point()) for k, v in sd.items()}
+    o = O.forward_train(sdg, cfg, t("tokens"), t("token_lengths"), t("mels"), t("mel_lengths"), spk, enc_drop=enc_drop, wn_drop=wn_drop)
+    stored = {tuple(k.split("/")[1:]) for k in d.files if k.startswith("mask/")}
+    assert {(n, str(c)) for n, c in used} == stored                      # every Dropout call of the reference has its hook call, and no other
+    assert len(stored) == cfg.prenet_stacks + 4 * cfg.enc_stacks + cfg.dp_stacks + cfg.n_flows * cfg.wn_layers
+
+    def chk(a, b, name, tol=2e-5):
+        b = torch.from_numpy(np.asarray(b))
+        err = (a.detach() - b).abs().max().item()
+        assert err <= tol * max(1.0, b.abs().max().item()), (name, err)
+    for k in ["z", "mel_mean", "mel_log_std", "log_dur", "log_dur_target"]:
+        chk(o[k], d[k], k)
+    chk(o["log_dets"], d["log_dets"], "log_dets", 1e-5)
+    assert torch.equal(o["attn"], torch.from_numpy(d["attn"]).to(o["attn"].dtype))
+    losses = O.train_losses(o, t("mel_lengths"), cfg)
+    chk(losses[0], d["mle"], "mle"); chk(losses[1], d["length"], "length")
+    sum(losses).backward()
+    grads = {k[5:]: torch.from_numpy(d[k]) for k in d.files if k.startswith("grad/")}
+    assert len(grads) > 50
+    for k, g in grads.items():
+        og = sdg[k].grad
+        og = torch.zeros_like(g) if og is None else og
+        rel = ((og - g).abs().max() / (g.abs().max() + 1e-5)).item()     # (+1e-5: Key.bias gradients are analytically 0, as in make_golden.py)
+        assert rel < 2e-3, (k, rel)
+    # eval mode is a different network: the stored train-mode outputs are not the eval ones (the masks were really applied)
+    assert (torch.from_numpy(d["log_dur"]) - t("log_dur")).abs().max() > 1e-3
+
+
 def test_actnorm_init_and_invertibility():
     sd, _, r = load_case("tiny_vanilla.npz")
     cfg = tiny_cfg("Vanilla")
