@@ -684,12 +684,15 @@ extern "C" int glowtts_actnorm_inv1x1_bwd(const float* dz, float* dx, const floa
     const int rpb = an_bwd_rpb();
     const int nblk = (int)((rows + rpb - 1) / rpb);
     const NextCoupling none{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1};
-    if (an_bwd_wide(C, dz, dx, x, 0))
+    if (an_bwd_wide(C, dz, dx, x, 0)) {
+        GLOWTTS_NOTE_STATIC("actnorm_inv_bwd<%s>", "16B");
         hipLaunchKernelGGL(actnorm_inv_bwd4_kernel, dim3(nblk), dim3(256), 32 * 256 * sizeof(float), s, dz, dx, x, logs, bias, winfo, rowmask,
                            scratch, (long)rows, C, rpb, none);
-    else
+    } else {
+        GLOWTTS_NOTE_STATIC("actnorm_inv_bwd<%s>", "8B");
         hipLaunchKernelGGL(actnorm_inv_bwd_kernel, dim3(nblk), dim3(256), 24 * 256 * sizeof(float), s, dz, dx, x, logs, bias, winfo, rowmask,
                            scratch, (long)rows, C, rpb, none);
+    }
     const int n = 2 * C + 16;
     // param_grads == NULL: the caller reduces the per-block partials of all its flows later with glowtts_colsum_batched
     if (param_grads) hipLaunchKernelGGL(colstats_final_kernel, dim3((n + 3) / 4), dim3(256), 0, s, scratch, param_grads, nblk, n, 0L, 0L);
@@ -708,12 +711,15 @@ extern "C" int glowtts_actnorm_inv1x1_bwd_coupling(const float* dz, float* dx, c
     const NextCoupling nc{prev_xmid, prev_outs, prev_douts, static_cast<__bf16*>(prev_douts_bf16), dlogdet, ldo, rows_per_utt};
     const bool al = !((reinterpret_cast<uintptr_t>(prev_xmid) | reinterpret_cast<uintptr_t>(prev_outs) | reinterpret_cast<uintptr_t>(prev_douts)) & 15) &&
                     !(reinterpret_cast<uintptr_t>(prev_douts_bf16) & 7);
-    if (al && an_bwd_wide(C, dz, dx, x, ldo))
+    if (al && an_bwd_wide(C, dz, dx, x, ldo)) {
+        GLOWTTS_NOTE_STATIC("actnorm_inv_bwd<%s>", "16B,coupling");
         hipLaunchKernelGGL(actnorm_inv_bwd4_kernel, dim3(nblk), dim3(256), 32 * 256 * sizeof(float), static_cast<hipStream_t>(stream), dz, dx, x, logs, bias,
                            winfo, rowmask, scratch, (long)rows, C, rpb, nc);
-    else
+    } else {
+        GLOWTTS_NOTE_STATIC("actnorm_inv_bwd<%s>", "8B,coupling");
         hipLaunchKernelGGL(actnorm_inv_bwd_kernel, dim3(nblk), dim3(256), 24 * 256 * sizeof(float), static_cast<hipStream_t>(stream), dz, dx, x, logs, bias,
                            winfo, rowmask, scratch, (long)rows, C, rpb, nc);
+    }
     RET_LAUNCH();
 }
 

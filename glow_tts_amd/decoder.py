@@ -468,6 +468,12 @@ class DecoderConfig:
         self.C = mel_dim * n_squeeze
         self.precision = precision
         assert n_layers <= MAXL and self.C % 4 == 0 and hidden % 4 == 0
+        if self.C % 8:
+            # the coupling's Start conv, its data gradient and its weight gradient work on the C/2 pass-through channels in 4-channel (16-byte)
+            # granules: glowtts_conv_cl / glowtts_wgrad_cl return an argument error for ca = C/2 not a multiple of 4, and the grouped
+            # weight-gradient launch does not check at all.  (The elementwise kernels of csrc/flow_ops.hip take any C % 4 == 0.)
+            raise ValueError(f"Sound.Mel_Dim * Decoder.Num_Squeeze = {self.C} must be a multiple of 8: the coupling network's convs read the "
+                             f"C/2 = {self.C // 2} pass-through channels in 4-channel granules (Mel_Dim {mel_dim} is not supported by the HIP decoder)")
         # bf16 precision: the GEMM-only activations (WaveNet state, gates, gate gradients) live in HBM as bf16
         # (glowtts_flow_dims.act_bf16); TUNE["act_bf16"] = False keeps them fp32 (same MFMA inputs, twice the traffic)
         self.act_bf16 = precision == ops.BF16 and hidden % 8 == 0 and TUNE["act_bf16"]
