@@ -47,6 +47,13 @@ def _declare(L):
     L.glowtts_mas_f32.argtypes = [c_void_p] * 5 + [c_int] * 3 + [c_float, c_void_p]
     L.glowtts_pack_weight.argtypes = [c_void_p] + [c_int] * 7 + [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p]
     L.glowtts_conv_cl.argtypes = [c_void_p, c_void_p]
+    # Griffin-Lim vocoder (csrc/vocoder_ops.hip)
+    L.glowtts_vocoder_supported.argtypes = [c_int] * 3
+    L.glowtts_mel_to_linear_f32.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_float, c_void_p]
+    L.glowtts_stft_f32.argtypes = [c_void_p] * 5 + [c_int] * 6 + [c_void_p]
+    L.glowtts_istft_f32.argtypes = [c_void_p] * 6 + [c_int] * 6 + [c_void_p]
+    L.glowtts_overlap_add_f32.argtypes = [c_void_p] * 4 + [c_int] * 6 + [c_void_p]
+    L.glowtts_griffin_lim_step_f32.argtypes = [c_void_p] * 6 + [c_float, c_void_p] + [c_int] * 6 + [c_void_p]
 
 
 def check(rc, what):

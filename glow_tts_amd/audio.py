@@ -22,6 +22,20 @@ def preemphasis(audio, pre_emphasis=0.97):
     return signal.lfilter([1.0, -pre_emphasis], [1.0], audio)
 
 
+def deemphasis(audio, pre_emphasis=0.97):
+    """Inverse of `preemphasis`: the one-pole filter 1 / (1 - p z^-1).  Host side: the vocoder's samples are on the host by then, to be written."""
+    return signal.lfilter([1.0], [1.0, -pre_emphasis], audio)
+
+
+def write_wav(path, audio, sample_rate):
+    """16-bit PCM through scipy.io.wavfile.  Peak-normalised to 0.99 only if |x| exceeds 1 (a Griffin-Lim waveform of a loud mel may)."""
+    x = np.asarray(audio, dtype=np.float64)
+    peak = float(np.abs(x).max()) if x.size else 0.0
+    if peak > 1.0:
+        x = x * (0.99 / peak)
+    wavfile.write(path, int(sample_rate), np.clip(np.round(x * 32767.0), -32768, 32767).astype(np.int16))
+
+
 def _frames(y, frame_length, hop_length):
     n = 1 + (len(y) - frame_length) // hop_length
     idx = np.arange(frame_length)[None, :] + hop_length * np.arange(n)[:, None]

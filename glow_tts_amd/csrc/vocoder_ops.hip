@@ -1,0 +1,393 @@
+// Griffin-Lim vocoder (waveform output of Inference.py; the reference stops at the mel): mel -> linear magnitudes, the STFT / inverse STFT that
+// glow_tts_amd/audio.py's front end defines (center = True, reflect padding by n_fft / 2, periodic Hann of win_length centred in n_fft), and one FUSED
+// Griffin-Lim iteration per launch.
+//
+// Data flow of an iteration (vocoder_frame_kernel<MODE_STEP>, one 256-thread workgroup per frame at a time, workgroups stride over the frames of the batch):
+//   HBM -> LDS   y = x_n + alpha (x_n - x_{n-1}) gathered for the win_length samples the window covers (reflect at the ends), windowed, packed as
+//                z[m] = y[2m] + i y[2m+1] and written at the bit-reversed index
+//   LDS          complex FFT of n_fft / 2 points (decimation in time, radix 4 with one radix-2 stage when log2 is odd), in place
+//   LDS          per bin pair (k, n_fft/2 - k): the real-input split Y = E + W^k O, the projection Y / max(|Y|, 1e-8) times the target magnitude (the only other HBM
+//                read: n_fft/2 + 1 floats), and the inverse split back to a packed spectrum - all in registers, in place
+//   LDS          inverse complex FFT (decimation in frequency: natural order in, bit-reversed out), in place
+//   LDS -> HBM   the win_length samples under the window, windowed again: the frame's overlap-add contribution
+// The complex spectrum never leaves LDS.  vocoder_ola_kernel then GATHERS every output sample from its win_length / hop contributing frames in ascending frame
+// order and divides by the summed squared window (floored at 1e-8): no floating-point atomics, bit-identical from run to run.
+// Twiddles exp(-2 pi i k / n_fft), k < n_fft / 2, and the window come from tables the host computes in float64 and rounds to fp32; no device sincos.
+// LDS per workgroup at n_fft = 2048, win 1024: 8 KiB twiddles + 4 KiB window + 8.3 KiB spectrum = 20.3 KiB -> 7 workgroups per CU (160 KiB).
+// Bank conflicts: element i of the spectrum lives at i + (i >> 5) (8-byte units), which shifts every 32-element row by one slot.  Counted with the
+// ds_read_b64 rule (32-lane groups, 8-byte slot modulo 32) at n_fft = 2048: the bit-reversed accesses (lane stride n_fft / 64 elements) go from 32-way
+// (scatter) and 16-way (final gather) to conflict-free and the h = 1 pass from 4-way to conflict-free; the h = 4 pass stays 4-way and the h = 16 pass
+// 2-way (their four-element runs still overlap after the shift), h >= 64 is conflict-free either way, and the split's ascending read becomes 2-way.
+// The stores are counted by the same rule although ds_write maps modulo 32 dwords: their true cost is not argued here.  The pad removes the worst conflicts, not all of them.
+// Lengths: an utterance whose length exceeds what the signal buffer holds (wav_lengths[b] > ldx, or hop (frame_lengths[b] - 1) > ldx) is a caller error that
+// the host cannot see without a synchronisation; the kernels never read beyond ldx, so such an utterance comes out as zeros (STFT) or is left unwritten
+// (inverse STFT, step).  vocoder.GriffinLim derives lengths and buffers from the same shapes, so the product path cannot reach this.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/glowtts_hip.h"
+#include "launch_log.h"
+
+namespace {
+
+constexpr int VOC_NT = 256;
+enum { MODE_STFT = 0, MODE_ISTFT = 1, MODE_STEP = 2 };
+
+__device__ __forceinline__ int voc_pad(int i) { return i + (i >> 5); }
+__device__ __forceinline__ float2 voc_add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ float2 voc_sub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+__device__ __forceinline__ float2 voc_mul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+__device__ __forceinline__ float2 voc_mulc(float2 a, float2 b) { return make_float2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }      // a * conj(b)
+
+// index of sample s of a signal of L samples under reflect padding (numpy's "reflect": period 2 (L - 1))
+__device__ __forceinline__ int voc_reflect(int s, int L) {
+    if (s >= 0 && s < L) return s;
+    if (L == 1) return 0;
+    const int p = 2 * (L - 1);
+    s %= p;
+    if (s < 0) s += p;
+    return s < L ? s : p - s;
+}
+
+// In-place complex FFT of M = 2^logM points in LDS (elements at voc_pad(i)); tw[k] = exp(-2 pi i k / N), N = 2 M = 2^logN.
+// Forward: decimation in time, input in bit-reversed order, output in natural order.  Inverse (unnormalised): decimation in frequency, natural order in,
+// bit-reversed order out.  Ends with a barrier.
+template <bool INV>
+__device__ __forceinline__ void voc_fft(float2* X, const float2* tw, int logM, int logN, int tid)
+{
+    const int M = 1 << logM;
+    if (!INV) {
+        int lh = 0;
+        if (logM & 1) {
+            for (int j = tid; j < (M >> 1); j += VOC_NT) {
+                const int i0 = voc_pad(2 * j), i1 = voc_pad(2 * j + 1);
+                const float2 a = X[i0], b = X[i1];
+                X[i0] = voc_add(a, b);
+                X[i1] = voc_sub(a, b);
+            }
+            __syncthreads();
+            lh = 1;
+        }
+        for (; lh < logM; lh += 2) {
+            const int h = 1 << lh;
+            for (int j = tid; j < (M >> 2); j += VOC_NT) {
+                const int pos = j & (h - 1), base = ((j >> lh) << (lh + 2)) + pos;
+                const float2 w1 = tw[pos << (logN - 1 - lh)], w2 = tw[pos << (logN - 2 - lh)];
+                const int i0 = voc_pad(base), i1 = voc_pad(base + h), i2 = voc_pad(base + 2 * h), i3 = voc_pad(base + 3 * h);
+                const float2 a0 = X[i0], a1 = X[i1], a2 = X[i2], a3 = X[i3];
+                float2 t = voc_mul(a1, w1);
+                const float2 b0 = voc_add(a0, t), b1 = voc_sub(a0, t);
+                t = voc_mul(a3, w1);
+                const float2 b2 = voc_add(a2, t), b3 = voc_sub(a2, t);
+                t = voc_mul(b2, w2);
+                X[i0] = voc_add(b0, t);
+                X[i2] = voc_sub(b0, t);
+                t = voc_mul(b3, w2);
+                t = make_float2(t.y, -t.x);                    // W_{4h}^{pos + h} = -i W_{4h}^{pos}
+                X[i1] = voc_add(b1, t);
+                X[i3] = voc_sub(b1, t);
+            }
+            __syncthreads();
+        }
+    } else {
+        for (int lh = logM - 2; lh >= 0; lh -= 2) {
+            const int h = 1 << lh;
+            for (int j = tid; j < (M >> 2); j += VOC_NT) {
+                const int pos = j & (h - 1), base = ((j >> lh) << (lh + 2)) + pos;
+                const float2 w1 = tw[pos << (logN - 1 - lh)], w2 = tw[pos << (logN - 2 - lh)];
+                const int i0 = voc_pad(base), i1 = voc_pad(base + h), i2 = voc_pad(base + 2 * h), i3 = voc_pad(base + 3 * h);
+                const float2 a0 = X[i0], a1 = X[i1], a2 = X[i2], a3 = X[i3];
+                const float2 b0 = voc_add(a0, a2), b2 = voc_mulc(voc_sub(a0, a2), w2);
+                const float2 b1 = voc_add(a1, a3);
+                float2 t = voc_mulc(voc_sub(a1, a3), w2);
+                const float2 b3 = make_float2(-t.y, t.x);      // conj(W_{4h}^{pos + h}) = i conj(W_{4h}^{pos})
+                X[i0] = voc_add(b0, b1);
+                X[i1] = voc_mulc(voc_sub(b0, b1), w1);
+                X[i2] = voc_add(b2, b3);
+                X[i3] = voc_mulc(voc_sub(b2, b3), w1);
+            }
+            __syncthreads();
+        }
+        if (logM & 1) {
+            for (int j = tid; j < (M >> 1); j += VOC_NT) {
+                const int i0 = voc_pad(2 * j), i1 = voc_pad(2 * j + 1);
+                const float2 a = X[i0], b = X[i1];
+                X[i0] = voc_add(a, b);
+                X[i1] = voc_sub(a, b);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+struct voc_args {
+    const float* x;            // STFT / STEP: signal [B][ldx]
+    const float* xp;           // STEP: previous signal
+    const float* spec;         // ISTFT: complex spectrum [B][T][F][2]
+    const float* mag;          // STEP: target magnitudes [B][T][F]
+    const int32_t* lengths;    // STFT: samples per utterance; ISTFT / STEP: frames per utterance
+    const float* window;       // [win]
+    const float2* twiddle;     // [n_fft / 2]
+    float* spec_out;           // STFT: [B][T][F][2]
+    float* frames;             // ISTFT / STEP: [B][T][win]
+    float alpha;
+    int B, T, ldx, logN, win, hop;
+};
+
+// Y -> target magnitude times the phase of Y (|Y| floored at 1e-8)
+__device__ __forceinline__ float2 voc_project(float2 y, float s) {
+    const float a = fmaxf(sqrtf(y.x * y.x + y.y * y.y), 1e-8f);
+    return make_float2(s * (y.x / a), s * (y.y / a));
+}
+
+template <int MODE>
+__global__ __launch_bounds__(VOC_NT) void vocoder_frame_kernel(const voc_args a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char voc_smem[];
+    const int N = 1 << a.logN, M = N >> 1, logM = a.logN - 1, F = M + 1;
+    float2* const tw = reinterpret_cast<float2*>(voc_smem);                    // [M]
+    float2* const X = tw + M;                                                  // [voc_pad(M) + 1]
+    float* const wnd = reinterpret_cast<float*>(X + voc_pad(M) + 1);           // [win]
+    const int tid = threadIdx.x;
+    const int lpad = (N - a.win) >> 1;
+    for (int i = tid; i < M; i += VOC_NT) tw[i] = a.twiddle[i];
+    for (int i = tid; i < a.win; i += VOC_NT) wnd[i] = a.window[i];
+    __syncthreads();
+    const int total = a.B * a.T;
+    for (int f = blockIdx.x; f < total; f += gridDim.x) {
+        const int b = f / a.T, t = f - b * a.T;
+        int L, Tb;                                                             // samples and frames of this utterance
+        if (MODE == MODE_STFT) { L = a.lengths[b]; Tb = L > 0 ? 1 + L / a.hop : 0; }
+        else { Tb = a.lengths[b]; L = a.hop * (Tb - 1); }
+        if (Tb > a.T) Tb = a.T;
+        if (MODE == MODE_STFT && (t >= Tb || L > a.ldx)) {                     // a frame beyond the utterance: zeros
+            float2* out = reinterpret_cast<float2*>(a.spec_out) + (int64_t)f * F;
+            for (int k = tid; k < F; k += VOC_NT) out[k] = make_float2(0.f, 0.f);
+            continue;
+        }
+        if (MODE != MODE_STFT && (t >= Tb || L < 1 || L > a.ldx)) continue;   // (uniform over the workgroup)
+        if (MODE != MODE_ISTFT) {
+            // ---- gather + window + pack, bit-reversed ----
+            const float* xb = a.x + (int64_t)b * a.ldx;
+            const float* xpb = MODE == MODE_STEP ? a.xp + (int64_t)b * a.ldx : nullptr;
+            for (int m = tid; m < M; m += VOC_NT) {
+                float v[2];
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const int n = 2 * m + e, j = n - lpad;
+                    v[e] = 0.f;
+                    if (j >= 0 && j < a.win) {
+                        const int s = voc_reflect(t * a.hop + n - M, L);
+                        float y = xb[s];
+                        if (MODE == MODE_STEP) y = y + a.alpha * (y - xpb[s]);
+                        v[e] = y * wnd[j];
+                    }
+                }
+                X[voc_pad((int)(__brev((unsigned)m) >> (32 - logM)))] = make_float2(v[0], v[1]);
+            }
+            __syncthreads();
+            voc_fft<false>(X, tw, logM, a.logN, tid);
+        }
+        // ---- split (real-input spectrum from the packed one), projection, inverse split: bin pairs (k, M - k) ----
+        {
+            const float* sp = MODE == MODE_ISTFT ? a.spec + (int64_t)f * F * 2 : nullptr;
+            const float* mg = MODE == MODE_STEP ? a.mag + (int64_t)f * F : nullptr;
+            float2* out = MODE == MODE_STFT ? reinterpret_cast<float2*>(a.spec_out) + (int64_t)f * F : nullptr;
+            for (int k = tid; k <= (M >> 1); k += VOC_NT) {
+                if (k == 0) {
+                    float y0, ym;                                             // bins 0 and M are real
+                    if (MODE == MODE_ISTFT) { y0 = sp[0]; ym = sp[2 * M]; }
+                    else {
+                        const float2 z = X[0];
+                        y0 = z.x + z.y;
+                        ym = z.x - z.y;
+                    }
+                    if (MODE == MODE_STFT) { out[0] = make_float2(y0, 0.f); out[M] = make_float2(ym, 0.f); continue; }
+                    if (MODE == MODE_STEP) { y0 = voc_project(make_float2(y0, 0.f), mg[0]).x; ym = voc_project(make_float2(ym, 0.f), mg[M]).x; }
+                    X[0] = make_float2(0.5f * (y0 + ym), 0.5f * (y0 - ym));
+                    continue;
+                }
+                const int ik = voc_pad(k), imk = voc_pad(M - k);
+                const float2 w = tw[k];
+                float2 yk, ymk;
+                if (MODE == MODE_ISTFT) {
+                    yk = make_float2(sp[2 * k], sp[2 * k + 1]);
+                    ymk = make_float2(sp[2 * (M - k)], sp[2 * (M - k) + 1]);
+                } else {
+                    const float2 za = X[ik], zb = X[imk];
+                    const float2 e = make_float2(0.5f * (za.x + zb.x), 0.5f * (za.y - zb.y));          // (Z[k] + conj Z[M-k]) / 2
+                    const float2 d = make_float2(0.5f * (za.x - zb.x), 0.5f * (za.y + zb.y));          // (Z[k] - conj Z[M-k]) / 2
+                    const float2 wo = voc_mul(make_float2(d.y, -d.x), w);                              // W^k O,  O = d / i
+                    yk = voc_add(e, wo);
+                    ymk = voc_sub(e, wo);
+                    ymk.y = -ymk.y;                                                                    // Y[M-k] = conj(E - W^k O)
+                }
+                if (MODE == MODE_STFT) { out[k] = yk; out[M - k] = ymk; continue; }
+                if (MODE == MODE_STEP) { yk = voc_project(yk, mg[k]); ymk = voc_project(ymk, mg[M - k]); }
+                const float2 e = make_float2(0.5f * (yk.x + ymk.x), 0.5f * (yk.y - ymk.y));
+                const float2 o = voc_mulc(make_float2(0.5f * (yk.x - ymk.x), 0.5f * (yk.y + ymk.y)), w);
+                X[ik] = make_float2(e.x - o.y, e.y + o.x);                                             // Z[k] = E + i O
+                X[imk] = make_float2(e.x + o.y, o.x - e.y);                                            // Z[M-k] = conj(E - i O)
+            }
+            __syncthreads();
+        }
+        if (MODE != MODE_STFT) {
+            voc_fft<true>(X, tw, logM, a.logN, tid);
+            // ---- the samples under the window, windowed again: this frame's overlap-add contribution ----
+            float* fr = a.frames + (int64_t)f * a.win;
+            const float scale = 1.f / (float)M;
+            for (int j = tid; j < a.win; j += VOC_NT) {
+                const int n = lpad + j;
+                const float2 z = X[voc_pad((int)(__brev((unsigned)(n >> 1)) >> (32 - logM)))];
+                fr[j] = ((n & 1) ? z.y : z.x) * scale * wnd[j];
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// Overlap-add as a gather: sample s of utterance b sums frames t_lo .. t_hi (ascending) at window position j = s + n_fft / 2 - lpad - t hop, and is divided by the
+// summed squared window, floored at 1e-8.  Samples at or beyond hop (T_b - 1) are written as zeros.
+__global__ __launch_bounds__(256) void vocoder_ola_kernel(const float* __restrict__ frames, const int32_t* __restrict__ lengths, const float* __restrict__ window,
+                                                          float* __restrict__ wav, int T, int ldx, int n_fft, int win, int hop)
+{
+    const int b = blockIdx.y, s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= ldx) return;
+    int Tb = lengths[b];
+    if (Tb > T) Tb = T;
+    const int L = hop * (Tb - 1);
+    float r = 0.f;
+    if (s < L) {
+        const int p = s + (n_fft >> 1) - ((n_fft - win) >> 1);   // position relative to the window start of frame 0
+        int t_hi = p / hop, t_lo = p >= win ? (p - win) / hop + 1 : 0;
+        if (t_hi > Tb - 1) t_hi = Tb - 1;
+        float acc = 0.f, wss = 0.f;
+        const float* fb = frames + (int64_t)b * T * win;
+        for (int t = t_lo; t <= t_hi; ++t) {
+            const int j = p - t * hop;
+            const float w = window[j];
+            acc += fb[(int64_t)t * win + j];
+            wss += w * w;
+        }
+        r = acc / fmaxf(wss, 1e-8f);
+    }
+    wav[(int64_t)b * ldx + s] = r;
+}
+
+// mels [B][Mel][T] (normalised to +- max_abs) -> linear magnitudes [B][T][F]: a workgroup takes MTL_TF frames; the de-normalised mel amplitudes go to LDS
+// (float64 arithmetic for the exponential, rounded once), every thread then owns output bins f, f + 256, ...
+constexpr int MTL_TF = 8;
+__global__ __launch_bounds__(256) void vocoder_mel_to_linear_kernel(const float* __restrict__ mels, const int32_t* __restrict__ lengths, const float* __restrict__ basis,
+                                                                    float* __restrict__ mag, int Mel, int T, int F, float max_abs)
+{
+    extern __shared__ float mtl_amp[];                         // [MTL_TF][Mel]
+    const int b = blockIdx.y, t0 = blockIdx.x * MTL_TF;
+    int Tb = lengths[b];
+    if (Tb > T) Tb = T;
+    for (int i = threadIdx.x; i < MTL_TF * Mel; i += 256) {
+        const int k = i / MTL_TF, tt = i - k * MTL_TF, t = t0 + tt;
+        float v = 0.f;
+        if (t < Tb) {
+            const double m = fmin(fmax((double)mels[((int64_t)b * Mel + k) * T + t], -(double)max_abs), (double)max_abs);
+            const double db = (m + (double)max_abs) / (2.0 * (double)max_abs) * 100.0 - 100.0;
+            v = (float)fmax(exp10(db / 20.0) - 1e-7, 0.0);
+        }
+        mtl_amp[tt * Mel + k] = v;
+    }
+    __syncthreads();
+    for (int f = threadIdx.x; f < F; f += 256) {
+        float acc[MTL_TF];
+#pragma unroll
+        for (int tt = 0; tt < MTL_TF; ++tt) acc[tt] = 0.f;
+        const float* row = basis + (int64_t)f * Mel;
+        for (int k = 0; k < Mel; ++k) {
+            const float p = row[k];
+#pragma unroll
+            for (int tt = 0; tt < MTL_TF; ++tt) acc[tt] = fmaf(p, mtl_amp[tt * Mel + k], acc[tt]);
+        }
+#pragma unroll
+        for (int tt = 0; tt < MTL_TF; ++tt) {
+            const int t = t0 + tt;
+            if (t < T) mag[((int64_t)b * T + t) * F + f] = t < Tb ? fmaxf(acc[tt], 1e-10f) : 0.f;
+        }
+    }
+}
+
+int voc_log2(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
+size_t voc_lds_bytes(int n_fft, int win) { const int M = n_fft / 2; return (size_t)(M + M + (M >> 5) + 1) * 8 + (size_t)win * 4; }
+int voc_grid(int frames) { return frames < 1792 ? frames : 1792; }             // 7 resident workgroups (by LDS at n_fft = 2048) on each of 256 CUs: one wave; more frames: strided
+
+template <int MODE>
+int voc_launch(const voc_args& a, int n_fft, void* stream)
+{
+    hipLaunchKernelGGL(vocoder_frame_kernel<MODE>, dim3(voc_grid(a.B * a.T)), dim3(VOC_NT), voc_lds_bytes(n_fft, a.win), static_cast<hipStream_t>(stream), a);
+    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+}
+int voc_ola(const float* frames, const int32_t* lengths, const float* window, float* wav, int B, int T, int ldx, int n_fft, int win, int hop, void* stream)
+{
+    hipLaunchKernelGGL(vocoder_ola_kernel, dim3((ldx + 255) / 256, B), dim3(256), 0, static_cast<hipStream_t>(stream), frames, lengths, window, wav, T, ldx, n_fft, win, hop);
+    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+}
+bool voc_bad_dims(int B, int T, int ldx, int n_fft, int win, int hop)
+{
+    return B < 1 || B > 65535 || T < 1 || ldx < 1 || !glowtts_vocoder_supported(n_fft, win, hop) || (int64_t)B * T > (int64_t)1 << 30;
+}
+
+}  // namespace
+
+extern "C" int glowtts_vocoder_supported(int n_fft, int win_length, int hop)
+{
+    return n_fft >= 256 && n_fft <= 4096 && (n_fft & (n_fft - 1)) == 0 && win_length >= 1 && win_length <= n_fft && hop >= 1 && win_length % hop == 0;
+}
+
+extern "C" int glowtts_mel_to_linear_f32(const float* mels, const int32_t* frame_lengths, const float* basis, float* mag, int B, int Mel, int T, int F, float max_abs,
+                                         void* stream)
+{
+    if (!mels || !frame_lengths || !basis || !mag || B < 1 || B > 65535 || Mel < 1 || Mel > 1024 || T < 1 || F < 1 || !(max_abs > 0.f)) return GLOWTTS_E_ARG;
+    GLOWTTS_NOTE_STATIC("vocoder_mel_to_linear");
+    hipLaunchKernelGGL(vocoder_mel_to_linear_kernel, dim3((T + MTL_TF - 1) / MTL_TF, B), dim3(256), (size_t)MTL_TF * Mel * 4, static_cast<hipStream_t>(stream), mels,
+                       frame_lengths, basis, mag, Mel, T, F, max_abs);
+    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+}
+
+extern "C" int glowtts_stft_f32(const float* wav, const int32_t* wav_lengths, const float* window, const float* twiddle, float* spec, int B, int ldx, int T, int n_fft,
+                                int win_length, int hop, void* stream)
+{
+    if (!wav || !wav_lengths || !window || !twiddle || !spec || voc_bad_dims(B, T, ldx, n_fft, win_length, hop)) return GLOWTTS_E_ARG;
+    voc_args a = {};
+    a.x = wav; a.lengths = wav_lengths; a.window = window; a.twiddle = reinterpret_cast<const float2*>(twiddle); a.spec_out = spec;
+    a.B = B; a.T = T; a.ldx = ldx; a.logN = voc_log2(n_fft); a.win = win_length; a.hop = hop;
+    GLOWTTS_NOTE_STATIC("vocoder_stft");
+    return voc_launch<MODE_STFT>(a, n_fft, stream);
+}
+
+extern "C" int glowtts_istft_f32(const float* spec, const int32_t* frame_lengths, const float* window, const float* twiddle, float* frames, float* wav, int B, int T,
+                                 int ldx, int n_fft, int win_length, int hop, void* stream)
+{
+    if (!spec || !frame_lengths || !window || !twiddle || !frames || !wav || voc_bad_dims(B, T, ldx, n_fft, win_length, hop) || ldx < hop * (T - 1)) return GLOWTTS_E_ARG;
+    voc_args a = {};
+    a.spec = spec; a.lengths = frame_lengths; a.window = window; a.twiddle = reinterpret_cast<const float2*>(twiddle); a.frames = frames;
+    a.B = B; a.T = T; a.ldx = ldx; a.logN = voc_log2(n_fft); a.win = win_length; a.hop = hop;
+    GLOWTTS_NOTE_STATIC("vocoder_istft");
+    const int rc = voc_launch<MODE_ISTFT>(a, n_fft, stream);
+    return rc != GLOWTTS_OK ? rc : voc_ola(frames, frame_lengths, window, wav, B, T, ldx, n_fft, win_length, hop, stream);
+}
+
+extern "C" int glowtts_griffin_lim_step_f32(const float* x, const float* x_prev, const float* mag, const int32_t* frame_lengths, const float* window,
+                                            const float* twiddle, float alpha, float* frames, int B, int T, int ldx, int n_fft, int win_length, int hop, void* stream)
+{
+    if (!x || !x_prev || !mag || !frame_lengths || !window || !twiddle || !frames || voc_bad_dims(B, T, ldx, n_fft, win_length, hop) || ldx < hop * (T - 1))
+        return GLOWTTS_E_ARG;
+    voc_args a = {};
+    a.x = x; a.xp = x_prev; a.mag = mag; a.lengths = frame_lengths; a.window = window; a.twiddle = reinterpret_cast<const float2*>(twiddle); a.frames = frames;
+    a.alpha = alpha; a.B = B; a.T = T; a.ldx = ldx; a.logN = voc_log2(n_fft); a.win = win_length; a.hop = hop;
+    GLOWTTS_NOTE_STATIC("vocoder_griffin_lim_step");
+    return voc_launch<MODE_STEP>(a, n_fft, stream);
+}
+
+extern "C" int glowtts_overlap_add_f32(const float* frames, const int32_t* frame_lengths, const float* window, float* wav, int B, int T, int ldx, int n_fft,
+                                       int win_length, int hop, void* stream)
+{
+    if (!frames || !frame_lengths || !window || !wav || voc_bad_dims(B, T, ldx, n_fft, win_length, hop)) return GLOWTTS_E_ARG;
+    GLOWTTS_NOTE_STATIC("vocoder_overlap_add");
+    return voc_ola(frames, frame_lengths, window, wav, B, T, ldx, n_fft, win_length, hop, stream);
+}

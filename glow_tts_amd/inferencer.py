@@ -1,7 +1,8 @@
 """The reference's inference entry point (`Inference.py:111-313`: `Inferencer(checkpoint_path).Inference(labels, texts, scales, speakers,
 references, inference_path)`), thin: text -> tokens (`Token.yaml`), optional reference mels for the prosody encoder / pitch tracks, `S_*.pt`
 checkpoint (ActNorm marked initialised, `Inference.py:258-270`), `GlowTTS.inference` (replayed as hipGraphs through `graph_infer.GraphedInference`
-where the mode allows it), one `.npy` mel per utterance (`Inference.py:213-220`; the PNG plots are out of scope).  `references` are either
+where the mode allows it), one `.npy` mel per utterance (`Inference.py:213-220`; the PNG plots are out of scope) and, with `wav=True`, one
+`WAV/<label>.wav` next to it from the Griffin-Lim vocoder (`vocoder.GriffinLim`: a baseline vocoder, not a neural one).  `references` are either
 `.npy` files / arrays holding mels [T, Mel] (what `Pattern_Generator.Pattern_Generate` produces) or wav files, which go through
 `glow_tts_amd.audio` (librosa-free restatement of `Audio.py`; resampling is not implemented: the wav must be at hp.Sound.Sample_Rate)."""
 import logging
@@ -20,6 +21,8 @@ class Inferencer:
         self.hp = hp if hp is not None else get_hp()
         self.device = torch.device(device)
         self.token_Dict = data.load_token_dict(self.hp.Token_Path)
+        self.last_wav_files = []                                                 # the wav files the last Inference / Voice_Conversion / Vocode call wrote
+        self._vocoder = None
         self.Model_Generate()
         self.Load_Checkpoint(checkpoint_path)
 
@@ -41,6 +44,20 @@ class Inferencer:
         self.model_Dict["GlowTTS"].to(self.device)
         logging.info("Checkpoint loaded at {} steps.".format(state_Dict.get("Steps")))
 
+    def _write_wavs(self, mels, mel_lengths, names, inference_path):
+        """Griffin-Lim on the mels as the model produced them ([B, Mel, T], on the device) -> WAV/<name>.wav: de-emphasised, 16-bit, Sound.Sample_Rate."""
+        from . import audio
+        from .vocoder import GriffinLim
+        if self._vocoder is None:
+            self._vocoder = GriffinLim(self.hp, self.device)
+        mels = mels[:, :, :int(mel_lengths.max())]                                # a served batch may be padded beyond its longest utterance
+        wavs = self._vocoder.to_host(*self._vocoder(mels, mel_lengths))
+        os.makedirs(os.path.join(inference_path, "WAV").replace("\\", "/"), exist_ok=True)
+        for name, x in zip(names, wavs):
+            path = os.path.join(inference_path, "WAV", name + ".wav").replace("\\", "/")
+            audio.write_wav(path, x, self.hp.Sound.Sample_Rate)
+            self.last_wav_files.append(path)
+
     def _reference(self, ref):
         """-> (mel [T, Mel] float32, pitch [T] float32 or None)"""
         if isinstance(ref, (tuple, list)):
@@ -54,7 +71,7 @@ class Inferencer:
 
     @torch.no_grad()
     def Inference_Step(self, tokens, token_lengths, prosodies, prosody_lengths, speakers, ge2es, pitches, pitch_lengths, length_scales, labels, texts,
-                       start_index=0, tag_index=False, inference_path="./inference", noise_scale=1.0):
+                       start_index=0, tag_index=False, inference_path="./inference", noise_scale=1.0, wav=False):
         """Inference.py:139-223 without the plots: returns the list of written .npy files."""
         dev = self.device
         mv = lambda t: t if t is None else t.to(dev)
@@ -69,17 +86,20 @@ class Inferencer:
                 self._graphed = GraphedInference(model)
             mels, mel_Lengths, attentions = self._graphed(mv(tokens), mv(token_lengths), noise_scale=noise_scale, length_scale=mv(length_scales), **kw)
         os.makedirs(os.path.join(inference_path, "NPY").replace("\\", "/"), exist_ok=True)
+        names = [".".join([str(label)] + (["IDX_{}".format(index + start_index)] if tag_index else [])) for index, label in enumerate(labels)]
+        if wav:                                                                  # on the device, before the copy to the host
+            self._write_wavs(mels, mel_Lengths, names, inference_path)
         files = []
-        for index, (label, mel, n) in enumerate(zip(labels, mels.cpu().numpy(), mel_Lengths.cpu().tolist())):
-            tags = [str(label)] + (["IDX_{}".format(index + start_index)] if tag_index else [])
-            path = os.path.join(inference_path, "NPY", ".".join(tags) + ".npy").replace("\\", "/")
+        for name, mel, n in zip(names, mels.cpu().numpy(), mel_Lengths.cpu().tolist()):
+            path = os.path.join(inference_path, "NPY", name + ".npy").replace("\\", "/")
             np.save(path, mel[:, :n].T, allow_pickle=False)                      # [T, Mel], Inference.py:216-220
             files.append(path)
         return files
 
-    def Inference(self, labels, texts, scales, speakers=None, references=None, inference_path="./inference", noise_scale=1.0):
-        """Inference.py:225-256."""
+    def Inference(self, labels, texts, scales, speakers=None, references=None, inference_path="./inference", noise_scale=1.0, wav=False):
+        """Inference.py:225-256.  wav: also WAV/<label>.wav per utterance (paths in `last_wav_files`; the returned list stays the .npy files)."""
         logging.info("Start inference.")
+        self.last_wav_files = []
         hp = self.hp
         bs = hp.Inference_Batch_Size or hp.Train.Batch_Size
         speakers = speakers or [None] * len(texts)
@@ -107,8 +127,21 @@ class Inferencer:
                         pit[b, :p.shape[0]] = torch.from_numpy(p)
             spk = None if any(x is None for x in speakers[sl]) else torch.tensor(speakers[sl], dtype=torch.int64)
             files += self.Inference_Step(tokens, tl, pros, pl, spk, None, pit, pitl, torch.tensor(scales[sl], dtype=torch.float32), labels[sl], texts[sl],
-                                         start_index=s, inference_path=inference_path, noise_scale=noise_scale)
+                                         start_index=s, inference_path=inference_path, noise_scale=noise_scale, wav=wav)
         return files
+
+    def Vocode(self, labels, mels, inference_path="./inference"):
+        """Recorded or previously generated mels - .npy paths or arrays [T, Mel] - through the Griffin-Lim vocoder, in batches of Inference_Batch_Size:
+        one WAV/<label>.wav per mel; returns the written files (also in `last_wav_files`)."""
+        logging.info("Start vocoding.")
+        hp = self.hp
+        bs = hp.Inference_Batch_Size or hp.Train.Batch_Size
+        self.last_wav_files = []
+        for s in range(0, len(mels), bs):
+            sl = slice(s, s + bs)
+            batch, lengths, _ = self._pad_mels([(np.load(m).astype(np.float32) if isinstance(m, str) else np.asarray(m, np.float32), None) for m in mels[sl]])
+            self._write_wavs(batch.to(self.device), lengths.to(self.device), [str(x) for x in labels[sl]], inference_path)
+        return list(self.last_wav_files)
 
 
     def _pad_mels(self, mp):
@@ -126,13 +159,16 @@ class Inferencer:
                 pitches[b, :n] = torch.from_numpy(p[:n])
         return mels, lengths, pitches
 
-    def Voice_Conversion(self, labels, sources, source_speakers=None, target_speakers=None, target_references=None, inference_path="./inference"):
+    def Voice_Conversion(self, labels, sources, source_speakers=None, target_speakers=None, target_references=None, inference_path="./inference",
+                         wav=False):
         """Voice conversion through the invertible decoder (GlowTTS.voice_conversion): `sources` - recorded mels as .npy files / arrays [T, Mel]
         or wav files (GR: a wav also gives the YIN pitch track the flows read; (mel, pitch) pairs are taken as they are) - go through the flows
         forward under their own conditioning and back under the target's.  SE-LUT: speaker indices; SE-GE2E: d-vectors [E]; PE / GR:
         `target_references` (same formats as `sources`) give the target prosody vector (GR: plus the target speaker).  A None target takes
-        the source's value.  Batches of Inference_Batch_Size; one NPY/<label>.npy [T, Mel] per utterance; returns the written files."""
+        the source's value.  Batches of Inference_Batch_Size; one NPY/<label>.npy [T, Mel] per utterance (wav: and WAV/<label>.wav, paths in
+        `last_wav_files`); returns the written .npy files."""
         logging.info("Start voice conversion.")
+        self.last_wav_files = []
         hp = self.hp
         model = self.model_Dict["GlowTTS"]
         mode = hp.Mode.upper()
@@ -167,6 +203,8 @@ class Inferencer:
                 tm, tl, _ = self._pad_mels([self._reference(r) for r in refs])
                 kw.update(target_mels_for_prosody=tm.to(dev), target_mel_lengths_for_prosody=tl.to(dev))
             out, out_lengths = model.voice_conversion(mels.to(dev), lengths.to(dev), pitches=None if pitches is None else pitches.to(dev), **kw)
+            if wav:
+                self._write_wavs(out, out_lengths, [str(x) for x in labels[sl]], inference_path)
             for label, mel, m in zip(labels[sl], out.cpu().numpy(), out_lengths.cpu().tolist()):
                 path = os.path.join(inference_path, "NPY", "{}.npy".format(label)).replace("\\", "/")
                 np.save(path, mel[:, :m].T, allow_pickle=False)                   # [T, Mel], like Inference_Step
@@ -193,6 +231,20 @@ def read_convert_list(path):
     return out
 
 
+def read_vocode_list(path):
+    """The --vocode list: one `label<TAB>mel.npy` per line; blank lines are skipped.  -> [(label, mel path)]"""
+    out = []
+    with open(path, "r", encoding="utf-8") as f:
+        for i, line in enumerate(f.read().splitlines()):
+            if not line.strip():
+                continue
+            cols = [x.strip() for x in line.split("\t")]
+            if len(cols) != 2 or not cols[0] or not cols[1]:
+                raise ValueError("{}:{}: expected label<TAB>mel.npy".format(path, i + 1))
+            out.append((cols[0], cols[1]))
+    return out
+
+
 def main(argv=None):
     import argparse
     logging.basicConfig(level=logging.INFO)
@@ -202,12 +254,19 @@ def main(argv=None):
     ap.add_argument("-o", "--out", default="./inference")
     ap.add_argument("--convert", default=None, metavar="LIST.tsv",
                     help="voice conversion instead of text-to-mel: label, source mel (.npy [T, Mel] or wav), source speaker, target speaker[, target reference]")
+    ap.add_argument("--wav", action="store_true", help="also write WAV/<label>.wav per utterance (Griffin-Lim: a baseline vocoder, not a neural one)")
+    ap.add_argument("--vocode", default=None, metavar="LIST", help="vocode existing mels instead of synthesising: one label<TAB>mel.npy ([T, Mel]) per line")
     args = ap.parse_args(argv)
     inf = Inferencer(checkpoint_path=args.checkpoint)
+    if args.vocode:
+        recs = read_vocode_list(args.vocode)
+        print("\n".join(inf.Vocode([r[0] for r in recs], [r[1] for r in recs], args.out)))
+        return
     if args.convert:
         recs = read_convert_list(args.convert)
         print("\n".join(inf.Voice_Conversion([r["label"] for r in recs], [r["source"] for r in recs], [r["source_speaker"] for r in recs],
-                                              [r["target_speaker"] for r in recs], [r["target_reference"] for r in recs], args.out)))
+                                              [r["target_speaker"] for r in recs], [r["target_reference"] for r in recs], args.out, wav=args.wav)
+                        + inf.last_wav_files))
         return
     if args.prompts:
         recs = [r for r in data.read_inference_prompts(args.prompts) if r["text"] is not None]
@@ -216,4 +275,4 @@ def main(argv=None):
         labels, texts, scales, speakers = ["Alpha", "Bravo"], ["Birds of a feather flock together.",
                                                                "A creative artist works on his next composition because he was not satisfied with his previous one."], [1.0, 0.9], [0, 1]
     mode = inf.hp.Mode.upper()
-    print("\n".join(inf.Inference(labels, texts, scales, speakers if mode in ("SE", "GR") else None, None, args.out)))
+    print("\n".join(inf.Inference(labels, texts, scales, speakers if mode in ("SE", "GR") else None, None, args.out, wav=args.wav) + inf.last_wav_files))

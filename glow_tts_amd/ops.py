@@ -156,3 +156,36 @@ def conv_cl(a, pw, ca, rows, *, lda=None, a2=None, lda2=0, ca1=0, apro=APRO_NONE
     args.io_flags = io_flags
     assert not (io_flags and (a_off or out0_off))
     _lib.check(_lib.lib().glowtts_conv_cl(ctypes.byref(args), _lib.stream()), "glowtts_conv_cl")
+
+
+# ---- Griffin-Lim vocoder (csrc/vocoder_ops.hip).  geo = (n_fft, win_length, hop); lengths: int32 device tensors [B] ----
+def mel_to_linear(mels, frame_lengths, basis, mag, max_abs):
+    """mels [B, Mel, T] -> mag [B, T, F] (glowtts_mel_to_linear_f32)."""
+    B, Mel, T = mels.shape
+    _lib.check(_lib.lib().glowtts_mel_to_linear_f32(_lib.ptr(mels), _lib.ptr(frame_lengths), _lib.ptr(basis), _lib.ptr(mag), B, Mel, T, mag.shape[2],
+                                                    float(max_abs), _lib.stream()), "glowtts_mel_to_linear_f32")
+
+
+def stft(wav, wav_lengths, window, twiddle, spec, geo):
+    """wav [B, L] -> spec [B, T, F, 2] (glowtts_stft_f32)."""
+    _lib.check(_lib.lib().glowtts_stft_f32(_lib.ptr(wav), _lib.ptr(wav_lengths), _lib.ptr(window), _lib.ptr(twiddle), _lib.ptr(spec), wav.shape[0],
+                                           wav.shape[1], spec.shape[1], *geo, _lib.stream()), "glowtts_stft_f32")
+
+
+def istft(spec, frame_lengths, window, twiddle, frames, wav, geo):
+    """spec [B, T, F, 2] -> wav [B, L >= hop (T - 1)] through frames [B, T, win] (glowtts_istft_f32)."""
+    _lib.check(_lib.lib().glowtts_istft_f32(_lib.ptr(spec), _lib.ptr(frame_lengths), _lib.ptr(window), _lib.ptr(twiddle), _lib.ptr(frames), _lib.ptr(wav),
+                                            spec.shape[0], spec.shape[1], wav.shape[1], *geo, _lib.stream()), "glowtts_istft_f32")
+
+
+def overlap_add(frames, frame_lengths, window, wav, geo):
+    """frames [B, T, win] -> wav [B, L] (glowtts_overlap_add_f32)."""
+    _lib.check(_lib.lib().glowtts_overlap_add_f32(_lib.ptr(frames), _lib.ptr(frame_lengths), _lib.ptr(window), _lib.ptr(wav), frames.shape[0], frames.shape[1],
+                                                  wav.shape[1], *geo, _lib.stream()), "glowtts_overlap_add_f32")
+
+
+def griffin_lim_step(x, x_prev, mag, frame_lengths, window, twiddle, alpha, frames, geo):
+    """One fused Griffin-Lim iteration: (x, x_prev) [B, L], mag [B, T, F] -> frames [B, T, win] (glowtts_griffin_lim_step_f32)."""
+    _lib.check(_lib.lib().glowtts_griffin_lim_step_f32(_lib.ptr(x), _lib.ptr(x_prev), _lib.ptr(mag), _lib.ptr(frame_lengths), _lib.ptr(window), _lib.ptr(twiddle),
+                                                       float(alpha), _lib.ptr(frames), mag.shape[0], mag.shape[1], x.shape[1], *geo, _lib.stream()),
+               "glowtts_griffin_lim_step_f32")

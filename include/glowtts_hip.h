@@ -803,6 +803,39 @@ int glowtts_sum_slices_seg(const float *partial, int S, int64_t stride, const gl
 int glowtts_multi_grad_scale(const glowtts_opt_job *dev_jobs, int njobs, int total_blocks, const float *coef, void *stream);
 int glowtts_radam_step(const glowtts_opt_job *dev_jobs, int njobs, int total_blocks, const float *hyper, const float *grad_scale, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Griffin-Lim vocoder (waveform output; no reference counterpart: the reference's Inference.py stops at the mel).  New symbols only, the ABI version stays 7.
+ * It inverts the front end of Audio.py:14-47 as glow_tts_amd/audio.py restates it: STFT with center = True, reflect padding by n_fft / 2, a periodic Hann
+ * window of win_length centred in n_fft, hop `hop`.  Supported geometry (glowtts_vocoder_supported, else GLOWTTS_E_ARG): n_fft a power of two in
+ * [256, 4096], win_length <= n_fft, win_length % hop == 0.  F = n_fft / 2 + 1 everywhere.
+ *   window  [win_length] f32, twiddle [n_fft / 2][2] f32 = (cos, -sin)(2 pi k / n_fft): tables the host computes in float64 and rounds.
+ *   A T-frame spectrogram corresponds to hop * (T - 1) samples; signals are [B][ldx] with ldx >= hop * (T - 1).
+ *   Lengths are device data and cannot be checked on the host without a synchronisation: they are the caller's to get right.  Lengths beyond T frames
+ *   are clamped to T.  An utterance longer than its signal row (wav_lengths[b] > ldx, or hop * (frame_lengths[b] - 1) > ldx) is never read or written
+ *   beyond ldx; it is a caller error, and the result for that utterance is then all zeros (glowtts_stft_f32) or frames left unwritten (the others).
+ *
+ * glowtts_mel_to_linear_f32: mels [B][Mel][T] normalised to +- max_abs (Audio.py:44-47) -> mag [B][T][F] = max(basis . amp, 1e-10) with
+ *   amp = max(10^(((clip(mel, +-max_abs) + max_abs) / (2 max_abs) * 100 - 100) / 20) - 1e-7, 0), basis [F][Mel]; frames t >= frame_lengths[b] are zeros.
+ * glowtts_stft_f32: wav [B][ldx], wav_lengths [B] i32 (samples; utterance b has 1 + len / hop frames) -> spec [B][T][F][2] (re, im); frames beyond: zeros.
+ * glowtts_istft_f32: spec [B][T][F][2], frame_lengths [B] i32 -> wav [B][ldx]: per frame the inverse real FFT, windowed again (into `frames`
+ *   [B][T][win_length], scratch), then glowtts_overlap_add_f32.  The imaginary parts of bins 0 and n_fft / 2 are ignored.
+ * glowtts_overlap_add_f32: every sample GATHERS its win_length / hop contributing frames in ascending frame order and is divided by the summed squared
+ *   window floored at 1e-8 (no atomics: bit-identical from run to run); samples at or beyond hop * (frame_lengths[b] - 1) are written as zeros.
+ * glowtts_griffin_lim_step_f32: one fused iteration.  Per frame: y = x + alpha (x - x_prev) gathered and windowed, forward FFT, P = Y / max(|Y|, 1e-8),
+ *   times mag [B][T][F], inverse FFT, windowed -> frames [B][T][win_length]; the spectrum stays in LDS.  glowtts_overlap_add_f32 turns `frames`
+ *   into the next signal.  Frames at or beyond frame_lengths[b] are left untouched. */
+int glowtts_vocoder_supported(int n_fft, int win_length, int hop);
+int glowtts_mel_to_linear_f32(const float *mels, const int32_t *frame_lengths, const float *basis, float *mag, int B, int Mel, int T, int F, float max_abs,
+                              void *stream);
+int glowtts_stft_f32(const float *wav, const int32_t *wav_lengths, const float *window, const float *twiddle, float *spec, int B, int ldx, int T, int n_fft,
+                     int win_length, int hop, void *stream);
+int glowtts_istft_f32(const float *spec, const int32_t *frame_lengths, const float *window, const float *twiddle, float *frames, float *wav, int B, int T,
+                      int ldx, int n_fft, int win_length, int hop, void *stream);
+int glowtts_overlap_add_f32(const float *frames, const int32_t *frame_lengths, const float *window, float *wav, int B, int T, int ldx, int n_fft,
+                            int win_length, int hop, void *stream);
+int glowtts_griffin_lim_step_f32(const float *x, const float *x_prev, const float *mag, const int32_t *frame_lengths, const float *window,
+                                 const float *twiddle, float alpha, float *frames, int B, int T, int ldx, int n_fft, int win_length, int hop, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
