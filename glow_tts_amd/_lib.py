@@ -54,6 +54,9 @@ def _declare(L):
     L.glowtts_istft_f32.argtypes = [c_void_p] * 6 + [c_int] * 6 + [c_void_p]
     L.glowtts_overlap_add_f32.argtypes = [c_void_p] * 4 + [c_int] * 6 + [c_void_p]
     L.glowtts_griffin_lim_step_f32.argtypes = [c_void_p] * 6 + [c_float, c_void_p] + [c_int] * 6 + [c_void_p]
+    # analysis front end (csrc/frontend_ops.hip)
+    L.glowtts_mel_analysis_f32.argtypes = [c_void_p] * 7 + [c_int] * 8 + [c_float] * 3 + [c_void_p]
+    L.glowtts_yin_f32.argtypes = [c_void_p] * 4 + [c_int] * 7 + [c_float] * 2 + [c_void_p]
 
 
 def check(rc, what):

@@ -169,10 +169,14 @@ def pitch_generate(audio, hp):
     return ((pitch - pitch.min()) / (pitch.max() - pitch.min() + 1e-7)).astype(np.float32)
 
 
-def pattern_from_wav(path, hp, top_db=30, with_pitch=False):
-    """`Pattern_Generate` (Pattern_Generator.py:54-70): -> (mel [T, Mel], pitch [T] or None).  top_db = 30 as Inference.py:57 passes."""
+def pattern_from_audio(audio, hp, with_pitch=False):
+    """The analysis of `Pattern_Generate` on prepared audio (what `audio_prep` returns): -> (mel [T, Mel], pitch [T] or None)."""
     s = hp.Sound
-    audio = audio_prep(path, s.Sample_Rate, top_db)
     mel = mel_generate(audio, s.Sample_Rate, s.Mel_Dim, s.Spectrogram_Dim, s.Frame_Length, s.Frame_Shift, mel_fmin=s.Mel_F_Min, mel_fmax=s.Mel_F_Max,
                        max_abs_value=s.Max_Abs_Mel)
     return mel, (pitch_generate(audio, hp) if with_pitch else None)
+
+
+def pattern_from_wav(path, hp, top_db=30, with_pitch=False):
+    """`Pattern_Generate` (Pattern_Generator.py:54-70): -> (mel [T, Mel], pitch [T] or None).  top_db = 30 as Inference.py:57 passes."""
+    return pattern_from_audio(audio_prep(path, hp.Sound.Sample_Rate, top_db), hp, with_pitch)

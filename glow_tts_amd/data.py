@@ -13,7 +13,7 @@ On-disk formats of the reference, read here so that pattern directories written 
   * `METADATA.PICKLE` (`Pattern_Generator.py:344-396`): 'File_List', '*_Length_Dict', 'File_List_by_Speaker_Dict', ... -> `PatternDataset`,
     `write_metadata` (the same keys, for pattern directories produced elsewhere);
   * the inference prompt TSV (`Datasets.py:137-144`) -> `read_inference_prompts`.
-The audio front-end (wav -> mel / pitch, `Audio.py`, `yin.py`) stays out of scope: it needs librosa, which this image does not have."""
+The same formats are written by `pattern_generator.py` (wav -> mel / pitch through `audio.py` on the host or `frontend.py` on the device)."""
 import bisect
 import math
 import os

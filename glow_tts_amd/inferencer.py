@@ -17,9 +17,12 @@ from .modules import GlowTTS
 
 
 class Inferencer:
-    def __init__(self, checkpoint_path, hp=None, device="cuda:0"):
+    def __init__(self, checkpoint_path, hp=None, device="cuda:0", device_frontend=False):
+        """device_frontend: wav references and wav voice-conversion sources are analysed on the device (`frontend.Analyzer`) instead of the host's
+        `audio.pattern_from_wav`; decoding, trimming and normalisation stay `audio.audio_prep` either way."""
         self.hp = hp if hp is not None else get_hp()
         self.device = torch.device(device)
+        self.device_frontend, self._analyzer = bool(device_frontend), None
         self.token_Dict = data.load_token_dict(self.hp.Token_Path)
         self.last_wav_files = []                                                 # the wav files the last Inference / Voice_Conversion / Vocode call wrote
         self._vocoder = None
@@ -67,7 +70,13 @@ class Inferencer:
         if str(ref).lower().endswith(".npy"):
             return np.load(ref).astype(np.float32), None
         from . import audio
-        return audio.pattern_from_wav(ref, self.hp, with_pitch=self.hp.Mode.upper() == "GR")       # GR: the YIN pitch track (Inference.py:56-58, Pattern_Generator.py:41-52)
+        gr = self.hp.Mode.upper() == "GR"                                        # GR: the YIN pitch track (Inference.py:56-58, Pattern_Generator.py:41-52)
+        if self.device_frontend:
+            if self._analyzer is None:
+                from .frontend import Analyzer
+                self._analyzer = Analyzer(self.hp, self.device, with_pitch=gr)
+            return self._analyzer([audio.audio_prep(ref, self.hp.Sound.Sample_Rate, 30)], with_pitch=gr)[0]
+        return audio.pattern_from_wav(ref, self.hp, with_pitch=gr)
 
     @torch.no_grad()
     def Inference_Step(self, tokens, token_lengths, prosodies, prosody_lengths, speakers, ge2es, pitches, pitch_lengths, length_scales, labels, texts,
@@ -256,8 +265,9 @@ def main(argv=None):
                     help="voice conversion instead of text-to-mel: label, source mel (.npy [T, Mel] or wav), source speaker, target speaker[, target reference]")
     ap.add_argument("--wav", action="store_true", help="also write WAV/<label>.wav per utterance (Griffin-Lim: a baseline vocoder, not a neural one)")
     ap.add_argument("--vocode", default=None, metavar="LIST", help="vocode existing mels instead of synthesising: one label<TAB>mel.npy ([T, Mel]) per line")
+    ap.add_argument("--device-frontend", action="store_true", help="analyse wav references / conversion sources on the device instead of the host")
     args = ap.parse_args(argv)
-    inf = Inferencer(checkpoint_path=args.checkpoint)
+    inf = Inferencer(checkpoint_path=args.checkpoint, device_frontend=args.device_frontend)
     if args.vocode:
         recs = read_vocode_list(args.vocode)
         print("\n".join(inf.Vocode([r[0] for r in recs], [r[1] for r in recs], args.out)))

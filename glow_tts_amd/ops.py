@@ -189,3 +189,19 @@ def griffin_lim_step(x, x_prev, mag, frame_lengths, window, twiddle, alpha, fram
     _lib.check(_lib.lib().glowtts_griffin_lim_step_f32(_lib.ptr(x), _lib.ptr(x_prev), _lib.ptr(mag), _lib.ptr(frame_lengths), _lib.ptr(window), _lib.ptr(twiddle),
                                                        float(alpha), _lib.ptr(frames), mag.shape[0], mag.shape[1], x.shape[1], *geo, _lib.stream()),
                "glowtts_griffin_lim_step_f32")
+
+
+# ---- analysis front end (csrc/frontend_ops.hip).  wav [B, L] fp32, wav_lengths int32 [B], both on the device ----
+def mel_analysis(wav, wav_lengths, window, twiddle, fb_index, fb_weight, mel, geo, pre_emphasis, min_db, max_abs):
+    """wav [B, L] -> normalised mel [B, T, Mel] (glowtts_mel_analysis_f32); fb_index [Mel, 3] int32 / fb_weight: the sparse filterbank."""
+    B, T, Mel = mel.shape
+    _lib.check(_lib.lib().glowtts_mel_analysis_f32(_lib.ptr(wav), _lib.ptr(wav_lengths), _lib.ptr(window), _lib.ptr(twiddle), _lib.ptr(fb_index),
+                                                   _lib.ptr(fb_weight), _lib.ptr(mel), B, wav.shape[1], T, Mel, fb_weight.numel(), *geo, float(pre_emphasis),
+                                                   float(min_db), float(max_abs), _lib.stream()), "glowtts_mel_analysis_f32")
+
+
+def yin(wav, wav_lengths, pitch, w_len, w_step, tau_min, tau_max, thresh, sample_rate, cmnd=None):
+    """wav [B, L] -> pitch [B, T] in Hz, 0 where unvoiced (glowtts_yin_f32); cmnd [B, T, tau_max]: optionally the normalised difference function."""
+    B, T = pitch.shape
+    _lib.check(_lib.lib().glowtts_yin_f32(_lib.ptr(wav), _lib.ptr(wav_lengths), _lib.ptr(pitch), _lib.ptr(cmnd), B, wav.shape[1], T, int(w_len), int(w_step),
+                                          int(tau_min), int(tau_max), float(thresh), float(sample_rate), _lib.stream()), "glowtts_yin_f32")

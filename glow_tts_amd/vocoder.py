@@ -31,6 +31,15 @@ def geometry(hp):
     return n_fft, win, hop
 
 
+def fft_tables(n_fft, win):
+    """(twiddle [n_fft / 2, 2] = (cos, -sin)(2 pi k / n_fft), window [win] = periodic Hann) in float64: the tables of the LDS FFT, shared with
+    `frontend.Analyzer`; the callers round them once to fp32."""
+    k = np.arange(n_fft // 2, dtype=np.float64)
+    tw = np.stack([np.cos(2.0 * np.pi * k / n_fft), -np.sin(2.0 * np.pi * k / n_fft)], axis=1)
+    w = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(win, dtype=np.float64) / win)                # periodic Hann (scipy get_window("hann", fftbins=True))
+    return tw, w
+
+
 def settings(hp):
     """(iterations, momentum) of the optional yaml block `Griffin_Lim: {Iterations: 60, Momentum: 0.99}`."""
     g = getattr(hp, "Griffin_Lim", None)
@@ -49,9 +58,7 @@ class GriffinLim:
         self.n_freq, self.n_mel, self.max_abs = n_fft // 2 + 1, int(s.Mel_Dim), float(s.Max_Abs_Mel)
         self.sample_rate, self.pre_emphasis = int(s.Sample_Rate), 0.97
         # tables in float64 on the host, rounded once to fp32
-        k = np.arange(n_fft // 2, dtype=np.float64)
-        tw = np.stack([np.cos(2.0 * np.pi * k / n_fft), -np.sin(2.0 * np.pi * k / n_fft)], axis=1)
-        w = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(win, dtype=np.float64) / win)            # periodic Hann (scipy get_window("hann", fftbins=True))
+        tw, w = fft_tables(n_fft, win)
         fb = audio.mel_filterbank(self.sample_rate, n_fft, self.n_mel, s.Mel_F_Min, s.Mel_F_Max).astype(np.float64)
         to = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
         self.twiddle, self.window, self.basis = to(tw), to(w), to(np.linalg.pinv(fb))

@@ -836,6 +836,29 @@ int glowtts_overlap_add_f32(const float *frames, const int32_t *frame_lengths, c
 int glowtts_griffin_lim_step_f32(const float *x, const float *x_prev, const float *mag, const int32_t *frame_lengths, const float *window,
                                  const float *twiddle, float alpha, float *frames, int B, int T, int ldx, int n_fft, int win_length, int hop, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Analysis front end (csrc/frontend_ops.hip): what Pattern_Generator.py computes per utterance - the mel of Audio.py:14-47 and the YIN pitch track of
+ * yin.py - as glow_tts_amd/audio.py restates them (`mel_generate`, `yin_pitch`), in fp32.  New symbols only, the ABI version stays 7.
+ * Signals are [B][ldx] f32 with wav_lengths [B] i32 on the device; an utterance with wav_lengths[b] > ldx is a caller error that is never read beyond
+ * ldx and comes out as padding.  1 <= B <= 65535, T >= 1, ldx >= 1 and B * T <= 2^30, else GLOWTTS_E_ARG.  Both are bit-identical from run to run and independent of the batch around an utterance (fixed reduction orders, no atomics).
+ *
+ * glowtts_mel_analysis_f32: -> mel [B][T][Mel], utterance b has T_b = 1 + len / hop frames (clamped to T); frames beyond are -max_abs.  Per frame:
+ *   pre-emphasis y[s] = x[s] - pre_emphasis x[s-1] (y[0] = x[0]) applied while gathering, reflect padding of y by n_fft / 2, the window / twiddle tables of
+ *   the vocoder, FFT, |Y|, the mel filterbank in SPARSE form - fb_index [Mel][3] i32 = (first bin, bin count, offset into fb_weight), fb_weight [n_weights]
+ *   f32: row j of the dense filterbank is fb_weight[offset_j .. offset_j + count_j) at bins first_j .. - then 20 log10(m + 1e-7) and
+ *   clip(2 max_abs (db - min_db) / (-min_db) - max_abs, +- max_abs).  Geometry: n_fft a power of two in [256, 4096], 1 <= win_length <= n_fft, hop >= 1
+ *   (no win_length % hop condition: nothing is overlap-added), Mel <= 1024; else GLOWTTS_E_ARG.
+ * glowtts_yin_f32: -> pitch [B][T] in Hz, 0 where unvoiced or beyond the utterance; when cmnd is not NULL also the cumulative-mean-normalised difference
+ *   cmnd [B][T][tau_max].  The signal is reflect-padded by (w_step + w_len - len % w_step) / 2 samples each side (index arithmetic), frames start every
+ *   w_step samples, ceil((padded length - w_len) / w_step) of them (clamped to T).  d(tau) = sum_{j < w_len - tau} (x_j - x_{j+tau})^2 summed directly,
+ *   cm[0] = 1, cm[tau] = d(tau) tau / (sum_{1..tau} d + 1e-8); the first tau in [tau_min, tau_max) with cm < thresh, walked forward while
+ *   cm[tau + 1] < cm[tau], gives pitch = sample_rate / tau.  Supported: w_len <= 2048, 1 <= tau_min < tau_max <= w_len; else GLOWTTS_E_ARG. */
+int glowtts_mel_analysis_f32(const float *wav, const int32_t *wav_lengths, const float *window, const float *twiddle, const int32_t *fb_index,
+                             const float *fb_weight, float *mel, int B, int ldx, int T, int Mel, int n_weights, int n_fft, int win_length, int hop,
+                             float pre_emphasis, float min_db, float max_abs, void *stream);
+int glowtts_yin_f32(const float *wav, const int32_t *wav_lengths, float *pitch, float *cmnd, int B, int ldx, int T, int w_len, int w_step, int tau_min,
+                    int tau_max, float thresh, float sample_rate, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
