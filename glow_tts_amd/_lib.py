@@ -7,6 +7,8 @@ import os
 
 import torch
 
+from . import abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libglowtts_hip.so")
 # tools/ab.sh (A/B measurements of launch heuristics) points this at the experiment build `make -C glow_tts_amd/csrc tools`, whose
@@ -14,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libglowtts_hip.so")
 if os.environ.get("GLOWTTS_LIB_PATH"):
     LIB_PATH = os.environ["GLOWTTS_LIB_PATH"]
 _lib = None
-ABI_VERSION = 7                          # GLOWTTS_ABI_VERSION of include/glowtts_hip.h
+ABI_VERSION = abi.ABI_VERSION
 
 c_int, c_float, c_void_p = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 
@@ -23,8 +25,16 @@ class GlowTTSHipError(RuntimeError):
     pass
 
 
+def _symbol(L, name):
+    try:
+        return getattr(L, name)
+    except AttributeError:
+        raise GlowTTSHipError(f"{LIB_PATH} does not export {name}, which include/glowtts_hip.h of ABI version {ABI_VERSION} declares: rebuild it") from None
+
+
 def lib():
-    """Loads the shared library (once).  Raises if it has not been built (python __graft_entry__.py)."""
+    """Loads the shared library (once) and binds every entry point of the C ABI as abi.SIGNATURES states it - callers never declare a signature.
+    Raises if the library has not been built (python __graft_entry__.py), is of another ABI version or lacks an entry point."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -32,31 +42,14 @@ def lib():
                 f"{LIB_PATH} not found: build it with `make -C glow_tts_amd/csrc` "
                 "(or __graft_entry__.build()); the HIP path has no CPU fallback")
         L = ctypes.CDLL(LIB_PATH)
-        _declare(L)
-        if L.glowtts_abi_version() != ABI_VERSION:       # struct layouts in decoder.py mirror include/glowtts_hip.h of exactly this version
-            raise GlowTTSHipError(f"{LIB_PATH} has ABI version {L.glowtts_abi_version()}, this package binds version {ABI_VERSION}: rebuild it")
+        version = _symbol(L, "glowtts_abi_version")()    # (int (void): ctypes' defaults) - the struct mirrors of abi.py are the layouts of exactly this version
+        if version != ABI_VERSION:
+            raise GlowTTSHipError(f"{LIB_PATH} has ABI version {version}, this package binds version {ABI_VERSION}: rebuild it")
+        for name, (restype, argtypes) in abi.SIGNATURES.items():
+            fn = _symbol(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
-
-
-def _declare(L):
-    L.glowtts_abi_version.restype = c_int
-    L.glowtts_device_arch.argtypes = [ctypes.c_char_p, c_int]
-    L.glowtts_mas_dp_f32.argtypes = [c_void_p] * 5 + [c_int] * 3 + [c_float, c_void_p]
-    L.glowtts_mas_path_from_idx.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
-    L.glowtts_mas_f32.argtypes = [c_void_p] * 5 + [c_int] * 3 + [c_float, c_void_p]
-    L.glowtts_pack_weight.argtypes = [c_void_p] + [c_int] * 7 + [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p]
-    L.glowtts_conv_cl.argtypes = [c_void_p, c_void_p]
-    # Griffin-Lim vocoder (csrc/vocoder_ops.hip)
-    L.glowtts_vocoder_supported.argtypes = [c_int] * 3
-    L.glowtts_mel_to_linear_f32.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_float, c_void_p]
-    L.glowtts_stft_f32.argtypes = [c_void_p] * 5 + [c_int] * 6 + [c_void_p]
-    L.glowtts_istft_f32.argtypes = [c_void_p] * 6 + [c_int] * 6 + [c_void_p]
-    L.glowtts_overlap_add_f32.argtypes = [c_void_p] * 4 + [c_int] * 6 + [c_void_p]
-    L.glowtts_griffin_lim_step_f32.argtypes = [c_void_p] * 6 + [c_float, c_void_p] + [c_int] * 6 + [c_void_p]
-    # analysis front end (csrc/frontend_ops.hip)
-    L.glowtts_mel_analysis_f32.argtypes = [c_void_p] * 7 + [c_int] * 8 + [c_float] * 3 + [c_void_p]
-    L.glowtts_yin_f32.argtypes = [c_void_p] * 4 + [c_int] * 7 + [c_float] * 2 + [c_void_p]
 
 
 def check(rc, what):

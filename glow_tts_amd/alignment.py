@@ -7,31 +7,10 @@ import math
 import torch
 
 from . import _lib, ops
-from .decoder import PackedBatch, _L
+from .decoder import PackedBatch
 
 LOG_2PI = math.log(2.0 * math.pi)
-_decl = False
-
-
-def _lib2():
-    global _decl
-    L = _L()
-    if not _decl:
-        L.glowtts_logprior_prep.argtypes = [ctypes.c_void_p] * 9 + [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)] * 2 + [ctypes.c_void_p]
-        L.glowtts_mas_dp_f32_t.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_void_p]
-        L.glowtts_expand_fwd.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [ctypes.c_void_p]
-        L.glowtts_expand_bwd.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [ctypes.c_void_p]
-        L.glowtts_duration_targets.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_void_p]
-        L.glowtts_mle_loss_fwd.argtypes = [ctypes.c_void_p] * 8 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-        L.glowtts_mle_loss_bwd.argtypes = [ctypes.c_void_p] * 8 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-        L.glowtts_expand_pair_targets.argtypes = [ctypes.c_void_p] * 8 + [ctypes.c_int] * 4 + [ctypes.c_void_p]
-        L.glowtts_prior_loss.argtypes = [ctypes.c_void_p] * 17 + [ctypes.c_int] * 6 + [ctypes.c_void_p]
-        L.glowtts_prior_loss_bwd.argtypes = [ctypes.c_void_p] * 10 + [ctypes.c_int] * 4 + [ctypes.c_void_p]
-        L.glowtts_mse_loss_fwd.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                           ctypes.c_void_p]
-        L.glowtts_mse_loss_bwd.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-        _decl = True
-    return L
+_lib2 = _lib.lib                         # the bound library (tests/test_gpu_mas.py calls alignment._lib2())
 
 
 @torch.no_grad()
@@ -40,7 +19,7 @@ def log_prior_prepare(mean, log_std, token_lengths, mel_lengths, Ty, mel_multipl
     (sigma^-2 | mu sigma^-2) weight image, the per-token constant, the frame mask and the int32 lengths.  `GlowTTS.forward` calls it on the encoder's stream, right
     behind the projection - off the chain between the flow decoder's last launch and its backward - and hands the result to `log_prior_t`."""
     B, Cm, Tx = mean.shape
-    L = _lib2()
+    L = _lib.lib()
     dev = mean.device
     mean, log_std = mean.contiguous(), log_std.contiguous()
     npad, kch = ctypes.c_int(0), ctypes.c_int(0)
@@ -103,7 +82,7 @@ def maximum_path_t(value_t, token_lengths, mel_lengths, max_neg_val=-1e9):
     idx = torch.empty(B, Ty, dtype=torch.int32, device=value_t.device)
     tx = token_lengths if token_lengths.dtype == torch.int32 else token_lengths.to(torch.int32).contiguous()
     ty = mel_lengths if mel_lengths.dtype == torch.int32 else mel_lengths.to(torch.int32).contiguous()
-    _lib.check(_lib2().glowtts_mas_dp_f32_t(_lib.ptr(value_t), _lib.ptr(tx), _lib.ptr(ty), _lib.ptr(idx), None, B, Tx, Ty,
+    _lib.check(_lib.lib().glowtts_mas_dp_f32_t(_lib.ptr(value_t), _lib.ptr(tx), _lib.ptr(ty), _lib.ptr(idx), None, B, Tx, Ty,
                                             max_neg_val, _lib.stream()), "glowtts_mas_dp_f32_t")
     return idx
 
@@ -122,7 +101,7 @@ class ExpandPrior(torch.autograd.Function):
         B, C, Tx = src.shape
         Ty = idx.shape[1]
         out = torch.empty(B, C, Ty, device=src.device)
-        _lib.check(_lib2().glowtts_expand_fwd(_lib.ptr(src), _lib.ptr(idx), _lib.ptr(out), B, C, Tx, Ty, _lib.stream()), "glowtts_expand_fwd")
+        _lib.check(_lib.lib().glowtts_expand_fwd(_lib.ptr(src), _lib.ptr(idx), _lib.ptr(out), B, C, Tx, Ty, _lib.stream()), "glowtts_expand_fwd")
         ctx.save_for_backward(idx)
         ctx.Tx, ctx.bwd_stream = Tx, bwd_stream
         return out
@@ -136,7 +115,7 @@ class ExpandPrior(torch.autograd.Function):
 
         def run():
             dsrc = torch.empty(B, C, ctx.Tx, device=dout.device)
-            _lib.check(_lib2().glowtts_expand_bwd(_lib.ptr(dout), _lib.ptr(idx), _lib.ptr(dsrc), B, C, ctx.Tx, Ty, _lib.stream()), "glowtts_expand_bwd")
+            _lib.check(_lib.lib().glowtts_expand_bwd(_lib.ptr(dout), _lib.ptr(idx), _lib.ptr(dsrc), B, C, ctx.Tx, Ty, _lib.stream()), "glowtts_expand_bwd")
             return dsrc
         if s is None or s == cur:
             return run(), None, None
@@ -153,7 +132,7 @@ def duration_targets(idx, token_lengths, Tx):
     """log(sum_t attentions + 1e-7) * token_mask (Modules.py:122) -> [B,1,Tx]."""
     B, Ty = idx.shape
     out = torch.empty(B, Tx, device=idx.device)
-    _lib.check(_lib2().glowtts_duration_targets(_lib.ptr(idx), _lib.ptr(token_lengths.contiguous()), _lib.ptr(out), B, Tx, Ty, _lib.stream()),
+    _lib.check(_lib.lib().glowtts_duration_targets(_lib.ptr(idx), _lib.ptr(token_lengths.contiguous()), _lib.ptr(out), B, Tx, Ty, _lib.stream()),
                "glowtts_duration_targets")
     return out.unsqueeze(1)
 
@@ -166,7 +145,7 @@ def _segment_sums(dout, idx, Tx, stream):
 
     def run():
         dsrc = torch.empty(B, C, Tx, device=dout.device)
-        _lib.check(_lib2().glowtts_expand_bwd(_lib.ptr(dout), _lib.ptr(idx), _lib.ptr(dsrc), B, C, Tx, Ty, _lib.stream()), "glowtts_expand_bwd")
+        _lib.check(_lib.lib().glowtts_expand_bwd(_lib.ptr(dout), _lib.ptr(idx), _lib.ptr(dsrc), B, C, Tx, Ty, _lib.stream()), "glowtts_expand_bwd")
         return dsrc
     if stream is None or stream == cur:
         return run()
@@ -193,7 +172,7 @@ class ExpandPair(torch.autograd.Function):
         dev = mean.device
         om, ol, tg = torch.empty(B, C, Ty, device=dev), torch.empty(B, C, Ty, device=dev), torch.empty(B, Tx, device=dev)
         path = None
-        L = _lib2()
+        L = _lib.lib()
         if Ty % 4 == 0:
             if want_path:
                 path = torch.empty(B, Tx, Ty, device=dev)
@@ -254,7 +233,7 @@ class MLELoss(torch.autograd.Function):
         dev = z.device
         loss, inv = torch.empty((), device=dev), torch.empty(1, device=dev)
         scratch = torch.empty(1024, device=dev)
-        _lib.check(_lib2().glowtts_mle_loss_fwd(_lib.ptr(z), _lib.ptr(mean), _lib.ptr(log_std), _lib.ptr(log_dets), _lib.ptr(lengths.contiguous()),
+        _lib.check(_lib.lib().glowtts_mle_loss_fwd(_lib.ptr(z), _lib.ptr(mean), _lib.ptr(log_std), _lib.ptr(log_dets), _lib.ptr(lengths.contiguous()),
                                                 loss.data_ptr(), inv.data_ptr(), _lib.ptr(scratch), z.numel(), z.shape[0], n_squeeze, mel_dim,
                                                 _lib.stream()), "glowtts_mle_loss_fwd")
         ctx.save_for_backward(z, mean, log_std, inv)
@@ -267,7 +246,7 @@ class MLELoss(torch.autograd.Function):
         dz, dm, dl = torch.empty_like(z), torch.empty_like(z), torch.empty_like(z)
         dl_ = dloss.contiguous().reshape(1)
         dlogdet = torch.empty(ctx.B, device=z.device)
-        _lib.check(_lib2().glowtts_mle_loss_bwd(_lib.ptr(z), _lib.ptr(mean), _lib.ptr(log_std), _lib.ptr(dl_), _lib.ptr(inv), _lib.ptr(dz),
+        _lib.check(_lib.lib().glowtts_mle_loss_bwd(_lib.ptr(z), _lib.ptr(mean), _lib.ptr(log_std), _lib.ptr(dl_), _lib.ptr(inv), _lib.ptr(dz),
                                                 _lib.ptr(dm), _lib.ptr(dl), z.numel(), _lib.ptr(dlogdet), ctx.B, _lib.stream()), "glowtts_mle_loss_bwd")
         return dz, dm, dl, dlogdet, None, None, None
 
@@ -291,7 +270,7 @@ class PriorLoss(torch.autograd.Function):
         Tx = mean_tok.shape[2]
         loss, inv = torch.empty((), device=dev), torch.empty(1, device=dev)
         scratch = torch.empty(1024, device=dev)
-        L = _lib2()
+        L = _lib.lib()
         counter = _lib.counter(dev, "prior_loss", owner) if seed is not None else None
         ctx.seed, ctx.stash = None, None
         if counter is not None:
@@ -321,7 +300,7 @@ class PriorLoss(torch.autograd.Function):
         Tx = mean_tok.shape[2]
         dz, dm, dl = torch.empty_like(z), torch.empty_like(mean_tok), torch.empty_like(ls_tok)
         dlogdet = torch.empty(B, device=z.device)
-        _lib.check(_lib2().glowtts_prior_loss_bwd(_lib.ptr(z), _lib.ptr(mean_tok), _lib.ptr(ls_tok), _lib.ptr(idx), _lib.ptr(dloss.contiguous().reshape(1)), _lib.ptr(inv),
+        _lib.check(_lib.lib().glowtts_prior_loss_bwd(_lib.ptr(z), _lib.ptr(mean_tok), _lib.ptr(ls_tok), _lib.ptr(idx), _lib.ptr(dloss.contiguous().reshape(1)), _lib.ptr(inv),
                                                   _lib.ptr(dz), _lib.ptr(dm), _lib.ptr(dl), _lib.ptr(dlogdet), B, C, Tx, Ty, _lib.stream()), "glowtts_prior_loss_bwd")
         return (dz, dm, dl, dlogdet) + none
 
@@ -402,7 +381,7 @@ class DurationMSE(torch.autograd.Function):
         one = _lib.one(a.device) if seed is not None else None
         unit = seed is not None and one is not None and seed.data_ptr() == one.data_ptr()        # (the forward writes the gradient for the seed 1 only)
         da = torch.empty_like(a) if unit else None
-        _lib.check(_lib2().glowtts_mse_loss_fwd(_lib.ptr(a), _lib.ptr(target), loss.data_ptr(), a.numel(), 1.0 / a.numel(), _lib.ptr(tl), B, _lib.ptr(ext),
+        _lib.check(_lib.lib().glowtts_mse_loss_fwd(_lib.ptr(a), _lib.ptr(target), loss.data_ptr(), a.numel(), 1.0 / a.numel(), _lib.ptr(tl), B, _lib.ptr(ext),
                                                 _lib.ptr(da), _lib.stream()), "glowtts_mse_loss_fwd")
         ctx.save_for_backward(a, target, tl, ext)
         ctx.seed, ctx.stash = (seed if unit else None), da
@@ -415,7 +394,7 @@ class DurationMSE(torch.autograd.Function):
         if ctx.seed is not None and dloss.data_ptr() == ctx.seed.data_ptr() and dloss.numel() == 1:
             return stash, None, None, None, None
         da = torch.empty_like(a)
-        _lib.check(_lib2().glowtts_mse_loss_bwd(_lib.ptr(a), _lib.ptr(target), _lib.ptr(dloss.contiguous().reshape(1)), _lib.ptr(da), a.numel(), 1.0 / a.numel(),
+        _lib.check(_lib.lib().glowtts_mse_loss_bwd(_lib.ptr(a), _lib.ptr(target), _lib.ptr(dloss.contiguous().reshape(1)), _lib.ptr(da), a.numel(), 1.0 / a.numel(),
                                                 _lib.ptr(tl), int(a.shape[0]), _lib.ptr(ext), _lib.stream()), "glowtts_mse_loss_bwd")
         return da, None, None, None, None
 

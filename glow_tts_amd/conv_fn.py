@@ -11,46 +11,9 @@ import math
 import torch
 
 from . import _lib, ops
+from .abi import WgradArgs  # noqa: F401
 
-_decl = False
-c_i64, c_int, c_f, c_u32, c_p = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_uint32, ctypes.c_void_p
-
-
-class WgradArgs(ctypes.Structure):
-    """Mirror of `glowtts_wgrad_args`."""
-    _fields_ = [("dy", c_p), ("lddy", c_i64), ("x", c_p), ("ldx", c_i64),
-                ("xpro", c_int), ("xmask", c_p),
-                ("rows", c_int), ("m", c_int), ("ca", c_int), ("taps", c_int), ("pad", c_int),
-                ("perm", c_int), ("perm_h", c_int), ("precision", c_int),
-                ("splits", c_int), ("accumulate", c_int),
-                ("dw", c_p), ("dbias", c_p), ("io_flags", c_int)]
-
-
-def _L():
-    global _decl
-    L = _lib.lib()
-    if not _decl:
-        L.glowtts_wgrad_cl.argtypes = [c_p, c_p]
-        L.glowtts_layernorm_fwd_io.argtypes = [c_p] * 8 + [c_i64, c_int, c_f, c_int, c_f, c_u32, c_p, c_p, c_p]
-        L.glowtts_layernorm_qkv.argtypes = [c_p] * 10 + [c_int, c_p, c_p, c_i64, c_int, c_f, c_p]
-        L.glowtts_proj_layernorm.argtypes = [c_p, c_i64, c_p, c_int] + [c_p] * 10 + [c_i64, c_int, c_f, c_f, c_u32, c_p, c_p]
-        L.glowtts_layernorm_scratch_floats.argtypes = [c_i64, c_int]
-        L.glowtts_layernorm_scratch_floats.restype = c_i64
-        L.glowtts_layernorm_bwd_io.argtypes = [c_p] * 9 + [c_i64, c_int, c_int, c_f, c_p, c_p, c_f, c_p]
-        L.glowtts_colsum_batched.argtypes = [c_p, c_p, c_int, c_int, c_int, c_i64, c_i64, c_p]
-        L.glowtts_gate_bwd_io.argtypes = [c_p] * 4 + [c_i64, c_int, c_f, c_int, c_p]
-        L.glowtts_embedding_fwd.argtypes = [c_p] * 4 + [c_int] * 3 + [c_f, c_p]
-        L.glowtts_embedding_bwd.argtypes = [c_p] * 4 + [c_int] * 4 + [c_f, c_p]
-        L.glowtts_rpr_attention_fwd_prec.argtypes = [c_p] * 6 + [c_int] * 5 + [c_f, c_u32, c_p, c_int, c_p]
-        L.glowtts_rpr_attention_fwd_eval.argtypes = [c_p] * 5 + [c_int] * 6 + [c_p]
-        L.glowtts_rpr_attention_scratch_floats.argtypes = [c_int] * 5
-        L.glowtts_rpr_attention_scratch_floats.restype = c_i64
-        L.glowtts_rpr_attention_bwd_prec.argtypes = [c_p] * 11 + [c_int] * 5 + [c_f, c_u32, c_p, c_int, c_p]
-        L.glowtts_rpr_attention_bwd_partial_rows.argtypes = [c_int] * 5
-        L.glowtts_sum_slices.argtypes = [c_p, c_p, c_int, c_i64, c_p]
-        L.glowtts_rpr_attention_bwd_partial_rows.restype = c_i64
-        _decl = True
-    return L
+_L = _lib.lib                            # the bound library (tools and tests call CF._L())
 
 
 def wgrad(dy, x, O, ca, taps, precision, want_bias=True, splits=0, xpro=0, io_flags=0):

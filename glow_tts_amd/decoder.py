@@ -12,127 +12,19 @@ import math
 
 import torch
 
-from . import _lib, ops
+from . import _lib, abi, ops
 from ._lib import c_int, c_void_p
+from .abi import FlowActs, FlowDims, FlowGrads, FlowParams, Packed, PrepJob, SumSeg, WgradJob, WnBwdJob  # noqa: F401
 
-MAXL = 8
-ROW_PAD = 2
+MAXL, ROW_PAD, WN_SLAB = abi.MAX_WN_LAYERS, abi.ROW_PAD, abi.WN_SLAB_BYTES
 c_i64 = ctypes.c_int64
-
-
-class Packed(ctypes.Structure):
-    _fields_ = [("w", c_void_p), ("npad", c_int), ("kchunks", c_int)]
-
-
-class FlowDims(ctypes.Structure):
-    _fields_ = [("B", c_int), ("T", c_int), ("C", c_int), ("H", c_int), ("L", c_int), ("ksize", c_int), ("precision", c_int),
-                ("drop_p", ctypes.c_float), ("seed", ctypes.c_uint32), ("seed_ptr", c_void_p), ("act_bf16", c_int)]
-
-
-class FlowParams(ctypes.Structure):
-    _fields_ = [("an_logs", c_void_p), ("an_bias", c_void_p), ("winfo", c_void_p),
-                ("start", Packed), ("in_", Packed * MAXL), ("rs", Packed * MAXL), ("end", Packed),
-                ("start_t", Packed), ("in_t", Packed * MAXL), ("rs_t", Packed * MAXL), ("end_t", Packed),
-                ("b_start", c_void_p), ("b_in", c_void_p * MAXL), ("b_rs", c_void_p * MAXL), ("b_end", c_void_p),
-                ("cond", c_void_p), ("ldcond", c_i64), ("cond_rows", c_int), ("wn_img", c_void_p), ("wn_img_t", c_void_p)]
-
-
-class FlowActs(ctypes.Structure):
-    _fields_ = [("xin", c_void_p), ("xmid", c_void_p), ("xout", c_void_p),
-                ("hs", c_void_p * MAXL), ("gates", c_void_p * MAXL), ("skip", c_void_p), ("outs", c_void_p),
-                ("rowmask", c_void_p), ("acts", c_void_p * MAXL), ("skip_bf", c_void_p), ("xa_bf", c_void_p),
-                ("next_an_logs", c_void_p), ("next_an_bias", c_void_p), ("next_winfo", c_void_p),
-                ("next_xmid", c_void_p), ("next_xout", c_void_p), ("next_xa_bf", c_void_p), ("actnorm_done", c_int)]
-
-
-class FlowGrads(ctypes.Structure):
-    _fields_ = [("dx", c_void_p), ("dlogdet", c_void_p), ("douts", c_void_p), ("dskip", c_void_p),
-                ("dh", c_void_p * MAXL), ("dins", c_void_p * MAXL), ("defer_wgrad", c_int),
-                ("scratch", c_void_p), ("d_an", c_void_p),
-                ("dw_start", c_void_p), ("db_start", c_void_p),
-                ("dw_in", c_void_p * MAXL), ("db_in", c_void_p * MAXL),
-                ("dw_rs", c_void_p * MAXL), ("db_rs", c_void_p * MAXL),
-                ("dw_end", c_void_p), ("db_end", c_void_p), ("dcond", c_void_p), ("douts_bf", c_void_p),
-                ("coupling_done", c_int), ("prev_xmid", c_void_p), ("prev_outs", c_void_p), ("prev_douts", c_void_p), ("prev_douts_bf", c_void_p),
-                ("pitch_rows", c_void_p), ("pitch_ns", c_int), ("dh0_bf16", c_int)]
-
-
-_declared = False
-
-
-def _L():
-    global _declared
-    L = _lib.lib()
-    if not _declared:
-        L.glowtts_pack_weight_batched.argtypes = [c_void_p] + [c_int] * 8 + [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p]
-        L.glowtts_squeeze_rows.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_void_p]
-        L.glowtts_unsqueeze_rows.argtypes = [c_void_p] * 3 + [c_int] * 5 + [ctypes.c_float, c_void_p]
-        L.glowtts_inv1x1_prepare.argtypes = [c_void_p, c_void_p, c_int, c_void_p]
-        L.glowtts_actnorm_stats.argtypes = [c_void_p] * 4 + [c_i64, c_int, c_void_p]
-        L.glowtts_actnorm_stats_scratch_floats.argtypes = [c_i64, c_int]
-        L.glowtts_actnorm_stats_scratch_floats.restype = c_i64
-        L.glowtts_actnorm_bwd_blocks.argtypes = [c_i64]
-        L.glowtts_actnorm_bwd_blocks.restype = c_i64
-        L.glowtts_actnorm_from_stats.argtypes = [c_void_p] * 3 + [c_int, c_void_p]
-        L.glowtts_actnorm_inv1x1.argtypes = [c_void_p] * 6 + [c_i64, c_int, c_int, c_void_p]
-        L.glowtts_flow_forward.argtypes = [c_void_p] * 4
-        L.glowtts_flow_inverse.argtypes = [c_void_p] * 4
-        L.glowtts_flow_encode.argtypes = [c_void_p] * 4
-        L.glowtts_flow_backward.argtypes = [c_void_p] * 5
-        L.glowtts_wgrad_grouped.argtypes = [c_void_p] + [c_int] * 9 + [c_void_p]
-        L.glowtts_wgrad_grouped_io.argtypes = [c_void_p] + [c_int] * 10 + [c_void_p]
-        L.glowtts_wgrad_grouped_phased.argtypes = [c_void_p] + [c_int] * 5 + [c_void_p]
-        L.glowtts_colsum_batched.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_i64, c_i64, c_void_p]
-        L.glowtts_weightnorm_fwd.argtypes = [c_void_p] * 4 + [c_i64, c_int, c_void_p]
-        L.glowtts_weightnorm_bwd.argtypes = [c_void_p] * 6 + [c_i64, c_int, c_void_p]
-        L.glowtts_decoder_logdet.argtypes = [c_void_p, c_i64] + [c_void_p] * 5 + [c_int] * 5 + [c_void_p]
-        L.glowtts_decoder_param_grads.argtypes = [c_void_p] * 7 + [c_int] * 4 + [c_void_p]
-        L.glowtts_wavenet_image_bytes.argtypes = [c_int, c_int, ctypes.POINTER(c_i64)]
-        L.glowtts_wavenet_pack_images.argtypes = [c_void_p] * 5 + [c_int] * 3 + [c_void_p] * 3
-        L.glowtts_prep_job_init.argtypes = [c_void_p] * 4 + [c_int] * 8 + [c_void_p] + [c_i64] * 4 + [c_int, ctypes.POINTER(c_int)]
-        L.glowtts_prep_launch.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p]
-        L.glowtts_wavenet_prep_jobs.argtypes = [c_void_p, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)] + [c_void_p] * 13 + [c_int] * 3 + [c_void_p, c_int, c_void_p]
-        L.glowtts_cond_linear_fwd.argtypes = [c_void_p] * 6 + [c_int] * 4 + [c_void_p]
-        L.glowtts_sum_slices_seg.argtypes = [c_void_p, c_int, c_i64, c_void_p, c_int, c_void_p]
-        L.glowtts_cond_linear_bwd.argtypes = [c_void_p, c_i64] + [c_void_p] * 9 + [c_int] * 3 + [c_void_p]
-        L.glowtts_cond_linear_bwd_scratch_floats.argtypes = [c_int] * 3
-        L.glowtts_cond_linear_bwd_scratch_floats.restype = c_i64
-        _declared = True
-    return L
-
-
-class WnBwdJob(ctypes.Structure):
-    """Mirror of `glowtts_wn_bwd_job`."""
-    _fields_ = [("dw", c_void_p), ("v", c_void_p), ("g", c_void_p), ("inv_norm", c_void_p), ("dv", c_void_p), ("dg", c_void_p),
-                ("rows", c_i64), ("cols", c_int), ("reserved", c_int)]
-
-
-class SumSeg(ctypes.Structure):
-    """Mirror of `glowtts_sum_seg`."""
-    _fields_ = [("dst", c_void_p), ("off", c_i64), ("n", c_i64)]
-
-
-class WgradJob(ctypes.Structure):
-    """Mirror of `glowtts_wgrad_job` (one weight-gradient problem of the grouped launch)."""
-    _fields_ = [("dy", c_void_p), ("x", c_void_p), ("xmask", c_void_p), ("dw", c_void_p), ("dbias", c_void_p),
-                ("lddy", c_i64), ("ldx", c_i64),
-                ("m", c_int), ("ca", c_int), ("xpro", c_int), ("perm", c_int), ("perm_h", c_int),
-                ("tile0", c_int), ("mt", c_int), ("nt", c_int), ("rows", c_int), ("reserved", c_int)]
-
-
-class PrepJob(ctypes.Structure):
-    """Mirror of `glowtts_prep_job` (weight norm + packing of one conv class into one image, csrc/prep_ops.hip)."""
-    _fields_ = [("v", c_void_p), ("g", c_void_p), ("inv_out", c_void_p), ("packed", c_void_p),
-                ("outer_stride", c_i64), ("inner_stride", c_i64), ("w_stride", c_i64), ("g_stride", c_i64),
-                ("batch", c_int), ("inner", c_int), ("O", c_int), ("I", c_int), ("taps", c_int), ("transpose", c_int), ("perm", c_int), ("perm_h", c_int),
-                ("o_ext", c_int), ("npad", c_int), ("kchunks", c_int), ("tiles", c_int), ("block0", c_int), ("reserved", c_int),
-                ("twin", c_void_p), ("twin_outer", c_i64), ("twin_inner", c_i64), ("twin_half", c_i64), ("twin_batch", c_int), ("twin_npad", c_int)]
+_L = _lib.lib                            # the bound library (bench.py, tools and tests call D._L())
 
 
 class PrepJobs:
     """Collects the weight-preparation jobs of a training step (every image of the decoder's convs, straight from the weight-norm pairs) and
     issues them as ONE launch (glowtts_prep_launch)."""
-    CAP = 22                             # GLOWTTS_PREP_MAX_JOBS
+    CAP = abi.PREP_MAX_JOBS
 
     def __init__(self):
         self.jobs = (PrepJob * self.CAP)()
@@ -154,7 +46,6 @@ class PrepJobs:
             return
         if TUNE["prep_twin"] and not getattr(self, "_twinned", False):
             # the In_l pairs are read ONCE: the forward image's tiles also write the two transposed half images (csrc/prep_ops.hip; no-op without that pattern)
-            _L().glowtts_prep_jobs_twin_in.argtypes = [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
             _lib.check(_L().glowtts_prep_jobs_twin_in(ctypes.cast(self.jobs, c_void_p), ctypes.byref(self.n), ctypes.byref(self.blocks)), "glowtts_prep_jobs_twin_in")
             self._twinned = True
         # (the table is a HOST array: it travels in the launch's argument segment - no copy node in a captured step)
@@ -222,9 +113,7 @@ def step_seed(device):
     if not capturing:
         return torch.randint(0, 2 ** 31 - 1, (1,), device=device, dtype=torch.int32)
     out = torch.empty(1, dtype=torch.int32, device=device)
-    L = _L()
-    L.glowtts_step_seed.argtypes = [c_void_p, c_void_p, c_void_p]
-    _lib.check(L.glowtts_step_seed(st.data_ptr(), out.data_ptr(), _lib.stream()), "glowtts_step_seed")
+    _lib.check(_L().glowtts_step_seed(st.data_ptr(), out.data_ptr(), _lib.stream()), "glowtts_step_seed")
     return out
 
 
@@ -236,10 +125,8 @@ def stamp(name):
     if i >= STAMPS["buf"].numel():                       # (an armed eager run of many steps: the buffer is full, stop stamping)
         return
     STAMPS["names"].append(name)
-    _L().glowtts_debug_stamp.argtypes = [c_void_p, c_void_p]
     _lib.check(_L().glowtts_debug_stamp(STAMPS["buf"].data_ptr() + 8 * i, _lib.stream()), "glowtts_debug_stamp")
 
-WN_SLAB = 24576                          # GLOWTTS_WN_SLAB_BYTES
 TAIL_STACKS = ("start_g", "start_v", "start_b", "rs_g", "rs_v", "rs_b", "rsl_g", "rsl_v", "rsl_b", "end_w", "end_b")
 
 
@@ -378,7 +265,7 @@ class WgradGroup:
                 else:
                     segs.append((ptr, n, tot))
                 tot += n
-        if len(segs) > 12:
+        if len(segs) > abi.SUM_MAX_SEGS:
             return False
         self.part = torch.empty(S, tot, device=device)
         Rs = (B // S) * rows_per_utt
@@ -456,7 +343,7 @@ class ImageSlices:
 
 def fused_wn_supported(cfg):
     """Shape contract of glowtts_wavenet_fwd (include/glowtts_hip.h): the reference's default decoder."""
-    return bool(TUNE["fused_wn"] and cfg.act_bf16 and cfg.H == 192 and cfg.k == 5 and 1 <= cfg.L <= 4 and 64 < cfg.C // 2 <= 96 and cfg.C % 8 == 0)
+    return bool(TUNE["fused_wn"] and cfg.act_bf16 and cfg.H == 192 and cfg.k == 5 and 1 <= cfg.L <= abi.WN_FUSED_MAX_LAYERS and 64 < cfg.C // 2 <= 96 and cfg.C % 8 == 0)
 
 
 class DecoderConfig:
@@ -1397,7 +1284,6 @@ class DecoderFunction(torch.autograd.Function):
 
             def wn_run(jobs, keep=wn_keep):
                 if jobs:                                        # (4.70 / 4.72 / 4.70 against 4.75 / 4.70 / 4.76 ms/step for one launch per class, three alternating pairs)
-                    L.glowtts_weightnorm_bwd_multi.argtypes = [c_void_p, c_int, c_void_p]
                     _lib.check(L.glowtts_weightnorm_bwd_multi((WnBwdJob * len(jobs))(*jobs), len(jobs), _lib.stream()), "glowtts_weightnorm_bwd_multi")
             if wn_pending:
                 TAIL["pending"].append(lambda jobs=wn_pending: wn_run(jobs))
@@ -1441,7 +1327,6 @@ class DecoderFunction(torch.autograd.Function):
         if dcond is not None:
             # (one launch; a non-finite gate gradient poisons its accumulator and reads NaN here - ADVICE r5)
             acc, dcond = dcond.contiguous(), torch.empty(dcond.shape, device=dcond.device)
-            _L().glowtts_fx_to_float.argtypes = [c_void_p, c_void_p, ctypes.c_int64, c_void_p]
             _lib.check(_L().glowtts_fx_to_float(acc.data_ptr(), dcond.data_ptr(), acc.numel(), _lib.stream()), "glowtts_fx_to_float")
         dpw = dpb = None
         if ctx.prow is not None:

@@ -15,10 +15,10 @@ import math
 import torch
 import torch.nn.functional as F
 
-from . import ops
+from . import _lib, ops
+from .abi import ROW_PAD
 from .conv_fn import AttentionBlock, EmbeddingRows, FFNBlock, ParamGate, RPRAttention, WgradTape, bf16_of, conv_rows, layernorm_rows
 
-ROW_PAD = 2
 
 # Test hook: when a list, every dropout site of a training-mode `encoder_forward` appends (site name, kind "linear" | "attention", site seed, rate,
 # shape of the tensor the element ids run over) in launch order - what a parity test needs to restate the masks (the step's seed word is added on
@@ -32,24 +32,6 @@ def _with_bf16(y, yb):
     return y
 
 
-_decl = False
-
-
-def _dur_lib():
-    global _decl
-    import ctypes
-    from . import _lib
-    L = _lib.lib()
-    if not _decl:
-        L.glowtts_dur_proj_supported.argtypes = [ctypes.c_int]
-        L.glowtts_dur_proj_fwd.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 4 + [ctypes.c_void_p]
-        L.glowtts_dur_proj_bwd.argtypes = [ctypes.c_void_p] * 9 + [ctypes.c_int] * 4 + [ctypes.c_void_p]
-        L.glowtts_prior_split_fwd.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [ctypes.c_void_p]
-        L.glowtts_prior_split_bwd.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [ctypes.c_void_p]
-        _decl = True
-    return L
-
-
 class DurProj(torch.autograd.Function):
     """Duration_Predictor's Projection (Modules.py:596-618: Conv1d(C -> 1, k = 1) on the masked features, times the mask) on rows, one launch per direction
     (csrc/dur_ops.hip; was mul / sum / add / mul forward and a dozen elementwise / reduce / fill launches at the head of the encoder's backward chain).
@@ -57,12 +39,11 @@ class DurProj(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, d, w, bias, mask, owner=None):
-        from . import _lib
         B, T = int(mask.shape[0]), int(mask.shape[2])
         C = int(d.shape[1])
         d, w, bias, mask = d.contiguous(), w.contiguous(), bias.contiguous(), mask.contiguous()
         out = torch.empty(B, 1, T, device=d.device)
-        _lib.check(_dur_lib().glowtts_dur_proj_fwd(_lib.ptr(d), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(mask), _lib.ptr(out), B, T, ROW_PAD, C, _lib.stream()),
+        _lib.check(_lib.lib().glowtts_dur_proj_fwd(_lib.ptr(d), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(mask), _lib.ptr(out), B, T, ROW_PAD, C, _lib.stream()),
                    "glowtts_dur_proj_fwd")
         ctx.save_for_backward(d, w, mask)
         ctx.owner = owner
@@ -70,7 +51,6 @@ class DurProj(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from . import _lib
         d, w, mask = ctx.saved_tensors
         B, T = int(mask.shape[0]), int(mask.shape[2])
         C = int(d.shape[1])
@@ -81,7 +61,7 @@ class DurProj(torch.autograd.Function):
         if counter is None:                                   # (first use inside a capture: a counter of this launch's own, zeroed by a fill)
             counter = torch.zeros(1, dtype=torch.int32, device=dev)
         scratch = torch.empty(B * (C + 1), device=dev)
-        _lib.check(_dur_lib().glowtts_dur_proj_bwd(_lib.ptr(g), _lib.ptr(mask), _lib.ptr(d), _lib.ptr(w), _lib.ptr(dd), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(scratch),
+        _lib.check(_lib.lib().glowtts_dur_proj_bwd(_lib.ptr(g), _lib.ptr(mask), _lib.ptr(d), _lib.ptr(w), _lib.ptr(dd), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(scratch),
                                                    _lib.ptr(counter), B, T, ROW_PAD, C, _lib.stream()), "glowtts_dur_proj_bwd")
         return dd, dw, db, None, None
 
@@ -92,17 +72,15 @@ class PriorSplit(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rows, B, T):
-        from . import _lib
         rows = rows.contiguous()
         M = int(rows.shape[1]) // 2
         mean, ls = torch.empty(B, M, T, device=rows.device), torch.empty(B, M, T, device=rows.device)
-        _lib.check(_dur_lib().glowtts_prior_split_fwd(_lib.ptr(rows), _lib.ptr(mean), _lib.ptr(ls), B, T, ROW_PAD, M, _lib.stream()), "glowtts_prior_split_fwd")
+        _lib.check(_lib.lib().glowtts_prior_split_fwd(_lib.ptr(rows), _lib.ptr(mean), _lib.ptr(ls), B, T, ROW_PAD, M, _lib.stream()), "glowtts_prior_split_fwd")
         ctx.dims = (B, T, M)
         return mean, ls
 
     @staticmethod
     def backward(ctx, dm, dl):
-        from . import _lib
         B, T, M = ctx.dims
         ref = dm if dm is not None else dl
         if ref is None:
@@ -110,7 +88,7 @@ class PriorSplit(torch.autograd.Function):
         dm = None if dm is None else dm.contiguous()
         dl = None if dl is None else dl.contiguous()
         drows = torch.empty(B * (T + 2 * ROW_PAD), 2 * M, device=ref.device)
-        _lib.check(_dur_lib().glowtts_prior_split_bwd(_lib.ptr(dm), _lib.ptr(dl), _lib.ptr(drows), B, T, ROW_PAD, M, _lib.stream()), "glowtts_prior_split_bwd")
+        _lib.check(_lib.lib().glowtts_prior_split_bwd(_lib.ptr(dm), _lib.ptr(dl), _lib.ptr(drows), B, T, ROW_PAD, M, _lib.stream()), "glowtts_prior_split_bwd")
         return drows, None, None
 
 
@@ -157,10 +135,7 @@ class _PackSets:
 
 def token_masks(token_lengths, T):
     """-> (mask [B, 1, T] float, rowmask [B * (T + 4)]) of a token batch, one launch (glowtts_token_masks)."""
-    import ctypes
-    from . import _lib
     L = _lib.lib()
-    L.glowtts_token_masks.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p]
     B = token_lengths.shape[0]
     tl = token_lengths.to(torch.int64).contiguous()
     mask = torch.empty(B, 1, T, device=tl.device)
@@ -361,7 +336,7 @@ def encoder_forward(P, hp, tokens, mask, speakers=None, prosodies=None, training
     # Projection to one channel: N = 1 is not a GEMM; a masked dot product per frame (multiply + row reduction: rocBLAS' gemv took
     # 82 us for these 3.5k x 256 rows, 5x the two elementwise kernels)
     wq = prefix + ".layer_Dict.Duration_Predictor.layer_Dict.Projection"
-    if d.is_cuda and d.dtype == torch.float32 and Pc[wq + ".weight"].dtype == torch.float32 and _dur_lib().glowtts_dur_proj_supported(int(d.shape[1])):
+    if d.is_cuda and d.dtype == torch.float32 and Pc[wq + ".weight"].dtype == torch.float32 and _lib.lib().glowtts_dur_proj_supported(int(d.shape[1])):
         log_dur = DurProj.apply(d, Pc[wq + ".weight"], Pc[wq + ".bias"], mask, cache)
     else:
         log_dur = ((d * Pc[wq + ".weight"][0, :, 0]).sum(-1) + Pc[wq + ".bias"]).view(B, Tp)[:, ROW_PAD:-ROW_PAD].unsqueeze(1) * mask

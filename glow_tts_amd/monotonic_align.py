@@ -40,7 +40,6 @@ def maximum_path_host(value, mask, max_neg_val=-1e9, num_threads=0):
     """The reference wrapper (monotonic_align/__init__.py:6-21) for HOST tensors / arrays, through the library's host twin
     `glowtts_mas_f32_host` (same arithmetic as core.pyx; utterances over host threads).  Not a fallback of the GPU path: `maximum_path`
     rejects CPU tensors; call this one explicitly when the score matrix lives in host memory."""
-    import ctypes
     import numpy as np
     is_t = torch.is_tensor(value)
     dtype = value.dtype if is_t else None
@@ -50,8 +49,6 @@ def maximum_path_host(value, mask, max_neg_val=-1e9, num_threads=0):
     t_x = np.ascontiguousarray(mk.sum(1)[:, 0], dtype=np.int32)
     t_y = np.ascontiguousarray(mk.sum(2)[:, 0], dtype=np.int32)
     path = np.zeros(v.shape, dtype=np.int32)
-    L = _lib.lib()
-    L.glowtts_mas_f32_host.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_int]
-    _lib.check(L.glowtts_mas_f32_host(v.ctypes.data, path.ctypes.data, t_x.ctypes.data, t_y.ctypes.data, v.shape[0], v.shape[1], v.shape[2],
+    _lib.check(_lib.lib().glowtts_mas_f32_host(v.ctypes.data, path.ctypes.data, t_x.ctypes.data, t_y.ctypes.data, v.shape[0], v.shape[1], v.shape[2],
                                       max_neg_val, int(num_threads)), "glowtts_mas_f32_host")
     return torch.from_numpy(path).to(dtype) if is_t else path

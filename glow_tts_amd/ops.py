@@ -5,47 +5,10 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import c_int, c_void_p
-
-F32, BF16 = 0, 1
-PERM_NONE, PERM_PAIR = 0, 1
-APRO_NONE, APRO_PAIRMUL, APRO_SQNEG = 0, 1, 2
-EPI_LINEAR, EPI_GATE, EPI_RESSKIP, EPI_COUPLE, EPI_DGATE = 0, 1, 2, 3, 4
-IO_A_BF16, IO_IN0_BF16, IO_OUT0_BF16 = 1, 2, 4      # glowtts_conv_args.io_flags
-WIO_DY_BF16, WIO_X_BF16, WIO_WIDE, WIO_DMA = 1, 2, 4, 8           # glowtts_wgrad_args.io_flags (DMA: grouped launches only)
-F_BIAS, F_RELU, F_ADD_IN0, F_MASK, F_ACCUM, F_FIRST, F_LAST, F_REVERSE, F_COLMASK, F_DROPOUT = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
-F_GATE_IN0 = 2048
-
-
-class ConvArgs(ctypes.Structure):
-    """Mirror of `glowtts_conv_args` (include/glowtts_hip.h)."""
-    _fields_ = [
-        ("a", c_void_p), ("lda", ctypes.c_int64),
-        ("a2", c_void_p), ("lda2", ctypes.c_int64),
-        ("ca1", c_int), ("ca", c_int),
-        ("apro", c_int),
-        ("rows", c_int),
-        ("w", c_void_p),
-        ("n", c_int), ("npad", c_int), ("kchunks", c_int),
-        ("taps", c_int), ("pad", c_int),
-        ("precision", c_int),
-        ("epi", c_int), ("flags", c_int),
-        ("h", c_int),
-        ("rows_per_utt", c_int),
-        ("bias", c_void_p),
-        ("rowmask", c_void_p),
-        ("cond", c_void_p), ("ldcond", ctypes.c_int64),
-        ("out0", c_void_p), ("ld0", ctypes.c_int64),
-        ("out1", c_void_p), ("ld1", ctypes.c_int64),
-        ("in0", c_void_p), ("ldi0", ctypes.c_int64),
-        ("batch", c_int),
-        ("a_bstride", ctypes.c_int64), ("w_bstride", ctypes.c_int64), ("bias_bstride", ctypes.c_int64),
-        ("out_bstride", ctypes.c_int64), ("mask_bstride", ctypes.c_int64),
-        ("ncols_valid", c_void_p),
-        ("seed", ctypes.c_uint32), ("drop_p", ctypes.c_float),
-        ("seed_ptr", c_void_p),
-        ("io_flags", c_int),
-    ]
+from ._lib import c_int
+from .abi import (APRO_NONE, APRO_PAIRMUL, APRO_SQNEG, BF16, EPI_COUPLE, EPI_DGATE, EPI_GATE, EPI_LINEAR, EPI_RESSKIP, F32, F_ACCUM, F_ADD_IN0, F_BIAS,  # noqa: F401
+                  F_COLMASK, F_DROPOUT, F_FIRST, F_GATE_IN0, F_LAST, F_MASK, F_RELU, F_REVERSE, IO_A_BF16, IO_IN0_BF16, IO_OUT0_BF16, PERM_NONE, PERM_PAIR,
+                  WIO_DMA, WIO_DY_BF16, WIO_WIDE, WIO_X_BF16, ConvArgs, PackJob)
 
 
 class PackedWeight:
@@ -71,12 +34,6 @@ def pack_weight(w, transpose=False, perm=PERM_NONE, perm_h=0, precision=BF16):
     return PackedWeight(buf, npad.value, kch.value, taps, precision, n)
 
 
-class PackJob(ctypes.Structure):
-    """Mirror of `glowtts_pack_job` (include/glowtts_hip.h)."""
-    _fields_ = [("w", c_void_p), ("packed", c_void_p)] + [(n, c_int) for n in
-                ("O", "I", "taps", "transpose", "perm", "perm_h", "N", "K", "npad", "kchunks", "block0", "reserved")]
-
-
 class PackSet:
     """Conv weights of different shapes packed by ONE launch (glowtts_pack_weight_multi) into one buffer.
     items: [(key, fp32 weight [O, I, taps], transpose)].  The device job table is built once; `run()` re-packs the current values
@@ -84,9 +41,6 @@ class PackSet:
 
     def __init__(self, items, precision=BF16):
         L = _lib.lib()
-        L.glowtts_pack_job_init.argtypes = [ctypes.POINTER(PackJob), c_void_p] + [c_int] * 7 + [c_void_p, c_int,
-                                            ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_int64)]
-        L.glowtts_pack_weight_multi.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p]
         assert items
         dev = items[0][1].device
         n = len(items)

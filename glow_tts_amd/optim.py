@@ -7,34 +7,12 @@ multi-tensor launch (`glowtts_radam_step`) over a device job table, and the glob
 (`glowtts_multi_grad_norm`).  Parameters whose data / gradients / moments are adjacent in memory - the decoder's stacked weight
 classes (decoder.LeafStack) - collapse into one job each.  State keys and `state_dict()` layout are the reference's
 (`step`, `exp_avg`, `exp_avg_sq`), so `Train.py:516,540` checkpoints load unchanged.  GPU only: no CPU fallback."""
-import ctypes
 import math
 
 import torch
 
 from . import _lib
-
-c_i64, c_p = ctypes.c_int64, ctypes.c_void_p
-
-
-class OptJob(ctypes.Structure):
-    """Mirror of `glowtts_opt_job`."""
-    _fields_ = [("p", c_p), ("g", c_p), ("m", c_p), ("v", c_p), ("n", c_i64), ("block0", c_i64)]
-
-
-_decl = False
-
-
-def _L():
-    global _decl
-    L = _lib.lib()
-    if not _decl:
-        L.glowtts_opt_chunk.restype = ctypes.c_int
-        L.glowtts_multi_grad_norm.argtypes = [c_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, c_p, c_p, c_p]
-        L.glowtts_multi_grad_scale.argtypes = [c_p, ctypes.c_int, ctypes.c_int, c_p, c_p]
-        L.glowtts_radam_step.argtypes = [c_p, ctypes.c_int, ctypes.c_int, c_p, c_p, c_p]
-        _decl = True
-    return L
+from .abi import OptJob
 
 
 class _JobTable:
@@ -53,7 +31,7 @@ class _JobTable:
         capturing = torch.cuda.is_current_stream_capturing()
         if sig == self.sig and not capturing:
             return
-        chunk = _L().glowtts_opt_chunk()
+        chunk = _lib.lib().glowtts_opt_chunk()
         order = range(len(items)) if canonical else sorted(range(len(items)), key=lambda i: sig[1 + i][0])
         jobs, cur = [], None
         for i in order:
@@ -88,7 +66,7 @@ def clip_grad_norm_(parameters, max_norm, _table_key=None):
     tab.update([(p.grad, p.grad, None, None) for p in params], dev, canonical=True)
     partial = torch.empty(tab.blocks, device=dev)
     out = torch.empty(2, device=dev)
-    L = _L()
+    L = _lib.lib()
     _lib.check(L.glowtts_multi_grad_norm(tab.table.data_ptr(), tab.njobs, tab.blocks, float(max_norm), partial.data_ptr(), out.data_ptr(),
                                          _lib.stream()), "glowtts_multi_grad_norm")
     _lib.check(L.glowtts_multi_grad_scale(tab.table.data_ptr(), tab.njobs, tab.blocks, out.data_ptr() + 4, _lib.stream()), "glowtts_multi_grad_scale")
@@ -169,7 +147,7 @@ class RAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        L = _L()
+        L = _lib.lib()
         for gi, group in enumerate(self.param_groups):
             plist = [p for p in group["params"] if p.grad is not None]
             if not plist:
@@ -205,7 +183,7 @@ def grad_norm_and_coef(parameters, max_norm, _table_key="fused"):
     tab = _CLIP_TABLES.setdefault((_table_key, id(params[0]), len(params)), _JobTable())
     tab.update([(p.grad, p.grad, None, None) for p in params], dev, canonical=True)
     partial, out = torch.empty(tab.blocks, device=dev), torch.empty(2, device=dev)
-    _lib.check(_L().glowtts_multi_grad_norm(tab.table.data_ptr(), tab.njobs, tab.blocks, float(max_norm), partial.data_ptr(), out.data_ptr(),
+    _lib.check(_lib.lib().glowtts_multi_grad_norm(tab.table.data_ptr(), tab.njobs, tab.blocks, float(max_norm), partial.data_ptr(), out.data_ptr(),
                                             _lib.stream()), "glowtts_multi_grad_norm")
     return out[0], out[1:2]
 

@@ -8,6 +8,9 @@ import math
 
 import torch
 
+from . import _lib
+from .abi import C2dPackJob as _PackJob, C2dReduceJob as _ReduceJob
+
 
 class _GRUFunction(torch.autograd.Function):
     """torch.nn.GRU (one layer, batch_first, h0 = 0) on the GPU: the input projection and the weight-gradient GEMMs are torch matmuls, the
@@ -15,10 +18,7 @@ class _GRUFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w_ih, w_hh, b_ih, b_hh):
-        import ctypes
-        from . import _lib
         L = _lib.lib()
-        L.glowtts_gru_fwd.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3 + [ctypes.c_void_p]
         B, T, _ = x.shape
         H = w_hh.shape[1]
         gi = torch.addmm(b_ih, x.reshape(B * T, -1), w_ih.t()).contiguous()
@@ -30,11 +30,8 @@ class _GRUFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dhs):
-        import ctypes
-        from . import _lib
         x, w_ih, w_hh, hs, keep = ctx.saved_tensors
         L = _lib.lib()
-        L.glowtts_gru_bwd.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_int] * 3 + [ctypes.c_void_p]
         B, T, H = hs.shape
         dgi, dgh = torch.empty(B, T, 3 * H, device=x.device), torch.empty(B, T, 3 * H, device=x.device)
         _lib.check(L.glowtts_gru_bwd(_lib.ptr(dhs.contiguous()), _lib.ptr(hs), _lib.ptr(keep), _lib.ptr(w_hh), _lib.ptr(dgi), _lib.ptr(dgh), B, T, H,
@@ -45,45 +42,12 @@ class _GRUFunction(torch.autograd.Function):
         return dx, dgi2.t() @ x.reshape(B * T, -1), dgh2.t() @ hprev, dgi2.sum(0), dgh2.sum(0)
 
 
-class _PackJob(ctypes.Structure):
-    """glowtts_c2d_pack_job (include/glowtts_hip.h)"""
-    _fields_ = [("w", ctypes.c_void_p), ("img", ctypes.c_void_p)] + [(k, ctypes.c_int) for k in ("Ci", "Co", "cls", "N", "K", "npad", "kchunks", "block0")]
-
-
-class _ReduceJob(ctypes.Structure):
-    """glowtts_c2d_reduce_job"""
-    _fields_ = [("partial", ctypes.c_void_p), ("dw", ctypes.c_void_p)] + [(k, ctypes.c_int) for k in ("splits", "Ci", "Co", "block0")]
-
-
-_C2D_DECLARED = []
-
-
-def _c2d():
-    from . import _lib
-    L = _lib.lib()
-    if not _C2D_DECLARED:
-        vp, ci, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-        L.glowtts_conv3x3s2_supported.argtypes = [ci] * 5
-        L.glowtts_conv3x3s2_image_bytes.argtypes = [ci, ci, ci, ctypes.POINTER(i64), ctypes.POINTER(i64)]
-        L.glowtts_conv3x3s2_pack_job_init.argtypes = [ctypes.POINTER(_PackJob), vp, ci, ci, ci, ci, vp, ci, ctypes.POINTER(ci)]
-        L.glowtts_conv3x3s2_pack.argtypes = [vp, ci, ci, ci, vp]
-        L.glowtts_conv3x3s2_fwd.argtypes = [vp, vp, vp, vp] + [ci] * 7 + [vp]
-        L.glowtts_conv3x3s2_dgrad.argtypes = [vp, ctypes.POINTER(vp), vp, vp] + [ci] * 6 + [vp]
-        L.glowtts_conv3x3s2_wgrad_scratch_floats.argtypes = [ci] * 5
-        L.glowtts_conv3x3s2_wgrad_scratch_floats.restype = i64
-        L.glowtts_conv3x3s2_wgrad.argtypes = [vp, vp, vp] + [ci] * 6 + [ctypes.POINTER(ci), vp]
-        L.glowtts_conv3x3s2_wgrad_reduce.argtypes = [ctypes.POINTER(_ReduceJob), ci, vp]
-        _C2D_DECLARED.append(True)
-    return L
-
-
 class _ConvImages:
     """Weight images of a conv stack (forward image per layer with Ci > 1, four data-gradient class images when gradients are needed) in one
     buffer, plus the device job table of the ONE launch that rewrites them from the current weights (static while the parameters stay in place)."""
 
     def __init__(self, weights, precision, need_bwd):
-        from . import _lib
-        L = _c2d()
+        L = _lib.lib()
         self.key = (tuple(w.data_ptr() for w in weights), int(precision), bool(need_bwd))
         dev = weights[0].device
         sizes = []
@@ -126,9 +90,8 @@ class _ConvImages:
         self.precision = precision
 
     def pack(self):
-        from . import _lib
         if self.table is not None:
-            _lib.check(_c2d().glowtts_conv3x3s2_pack(self.table.data_ptr(), self.njobs, self.blocks, self.precision, _lib.stream()), "glowtts_conv3x3s2_pack")
+            _lib.check(_lib.lib().glowtts_conv3x3s2_pack(self.table.data_ptr(), self.njobs, self.blocks, self.precision, _lib.stream()), "glowtts_conv3x3s2_pack")
 
 
 class _ConvStack(torch.autograd.Function):
@@ -139,8 +102,7 @@ class _ConvStack(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mels, images, precision, *weights):
-        from . import _lib
-        L = _c2d()
+        L = _lib.lib()
         x = mels.contiguous()                                  # [B][H = Mel][W = T] == channels-last with C = 1
         B, H, W = x.shape
         images.pack()
@@ -163,8 +125,7 @@ class _ConvStack(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        from . import _lib
-        L = _c2d()
+        L = _lib.lib()
         images, precision, shapes, B = ctx.cfg
         n = len(shapes)
         acts, weights = ctx.saved_tensors[:n + 1], ctx.saved_tensors[n + 1:]
@@ -174,7 +135,6 @@ class _ConvStack(torch.autograd.Function):
         # the last layer's ReLU (tiny: [B, 2, 13, 128] at the default sizes): d pre = d out where the output is not zero - one launch
         dout = dout.contiguous()
         dpre = torch.empty_like(dout)
-        L.glowtts_gate_bwd.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p]
         _lib.check(L.glowtts_gate_bwd(_lib.ptr(dout), _lib.ptr(acts[n]), None, _lib.ptr(dpre), dout.numel() // dout.shape[-1], int(dout.shape[-1]), 1.0, s),
                    "glowtts_gate_bwd")
         jobs = (_ReduceJob * n)()
@@ -209,7 +169,7 @@ def conv_stack_supported(convs, mels):
         return False
     if not all(c.kernel_size == (3, 3) and c.stride == (2, 2) and c.padding == (1, 1) and c.bias is None and c.weight.dtype == torch.float32 for c in convs):
         return False
-    L = _c2d()
+    L = _lib.lib()
     B, H, W = (int(v) for v in mels.shape)
     for c in convs:
         if not L.glowtts_conv3x3s2_supported(B, H, W, c.in_channels, c.out_channels):
@@ -233,23 +193,6 @@ def conv_stack_hip(convs, mels, precision, cache=None):
     return x.permute(0, 2, 3, 1).reshape(B, W, C * H)
 
 
-_GST_DECLARED = []
-
-
-def _gst():
-    from . import _lib
-    L = _lib.lib()
-    if not _GST_DECLARED:
-        vp, ci, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-        L.glowtts_gst_supported.argtypes = [ci] * 7
-        L.glowtts_gst_keep_floats.argtypes = [ci] * 6
-        L.glowtts_gst_keep_floats.restype = i64
-        L.glowtts_gst_fwd.argtypes = [vp, vp, ci] + [vp] * 13 + [ci] * 7 + [vp]
-        L.glowtts_gst_bwd.argtypes = [vp, vp, vp, ci] + [vp] * 18 + [ci] * 7 + [vp]
-        _GST_DECLARED.append(True)
-    return L
-
-
 class _GSTTail(torch.autograd.Function):
     """Modules.py:371-385 behind the GRU - the state at each utterance's last valid step attends over tanh(gst_Tokens) - as two launches forward (token keys / values;
     one workgroup per utterance for gather, query, four-head softmax attention and output projection) and three backward (csrc/gst_ops.hip).  PyTorch ran ~35 / ~45
@@ -258,8 +201,7 @@ class _GSTTail(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, hs, lengths, stride_prod, heads, tokens, Wq, bq, Wk, bk, Wv, bv, Wp, bp):
-        from . import _lib
-        L = _gst()
+        L = _lib.lib()
         hs = hs.contiguous()
         B, Tp, G = hs.shape
         I, NT = tokens.shape
@@ -279,8 +221,7 @@ class _GSTTail(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        from . import _lib
-        L = _gst()
+        L = _lib.lib()
         keep, lengths, tokens, Wq, Wk, Wv, Wp, K, V = ctx.saved_tensors
         B, Tp, G, C, H, NT, I, sp, hbq, hbk, hbv, hbp = ctx.cfg
         dev = dout.device
@@ -388,7 +329,7 @@ class Prosody_Encoder(torch.nn.Module):
         att = self.layer_Dict["Attention"]
         q_, k_, v_, p_ = (att.layer_Dict[n] for n in ("Query", "Key", "Value", "Projection"))
         if (self.use_hip_gst and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and
-                _gst().glowtts_gst_supported(x.size(0), x.size(1), x.size(2), q_.weight.shape[0], att.heads, self.gst_Tokens.shape[1], self.gst_Tokens.shape[0])):
+                _lib.lib().glowtts_gst_supported(x.size(0), x.size(1), x.size(2), q_.weight.shape[0], att.heads, self.gst_Tokens.shape[1], self.gst_Tokens.shape[0])):
             sq = lambda w: w.squeeze(-1)                       # Conv1d(k = 1) weights [O, I, 1]
             return _GSTTail.apply(x, lengths, int(math.prod(self.strides)), att.heads, self.gst_Tokens, sq(q_.weight), q_.bias, sq(k_.weight), k_.bias,
                                   sq(v_.weight), v_.bias, sq(p_.weight), p_.bias)

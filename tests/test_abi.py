@@ -58,7 +58,8 @@ def test_host_mas_twin_matches_core_pyx_vectors(golden_dir):
     import numpy as np
     import torch
     L = ctypes.CDLL(os.path.join(REPO, "glow_tts_amd", "libglowtts_hip.so"))
-    L.glowtts_mas_f32_host.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_int]
+    from glow_tts_amd import abi
+    _, L.glowtts_mas_f32_host.argtypes = abi.SIGNATURES["glowtts_mas_f32_host"]
     d = np.load(os.path.join(golden_dir, "mas_cases.npz"))
     for name in ["ragged", "ties", "square", "one_token", "x1000", "wide", "more_tokens"]:
         for threads in (1, 3):
@@ -169,3 +170,203 @@ def test_hot_kernels_use_no_scratch_memory(tmp_path):
                 assert scratch == 0, f"{name} spills: {scratch} bytes of scratch per lane at {vgpr} VGPRs"
     for h, n in seen.items():
         assert n > 0 or h == r"optim|radam|adam", f"pattern {h} matched no kernel"
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# glow_tts_amd/abi.py - the package's only restatement of include/glowtts_hip.h - against the header: signatures by parsing the prototypes,
+# struct layouts through the C compiler, constants by value.  A wrong entry fails here, on the CPU, instead of truncating a pointer on the GPU.
+# ---------------------------------------------------------------------------------------------------------------------------------------
+HEADER = os.path.join(REPO, "include", "glowtts_hip.h")
+C_SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "uint32_t": ctypes.c_uint32}
+STRUCT_RE = re.compile(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", re.S)
+
+
+def header_text():
+    return re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S))
+
+
+def c_param_kind(decl):
+    """`const float *x` -> "ptr", `int64_t rows` -> "int64_t"; an unknown type raises."""
+    if "*" in decl:
+        return "ptr"
+    words = [w for w in decl.split() if w != "const"]
+    kind = " ".join(words[:-1])                              # (every parameter of the header is named)
+    if kind not in C_SCALARS:
+        raise ValueError(f"parameter type of `{decl.strip()}` is not one the signature check knows")
+    return kind
+
+
+def header_prototypes(text):
+    """name -> (return kind, [parameter kinds]) of every prototype.  Whatever is left of the header after the struct bodies, the preprocessor lines
+    and the extern "C" braces must be a prototype of known return and parameter types: anything else raises instead of being skipped."""
+    text = re.sub(r'extern\s+"C"\s*\{', " ", re.sub(r"(?m)^\s*#.*$", " ", STRUCT_RE.sub(" ", text)))
+    protos = {}
+    for stmt in text.split(";"):
+        stmt = " ".join(stmt.split())
+        if stmt in ("", "}"):
+            continue
+        m = re.fullmatch(r"(\w+) (glowtts_\w+) ?\((.*)\)", stmt)
+        if not m or m.group(1) not in ("int", "int64_t", "void") or m.group(2) in protos:
+            raise ValueError(f"not a prototype the signature check knows: `{stmt}`")
+        params = m.group(3).strip()
+        protos[m.group(2)] = (m.group(1), [] if params == "void" else [c_param_kind(p) for p in params.split(",")])
+    return protos
+
+
+def ctypes_kind(t):
+    if t is None:
+        return "void"
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(t, type) and issubclass(t, ctypes._Pointer)):
+        return "ptr"
+    return {v: k for k, v in C_SCALARS.items()}[t]           # (KeyError: a ctypes type no parameter of the header has)
+
+
+def signature_errors(protos, table):
+    errs = [f"{n}: in the header, not in abi.SIGNATURES" for n in protos.keys() - table.keys()]
+    errs += [f"{n}: in abi.SIGNATURES, not in the header" for n in table.keys() - protos.keys()]
+    for n in sorted(protos.keys() & table.keys()):
+        (ret, params), (restype, argtypes) = protos[n], table[n]
+        if ctypes_kind(restype) != ret:
+            errs.append(f"{n}: returns {ret}, restype is {restype}")
+        if len(params) != len(argtypes):
+            errs.append(f"{n}: {len(params)} parameters, {len(argtypes)} argtypes")
+            continue
+        errs += [f"{n}: parameter {i} is {k}, argtypes[{i}] is {t}" for i, (k, t) in enumerate(zip(params, argtypes)) if ctypes_kind(t) != k]
+    return errs
+
+
+def header_structs(text):
+    """C struct name -> field names in order (`int a, b;`, `const float *p, *q[N];` and array declarators handled)."""
+    out = {}
+    for tag, body, name in STRUCT_RE.findall(text):
+        assert tag == name, (tag, name)
+        fields = []
+        for decl in body.split(";"):
+            if decl.strip():
+                fields += [re.fullmatch(r".*?(\w+)\s*(\[[^\]]*\])?\s*", d, re.S).group(1) for d in decl.split(",")]
+        out[name] = fields
+    return out
+
+
+def c_layouts(structs, tmp_path):
+    """C struct name -> (sizeof, [(field, offsetof, sizeof)]) as the system C compiler lays the header's structs out."""
+    import subprocess
+    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', 'int main(void) {']
+    for s, fields in structs.items():
+        lines.append(f'    printf("S {s} %zu\\n", sizeof({s}));')
+        lines += [f'    printf("F {s} {f} %zu %zu\\n", offsetof({s}, {f}), sizeof((({s} *)0)->{f}));' for f in fields]
+    lines += ['    return 0;', '}']
+    (tmp_path / "layout.c").write_text("\n".join(lines) + "\n")
+    subprocess.run([os.environ.get("CC", "cc"), "-o", str(tmp_path / "layout"), str(tmp_path / "layout.c")], check=True)
+    out = {}
+    for line in subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.splitlines():
+        w = line.split()
+        if w[0] == "S":
+            out[w[1]] = (int(w[2]), [])
+        else:
+            out[w[1]][1].append((w[2], int(w[3]), int(w[4])))
+    return out
+
+
+def mirror_classes():
+    from glow_tts_amd import abi
+    return [v for v in vars(abi).values() if isinstance(v, type) and issubclass(v, ctypes.Structure) and v is not ctypes.Structure]
+
+
+def layout_errors(layouts, mirrors):
+    """Every header struct mirrored, every mirror's C struct present; per struct the same size, field count, names (a trailing underscore in Python
+    ignored: `in_` is `in`) and (offset, size) sequence."""
+    named = {}
+    for m in mirrors:
+        named.setdefault(getattr(m, "c_name", None), []).append(m)
+    errs = [f"{s}: no mirror in abi.py" for s in layouts.keys() - named.keys()]
+    for c_name, ms in named.items():
+        for m in ms:
+            if c_name not in layouts:
+                errs.append(f"{m.__name__}: names `{c_name}`, which is no struct of the header")
+                continue
+            size, fields = layouts[c_name]
+            mine = [(n.rstrip("_"), getattr(m, n).offset, getattr(m, n).size) for n, *_ in m._fields_]
+            if ctypes.sizeof(m) != size:
+                errs.append(f"{c_name}: sizeof is {size}, {m.__name__} has {ctypes.sizeof(m)}")
+            if len(mine) != len(fields):
+                errs.append(f"{c_name}: {len(fields)} fields, {m.__name__} has {len(mine)}")
+            if [f[0] for f in mine] != [f[0] for f in fields]:
+                errs.append(f"{c_name}: field names {[f[0] for f in fields]}, {m.__name__} has {[f[0] for f in mine]}")
+            if [f[1:] for f in mine] != [f[1:] for f in fields]:
+                errs.append(f"{c_name}: (offset, size) sequence {[f[1:] for f in fields]}, {m.__name__} has {[f[1:] for f in mine]}")
+    return errs
+
+
+def test_signature_table_matches_header_prototypes():
+    from glow_tts_amd import abi
+    protos = header_prototypes(header_text())
+    assert set(protos) == set(declared_symbols())
+    assert signature_errors(protos, abi.SIGNATURES) == []
+    bench = {"glowtts_wavenet_fwd": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),      # what bench.py assigns itself
+             "glowtts_launch_count": (ctypes.c_int64, [ctypes.c_char_p]),
+             "glowtts_mfma_clock_probe": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_void_p])}
+    for n, sig in bench.items():
+        assert abi.SIGNATURES[n] == sig, n
+    with pytest.raises(ValueError):
+        c_param_kind("double x")
+    with pytest.raises(ValueError):
+        header_prototypes("int glowtts_a(int n); typedef int glowtts_t;")
+
+
+def test_struct_mirrors_match_compiled_layout(tmp_path):
+    structs = header_structs(header_text())
+    assert structs["glowtts_wn_bwd_job"] == ["dw", "v", "g", "inv_norm", "dv", "dg", "rows", "cols", "reserved"]
+    assert structs["glowtts_flow_params"][3:7] == ["start", "in", "rs", "end"]
+    assert layout_errors(c_layouts(structs, tmp_path), mirror_classes()) == []
+
+
+def test_constants_match_header_defines():
+    from glow_tts_amd import abi
+    defines = {k: int(v) for k, v in re.findall(r"(?m)^\s*#define\s+GLOWTTS_(\w+)\s+(-?\d+)\s*$", header_text())}
+    mine = {k: v for k, v in vars(abi).items() if k.isupper() and isinstance(v, int)}
+    assert mine == defines                                   # every define restated, no constant of abi.py without one, equal values
+    for p in ("PERM_", "APRO_", "EPI_", "F_", "WIO_", "IO_"):
+        assert any(k.startswith(p) for k in defines), p
+    for k in ("ABI_VERSION", "MAX_WN_LAYERS", "ROW_PAD", "WN_SLAB_BYTES", "PREP_MAX_JOBS", "SUM_MAX_SEGS", "WN_BWD_MAX_JOBS", "WN_FUSED_MAX_LAYERS"):
+        assert k in defines
+
+
+def test_abi_checks_report_a_wrong_signature_and_a_swapped_field(tmp_path):
+    from glow_tts_amd import abi
+    protos = header_prototypes(header_text())
+    assert protos["glowtts_fill_zero"] == ("int", ["ptr", "int64_t", "ptr"])
+    wrong = dict(abi.SIGNATURES, glowtts_fill_zero=(ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]))
+    errs = signature_errors(protos, wrong)
+    assert len(errs) == 1 and errs[0].startswith("glowtts_fill_zero: parameter 1 is int64_t")
+
+    class Swapped(ctypes.Structure):                         # glowtts_wn_bwd_job with `int64_t rows` and `int cols` exchanged
+        c_name = "glowtts_wn_bwd_job"
+        _fields_ = [(n, ctypes.c_void_p) for n in ("dw", "v", "g", "inv_norm", "dv", "dg")] + [("cols", ctypes.c_int), ("rows", ctypes.c_int64), ("reserved", ctypes.c_int)]
+    layouts = c_layouts(header_structs(header_text()), tmp_path)
+    errs = layout_errors(layouts, [m for m in mirror_classes() if m.c_name != "glowtts_wn_bwd_job"] + [Swapped])
+    assert errs and all(e.startswith("glowtts_wn_bwd_job:") for e in errs) and any("(offset, size)" in e for e in errs)
+
+
+def test_package_declares_the_abi_in_one_place():
+    pkg = os.path.join(REPO, "glow_tts_amd")
+    for root, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith(".py") and os.path.relpath(os.path.join(root, f), pkg) not in ("abi.py", "_lib.py"):
+                src = open(os.path.join(root, f)).read()
+                assert not re.search(r"\.argtypes|\.restype", src), f"{f} declares a signature: abi.SIGNATURES is the place"
+                assert not re.search(r"\(\s*(ctypes\.)?(Structure|Union)\s*\)", src), f"{f} defines a ctypes structure: abi.py is the place"
+    assert "CDLL" not in open(os.path.join(pkg, "abi.py")).read()
+
+
+def test_loaded_library_is_bound_as_tabulated():
+    from glow_tts_amd import _lib, abi
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    L = _lib.lib()
+    for n, (restype, argtypes) in abi.SIGNATURES.items():
+        fn = getattr(L, n)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, n
+    with pytest.raises(_lib.GlowTTSHipError, match="glowtts_not_there"):
+        _lib._symbol(L, "glowtts_not_there")

@@ -8,7 +8,6 @@ guard bands that must come back untouched; rowmask is what glowtts_squeeze_rows 
 No tolerance below was set from a kernel's output.  Each is one of: exact; assert_elementwise (16 * 2**-24 * sum|terms|); assert_reduction
 (1e-5 * sum|terms|); the propagated statistics bar - all derived in flow_ops_ref.py.  The worst error / bar per entry point is printed at the end of
 the module (a report of how much room the derived bars leave, not an assertion)."""
-import ctypes
 import json
 import math
 import os
@@ -27,7 +26,6 @@ NAN = float("nan")
 GUARD = 64                     # elements of sentinel either side of every device buffer (256 bytes of fp32: the body stays 16-byte aligned)
 SENT = -7.0                    # exact in fp32 and bf16
 E_ARG = -1
-c_i64, c_int, vp = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p
 
 CHANNELS = [4, 12, 20, 24, 36, 160, 164, 264, 1024]
 SMALL_ROWS = [(1, 1), (4, 5), (1, 33), (5, 9)]          # B (T + 4) = 5 rows, exactly one block of 36, 37, 64 + 1
@@ -45,23 +43,11 @@ def _shapes():
 
 
 SHAPES = _shapes()
-_declared = False
 
 
 def L():
-    """The library with argtypes for the entry points decoder.py does not bind."""
-    global _declared
-    from glow_tts_amd import decoder as D
-    lib = D._L()
-    if not _declared:
-        lib.glowtts_actnorm_inv1x1_pass.argtypes = [vp] * 7 + [c_i64, c_int, vp]
-        lib.glowtts_actnorm_inv1x1_pass_bf.argtypes = [vp] * 8 + [c_i64, c_int, vp]
-        lib.glowtts_coupling_bwd.argtypes = [vp] * 6 + [c_i64, c_int, c_int, c_int, vp]
-        lib.glowtts_coupling_bwd_bf16.argtypes = [vp] * 7 + [c_i64, c_int, c_int, c_int, vp]
-        lib.glowtts_actnorm_inv1x1_bwd.argtypes = [vp] * 9 + [c_i64, c_int, vp]
-        lib.glowtts_actnorm_inv1x1_bwd_coupling.argtypes = [vp] * 8 + [c_i64, c_int] + [vp] * 5 + [c_int, c_int, vp]
-        _declared = True
-    return lib
+    from glow_tts_amd import _lib
+    return _lib.lib()
 
 
 def stream():

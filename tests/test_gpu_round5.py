@@ -4,7 +4,6 @@
   GRU recurrence, rows in regs  == torch.nn.GRU (Modules.py:338-343, 371), forward and every gradient
   GLOWTTS_F_GATE_IN0            == data-gradient conv followed by the separate relu / dropout gate pass, to bf16 rounding of the intermediate
   row splits of weight gradients (encoder tape, decoder one-tap group) == the unsplit launches, to fp32 summation order"""
-import ctypes
 
 import pytest
 import torch
@@ -26,7 +25,6 @@ def test_token_masks_equal_mask_generate_and_pad():
 def test_sum_slices_and_segments(S):
     from glow_tts_amd import _lib, decoder as D
     L = D._L()
-    L.glowtts_sum_slices.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]
     torch.manual_seed(S)
     n = 4 * 12345
     part = torch.randn(S, n, device="cuda")

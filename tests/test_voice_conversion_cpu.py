@@ -16,7 +16,9 @@ def test_flow_encode_is_declared_bound_and_exported():
     header = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "glowtts_hip.h")).read(), flags=re.S)
     assert re.search(r"\bint\s+glowtts_flow_encode\s*\(\s*const glowtts_flow_dims \*d,\s*const glowtts_flow_params \*p,\s*const glowtts_flow_acts \*a,"
                      r"\s*void \*stream\)", header)
-    assert "L.glowtts_flow_encode.argtypes = [c_void_p] * 4" in open(os.path.join(REPO, "glow_tts_amd", "decoder.py")).read()
+    from glow_tts_amd import abi
+    restype, argtypes = abi.SIGNATURES["glowtts_flow_encode"]
+    assert restype is ctypes.c_int and argtypes == [ctypes.c_void_p] * 4
     so = os.path.join(REPO, "glow_tts_amd", "libglowtts_hip.so")
     if not os.path.exists(so):
         import __graft_entry__

@@ -14,7 +14,6 @@ import torch
 from glow_tts_amd import _lib
 
 L = _lib.lib()
-L.glowtts_mfma_clock_probe.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]
 ncu = torch.cuda.get_device_properties(0).multi_processor_count
 out = torch.zeros(ncu, 2, dtype=torch.int64, device="cuda")
 khz = ctypes.c_int(0)

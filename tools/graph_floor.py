@@ -4,8 +4,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from glow_tts_amd import _lib
 L = _lib.lib()
-import ctypes
-L.glowtts_fill_zero.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
 x = torch.ones(1 << 20, device="cuda")
 for n_elem in (64, 1 << 20):
     s = torch.cuda.Stream()

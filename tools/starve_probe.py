@@ -1,7 +1,7 @@
 """How fast does a chain of one-workgroup kernels on a second stream advance beside back-to-back fused coupling launches (249 one-per-CU workgroups)?
 Stream A: N fused forward launches (B utterances).  Stream B: a chain of glowtts_debug_stamp launches (one wave each, each writes the wall clock).  Both as ONE captured
 hipGraph (fork / join), replayed; prints the stamps' spacing while A is busy and while it is idle.   usage: starve_probe.py [B=32] [variant]"""
-import ctypes, os, sys
+import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
@@ -11,7 +11,6 @@ NA, NB = 12, 60
 case = bench.fused_forward_case(B, 400)
 run = case["run"]
 L = D._L()
-L.glowtts_debug_stamp.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 buf = torch.zeros(NB + 8, dtype=torch.int64, device="cuda")
 small = torch.zeros(3840, device="cuda")
 sa, sb = torch.cuda.Stream(), torch.cuda.Stream()

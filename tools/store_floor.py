@@ -1,11 +1,10 @@
 """What a dependent chain of STORE-only kernels costs per launch on the 8-XCD part: the same 12 MiB buffer rewritten vs 50 different buffers
 (glowtts_fill_zero, hipGraph replay, no host time)."""
-import os, sys, ctypes
+import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from glow_tts_amd import _lib
 L = _lib.lib()
-L.glowtts_fill_zero.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
 for mb in (1, 4, 12, 48, 192):
     n = mb * (1 << 20) // 4
     for nbuf in (1, 50):
