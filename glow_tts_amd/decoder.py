@@ -66,31 +66,31 @@ def _engine_callbacks_ok():
 # backward queues the tail's launches here instead of issuing them; `flush_tail_wgrads()` issues them (bench.py captures that as a
 # second hipGraph).  The gradient tensors of the tail classes exist (autograd has already handed them to .grad) but hold no data until then.
 TAIL = {"defer": False, "pending": []}
-# Measured design choices that tools / tests may flip programmatically (never read from the environment: DESIGN.md section 5 has the numbers).
-#   wgrad_wide: 16-byte staging items in the weight-gradient kernel; fuse_coupling_bwd: the next flow's coupling backward rides in the
-#   ActNorm / 1x1 backward pass; wgrad_split: weight gradients in n segments on a second stream (1 = one grouped launch per class);
+# Measured design choices that tools / tests may flip programmatically (never read from the environment).  One line per switch; the numbers behind
+# each are in DESIGN.md section 5.
+#   chain_actnorm: a flow on the fused coupling launch also applies the NEXT flow's ActNorm + 1x1 conv in its epilogue (one launch less per flow)
+#   enc_ln_qkv / enc_proj_ln: the encoder's block-closing LayerNorm computes the next block's Q|K|V conv / the attention projection carries its LayerNorm
+#   wgrad_dma: the LDS-DMA weight-gradient kernel for groups of bf16 rows (csrc/wgrad_cl.hip wgrad_dma_kernel)
+#   wgrad_wide: 16-byte staging items in the weight-gradient kernel
+#   wgrad_tail_splits: row splits S of the one-tap weight-gradient group, summed in a fixed order by one launch (round 5)
+#   wgrad_balance: the In_l group as a two-phase launch (WgradGroup.balance, round 6).  OFF: the idle CUs of the unbalanced second round are where the
+#       encoder's backward runs, so the step takes as long.  What would turn it on: a step whose second half is not shared with another stream
+#   prep_fused: training on the fused bf16 path forms w = g v / ||v|| and every weight image in ONE launch (csrc/prep_ops.hip, round 4)
+#   prep_early: that launch is issued before the text encoder is launched on its stream (see EARLY)
+#   prep_twin: the In_l pairs are read once - the forward image's tiles also write the two transposed half images
+#   prep_bwd_late: the images only the backward reads as a second, deferred launch (round 5).  OFF since round 6: it saves ~40 us at the head of the
+#       step and adds two cross-stream edges to the replayed graph.  What would turn it on: those two edges costing the graph less than ~40 us
+#   prep_bwd_gentle: that deferred launch with one workgroup per CU (it runs beside the log-prior's latency-critical kernels)
+#   fuse_coupling_bwd: the next flow's coupling backward rides in the ActNorm / 1x1 backward pass
 #   act_bf16: WaveNet state / gates / gate gradients stored as bf16 in bf16 precision
-#   fused_wn_bwd: its data gradients likewise (csrc/wavenet_fused_bwd.hip; every mode but GR's per-frame pitch), for flows 0 .. n-1 - the flows the backward
-#       reaches LAST.  n: a count, True = all flows, -1 (default) = automatic: all flows when the batch leaves a quarter of the CUs free, else 7 of 12 (5 until the encoder's attention backward got shorter).  Alone the fused kernel is faster than the ten launches it
-#       replaces (126 vs 155 us per flow, 151 vs 178 with cold caches: tools/bench_wn.py), but a workgroup that owns a whole CU (150 KB of LDS,
-#       3 x 168 VGPRs per SIMD) for 126 us leaves the encoder stream's backward no CU to share, and while that stream is busy the step LOSES:
-#       all 12 flows 6.33 vs 5.90 ms/step, 9 flows 5.95.  The encoder's backward has drained by the time the decoder's backward is half way:
-#       the last 6 flows fused 5.70 vs 5.85 and 5.82 vs 5.92 ms/step on two boxes
 #   fused_wn: the coupling network of a flow (Start .. End + coupling) as ONE launch (csrc/wavenet_fused.hip) where its shape contract holds
-#   fused_wn_fwd_skip: training forward, the first n flows on the per-conv launches (they run beside the text encoder's forward, which the
-#       CU-filling fused workgroups starve).  -1 (default) = automatic: 1 for a chip-filling batch, else 0.  The encoder's forward is what the
-#       first half of the step waits for (enc_fwd_project 87 us after dec_fwd_end with every flow fused); one per-conv flow gives it the
-#       CUs it needs: 5.55 / 5.56 vs 5.61 / 5.59 ms/step (2 flows: 5.57 / 5.56), same box, alternating runs.  (Round 3's first measurement,
-#       before the alignment test compared path QUALITY instead of a count of moved frames, had left it off.)
-#   bwd_packs_side: a scheduling experiment of round 3, off: the backward-only weight images
-#       packed on a third stream joined when the backward starts (5.61 / 5.67 vs 5.68 / 5.66 ms/step: inside the spread)
-#   enc_pack_split: round-4 experiment, off.  The encoder's weight images in two launches - the prenet's forward images on its stream, the other 95 % on a
-#       third stream forked from the origin stream and joined in front of the transformer (forked from the encoder's stream - a fork of a fork - hipStreamEndCapture
-#       crashed on ROCm 7.2): the encoder's projection then lands 7 us after the decoder's forward instead of 60-90, but the three packing kernels share the
-#       memory system at the head of the step and the decoder's forward ends 45 us later: 5.24-5.30 against 5.20-5.23 ms/step (three alternating pairs)
-#   prep_fused: training on the fused bf16 path forms w = g v / ||v|| and every weight image in ONE launch (csrc/prep_ops.hip) instead of 4 weight-norm +
-#       ~22 packing launches (0.42 -> ~0.1 ms at the head of the step, round 4)
-TUNE = {"chain_actnorm": True, "enc_ln_qkv": True, "enc_proj_ln": True, "enc_pack_split": False, "wgrad_dma": True, "wgrad_dma_k1": False, "prep_fused": True, "prep_early": True, "wgrad_wide": True, "fuse_coupling_bwd": True, "wgrad_split": 1, "act_bf16": True, "fused_wn": True, "fused_wn_bwd": -1, "fused_wn_bwd_from": 0, "fused_wn_fwd_skip": -1, "bwd_packs_side": 0, "fwd_packs_split": 0, "cond_hip": True, "drop_skip32": True, "wgrad_tail_splits": 2, "prep_bwd_late": False, "prep_bwd_gentle": True, "tail_aside": True, "wgrad_balance": False, "prep_twin": True}
+#   fused_wn_fwd_skip: training forward, the first n flows on the per-conv launches; -1 (default) = automatic (fused_flow_plan)
+#   fused_wn_bwd: flows 0 .. n-1 - the flows the backward reaches LAST - on the fused data-gradient kernel (csrc/wavenet_fused_bwd.hip; every mode but
+#       GR's per-frame pitch).  n: a count, True = all flows, -1 (default) = automatic (fused_flow_plan)
+#   cond_hip: the decoder's conditioning convs through CondLinear (csrc/cond_ops.hip) instead of weight norm + a batched matmul
+#   drop_skip32: a fused forward flow whose backward reads the bf16 skip sum does not keep the fp32 one
+#   tail_aside: conditioned modes run the weight-gradient tail on the weight-gradient stream beside the conditioning encoders' backward
+TUNE = {"chain_actnorm": True, "enc_ln_qkv": True, "enc_proj_ln": True, "wgrad_dma": True, "prep_fused": True, "prep_early": True, "wgrad_wide": True, "fuse_coupling_bwd": True, "act_bf16": True, "fused_wn": True, "fused_wn_bwd": -1, "fused_wn_fwd_skip": -1, "cond_hip": True, "drop_skip32": True, "wgrad_tail_splits": 2, "prep_bwd_late": False, "prep_bwd_gentle": True, "tail_aside": True, "wgrad_balance": False, "prep_twin": True}
 STAMPS = {"buf": None, "names": []}      # tools/step_timeline.py: an int64 device buffer; stamp(name) appends a slot
 
 
@@ -146,13 +146,6 @@ def flush_tail_wgrads():
         fn()
 
 
-def _pack_stream(device):
-    key = "pack:" + str(device)
-    if key not in _WSTREAM:
-        _WSTREAM[key] = torch.cuda.Stream(device=device)
-    return _WSTREAM[key]
-
-
 def _wgrad_stream(device):
     key = str(device)
     if key not in _WSTREAM:
@@ -162,7 +155,8 @@ def _wgrad_stream(device):
 
 class WgradGroup:
     """Weight-gradient problems sharing (rows, taps, X prologue).  Problems are added in *segments* (one per flow); the whole
-    job table is uploaded once and every segment is one glowtts_wgrad_grouped launch (tile indices restart per segment)."""
+    job table is uploaded once and every segment is one glowtts_wgrad_grouped launch (tile indices restart per segment).
+    dma_k1: a one-tap group takes the LDS-DMA kernel only when its builder asks (the decoder's tail group in row splits); None = no."""
 
     def __init__(self, rows, taps, precision, xpro=ops.APRO_NONE, io_flags=0, tag="dec", dma_k1=None):
         self.rows, self.taps, self.precision, self.xpro, self.io_flags, self.tag = rows, taps, precision, xpro, io_flags, tag
@@ -171,7 +165,7 @@ class WgradGroup:
         # 16-byte staging items (glowtts_wgrad WIO_WIDE): both operands bf16, no prologue, and every job 8-channel / 16-byte aligned
         self._wide = io_flags in (0, ops.WIO_DY_BF16 | ops.WIO_X_BF16) and xpro == ops.APRO_NONE and precision == ops.BF16 and TUNE["wgrad_wide"]
         # the LDS-DMA / 16x16x32 kernel (csrc/wgrad_cl.hip wgrad_dma_kernel): both operands bf16 rows
-        self._dma = self._wide and io_flags == (ops.WIO_DY_BF16 | ops.WIO_X_BF16) and bool(TUNE["wgrad_dma"]) and (taps > 1 or bool(TUNE["wgrad_dma_k1"] if dma_k1 is None else dma_k1))
+        self._dma = self._wide and io_flags == (ops.WIO_DY_BF16 | ops.WIO_X_BF16) and bool(TUNE["wgrad_dma"]) and (taps > 1 or bool(dma_k1))
 
     def add(self, dy, lddy, m, x, ldx, ca, dw, dbias, perm=ops.PERM_NONE, perm_h=0):
         j = WgradJob()
@@ -346,6 +340,41 @@ def fused_wn_supported(cfg):
     return bool(TUNE["fused_wn"] and cfg.act_bf16 and cfg.H == 192 and cfg.k == 5 and 1 <= cfg.L <= abi.WN_FUSED_MAX_LAYERS and 64 < cfg.C // 2 <= 96 and cfg.C % 8 == 0)
 
 
+def fused_flow_plan(cfg, rows, cus, need_bwd, conditioned, fused_bwd_ok=True, have_image=True):
+    """The step's scheduling policy for the fused coupling-network kernels -> (nskip, nfb): the first `nskip` flows of the training forward stay on the
+    per-conv launches (TUNE["fused_wn_fwd_skip"]), flows 0 .. nfb-1 of the backward take the fused data-gradient kernel (TUNE["fused_wn_bwd"]).
+    rows: B * (T + 4) of the batch (None: unknown); cus: the device's CU count; conditioned: a conditioning vector is set; fused_bwd_ok / have_image: the
+    fused backward serves this mode / the fused forward images exist (fused_wn_supported).  Pure: reads TUNE and nothing from the device."""
+    F_, Lw = cfg.F, cfg.L
+    nwg = -(-rows // (64 - 4 * (Lw - 1))) if rows else None      # fused workgroups of the batch: one per 52-row window (L = 4), each owns its CU
+    # forward: the first flows run beside the text encoder's forward on the other stream, which a CU-filling fused workgroup starves
+    nskip = int(TUNE["fused_wn_fwd_skip"])
+    if nskip < 0:                                           # automatic: three flows when the batch's fused workgroups fill the chip
+        nskip = 3 if (nwg is not None and 4 * nwg > 3 * cus) else 0   # (round 4, with the early weight preparation: 1 / 2 / 3 / 4 flows = 5.36 / 5.31 / 5.28 / 5.29 ms/step on one box)
+    nskip = min(nskip, F_) if (need_bwd and have_image) else 0
+    nfb = TUNE["fused_wn_bwd"]
+    if nfb is True:
+        nfb = F_
+    elif int(nfb) < 0:
+        # automatic: a fused workgroup owns its CU.  A batch whose 52-row windows leave a quarter of the CUs free (B = 16 x 800 frames: 125
+        # workgroups) shares the chip with the encoder stream anyway - every flow takes the fused kernel (config 4: 4.28 vs 4.68 ms/step);
+        # a chip-filling one (B = 32: 249) only the last 7 of 12 flows: there the in-graph timeline (bench.py --timeline) shows the two
+        # streams finishing their weight gradients together.  (It was 5 of 12 until the encoder's attention kernels stopped waiting for
+        # every load of their operand staging - backward 81 -> 46 us, forward 36 -> 25 us per layer: with the shorter encoder backward
+        # 6 / 7 / 8 / 9 / 10 / 12 fused flows measure 5.61 / 5.54-5.59 / 5.54-5.61 / 5.59-5.73 / 5.88 / 6.08 ms/step against 5.58-5.66 for 5.)
+        # (round 5: 8 of 12 - the encoder's backward chain lost its gate passes, the relative-position sums and ~100 us of weight packing at its head:
+        # 5.02 vs 5.07 ms/step for 7, three alternating pairs on one box; 9: 5.23)
+        # (round 6: 9 of 12 - the head of the encoder's backward lost its dozen PyTorch launches (duration projection, prior split: enc_dgrads_done 4 006 ->
+        # 3 580 us): 4.69 / 4.73 vs 4.77 / 4.78 ms/step for 8, two alternating rounds on one box; 10: 4.80, 12: 4.95)
+        # (conditioned modes stay at 8 of 12: config 3 5.01 vs 5.11 ms/step for 9 - their encoder stream also carries the conditioning encoders' backward)
+        nfb = F_ if (nwg is not None and 4 * nwg <= 3 * cus) else max(1, ((2 if conditioned else 3) * F_) // (3 if conditioned else 4))
+    else:
+        nfb = min(int(nfb), F_)
+    if not (need_bwd and have_image and fused_bwd_ok and nfb > 0):
+        nfb = 0
+    return nskip, nfb
+
+
 class DecoderConfig:
     """Shapes of the decoder, from Hyper_Parameters.yaml (Decoder.*, Sound.Mel_Dim)."""
 
@@ -422,11 +451,11 @@ class _Prepared:
             w, g = src(key, sl)
             return PackedBatch(w.reshape(shape), transpose, perm, perm_h, P, g=g, jobs=cur[0])
 
-        def images(sl, nflows, img_fwd, nbwd, img_bwd, with_inv):
-            """the fused kernels' weight images of flows `sl` (forward: nflows of them; transposed: the first nbwd)"""
+        def images(nflows, img_fwd, nbwd, img_bwd, with_inv):
+            """the fused kernels' weight images (forward: of the first nflows flows; transposed: of the first nbwd)"""
             if GV is None:
-                _lib.check(L.glowtts_wavenet_pack_images(_lib.ptr(W["w_start"][sl]), _lib.ptr(W["w_in"][sl]), _lib.ptr(W["w_rs"][sl]) if Lw > 1 else None,
-                                                         _lib.ptr(W["w_rs_last"][sl]), _lib.ptr(W["w_end"][sl]), nflows if img_fwd is not None else nbwd, Lw, C // 2,
+                _lib.check(L.glowtts_wavenet_pack_images(_lib.ptr(W["w_start"]), _lib.ptr(W["w_in"]), _lib.ptr(W["w_rs"]) if Lw > 1 else None,
+                                                         _lib.ptr(W["w_rs_last"]), _lib.ptr(W["w_end"]), nflows if img_fwd is not None else nbwd, Lw, C // 2,
                                                          _lib.ptr(img_fwd), _lib.ptr(img_bwd), _lib.stream()), "wavenet_pack_images")
                 return
             a = []
@@ -436,25 +465,20 @@ class _Prepared:
                 if key == "w_rs" and Lw == 1:
                     a += [None, None, None]
                 else:
-                    a += [v[sl].data_ptr(), g[sl].data_ptr(), inv[sl].data_ptr() if inv is not None else None]
+                    a += [v.data_ptr(), g.data_ptr(), inv.data_ptr() if inv is not None else None]
             jb = cur[0]
             _lib.check(L.glowtts_wavenet_prep_jobs(ctypes.cast(jb.jobs, c_void_p), PrepJobs.CAP, ctypes.byref(jb.n), ctypes.byref(jb.blocks), *a,
-                                                   W["w_end"][sl].data_ptr(), nflows, Lw, C // 2, _lib.ptr(img_fwd), nbwd, _lib.ptr(img_bwd)), "wavenet_prep_jobs")
+                                                   W["w_end"].data_ptr(), nflows, Lw, C // 2, _lib.ptr(img_fwd), nbwd, _lib.ptr(img_bwd)), "wavenet_prep_jobs")
             jb.max_cols = max(jb.max_cols, H * cfg.k)
 
         self.wn_img = None
-        ksplit = 0
         if fused_wn_supported(cfg):
             # one image per flow holding every forward weight of its coupling network as 24-KiB slabs (glowtts_wavenet_pack_images)
             nb = c_i64(0)
             _lib.check(L.glowtts_wavenet_image_bytes(Lw, 0, ctypes.byref(nb)), "wavenet_image_bytes")
             nb = nb.value
             self.wn_img = torch.empty(F_, nb, dtype=torch.uint8, device=dev)
-            # (experiment, TUNE["fwd_packs_split"] = k: only the first k flows' images here, the others on the side stream below - the
-            # decoder's first flow then waits for k flows' worth of packing instead of twelve)
-            ksplit = int(TUNE["fwd_packs_split"]) if (need_bwd and dev.type == "cuda" and GV is None) else 0
-            ksplit = ksplit if 0 < ksplit < F_ else 0
-            images(slice(None), ksplit or F_, self.wn_img, 0, None, True)
+            images(F_, self.wn_img, 0, None, True)
             S = WN_SLAB
             self.pk = {
                 "start": ImageSlices(self.wn_img, nb, 0, 1, 0, 192, 3),
@@ -464,14 +488,10 @@ class _Prepared:
             }
             if Lw > 1:
                 self.pk["rs"] = ImageSlices(self.wn_img, nb, 32 * S, Lw - 1, 36 * S, 2 * H, H // 32)       # (PAIR-packed: read by the fused kernel only)
-        # training: the first flows of the forward can stay on the per-conv launches (TUNE["fused_wn_fwd_skip"]) - they run beside the
-        # text encoder's forward on the other stream, which a CU-filling fused workgroup starves
-        nskip = int(TUNE["fused_wn_fwd_skip"])
-        if nskip < 0:                                           # automatic: one flow when the batch's fused workgroups fill the chip (see fused_wn_bwd)
-            nwg_ = -(-rows // (64 - 4 * (Lw - 1))) if rows else 0
-            cus_ = torch.cuda.get_device_properties(dev).multi_processor_count if dev.type == "cuda" else 256
-            nskip = 3 if 4 * nwg_ > 3 * cus_ else 0             # (round 4, with the early weight preparation: 1 / 2 / 3 / 4 flows = 5.36 / 5.31 / 5.28 / 5.29 ms/step on one box)
-        nskip = min(nskip, F_) if (need_bwd and self.wn_img is not None) else 0
+        # how many forward flows stay on the per-conv launches, how many backward flows take the fused data-gradient kernel
+        cus = torch.cuda.get_device_properties(dev).multi_processor_count if dev.type == "cuda" else 256
+        nskip, nfb = fused_flow_plan(cfg, rows, cus, need_bwd, (cond is not None) if conditioned is None else bool(conditioned),
+                                     fused_bwd_ok=fused_bwd_ok, have_image=self.wn_img is not None)
         pk_conv = None
         all_f = slice(None)
         if self.wn_img is None:
@@ -495,49 +515,13 @@ class _Prepared:
         # backward: the transposed image of the fused data-gradient kernel (glowtts_wavenet_bwd) where it applies - no conditioning gradient -
         # else the per-conv transposed images
         self.wn_img_t = None
-        nfb = TUNE["fused_wn_bwd"]
-        if nfb is True:
-            nfb = F_
-        elif int(nfb) < 0:
-            # automatic: a fused workgroup owns its CU.  A batch whose 52-row windows leave a quarter of the CUs free (B = 16 x 800 frames: 125
-            # workgroups) shares the chip with the encoder stream anyway - every flow takes the fused kernel (config 4: 4.28 vs 4.68 ms/step);
-            # a chip-filling one (B = 32: 249) only the last 7 of 12 flows: there the in-graph timeline (bench.py --timeline) shows the two
-            # streams finishing their weight gradients together.  (It was 5 of 12 until the encoder's attention kernels stopped waiting for
-            # every load of their operand staging - backward 81 -> 46 us, forward 36 -> 25 us per layer: with the shorter encoder backward
-            # 6 / 7 / 8 / 9 / 10 / 12 fused flows measure 5.61 / 5.54-5.59 / 5.54-5.61 / 5.59-5.73 / 5.88 / 6.08 ms/step against 5.58-5.66 for 5.)
-            nwg = -(-rows // (64 - 4 * (Lw - 1))) if rows else None
-            cus = torch.cuda.get_device_properties(dev).multi_processor_count if dev.type == "cuda" else 256
-            # (round 5: 8 of 12 - the encoder's backward chain lost its gate passes, the relative-position sums and ~100 us of weight packing at its head:
-            # 5.02 vs 5.07 ms/step for 7, three alternating pairs on one box; 9: 5.23)
-            # (round 6: 9 of 12 - the head of the encoder's backward lost its dozen PyTorch launches (duration projection, prior split: enc_dgrads_done 4 006 ->
-            # 3 580 us): 4.69 / 4.73 vs 4.77 / 4.78 ms/step for 8, two alternating rounds on one box; 10: 4.80, 12: 4.95)
-            # (conditioned modes stay at 8 of 12: config 3 5.01 vs 5.11 ms/step for 9 - their encoder stream also carries the conditioning encoders' backward)
-            is_cond = (cond is not None) if conditioned is None else bool(conditioned)
-            nfb = F_ if (nwg is not None and 4 * nwg <= 3 * cus) else max(1, ((2 if is_cond else 3) * F_) // (3 if is_cond else 4))
-        else:
-            nfb = min(int(nfb), F_)                             # flows 0 .. nfb-1 take the fused kernel
-        f0 = min(max(int(TUNE["fused_wn_bwd_from"]), 0), F_ - nfb)               # (experiments: the fused flows are f0 .. f0 + nfb - 1)
-        # (experiment, TUNE["bwd_packs_side"]: the images only the backward reads are packed on a stream of their own, joined when the backward starts)
-        self.bwd_side = None
-        main_s = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
-        self.fwd_side_from = None
-        if need_bwd and GV is None and (TUNE["bwd_packs_side"] or ksplit) and main_s is not None:
-            self.bwd_side = _pack_stream(dev)
-            self.bwd_side.wait_stream(main_s)
-            torch.cuda.set_stream(self.bwd_side)
-            if ksplit:
-                self.fwd_side_from = ksplit
-                images(slice(ksplit, None), F_ - ksplit, self.wn_img[ksplit:], 0, None, False)
         if jobs_b is not None:
             cur[0] = jobs_b                                                    # everything from here on is read by the backward only
-        if need_bwd and self.wn_img is not None and fused_bwd_ok and nfb > 0:
+        if nfb > 0:
             self.wn_img_t = torch.empty_like(self.wn_img[:nfb])                # (the fused flows only)
-            images(slice(f0, None), nfb, None, nfb, self.wn_img_t, False)
-        else:
-            nfb = 0
-        c0 = nfb if f0 == 0 else 0                                             # per-conv transposed images: flows c0 .. F-1 (element i = flow c0 + i)
-        if need_bwd and c0 < F_:
-            rest, nr = slice(c0, None), F_ - c0
+            images(nfb, None, nfb, self.wn_img_t, False)
+        if need_bwd and nfb < F_:                                              # per-conv transposed images: flows nfb .. F-1 (element i = flow nfb + i)
+            rest, nr = slice(nfb, None), F_ - nfb
             self.pk.update({
                 "start_t": batch("w_start", rest, (nr, H, C // 2, 1), True, ops.PERM_NONE, 0),
                 "in_t": batch("w_in", rest, (nr * Lw, 2 * H, H, cfg.k), True, ops.PERM_PAIR, H),
@@ -546,11 +530,6 @@ class _Prepared:
             })
             if Lw > 1:
                 self.pk["rs_t"] = batch("w_rs", rest, (nr * (Lw - 1), 2 * H, H, 1), True, ops.PERM_NONE, 0)
-        if self.bwd_side is not None:
-            torch.cuda.set_stream(main_s)
-            for t in [self.wn_img_t] + [self.pk[k].data for k in ("start_t", "in_t", "rs_last_t", "end_t", "rs_t") if k in self.pk]:
-                if t is not None:
-                    t.record_stream(main_s)
         if jobs is not None:
             stamp("dec_prep_begin")
             jobs.launch(dev)
@@ -582,9 +561,9 @@ class _Prepared:
                 else:
                     p.rs[l] = pkf["rs_last"].at(f)
                     p.b_rs[l] = W["b_rs_last"][f].data_ptr()
-            p.wn_img_t = self.wn_img_t[f - f0].data_ptr() if f0 <= f < f0 + nfb else None
+            p.wn_img_t = self.wn_img_t[f].data_ptr() if f < nfb else None
             if need_bwd and p.wn_img_t is None:
-                fc = f - c0
+                fc = f - nfb
                 p.start_t = self.pk["start_t"].at(fc)
                 p.end_t = self.pk["end_t"].at(fc)
                 for l in range(Lw):
@@ -633,10 +612,9 @@ class _Prepared:
         p.cond, p.ldcond, p.cond_rows = rows.data_ptr(), self._Lw * 2 * self._H, 1
 
 
-def _dims(cfg, B, T, drop_p=0.0, seed=None, flow=0, chunk=0):
-    """seed: None or a device int32/uint32 tensor with one element (re-drawn on device every step, hipGraph-safe).
-    chunk: 0 (round 5's utterance-chunk experiment numbered its chunks' rows from 0 and gave each its own dropout key)."""
-    return FlowDims(B, T, cfg.C, cfg.H, cfg.L, cfg.k, cfg.precision, float(drop_p), (1000003 * flow + 7368787 * chunk) & 0xFFFFFFFF,
+def _dims(cfg, B, T, drop_p=0.0, seed=None, flow=0):
+    """seed: None or a device int32/uint32 tensor with one element (re-drawn on device every step, hipGraph-safe)."""
+    return FlowDims(B, T, cfg.C, cfg.H, cfg.L, cfg.k, cfg.precision, float(drop_p), (1000003 * flow) & 0xFFFFFFFF,
                     seed.data_ptr() if seed is not None else None, int(cfg.act_bf16))
 
 
@@ -681,21 +659,19 @@ class _Buffers:
         bf_tail = self.skipb is not None and self.xa_bf is not None
         self.keep_skip32 = [not (bf_tail and TUNE["drop_skip32"] and bool(prep.params[f].wn_img)) for f in range(F_)]
 
-    def acts(self, f, L, rowmask, row0=0):
-        """row0: first row of the utterance chunk the launch serves (every kept tensor is rows-major: a chunk is a row range of each)."""
-        at = lambda t: t.data_ptr() + row0 * t.stride(-2) * t.element_size()
+    def acts(self, f, L, rowmask):
         a = FlowActs()
-        a.xin, a.xmid, a.xout = at(self.x[f]), at(self.xmid[f]), at(self.x[f + 1])
+        a.xin, a.xmid, a.xout = self.x[f].data_ptr(), self.xmid[f].data_ptr(), self.x[f + 1].data_ptr()
         for l in range(L):
-            a.hs[l] = at(self.hs[f, l])
-            a.gates[l] = at(self.gates[f, l])
+            a.hs[l] = self.hs[f, l].data_ptr()
+            a.gates[l] = self.gates[f, l].data_ptr()
             if self.actp is not None:
-                a.acts[l] = at(self.actp[f, l])
+                a.acts[l] = self.actp[f, l].data_ptr()
         if self.skipb is not None:
-            a.skip_bf = at(self.skipb[f])
+            a.skip_bf = self.skipb[f].data_ptr()
         if self.xa_bf is not None:
-            a.xa_bf = at(self.xa_bf[f])
-        a.skip, a.outs, a.rowmask = (at(self.skip[f]) if self.keep_skip32[f] else None), at(self.outs[f]), rowmask.data_ptr() + 4 * row0
+            a.xa_bf = self.xa_bf[f].data_ptr()
+        a.skip, a.outs, a.rowmask = (self.skip[f].data_ptr() if self.keep_skip32[f] else None), self.outs[f].data_ptr(), rowmask.data_ptr()
         return a
 
 
@@ -716,16 +692,6 @@ def _cond_rows(cfg, prep, f, prow, pitch_w, pitch_b, Tp):
     return cr.contiguous()
 
 
-def _params_at(prep, f, b0):
-    """Flow f's parameter struct as utterance b0's chunk sees it: the per-utterance conditioning rows start at b0."""
-    p = prep.params[f]
-    if b0 == 0 or not p.cond:
-        return p
-    q = FlowParams.from_buffer_copy(p)
-    q.cond = p.cond + 4 * b0 * p.ldcond
-    return q
-
-
 def _run_forward(cfg, prep, mels, lengths, drop_p=0.0, seed=None, pitch=None):
     """pitch: None or (pitches [B, Tm], pitch_w [F, L, 2H, ns], pitch_b [F, L, 2H]) - GR mode."""
     L = _L()
@@ -737,28 +703,23 @@ def _run_forward(cfg, prep, mels, lengths, drop_p=0.0, seed=None, pitch=None):
     stamp("dec_fwd_begin")
     Tp = T + 2 * ROW_PAD
 
-    def chain(ci, b0, nb):
-        """All flows of utterances [b0, b0 + nb) on the current stream."""
-        chained = False
-        for f in range(cfg.F):
-            if pitch is not None:
-                cr = _cond_rows(cfg, prep, f, prow, pitch[1], pitch[2], Tp)
-                prep.set_cond_rows(f, cr)
-            if getattr(prep, "fwd_side_from", None) == f:
-                torch.cuda.current_stream(mels.device).wait_stream(prep.bwd_side)
-            acts = buf.acts(f, cfg.L, rowmask, b0 * Tp)
-            acts.actnorm_done = int(chained)
-            # a flow on the fused coupling launch also applies the NEXT flow's ActNorm + 1x1 conv in that launch's epilogue (one launch less per flow on the
-            # decoder's forward chain; csrc/wavenet_fused.hip)
-            chained = bool(TUNE["chain_actnorm"]) and f + 1 < cfg.F and bool(prep.params[f].wn_img) and pitch is None
-            if chained:
-                nxt, pn = buf.acts(f + 1, cfg.L, rowmask, b0 * Tp), prep.params[f + 1]
-                acts.next_an_logs, acts.next_an_bias, acts.next_winfo = pn.an_logs, pn.an_bias, pn.winfo
-                acts.next_xmid, acts.next_xout, acts.next_xa_bf = nxt.xmid, nxt.xout, nxt.xa_bf
-            dims = _dims(cfg, nb, T, drop_p, seed, f, ci)
-            _lib.check(L.glowtts_flow_forward(ctypes.byref(dims), ctypes.byref(_params_at(prep, f, b0)), ctypes.byref(acts), _lib.stream()),
-                       "glowtts_flow_forward")
-    chain(0, 0, B)
+    chained = False
+    for f in range(cfg.F):
+        if pitch is not None:
+            cr = _cond_rows(cfg, prep, f, prow, pitch[1], pitch[2], Tp)
+            prep.set_cond_rows(f, cr)
+        acts = buf.acts(f, cfg.L, rowmask)
+        acts.actnorm_done = int(chained)
+        # a flow on the fused coupling launch also applies the NEXT flow's ActNorm + 1x1 conv in that launch's epilogue (one launch less per flow on the
+        # decoder's forward chain; csrc/wavenet_fused.hip)
+        chained = bool(TUNE["chain_actnorm"]) and f + 1 < cfg.F and bool(prep.params[f].wn_img) and pitch is None
+        if chained:
+            nxt, pn = buf.acts(f + 1, cfg.L, rowmask), prep.params[f + 1]
+            acts.next_an_logs, acts.next_an_bias, acts.next_winfo = pn.an_logs, pn.an_bias, pn.winfo
+            acts.next_xmid, acts.next_xout, acts.next_xa_bf = nxt.xmid, nxt.xout, nxt.xa_bf
+        dims = _dims(cfg, B, T, drop_p, seed, f)
+        _lib.check(L.glowtts_flow_forward(ctypes.byref(dims), ctypes.byref(prep.params[f]), ctypes.byref(acts), _lib.stream()),
+                   "glowtts_flow_forward")
     stamp("dec_fwd_end")
     # (z in the reference's [B, C, T] layout and the log-determinants on the encoder's stream, off the chain to the log-prior, was measured in round 5 and lost:
     #  5.07 against 5.01 ms/step - the extra cross-stream edges cost the replayed graph more than the two passes take; DESIGN.md section 5)
@@ -952,8 +913,8 @@ def actnorm_data_init(cfg, W, mels, lengths, cond=None, allreduce=None, pitch=No
 # replayed hipGraph the decoder's branch otherwise starts ~180 us after the encoder's (measured with in-graph stamps: the runtime reaches the nodes of
 # the second branch late), and the 80-us preparation launch sat behind that.  `early_prepare` builds the _Prepared; DecoderFunction.forward picks it up.
 EARLY = {"prep": None, "key": None}
-# A stream the caller joins with its own before it consumes z / the log-determinants (modules.GlowTTS.forward: the text encoder's stream), or None
-AUX = {"stream": None, "stacks": None, "seed": None}
+# What modules.GlowTTS.forward hands to the DecoderFunction call it is about to make: a weak reference to the model's DecoderStacks, the step's dropout seed word
+AUX = {"stacks": None, "seed": None}
 
 
 def _leaf_grads_unset():
@@ -1037,8 +998,6 @@ class DecoderFunction(torch.autograd.Function):
         if dz is None:                                       # (only the log-determinant was differentiated: tests)
             dz = torch.zeros(ctx.mel_shape, device=dlogdet.device)
         dev = dz.device
-        if getattr(prep, "bwd_side", None) is not None:
-            torch.cuda.current_stream(dev).wait_stream(prep.bwd_side)
         prep.launch_bwd_images()                                 # (nobody has issued the backward-only images yet: here, on this stream)
         F_, Lw, H, C = cfg.F, cfg.L, cfg.H, cfg.C
         dx, _, _ = squeeze_rows(cfg, dz.contiguous(), ctx.lengths, want_mask=False)
@@ -1080,8 +1039,8 @@ class DecoderFunction(torch.autograd.Function):
         # two grouped launches (k-tap problems, 1x1 problems) whose tiles fill the chip without split-K or atomics
         # (fp32 rows of d(m, logs): only where somebody reads them - with bf16-stored activations every consumer, the End conv's data and weight gradients, takes
         #  the bf16 copy below, and the coupling backward then writes that copy alone: 768 of the 4 480 bytes per row of its pass, round 6)
-        h0bf_ = bool(cfg.act_bf16 and buf.xa_bf is not None and buf.skipb is not None)
-        douts = None if h0bf_ else torch.empty(F_, R, prep.ldo, device=dev)           # (pad columns are zeroed by the coupling backward kernel)
+        h0bf = bool(cfg.act_bf16 and buf.xa_bf is not None and buf.skipb is not None)
+        douts = None if h0bf else torch.empty(F_, R, prep.ldo, device=dev)           # (pad columns are zeroed by the coupling backward kernel)
         # bf16 copy of d(m, logs): the End data gradient's operand and (round 4) DY of the End conv's weight gradient - one per flow, like everything the
         # deferred weight-gradient launches read
         douts_bf = torch.empty(F_, R, prep.ldo, device=dev, dtype=torch.bfloat16) if cfg.act_bf16 else None
@@ -1090,7 +1049,6 @@ class DecoderFunction(torch.autograd.Function):
         dskip = torch.empty(F_, R, H, device=dev, dtype=cfg.act_dtype)
         # d h0: bf16 like d x_l (round 4: the Start conv's data gradient reads bf16 rows, its weight gradient raw bf16 operands) where the
         # bf16 copy of x_a exists; else fp32
-        h0bf = bool(cfg.act_bf16 and buf.xa_bf is not None and buf.skipb is not None)
         dh0 = torch.empty(F_, R, H, device=dev, dtype=cfg.act_dtype if h0bf else torch.float32)
         dhn = torch.empty(F_, max(Lw - 1, 1), R, H, device=dev, dtype=cfg.act_dtype)       # d x_l, l >= 1
         dh_ptr = lambda f, l: dh0[f].data_ptr() if l == 0 else dhn[f, l - 1].data_ptr()
@@ -1109,7 +1067,7 @@ class DecoderFunction(torch.autograd.Function):
         # summed in a fixed order into the gradient tensors by ONE launch (glowtts_sum_slices_seg)
         S_t = int(TUNE["wgrad_tail_splits"])
         tail_seg = tail_part = tail_fns = None
-        if S_t > 1 and h0bf and B % S_t == 0 and int(TUNE["wgrad_split"]) == 1:
+        if S_t > 1 and h0bf and B % S_t == 0:
             names = ["w_end", "b_end", "w_rs_last", "b_rs_last", "w_start", "b_start"] + (["w_rs", "b_rs"] if Lw > 1 else [])
             if all(G[k].is_contiguous() and G[k].numel() % 4 == 0 and G[k].data_ptr() % 16 == 0 for k in names):
                 tot, tail_seg = 0, []
@@ -1158,27 +1116,17 @@ class DecoderFunction(torch.autograd.Function):
                 gp.add(dh0[f].data_ptr(), H, H, buf.xa_bf[f].data_ptr(), C2, C2, G["w_start"][f].data_ptr(), G["b_start"][f].data_ptr())
             else:
                 g1.add(dh0[f].data_ptr(), H, H, buf.xmid[f].data_ptr(), C, C2, G["w_start"][f].data_ptr(), G["b_start"][f].data_ptr())
-            # TUNE["wgrad_split"] = n: weight gradients in n segments, each launched on a second stream as soon as its flows' chain is
-            # done (default 1: one launch per class after the chain; see DESIGN.md for the measurements)
-            nseg = int(TUNE["wgrad_split"])
-            if nseg > 1:
-                per = -(-len(order) // nseg)
-                pos = order.index(f) + 1
-                if pos % per == 0 and pos < len(order):
-                    for grp in (gk, g1, gp):
-                        grp.end_segment()
         # Few, large launches: 216-432 k-tap tiles per launch fill the chip without split-K (per-flow launches of 36 tiles were
         # measured 3x slower in total, even on a second stream).
         # TUNE["wgrad_balance"] (round 6, OFF): 288 one-per-CU In_l tiles on 256 CUs are two rounds, the second with 32 tiles; the balanced two-phase launch
         # (WgradGroup.balance) runs them in 1 + 1/8 rounds and ends the decoder's tail 126 us earlier (dec_wgrads_done 4 311 against 4 437 us) - and the step
         # takes as long as before (4.71-4.77 against 4.66-4.76 ms/step, five alternating pairs on two boxes): the idle CUs of the second round were where the
         # encoder's backward ran, which now ends that much later (enc_wgrads_done 4 523 against 4 292).  Kept for a step whose second half is not shared.
-        if TUNE["wgrad_balance"] and int(TUNE["wgrad_split"]) == 1 and bf:
+        if TUNE["wgrad_balance"] and bf:
             gk.balance(B, T + 2 * ROW_PAD, dev)
         for grp in (gk, g1, gp):
             grp.end_segment()
         WgradGroup.upload_all((gk, g1, gp), dev)
-        halves = len(gk.segments)
 
         def sum_tail():
             if tail_seg is not None:                       # the one-tap group's partial images -> the gradient tensors
@@ -1187,58 +1135,33 @@ class DecoderFunction(torch.autograd.Function):
         main = torch.cuda.current_stream()
         side = _wgrad_stream(dev)
         stamp("dec_bwd_begin")
-        Tp = T + 2 * ROW_PAD
-        chunks = [(0, 0, B)]
-        # the ActNorm / 1x1 backward leaves one row of partial sums per block of its launch: a chunk's blocks follow the previous chunk's
-        blk_off, nblk_all = [], 0
-        for _, _, nb in chunks:
-            blk_off.append(nblk_all)
-            nblk_all += L.glowtts_actnorm_bwd_blocks(nb * Tp)
+        # the ActNorm / 1x1 backward leaves one row of partial sums per block of its launch
+        nblk_all = L.glowtts_actnorm_bwd_blocks(B * (T + 2 * ROW_PAD))
         assert nblk_all * (2 * C + 16) <= nscr
-        at = lambda t, row0: t.data_ptr() + row0 * t.stride(-2) * t.element_size()
-
-        def chain(ci, b0, nb):
-            r0 = b0 * Tp
-            for f in order:
-                g = FlowGrads()
-                g.dx, g.dlogdet, g.douts, g.dskip = at(dx, r0), dld.data_ptr() + 4 * b0, (at(douts[f], r0) if douts is not None else None), at(dskip[f], r0)
-                g.douts_bf = at(douts_bf[f], r0) if douts_bf is not None else None
-                g.dh0_bf16 = int(h0bf)
-                # the last kernel of this flow's backward also applies the coupling backward of the flow that runs next (f - 1)
-                g.coupling_done = int(fuse and f != order[0])
-                if fuse and f > 0:
-                    g.prev_xmid, g.prev_outs, g.prev_douts = at(buf.xmid[f - 1], r0), at(buf.outs[f - 1], r0), (at(douts[f - 1], r0) if douts is not None else None)
-                    g.prev_douts_bf = at(douts_bf[f - 1], r0) if douts_bf is not None else None
-                g.scratch, g.d_an, g.defer_wgrad = scratch[f].data_ptr() + 4 * blk_off[ci] * (2 * C + 16), None, 1
-                for l in range(Lw):
-                    g.dh[l] = at(dh0[f], r0) if l == 0 else at(dhn[f, l - 1], r0)
-                    g.dins[l] = at(dins[f, l], r0)
-                if dcond is not None:
-                    g.dcond = dcond.data_ptr() + 8 * f * Lw * 2 * H + 8 * b0 * dcond.stride(0)
-                    if npit:
-                        g.pitch_rows, g.pitch_ns = ctx.prow.data_ptr(), npit
-                acts = buf.acts(f, Lw, rowmask, r0)
-                dims = _dims(cfg, nb, T, ctx.drop[0], ctx.drop[1], f, ci)
-                _lib.check(L.glowtts_flow_backward(ctypes.byref(dims), ctypes.byref(_params_at(prep, f, b0)), ctypes.byref(acts), ctypes.byref(g),
-                                                   _lib.stream()), "glowtts_flow_backward")
-                if ci == 0:
-                    stamp(f"dec_bwd_flow{f}")
-                if halves > 1:
-                    per = -(-len(order) // halves)
-                    pos = order.index(f) + 1
-                    if pos % per == 0 and pos < len(order):
-                        side.wait_stream(main)
-                        with torch.cuda.stream(side):
-                            for grp in (gk, gp, g1):
-                                grp.launch_segment(pos // per - 1)
-        chain(0, 0, B)
-        if halves > 1:
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                for grp in (gk, gp, g1):
-                    grp.launch_segment(halves - 1)
-            main.wait_stream(side)
-        elif TAIL["defer"]:
+        for f in order:
+            g = FlowGrads()
+            g.dx, g.dlogdet, g.douts, g.dskip = dx.data_ptr(), dld.data_ptr(), (douts[f].data_ptr() if douts is not None else None), dskip[f].data_ptr()
+            g.douts_bf = douts_bf[f].data_ptr() if douts_bf is not None else None
+            g.dh0_bf16 = int(h0bf)
+            # the last kernel of this flow's backward also applies the coupling backward of the flow that runs next (f - 1)
+            g.coupling_done = int(fuse and f != order[0])
+            if fuse and f > 0:
+                g.prev_xmid, g.prev_outs, g.prev_douts = buf.xmid[f - 1].data_ptr(), buf.outs[f - 1].data_ptr(), (douts[f - 1].data_ptr() if douts is not None else None)
+                g.prev_douts_bf = douts_bf[f - 1].data_ptr() if douts_bf is not None else None
+            g.scratch, g.d_an, g.defer_wgrad = scratch[f].data_ptr(), None, 1
+            for l in range(Lw):
+                g.dh[l] = dh_ptr(f, l)
+                g.dins[l] = dins[f, l].data_ptr()
+            if dcond is not None:
+                g.dcond = dcond.data_ptr() + 8 * f * Lw * 2 * H
+                if npit:
+                    g.pitch_rows, g.pitch_ns = ctx.prow.data_ptr(), npit
+            acts = buf.acts(f, Lw, rowmask)
+            dims = _dims(cfg, B, T, ctx.drop[0], ctx.drop[1], f)
+            _lib.check(L.glowtts_flow_backward(ctypes.byref(dims), ctypes.byref(prep.params[f]), ctypes.byref(acts), ctypes.byref(g),
+                                               _lib.stream()), "glowtts_flow_backward")
+            stamp(f"dec_bwd_flow{f}")
+        if TAIL["defer"]:
             gk.launch_segment(0)
             # the queued launches read the kept activations and this backward's gradient buffers through raw pointers: the closure
             # keeps them alive (also across replays when the flush is captured as its own hipGraph)
@@ -1280,7 +1203,7 @@ class DecoderFunction(torch.autograd.Function):
                 j.dw, j.v, j.g, j.inv_norm, j.dv, j.dg = G[k].data_ptr(), v_.data_ptr(), g_.data_ptr(), prep.inv[k].data_ptr(), dv.data_ptr(), dg.data_ptr()
                 j.rows, j.cols = rows_, cols
                 wn_keep.append((g_, v_, dv, dg, prep.inv[k], G[k]))
-                (wn_pending if (TAIL["defer"] and halves == 1 and k != "w_in") else wn_now).append(j)
+                (wn_pending if (TAIL["defer"] and k != "w_in") else wn_now).append(j)
 
             def wn_run(jobs, keep=wn_keep):
                 if jobs:                                        # (4.70 / 4.72 / 4.70 against 4.75 / 4.70 / 4.76 ms/step for one launch per class, three alternating pairs)

@@ -213,7 +213,6 @@ class GlowTTS(torch.nn.Module):
             self.layer_Dict["Prosody_Encoder"].hip_precision = prec
         self.actnorm_allreduce = None     # set by the data-parallel wrapper (glow_tts_amd.distributed)
         self._enc_stream = None
-        self._pack_stream = None
         self._pcache = None               # name -> Parameter (see _params)
         self._dec_stacks = None           # decoder.DecoderStacks: flat per-class parameter storage, built on first use
         self._enc_cache = {}              # encoder leaf stacks (fused Query/Key/Value weights)
@@ -225,7 +224,7 @@ class GlowTTS(torch.nn.Module):
     def __getstate__(self):
         # run-time caches (HIP stream, flat parameter storage views) are rebuilt on first use: keep them out of copies / pickles
         st = self.__dict__.copy()
-        st["_enc_stream"], st["_pack_stream"], st["_dec_stacks"], st["_enc_cache"], st["_pcache"] = None, None, None, {}, None
+        st["_enc_stream"], st["_dec_stacks"], st["_enc_cache"], st["_pcache"] = None, None, {}, None
         return st
 
     def __deepcopy__(self, memo):
@@ -329,12 +328,6 @@ class GlowTTS(torch.nn.Module):
         side.wait_stream(main)
         if seed_word is not None and side is not main:
             seed_word.record_stream(side)
-        pack_aux = None
-        if side is not main and decoder.TUNE["enc_pack_split"]:
-            if self._pack_stream is None:
-                self._pack_stream = torch.cuda.Stream()
-            pack_aux = self._pack_stream
-            pack_aux.wait_stream(main)                        # (forked HERE, from the origin stream: see encoder._PackSets.run)
         prior_ready = torch.cuda.Event() if side is not main else None
         # (behind the fork: the encoder's stream does not wait for it)
         if use_gv and decoder.TUNE["prep_early"] and all(f.layers[0].initialized for f in self._flows()):
@@ -369,8 +362,7 @@ class GlowTTS(torch.nn.Module):
             token_mask, token_rowmask = encoder.token_masks(token_lengths, tokens.shape[1])
             mean, log_std, log_dur = encoder.encoder_forward(P, hp, tokens, token_mask, spk, pro, self.training, precision=self.dec_cfg.precision,
                                                              cache=self._enc_cache, rowmask=token_rowmask,
-                                                             on_prior_ready=prior_done if prior_ready is not None else None,
-                                                             pack_stream=pack_aux, seed_t=seed_word)
+                                                             on_prior_ready=prior_done if prior_ready is not None else None, seed_t=seed_word)
         decoder.stamp("main_after_enc_launch")
         # (the conditioning convs on a third stream, forked in front of the decoder's weight preparation and joined here, were measured in round 6: config 3 6.00
         #  against 5.11 ms/step, config 4 4.65 against 3.9 - a third branch in the replayed graph costs far more than the ~35 us it would hide)
@@ -383,13 +375,12 @@ class GlowTTS(torch.nn.Module):
         self._maybe_init_actnorm(P, mels, mel_lengths, cond, None if pitches is None else (pitches, pitch_w.detach(), pitch_b.detach()))
         # (training on the fused bf16 path: W holds the weight-norm pairs themselves - every weight image was prepared by one launch above)
         drop_p = float(hp.Decoder.Affine_Coupling.WaveNet.Dropout_Rate) if self.training else 0.0      # Modules.py:854-862
-        decoder.AUX["stream"] = side if side is not main else None          # (z / log-determinant passes: off the chain to the log-prior, joined below)
         decoder.AUX["seed"] = seed_word
         try:
             z, log_dets, z_rows = decoder.DecoderFunction.apply(self.dec_cfg, mels, mel_lengths, cond, drop_p, pitches, pitch_w if pitches is not None else None,
                                                                 pitch_b if pitches is not None else None, *W)
         finally:
-            decoder.AUX["stream"] = decoder.AUX["seed"] = None
+            decoder.AUX["seed"] = None
         if side is not main:
             # the log-prior needs mean / log_std only: the duration predictor still runs on the encoder's stream (joined below, before the
             # losses read log_dur) - the encoder's forward is what this point of the step waits for (timeline).  (One join behind
