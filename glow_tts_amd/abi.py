@@ -23,6 +23,8 @@ PREP_MAX_JOBS = 22
 WN_BWD_MAX_JOBS = 8
 SUM_MAX_SEGS = 12
 C2D_MAX_LAYERS = 8
+SAMPLE_SCAN_CHUNK = 1024
+SAMPLE_TILE = 64
 
 # ---- struct mirrors: `c_name` is the C struct whose layout the class restates ------------------------------------------------------------
 I, L, F, U, P = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_uint32, ctypes.c_void_p
@@ -258,4 +260,5 @@ SIGNATURES = {
     "glowtts_griffin_lim_step_f32": (I, [P] * 6 + [F, P] + [I] * 6 + [P]),
     "glowtts_mel_analysis_f32": (I, [P] * 7 + [I] * 8 + [F] * 3 + [P]),
     "glowtts_yin_f32": (I, [P] * 4 + [I] * 7 + [F, F, P]),
+    "glowtts_prior_sample": (I, [P] * 9 + [I] * 4 + [P]),
 }

@@ -127,6 +127,45 @@ class ExpandPrior(torch.autograd.Function):
         return dsrc, None, None
 
 
+def seed_words(seeds, B, device):
+    """`seeds` [B, 2] (int64 or uint32; the low 32 bits of every word count) -> the device buffer [B, 2] glowtts_prior_sample reads: the words' bit patterns,
+    held as int32 (torch has few uint32 kernels).  The arithmetic runs where `seeds` lives - on the host for a host tensor, then one small upload."""
+    if not torch.is_tensor(seeds):
+        seeds = torch.tensor(seeds, dtype=torch.int64)
+    if tuple(seeds.shape) != (B, 2) or seeds.is_floating_point() or seeds.dtype == torch.bool:
+        raise ValueError(f"seeds must be an integer tensor of shape [{B}, 2] (two 32-bit words per utterance), got {tuple(seeds.shape)} {seeds.dtype}")
+    if seeds.dtype == torch.uint32:
+        words = seeds.contiguous().view(torch.int32)
+    elif seeds.dtype == torch.int32:
+        words = seeds
+    else:
+        w = seeds.to(torch.int64) & 0xFFFFFFFF
+        words = torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+    return words.to(device).contiguous()
+
+
+@torch.no_grad()
+def prior_sample(mean, log_std, dur, mel_lengths, seeds, noise_scales, Tmax, want_attn=True):
+    """Modules.py:175-191 in one launch (csrc/sample_ops.hip): mean / log_std [B, C, Tx], dur [B, Tx] (integer-valued), mel_lengths [B] i64, seeds [B, 2]
+    (the device buffer `seed_words` makes, or any integer tensor), noise_scales [B] f32 -> (z [B, C, Tmax], idx [B, Tmax] i32, attentions
+    [B, Tx, Tmax] or None).  z's noise is a function of (seed words, channel, frame) only: see DESIGN.md "Seeded sampling"."""
+    mean, log_std, dur = mean.contiguous(), log_std.contiguous(), dur.contiguous()
+    B, C, Tx = mean.shape
+    Tmax = int(Tmax)
+    dev = mean.device
+    if not torch.is_tensor(seeds) or seeds.dtype != torch.int32 or seeds.device != dev or tuple(seeds.shape) != (B, 2):
+        seeds = seed_words(seeds, B, dev)
+    if tuple(noise_scales.shape) != (B,) or noise_scales.dtype != torch.float32 or tuple(dur.shape) != (B, Tx) or dur.dtype != torch.float32 or \
+            tuple(log_std.shape) != (B, C, Tx) or tuple(mel_lengths.shape) != (B,) or mel_lengths.dtype != torch.int64:
+        raise ValueError("prior_sample: mean / log_std [B, C, Tx] f32, dur [B, Tx] f32, mel_lengths [B] i64, noise_scales [B] f32")
+    z, idx = torch.empty(B, C, Tmax, device=dev), torch.empty(B, Tmax, dtype=torch.int32, device=dev)
+    attn = torch.empty(B, Tx, Tmax, device=dev) if want_attn else None
+    _lib.check(_lib.lib().glowtts_prior_sample(_lib.ptr(mean), _lib.ptr(log_std), _lib.ptr(dur), _lib.ptr(mel_lengths.contiguous()), _lib.ptr(seeds.contiguous()),
+                                               _lib.ptr(noise_scales.contiguous()), _lib.ptr(z), _lib.ptr(idx), _lib.ptr(attn), B, C, Tx, Tmax, _lib.stream()),
+               "glowtts_prior_sample")
+    return z, idx, attn
+
+
 @torch.no_grad()
 def duration_targets(idx, token_lengths, Tx):
     """log(sum_t attentions + 1e-7) * token_mask (Modules.py:122) -> [B,1,Tx]."""

@@ -459,6 +459,7 @@ __global__ __launch_bounds__(256) void expand_fwd4_kernel(const float* __restric
 extern "C" int glowtts_expand_fwd(const float* src, const int32_t* idx, float* out, int B, int C, int Tx, int Ty, void* stream)
 {
     if (!src || !idx || !out || B < 1 || C < 1 || Tx < 1 || Ty < 1) return GLOWTTS_E_ARG;
+    GLOWTTS_NOTE_STATIC("expand_fwd");
     const uint64_t total4 = (uint64_t)B * C * Ty / 4;
     if ((Ty & 3) == 0 && ((reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(out)) & 15) == 0 && total4 < (1ull << 31)) {
         const unsigned int blocks = (unsigned int)((total4 + 255) / 256 < 8192 ? (total4 + 255) / 256 : 8192);

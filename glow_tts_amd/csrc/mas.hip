@@ -305,6 +305,7 @@ extern "C" int glowtts_mas_path_from_idx(const int32_t* idx, void* path, int B, 
 {
     if (!idx || !path || B < 0 || Tx < 1 || Ty < 1 || (out_dtype != 0 && out_dtype != 1)) return GLOWTTS_E_ARG;
     if (B == 0) return GLOWTTS_OK;
+    GLOWTTS_NOTE_STATIC("mas_path_from_idx");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const uint64_t total4 = (uint64_t)B * Tx * Ty / 4;
     if ((Ty % 4 == 0) && ((reinterpret_cast<uintptr_t>(path) & 15) == 0) && ((reinterpret_cast<uintptr_t>(idx) & 15) == 0) && total4 < (1ull << 31) &&

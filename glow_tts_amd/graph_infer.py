@@ -54,11 +54,24 @@ class GraphedInference:
 
     @torch.no_grad()
     def __call__(self, tokens, token_lengths, speakers=None, mels_for_ge2e=None, noise_scale=1.0, length_scale=1.0, noises=None,
-                 mels_for_prosody=None, mel_lengths_for_prosody=None):
+                 mels_for_prosody=None, mel_lengths_for_prosody=None, seeds=None):
         """-> (mels [B, Mel, T], mel_lengths [B], attentions [B, T_token, T]) like `GlowTTS.inference`; T = the batch's longest utterance
-        rounded down to a multiple of Num_Squeeze (as the reference).  `noises` [B, Mel, >= T] replaces the internal Gaussian draw."""
+        rounded down to a multiple of Num_Squeeze (as the reference).  `noises` [B, Mel, >= T] replaces the internal Gaussian draw; `seeds` (integer
+        [B, 2]) draws it from the per-utterance seed words instead (`GlowTTS.inference`), with `noise_scale` a float or a [B] tensor: the seeded graph
+        reads both from static device buffers filled before every replay."""
         m = self.model
         dev = tokens.device
+        m._check_sampling_args(noise_scale, noises, seeds)
+        B = tokens.shape[0]
+        if seeds is not None:
+            from .alignment import seed_words
+            seeds = seed_words(seeds, B, dev)
+            if torch.is_tensor(noise_scale):
+                scales = noise_scale.to(device=dev, dtype=torch.float32).reshape(-1)
+                if scales.numel() not in (1, B):
+                    raise ValueError(f"`noise_scale` must be a scalar or a [B] tensor (B = {B}), got {tuple(noise_scale.shape)}")
+            else:
+                scales = float(noise_scale)
         if not torch.is_tensor(length_scale):
             length_scale = torch.tensor([float(length_scale)], device=dev)
         cond_in = speakers if speakers is not None else mels_for_ge2e
@@ -86,9 +99,26 @@ class GraphedInference:
         ns = int(m.hp.Decoder.Num_Squeeze)
         T = (tmax // ns) * ns
         if i == len(self.buckets):                                     # longer than the largest bucket: the back half eagerly, nothing captured
-            mels, lengths, attn = m.inference_back(front, None, noise_scale, noises, prep=self.prep)
+            if seeds is not None and not torch.is_tensor(scales):
+                scales = torch.full((B,), scales, device=dev)
+            mels, lengths, attn = m.inference_back(front, None, noise_scale if seeds is None else scales, noises, prep=self.prep, seeds=seeds)
             return mels[:, :, :T], lengths, attn[:, :, :tmax]
         Tb = self.buckets[i]
+        if seeds is not None:
+            bkey = (key, Tb, "seeded")
+            if bkey not in self.back:
+                sd_t, sc_t = torch.zeros(B, 2, dtype=torch.int32, device=dev), torch.ones(B, device=dev)
+                fn = lambda: m.inference_back(front, Tb, sc_t, None, prep=self.prep, seeds=sd_t)
+                g2, out2 = self._graph(fn)
+                self.back[bkey] = (g2, sc_t, sd_t, out2)
+            g2, sc_t, sd_t, (mels, lengths, attn) = self.back[bkey]
+            sd_t.copy_(seeds, non_blocking=True)
+            if torch.is_tensor(scales):
+                sc_t.copy_(scales.expand(B) if scales.numel() == 1 else scales, non_blocking=True)
+            else:
+                sc_t.fill_(scales)
+            g2.replay()
+            return mels[:, :, :T], lengths, attn[:, :, :tmax]
         bkey = (key, Tb, noises is not None)
         if bkey not in self.back:
             ns_t = torch.tensor(float(noise_scale), device=dev)

@@ -5,6 +5,7 @@ where the mode allows it), one `.npy` mel per utterance (`Inference.py:213-220`;
 `WAV/<label>.wav` next to it from the Griffin-Lim vocoder (`vocoder.GriffinLim`: a baseline vocoder, not a neural one).  `references` are either
 `.npy` files / arrays holding mels [T, Mel] (what `Pattern_Generator.Pattern_Generate` produces) or wav files, which go through
 `glow_tts_amd.audio` (librosa-free restatement of `Audio.py`; resampling is not implemented: the wav must be at hp.Sound.Sample_Rate)."""
+import hashlib
 import logging
 import os
 
@@ -14,6 +15,13 @@ import torch
 from . import data
 from .hparams import get_hp
 from .modules import GlowTTS
+
+
+def utterance_seed_words(seed, label, k=0):
+    """The two 32-bit seed words of sample `k` of the utterance `label` under the run seed `seed`: the first 8 bytes of blake2b of "<seed> NUL <label> NUL <k>", little
+    endian.  A function of the three only (not Python's per-process salted hash()): the same in every process, whatever the order or the batch size."""
+    d = hashlib.blake2b("{}\0{}\0{}".format(seed, label, k).encode()).digest()
+    return int.from_bytes(d[:4], "little"), int.from_bytes(d[4:8], "little")
 
 
 class Inferencer:
@@ -47,14 +55,25 @@ class Inferencer:
         self.model_Dict["GlowTTS"].to(self.device)
         logging.info("Checkpoint loaded at {} steps.".format(state_Dict.get("Steps")))
 
-    def _write_wavs(self, mels, mel_lengths, names, inference_path):
-        """Griffin-Lim on the mels as the model produced them ([B, Mel, T], on the device) -> WAV/<name>.wav: de-emphasised, 16-bit, Sound.Sample_Rate."""
+    def _write_wavs(self, mels, mel_lengths, names, inference_path, seeds=None):
+        """Griffin-Lim on the mels as the model produced them ([B, Mel, T], on the device) -> WAV/<name>.wav: de-emphasised, 16-bit, Sound.Sample_Rate.
+        seeds (integer [B, 2], seeded sampling): Griffin-Lim's start phase of every utterance is drawn from a host generator seeded with its two seed words,
+        over that utterance's own frames (zero beyond) - a function of the seed and the utterance's length only, so the wav is as reproducible as the mel.
+        None: torch's device generator, as before."""
         from . import audio
         from .vocoder import GriffinLim
         if self._vocoder is None:
             self._vocoder = GriffinLim(self.hp, self.device)
         mels = mels[:, :, :int(mel_lengths.max())]                                # a served batch may be padded beyond its longest utterance
-        wavs = self._vocoder.to_host(*self._vocoder(mels, mel_lengths))
+        phase = None
+        if seeds is not None:
+            T, F = mels.shape[2], self._vocoder.n_freq
+            phase = torch.zeros(mels.shape[0], T, F)
+            for b, (n, (s0, s1)) in enumerate(zip(mel_lengths.cpu().tolist(), seeds.tolist())):
+                n = min(int(n), T)
+                g = torch.Generator().manual_seed((int(s0) & 0xFFFFFFFF) | ((int(s1) & 0x7FFFFFFF) << 32))
+                phase[b, :n] = (torch.rand(n, F, generator=g) * 2.0 - 1.0) * float(np.pi)
+        wavs = self._vocoder.to_host(*self._vocoder(mels, mel_lengths, initial_phase=phase))
         os.makedirs(os.path.join(inference_path, "WAV").replace("\\", "/"), exist_ok=True)
         for name, x in zip(names, wavs):
             path = os.path.join(inference_path, "WAV", name + ".wav").replace("\\", "/")
@@ -80,12 +99,17 @@ class Inferencer:
 
     @torch.no_grad()
     def Inference_Step(self, tokens, token_lengths, prosodies, prosody_lengths, speakers, ge2es, pitches, pitch_lengths, length_scales, labels, texts,
-                       start_index=0, tag_index=False, inference_path="./inference", noise_scale=1.0, wav=False):
-        """Inference.py:139-223 without the plots: returns the list of written .npy files."""
+                       start_index=0, tag_index=False, inference_path="./inference", noise_scale=1.0, wav=False, seeds=None, sample_index=None):
+        """Inference.py:139-223 without the plots: returns the list of written .npy files.  seeds: integer [B, 2], the utterances' seed words (None: the
+        unseeded draw); sample_index k: the files are <label>.S<k>.npy / .wav."""
         dev = self.device
         mv = lambda t: t if t is None else t.to(dev)
         model = self.model_Dict["GlowTTS"]
         kw = dict(mels_for_prosody=mv(prosodies), mel_lengths_for_prosody=mv(prosody_lengths), speakers=mv(speakers), mels_for_ge2e=mv(ge2es))
+        if seeds is not None:
+            kw["seeds"] = seeds
+            if torch.is_tensor(noise_scale):
+                noise_scale = noise_scale.to(dev)
         if "Pitch_Interpolater" in model.layer_Dict:                             # GR: the pitch track rides the eager path
             mels, mel_Lengths, attentions = model.inference(mv(tokens), mv(token_lengths), pitches=mv(pitches), pitch_lengths=mv(pitch_lengths),
                                                             noise_scale=noise_scale, length_scale=mv(length_scales), **kw)
@@ -95,9 +119,10 @@ class Inferencer:
                 self._graphed = GraphedInference(model)
             mels, mel_Lengths, attentions = self._graphed(mv(tokens), mv(token_lengths), noise_scale=noise_scale, length_scale=mv(length_scales), **kw)
         os.makedirs(os.path.join(inference_path, "NPY").replace("\\", "/"), exist_ok=True)
-        names = [".".join([str(label)] + (["IDX_{}".format(index + start_index)] if tag_index else [])) for index, label in enumerate(labels)]
+        names = [".".join([str(label)] + (["S{}".format(sample_index)] if sample_index is not None else []) +
+                          (["IDX_{}".format(index + start_index)] if tag_index else [])) for index, label in enumerate(labels)]
         if wav:                                                                  # on the device, before the copy to the host
-            self._write_wavs(mels, mel_Lengths, names, inference_path)
+            self._write_wavs(mels, mel_Lengths, names, inference_path, seeds=seeds)
         files = []
         for name, mel, n in zip(names, mels.cpu().numpy(), mel_Lengths.cpu().tolist()):
             path = os.path.join(inference_path, "NPY", name + ".npy").replace("\\", "/")
@@ -105,11 +130,23 @@ class Inferencer:
             files.append(path)
         return files
 
-    def Inference(self, labels, texts, scales, speakers=None, references=None, inference_path="./inference", noise_scale=1.0, wav=False):
-        """Inference.py:225-256.  wav: also WAV/<label>.wav per utterance (paths in `last_wav_files`; the returned list stays the .npy files)."""
+    def Inference(self, labels, texts, scales, speakers=None, references=None, inference_path="./inference", noise_scale=1.0, wav=False, seed=None, samples=1):
+        """Inference.py:225-256.  wav: also WAV/<label>.wav per utterance (paths in `last_wav_files`; the returned list stays the .npy files).
+        seed (an int): reproducible sampling - every utterance draws its noise from `utterance_seed_words(seed, label, k)`, so its mel depends on the seed, its
+        label and the sample number k only, not on the order of the prompts or Inference_Batch_Size; None: the unseeded draw.  noise_scale: the sampling
+        temperature, a float or - seeded only - one float per utterance.  samples = N > 1: N takes of every prompt, written as <label>.S<k>.npy (and .wav),
+        k < N; samples = 1 keeps the plain names."""
         logging.info("Start inference.")
         self.last_wav_files = []
         hp = self.hp
+        samples = int(samples)
+        if samples < 1:
+            raise ValueError("`samples` must be at least 1")
+        per_utterance = isinstance(noise_scale, (list, tuple))
+        if per_utterance and seed is None:
+            raise ValueError("a per-utterance `noise_scale` list needs `seed` (the unseeded draw takes one `noise_scale` for all utterances)")
+        if per_utterance and len(noise_scale) != len(texts):
+            raise ValueError("`noise_scale` lists one value per text")
         bs = hp.Inference_Batch_Size or hp.Train.Batch_Size
         speakers = speakers or [None] * len(texts)
         references = references or [None] * len(texts)
@@ -135,8 +172,12 @@ class Inferencer:
                     for b, (_, p) in enumerate(mp):
                         pit[b, :p.shape[0]] = torch.from_numpy(p)
             spk = None if any(x is None for x in speakers[sl]) else torch.tensor(speakers[sl], dtype=torch.int64)
-            files += self.Inference_Step(tokens, tl, pros, pl, spk, None, pit, pitl, torch.tensor(scales[sl], dtype=torch.float32), labels[sl], texts[sl],
-                                         start_index=s, inference_path=inference_path, noise_scale=noise_scale, wav=wav)
+            ns = torch.tensor([float(x) for x in noise_scale[sl]], dtype=torch.float32) if per_utterance else noise_scale
+            for k in range(samples):
+                seeds = None if seed is None else torch.tensor([utterance_seed_words(seed, label, k) for label in labels[sl]], dtype=torch.int64)
+                files += self.Inference_Step(tokens, tl, pros, pl, spk, None, pit, pitl, torch.tensor(scales[sl], dtype=torch.float32), labels[sl], texts[sl],
+                                             start_index=s, inference_path=inference_path, noise_scale=ns, wav=wav, seeds=seeds,
+                                             sample_index=k if samples > 1 else None)
         return files
 
     def Vocode(self, labels, mels, inference_path="./inference"):
@@ -254,9 +295,9 @@ def read_vocode_list(path):
     return out
 
 
-def main(argv=None):
+def build_parser():
+    """The command line of Inference.py."""
     import argparse
-    logging.basicConfig(level=logging.INFO)
     ap = argparse.ArgumentParser()
     ap.add_argument("-c", "--checkpoint", required=True)
     ap.add_argument("-t", "--prompts", default=None, help="inference prompt TSV (Datasets.py:137-144); default: the reference's two example sentences")
@@ -266,7 +307,15 @@ def main(argv=None):
     ap.add_argument("--wav", action="store_true", help="also write WAV/<label>.wav per utterance (Griffin-Lim: a baseline vocoder, not a neural one)")
     ap.add_argument("--vocode", default=None, metavar="LIST", help="vocode existing mels instead of synthesising: one label<TAB>mel.npy ([T, Mel]) per line")
     ap.add_argument("--device-frontend", action="store_true", help="analyse wav references / conversion sources on the device instead of the host")
-    args = ap.parse_args(argv)
+    ap.add_argument("--seed", type=int, default=None, help="reproducible sampling: an utterance's mel depends on this seed, its label and the sample number only")
+    ap.add_argument("--noise-scale", type=float, default=1.0, help="sampling temperature (the standard deviation of the prior is multiplied by it)")
+    ap.add_argument("--samples", type=int, default=1, help="takes per prompt; N > 1 writes <label>.S<k>.npy (and .wav) for k < N")
+    return ap
+
+
+def main(argv=None):
+    logging.basicConfig(level=logging.INFO)
+    args = build_parser().parse_args(argv)
     inf = Inferencer(checkpoint_path=args.checkpoint, device_frontend=args.device_frontend)
     if args.vocode:
         recs = read_vocode_list(args.vocode)
@@ -285,4 +334,5 @@ def main(argv=None):
         labels, texts, scales, speakers = ["Alpha", "Bravo"], ["Birds of a feather flock together.",
                                                                "A creative artist works on his next composition because he was not satisfied with his previous one."], [1.0, 0.9], [0, 1]
     mode = inf.hp.Mode.upper()
-    print("\n".join(inf.Inference(labels, texts, scales, speakers if mode in ("SE", "GR") else None, None, args.out, wav=args.wav) + inf.last_wav_files))
+    print("\n".join(inf.Inference(labels, texts, scales, speakers if mode in ("SE", "GR") else None, None, args.out, wav=args.wav, seed=args.seed,
+                                  noise_scale=args.noise_scale, samples=args.samples) + inf.last_wav_files))

@@ -426,11 +426,21 @@ class GlowTTS(torch.nn.Module):
     # ---------------------------------------------------------------- inverse flow
     @torch.no_grad()
     def inference(self, tokens, token_lengths, mels_for_prosody=None, mel_lengths_for_prosody=None, speakers=None,
-                  mels_for_ge2e=None, pitches=None, pitch_lengths=None, noise_scale=1.0, length_scale=1.0, noises=None):
+                  mels_for_ge2e=None, pitches=None, pitch_lengths=None, noise_scale=1.0, length_scale=1.0, noises=None, seeds=None):
         """Modules.py:128-204.  `noises` (optional, [B, Mel_Dim, >= max T_mel]) injects the Gaussian noise the reference
-        draws with torch.randn_like (:187) so that results are reproducible."""
+        draws with torch.randn_like (:187) so that results are reproducible.  `seeds` (optional, int64 / uint32 [B, 2]: two 32-bit words per
+        utterance) draws it on the device instead, as a function of (seed words, channel, frame) only - the same utterance with the same seed gets
+        the same noise in any batch, at any padding (one fused launch, `alignment.prior_sample`); `noise_scale` may then be a [B] tensor."""
+        self._check_sampling_args(noise_scale, noises, seeds)
         front = self.inference_front(tokens, token_lengths, mels_for_prosody, mel_lengths_for_prosody, speakers, mels_for_ge2e, length_scale)
-        return self.inference_back(front, None, noise_scale, noises, pitches=pitches, pitch_lengths=pitch_lengths)
+        return self.inference_back(front, None, noise_scale, noises, pitches=pitches, pitch_lengths=pitch_lengths, seeds=seeds)
+
+    @staticmethod
+    def _check_sampling_args(noise_scale, noises, seeds):
+        if seeds is not None and noises is not None:
+            raise ValueError("`seeds` and `noises` both given: the noise is either drawn on the device from `seeds` or injected as `noises`")
+        if seeds is None and torch.is_tensor(noise_scale) and noise_scale.dim() > 0 and noise_scale.numel() > 1:
+            raise ValueError("a per-utterance `noise_scale` [B] needs `seeds` (the unseeded path takes one scalar `noise_scale` for the batch)")
 
     @torch.no_grad()
     def inference_front(self, tokens, token_lengths, mels_for_prosody=None, mel_lengths_for_prosody=None, speakers=None, mels_for_ge2e=None,
@@ -450,11 +460,20 @@ class GlowTTS(torch.nn.Module):
         return mean, log_std, dur, mel_lengths, token_mask, spk, pro
 
     @torch.no_grad()
-    def inference_back(self, front, max_mel_length=None, noise_scale=1.0, noises=None, prep=None, pitches=None, pitch_lengths=None):
+    def inference_back(self, front, max_mel_length=None, noise_scale=1.0, noises=None, prep=None, pitches=None, pitch_lengths=None, seeds=None):
         """Second half (Modules.py:175-204): hard alignment, prior sample, inverse flow.  max_mel_length: padded frame count (None: the batch
-        maximum, read back from the device like the reference's torch.max); prep: a decoder._Prepared kept by the caller (static weights)."""
-        hp = self.hp
+        maximum, read back from the device like the reference's torch.max); prep: a decoder._Prepared kept by the caller (static weights);
+        seeds: see `inference` (the device buffer of `alignment.seed_words`, or any integer [B, 2] tensor)."""
         mean, log_std, dur, mel_lengths, token_mask, spk, pro = front
+        self._check_sampling_args(noise_scale, noises, seeds)
+        if seeds is not None:
+            sample = self._seeded_sample(mean, log_std, dur, mel_lengths, max_mel_length, noise_scale, seeds)
+        else:
+            sample = self._unseeded_sample(mean, log_std, dur, mel_lengths, max_mel_length, noise_scale, noises)
+        return self._inverse_flow(sample, mel_lengths, spk, pro, prep, pitches, pitch_lengths)
+
+    def _unseeded_sample(self, mean, log_std, dur, mel_lengths, max_mel_length, noise_scale, noises):
+        """Modules.py:175-191 with torch's draw (or the injected `noises`) -> (z, attentions)"""
         mel_mask = self.Mask_Generate(mel_lengths, max_mel_length)
         # Path_Generate (:181, :213-229) makes the hard alignment dense - attentions[x, y] = 1 iff cum[x-1] <= y < cum[x] - and the reference
         # expands mean / log_Std with two dense bmm (:183-184).  Here the per-frame token index comes from one search over the cumulative
@@ -471,6 +490,28 @@ class GlowTTS(torch.nn.Module):
         if noises is None:
             noises = torch.randn_like(mel_mean)
         z = (mel_mean + torch.exp(mel_log_std) * noises[:, :, :mel_mean.shape[2]] * noise_scale) * mel_mask   # :187-191
+        return z, attn
+
+    def _seeded_sample(self, mean, log_std, dur, mel_lengths, max_mel_length, noise_scale, seeds):
+        """Modules.py:175-191 as ONE launch (durations -> hard alignment -> dense attentions, expanded prior, sample) with counter-hash noise."""
+        B = mean.shape[0]
+        Tmax = int(max_mel_length) if max_mel_length is not None else int(torch.max(mel_lengths))
+        if torch.is_tensor(noise_scale):
+            scales = noise_scale.to(device=mean.device, dtype=torch.float32).reshape(-1)
+            if scales.numel() == 1:
+                scales = scales.expand(B)
+            elif scales.numel() != B:
+                raise ValueError(f"`noise_scale` must be a scalar or a [B] tensor (B = {B}), got {tuple(noise_scale.shape)}")
+            scales = scales.contiguous()
+        else:
+            scales = torch.full((B,), float(noise_scale), device=mean.device)
+        z, _, attn = alignment.prior_sample(mean, log_std, dur, mel_lengths, seeds, scales, Tmax)
+        return z, attn
+
+    def _inverse_flow(self, sample, mel_lengths, spk, pro, prep, pitches, pitch_lengths):
+        """Modules.py:193-204 on the sampled z: -> (mels, mel_lengths, attentions)"""
+        hp = self.hp
+        z, attn = sample
         P = self._params()
         stacks = self._stacks(P)
         cond = stacks.conditioning(spk, pro)

@@ -859,6 +859,21 @@ int glowtts_mel_analysis_f32(const float *wav, const int32_t *wav_lengths, const
 int glowtts_yin_f32(const float *wav, const int32_t *wav_lengths, float *pitch, float *cmnd, int B, int ldx, int T, int w_len, int w_step, int tau_min,
                     int tau_max, float thresh, float sample_rate, void *stream);
 
+/* ---- seeded prior sample of GlowTTS.inference (csrc/sample_ops.hip; an addition, the ABI version stays) ----
+ * Modules.py:175-191 in ONE launch, logged as `prior_sample`: mean / log_std [B][C][Tx] (the text encoder's), dur [B][Tx] (integer-valued, >= 0),
+ * mel_lengths [B] -> with cum the running sum of dur (int32):
+ *   idx  [B][Tmax]      idx[y] = #{x : cum[x] <= y} where y < mel_lengths[b] and that count is < Tx, else -1
+ *   attn [B][Tx][Tmax]  attn[x][y] = (idx[y] == x), every element written; NULL: not written
+ *   z    [B][C][Tmax]   mean[idx] + exp(log_std[idx]) * gauss(seeds[b][0], seeds[b][1], c, y, C) * noise_scales[b] where idx >= 0, exactly 0 elsewhere
+ * gauss is the counter hash of csrc/gauss_hash.h (a frozen contract, DESIGN.md "Seeded sampling"): a function of the utterance's two seed words, the
+ * channel and the frame only - not of B, Tx, Tmax or the utterance's place in the batch.  seeds [B][2] and noise_scales [B] are DEVICE buffers read by the
+ * kernel (a captured graph reads them at every replay).  Tx of any length: the durations are scanned through LDS in chunks of GLOWTTS_SAMPLE_SCAN_CHUNK
+ * tokens; grid (ceil(Tmax / GLOWTTS_SAMPLE_TILE), B).  16-byte stores when Tmax % 4 == 0 and z / attn are 16-byte aligned, the same values otherwise. */
+#define GLOWTTS_SAMPLE_SCAN_CHUNK 1024
+#define GLOWTTS_SAMPLE_TILE 64
+int glowtts_prior_sample(const float *mean, const float *log_std, const float *dur, const int64_t *mel_lengths, const uint32_t *seeds,
+                         const float *noise_scales, float *z, int32_t *idx, float *attn, int B, int C, int Tx, int Tmax, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
