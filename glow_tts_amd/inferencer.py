@@ -2,7 +2,8 @@
 references, inference_path)`), thin: text -> tokens (`Token.yaml`), optional reference mels for the prosody encoder / pitch tracks, `S_*.pt`
 checkpoint (ActNorm marked initialised, `Inference.py:258-270`), `GlowTTS.inference` (replayed as hipGraphs through `graph_infer.GraphedInference`
 where the mode allows it), one `.npy` mel per utterance (`Inference.py:213-220`; the PNG plots are out of scope) and, with `wav=True`, one
-`WAV/<label>.wav` next to it from the Griffin-Lim vocoder (`vocoder.GriffinLim`: a baseline vocoder, not a neural one).  `references` are either
+`WAV/<label>.wav` next to it from the active vocoder: Griffin-Lim (`vocoder.GriffinLim`: a baseline vocoder, not a neural one) or, with the yaml block
+`Vocoder` / `vocoder='pwg'` and a checkpoint, the Parallel WaveGAN generator (`vocoder.ParallelWaveGAN`).  `references` are either
 `.npy` files / arrays holding mels [T, Mel] (what `Pattern_Generator.Pattern_Generate` produces) or wav files, which go through
 `glow_tts_amd.audio` (librosa-free restatement of `Audio.py`; resampling is not implemented: the wav must be at hp.Sound.Sample_Rate)."""
 import hashlib
@@ -25,10 +26,16 @@ def utterance_seed_words(seed, label, k=0):
 
 
 class Inferencer:
-    def __init__(self, checkpoint_path, hp=None, device="cuda:0", device_frontend=False):
+    def __init__(self, checkpoint_path, hp=None, device="cuda:0", device_frontend=False, vocoder=None, vocoder_checkpoint=None):
         """device_frontend: wav references and wav voice-conversion sources are analysed on the device (`frontend.Analyzer`) instead of the host's
-        `audio.pattern_from_wav`; decoding, trimming and normalisation stay `audio.audio_prep` either way."""
+        `audio.pattern_from_wav`; decoding, trimming and normalisation stay `audio.audio_prep` either way.
+        vocoder: 'pwg' (the neural vocoder), 'griffin_lim' (forces the baseline) or None: 'pwg' when the yaml has the `Vocoder` block or
+        `vocoder_checkpoint` (overrides `Vocoder.Checkpoint_Path`) is given, Griffin-Lim otherwise."""
         self.hp = hp if hp is not None else get_hp()
+        if vocoder not in (None, "pwg", "griffin_lim"):
+            raise ValueError("vocoder must be 'pwg', 'griffin_lim' or None, got {!r}".format(vocoder))
+        self.vocoder_kind = vocoder or ("pwg" if vocoder_checkpoint or getattr(self.hp, "Vocoder", None) is not None else "griffin_lim")
+        self.vocoder_checkpoint = vocoder_checkpoint
         self.device = torch.device(device)
         self.device_frontend, self._analyzer = bool(device_frontend), None
         self.token_Dict = data.load_token_dict(self.hp.Token_Path)
@@ -55,25 +62,42 @@ class Inferencer:
         self.model_Dict["GlowTTS"].to(self.device)
         logging.info("Checkpoint loaded at {} steps.".format(state_Dict.get("Steps")))
 
-    def _write_wavs(self, mels, mel_lengths, names, inference_path, seeds=None):
-        """Griffin-Lim on the mels as the model produced them ([B, Mel, T], on the device) -> WAV/<name>.wav: de-emphasised, 16-bit, Sound.Sample_Rate.
+    def _make_vocoder(self):
+        from . import vocoder
+        if self.vocoder_kind != "pwg":
+            return vocoder.GriffinLim(self.hp, self.device)
+        hp = self.hp
+        if self.vocoder_checkpoint:                                              # the argument overrides the yaml's path
+            import argparse
+            import copy
+            hp = copy.copy(hp)
+            hp.Vocoder = argparse.Namespace(**dict(vocoder.pwg_settings(hp), Checkpoint_Path=self.vocoder_checkpoint))
+        return vocoder.ParallelWaveGAN(hp, self.device)
+
+    def _write_wavs(self, mels, mel_lengths, names, inference_path, seeds=None, vocoder_seeds=None):
+        """The active vocoder on the mels as the model produced them ([B, Mel, T], on the device) -> WAV/<name>.wav, 16-bit, Sound.Sample_Rate.
+        Neural vocoder: frames * Frame_Shift samples, clipped to [-1, 1], no de-emphasis; vocoder_seeds (integer [B, 2], `vocoder.pwg_seed_words`): its noise is
+        the counter hash of those words, so the wav repeats byte for byte; None: torch's device generator.
+        Griffin-Lim: de-emphasised.
         seeds (integer [B, 2], seeded sampling): Griffin-Lim's start phase of every utterance is drawn from a host generator seeded with its two seed words,
         over that utterance's own frames (zero beyond) - a function of the seed and the utterance's length only, so the wav is as reproducible as the mel.
         None: torch's device generator, as before."""
         from . import audio
-        from .vocoder import GriffinLim
         if self._vocoder is None:
-            self._vocoder = GriffinLim(self.hp, self.device)
+            self._vocoder = self._make_vocoder()
         mels = mels[:, :, :int(mel_lengths.max())]                                # a served batch may be padded beyond its longest utterance
         phase = None
-        if seeds is not None:
+        if self.vocoder_kind == "pwg":
+            wavs = self._vocoder.to_host(*self._vocoder(mels, mel_lengths, seeds=vocoder_seeds))
+        elif seeds is not None:
             T, F = mels.shape[2], self._vocoder.n_freq
             phase = torch.zeros(mels.shape[0], T, F)
             for b, (n, (s0, s1)) in enumerate(zip(mel_lengths.cpu().tolist(), seeds.tolist())):
                 n = min(int(n), T)
                 g = torch.Generator().manual_seed((int(s0) & 0xFFFFFFFF) | ((int(s1) & 0x7FFFFFFF) << 32))
                 phase[b, :n] = (torch.rand(n, F, generator=g) * 2.0 - 1.0) * float(np.pi)
-        wavs = self._vocoder.to_host(*self._vocoder(mels, mel_lengths, initial_phase=phase))
+        if self.vocoder_kind != "pwg":
+            wavs = self._vocoder.to_host(*self._vocoder(mels, mel_lengths, initial_phase=phase))
         os.makedirs(os.path.join(inference_path, "WAV").replace("\\", "/"), exist_ok=True)
         for name, x in zip(names, wavs):
             path = os.path.join(inference_path, "WAV", name + ".wav").replace("\\", "/")
@@ -99,9 +123,9 @@ class Inferencer:
 
     @torch.no_grad()
     def Inference_Step(self, tokens, token_lengths, prosodies, prosody_lengths, speakers, ge2es, pitches, pitch_lengths, length_scales, labels, texts,
-                       start_index=0, tag_index=False, inference_path="./inference", noise_scale=1.0, wav=False, seeds=None, sample_index=None):
+                       start_index=0, tag_index=False, inference_path="./inference", noise_scale=1.0, wav=False, seeds=None, sample_index=None, vocoder_seeds=None):
         """Inference.py:139-223 without the plots: returns the list of written .npy files.  seeds: integer [B, 2], the utterances' seed words (None: the
-        unseeded draw); sample_index k: the files are <label>.S<k>.npy / .wav."""
+        unseeded draw); sample_index k: the files are <label>.S<k>.npy / .wav; vocoder_seeds: the neural vocoder's seed words (`_write_wavs`)."""
         dev = self.device
         mv = lambda t: t if t is None else t.to(dev)
         model = self.model_Dict["GlowTTS"]
@@ -122,7 +146,10 @@ class Inferencer:
         names = [".".join([str(label)] + (["S{}".format(sample_index)] if sample_index is not None else []) +
                           (["IDX_{}".format(index + start_index)] if tag_index else [])) for index, label in enumerate(labels)]
         if wav:                                                                  # on the device, before the copy to the host
-            self._write_wavs(mels, mel_Lengths, names, inference_path, seeds=seeds)
+            if vocoder_seeds is not None:
+                self._write_wavs(mels, mel_Lengths, names, inference_path, seeds=seeds, vocoder_seeds=vocoder_seeds)
+            else:
+                self._write_wavs(mels, mel_Lengths, names, inference_path, seeds=seeds)
         files = []
         for name, mel, n in zip(names, mels.cpu().numpy(), mel_Lengths.cpu().tolist()):
             path = os.path.join(inference_path, "NPY", name + ".npy").replace("\\", "/")
@@ -175,13 +202,17 @@ class Inferencer:
             ns = torch.tensor([float(x) for x in noise_scale[sl]], dtype=torch.float32) if per_utterance else noise_scale
             for k in range(samples):
                 seeds = None if seed is None else torch.tensor([utterance_seed_words(seed, label, k) for label in labels[sl]], dtype=torch.int64)
+                vseeds = None
+                if seed is not None and wav and self.vocoder_kind == "pwg":
+                    from .vocoder import pwg_seed_words
+                    vseeds = torch.tensor([pwg_seed_words(seed, label, k) for label in labels[sl]], dtype=torch.int64)
                 files += self.Inference_Step(tokens, tl, pros, pl, spk, None, pit, pitl, torch.tensor(scales[sl], dtype=torch.float32), labels[sl], texts[sl],
                                              start_index=s, inference_path=inference_path, noise_scale=ns, wav=wav, seeds=seeds,
-                                             sample_index=k if samples > 1 else None)
+                                             sample_index=k if samples > 1 else None, vocoder_seeds=vseeds)
         return files
 
     def Vocode(self, labels, mels, inference_path="./inference"):
-        """Recorded or previously generated mels - .npy paths or arrays [T, Mel] - through the Griffin-Lim vocoder, in batches of Inference_Batch_Size:
+        """Recorded or previously generated mels - .npy paths or arrays [T, Mel] - through the active vocoder, in batches of Inference_Batch_Size:
         one WAV/<label>.wav per mel; returns the written files (also in `last_wav_files`)."""
         logging.info("Start vocoding.")
         hp = self.hp
@@ -304,7 +335,11 @@ def build_parser():
     ap.add_argument("-o", "--out", default="./inference")
     ap.add_argument("--convert", default=None, metavar="LIST.tsv",
                     help="voice conversion instead of text-to-mel: label, source mel (.npy [T, Mel] or wav), source speaker, target speaker[, target reference]")
-    ap.add_argument("--wav", action="store_true", help="also write WAV/<label>.wav per utterance (Griffin-Lim: a baseline vocoder, not a neural one)")
+    ap.add_argument("--wav", action="store_true", help="also write WAV/<label>.wav per utterance: Griffin-Lim (a baseline vocoder, not a neural one) or, see --vocoder, the Parallel WaveGAN generator")
+    ap.add_argument("--vocoder", choices=["griffin_lim", "pwg"], default=None,
+                    help="the vocoder behind --wav / --vocode: pwg = the neural vocoder (Parallel WaveGAN generator; needs a checkpoint), griffin_lim = the baseline; "
+                         "default: pwg when the yaml has a `Vocoder` block or --vocoder-checkpoint is given, else griffin_lim")
+    ap.add_argument("--vocoder-checkpoint", default=None, metavar="PATH", help="Parallel WaveGAN generator checkpoint (overrides Vocoder.Checkpoint_Path of the yaml)")
     ap.add_argument("--vocode", default=None, metavar="LIST", help="vocode existing mels instead of synthesising: one label<TAB>mel.npy ([T, Mel]) per line")
     ap.add_argument("--device-frontend", action="store_true", help="analyse wav references / conversion sources on the device instead of the host")
     ap.add_argument("--seed", type=int, default=None, help="reproducible sampling: an utterance's mel depends on this seed, its label and the sample number only")
@@ -316,7 +351,7 @@ def build_parser():
 def main(argv=None):
     logging.basicConfig(level=logging.INFO)
     args = build_parser().parse_args(argv)
-    inf = Inferencer(checkpoint_path=args.checkpoint, device_frontend=args.device_frontend)
+    inf = Inferencer(checkpoint_path=args.checkpoint, device_frontend=args.device_frontend, vocoder=args.vocoder, vocoder_checkpoint=args.vocoder_checkpoint)
     if args.vocode:
         recs = read_vocode_list(args.vocode)
         print("\n".join(inf.Vocode([r[0] for r in recs], [r[1] for r in recs], args.out)))

@@ -159,3 +159,30 @@ def yin(wav, wav_lengths, pitch, w_len, w_step, tau_min, tau_max, thresh, sample
     B, T = pitch.shape
     _lib.check(_lib.lib().glowtts_yin_f32(_lib.ptr(wav), _lib.ptr(wav_lengths), _lib.ptr(pitch), _lib.ptr(cmnd), B, wav.shape[1], T, int(w_len), int(w_step),
                                           int(tau_min), int(tau_max), float(thresh), float(sample_rate), _lib.stream()), "glowtts_yin_f32")
+
+
+# ---- neural vocoder (csrc/pwg_ops.hip).  Rows are samples, channels-last; frame_lengths: int32 device tensor [B] ----
+def pwg_condition(mels, frame_lengths, w_in, firs, scales, work, c, ctx):
+    """mels [B, A, Lmax] -> c [B, Lmax * hop, A] (glowtts_pwg_condition); scales: a ctypes int array on the host."""
+    B, A, Lmax = mels.shape
+    _lib.check(_lib.lib().glowtts_pwg_condition(_lib.ptr(mels), _lib.ptr(frame_lengths), _lib.ptr(w_in), _lib.ptr(firs), scales, len(scales), _lib.ptr(work),
+                                                _lib.ptr(c), B, A, Lmax, int(ctx), _lib.stream()), "glowtts_pwg_condition")
+
+
+def pwg_first(noises, seeds, frame_lengths, w, bias, x, Lmax, hop):
+    """x [B, Lmax * hop, R] = first_conv(z); z: noises [B, Lmax * hop] or the in-kernel draw from seeds [B, 2] (glowtts_pwg_first)."""
+    _lib.check(_lib.lib().glowtts_pwg_first(_lib.ptr(noises), _lib.ptr(seeds), _lib.ptr(frame_lengths), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(x), x.shape[0],
+                                            int(Lmax), int(hop), x.shape[2], _lib.stream()), "glowtts_pwg_first")
+
+
+def pwg_layer(x, c, w1, b1, w2, b2, x_out, skips, frame_lengths, Lmax, hop, dilation, accumulate):
+    """One WaveNet layer (glowtts_pwg_layer): x, x_out [B, Lmax * hop, R], c [.., A], skips [.., S]."""
+    _lib.check(_lib.lib().glowtts_pwg_layer(_lib.ptr(x), _lib.ptr(c), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(x_out), _lib.ptr(skips),
+                                            _lib.ptr(frame_lengths), x.shape[0], int(Lmax), int(hop), x.shape[2], skips.shape[2], c.shape[2], int(dilation),
+                                            int(bool(accumulate)), _lib.stream()), "glowtts_pwg_layer")
+
+
+def pwg_head(skips, frame_lengths, w1, b1, w2, b2, wav, Lmax, hop, scale):
+    """skips [B, Lmax * hop, S] -> wav [B, Lmax * hop], zero beyond each utterance (glowtts_pwg_head)."""
+    _lib.check(_lib.lib().glowtts_pwg_head(_lib.ptr(skips), _lib.ptr(frame_lengths), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(wav),
+                                           skips.shape[0], int(Lmax), int(hop), skips.shape[2], float(scale), _lib.stream()), "glowtts_pwg_head")

@@ -1,4 +1,7 @@
-"""Waveform output: a Griffin-Lim vocoder on the HIP kernels of csrc/vocoder_ops.hip.  A BASELINE vocoder (no weights, audibly phasey), not a neural one:
+"""Waveform output.  Two vocoders: Griffin-Lim (below, the default) and - with the optional yaml block `Vocoder` and a checkpoint - the Parallel WaveGAN
+generator `ParallelWaveGAN` on the kernels of csrc/pwg_ops.hip (second half of this file).
+
+Griffin-Lim: a vocoder on the HIP kernels of csrc/vocoder_ops.hip.  A BASELINE vocoder (no weights, audibly phasey), not a neural one:
 it inverts exactly the front end `audio.py` restates (pre-emphasis, centred reflect-padded STFT, periodic Hann of Frame_Length zero-padded to n_fft, hop
 Frame_Shift, Slaney mel filterbank, dB normalisation to +- Max_Abs_Mel), so a generated or converted mel can be listened to without a second project.
 
@@ -7,6 +10,10 @@ Frame_Shift, Slaney mel filterbank, dB normalisation to +- Max_Abs_Mel), so a ge
 Fast Griffin-Lim with the momentum applied to the SIGNAL (the STFT is linear): y = x_n + alpha (x_n - x_n-1), x_n+1 = istft(|S| * Y / max(|Y|, 1e-8)) with
 Y = stft(y); two signals are kept, never a previous spectrogram, and the complex spectrum of an iteration never leaves LDS.  The waveform is still
 pre-emphasised: `audio.deemphasis` undoes that on the host before the samples are written."""
+import ctypes
+import hashlib
+import math
+
 import numpy as np
 import torch
 
@@ -156,3 +163,225 @@ class GriffinLim:
         """Device waveforms -> list of de-emphasised float32 numpy arrays (what `audio.write_wav` takes)."""
         wav, n = wav.cpu().numpy(), wav_lengths.cpu().tolist()
         return [audio.deemphasis(w[:m], self.pre_emphasis).astype(np.float32) for w, m in zip(wav, n)]
+
+
+# ================================================================================================================================================
+# Neural vocoder: the Parallel WaveGAN generator (Yamamoto et al. 2020), inference only, f32.  The network, the launch plan and the noise contract are
+# written down in DESIGN.md ("Neural vocoder"); the checkpoint layout restates the most widely used implementation's names and is UNPINNED (no such
+# checkpoint was at hand when this was written).
+# ================================================================================================================================================
+PWG_DEFAULTS = {"Type": "PWG", "Checkpoint_Path": None, "Layers": 30, "Stacks": 3, "Residual_Channels": 64, "Gate_Channels": 128, "Skip_Channels": 64,
+                "Aux_Context_Window": 2, "Upsample_Scales": [4, 4, 4, 4]}
+PWG_TILE, PWG_MAX_CHANNELS, PWG_MAX_DILATION, PWG_MAX_SCALE, PWG_MAX_SCALES, PWG_MAX_CTX, PWG_LDS = 64, 256, 1024, 16, 8, 16, 160 * 1024
+
+
+def pwg_settings(hp):
+    """The `Vocoder` block of the yaml over PWG_DEFAULTS (an absent block: the defaults)."""
+    v = getattr(hp, "Vocoder", None)
+    return {k: getattr(v, k, d) if v is not None else d for k, d in PWG_DEFAULTS.items()}
+
+
+def pwg_geometry(hp):
+    """The generator's sizes as a dict (layers, stacks, R, G, S, A, ctx, scales, hop, dilations); raises ValueError naming the offending yaml keys when the
+    kernels do not support them - the idiom of `geometry`."""
+    v = pwg_settings(hp)
+    if v["Type"] != "PWG":
+        raise ValueError(f"Vocoder.Type = {v['Type']!r}: the only neural vocoder is 'PWG' (the Parallel WaveGAN generator)")
+    layers, stacks, R, G, S, ctx = (int(v[k]) for k in ("Layers", "Stacks", "Residual_Channels", "Gate_Channels", "Skip_Channels", "Aux_Context_Window"))
+    scales = [int(s) for s in v["Upsample_Scales"]]
+    A, hop = int(hp.Sound.Mel_Dim), int(hp.Sound.Frame_Shift)
+    if G != 2 * R:
+        raise ValueError(f"Vocoder.Gate_Channels = {G} must be 2 * Vocoder.Residual_Channels = {2 * R} (the gate halves feed 1x1s of Residual_Channels inputs)")
+    if R < 16 or R % 16 or R > PWG_MAX_CHANNELS:
+        raise ValueError(f"Vocoder.Residual_Channels = {R} must be a multiple of 16 in [16, {PWG_MAX_CHANNELS}]")
+    if S < 16 or S % 16 or S > PWG_MAX_CHANNELS:
+        raise ValueError(f"Vocoder.Skip_Channels = {S} must be a multiple of 16 in [16, {PWG_MAX_CHANNELS}]")
+    if A < 4 or A % 4 or A > PWG_MAX_CHANNELS:
+        raise ValueError(f"Sound.Mel_Dim = {A} must be a multiple of 4 in [4, {PWG_MAX_CHANNELS}] for the neural vocoder (Vocoder block)")
+    if layers < 1 or stacks < 1 or layers % stacks:
+        raise ValueError(f"Vocoder.Layers = {layers} must be a positive multiple of Vocoder.Stacks = {stacks}")
+    dilations = [2 ** (i % (layers // stacks)) for i in range(layers)]
+    if max(dilations) > PWG_MAX_DILATION:
+        raise ValueError(f"Vocoder.Layers = {layers} / Vocoder.Stacks = {stacks} gives dilations up to {max(dilations)}; at most {PWG_MAX_DILATION} is supported")
+    if not 0 <= ctx <= PWG_MAX_CTX:
+        raise ValueError(f"Vocoder.Aux_Context_Window = {ctx} must lie in [0, {PWG_MAX_CTX}]")
+    if not 1 <= len(scales) <= PWG_MAX_SCALES or any(s < 1 or s > PWG_MAX_SCALE for s in scales):
+        raise ValueError(f"Vocoder.Upsample_Scales = {scales}: 1 to {PWG_MAX_SCALES} scales, each in [1, {PWG_MAX_SCALE}]")
+    if math.prod(scales) != hop:
+        raise ValueError(f"Vocoder.Upsample_Scales = {scales} multiply to {math.prod(scales)}, Sound.Frame_Shift is {hop}: the vocoder must produce one hop per frame")
+    K = 3 * R + A
+    lds = 4 * PWG_TILE * ((K if (K // 4) % 2 else K + 4) + (0 if R <= 64 else R + 4))
+    if lds > PWG_LDS:
+        raise ValueError(f"Vocoder.Residual_Channels = {R} with Sound.Mel_Dim = {A}: a layer's tile of {lds} bytes exceeds the {PWG_LDS} bytes of LDS")
+    return {"layers": layers, "stacks": stacks, "R": R, "G": G, "S": S, "A": A, "ctx": ctx, "scales": scales, "hop": hop, "dilations": dilations}
+
+
+def pwg_seed_words(seed, label, k=0):
+    """The vocoder's two 32-bit seed words of sample `k` of the utterance `label` under the run seed `seed`: the first 8 bytes of blake2b of
+    "<seed> NUL <label> NUL <k> NUL pwg", little endian - distinct from the mel's words (`inferencer.utterance_seed_words`), so the two streams are unrelated."""
+    d = hashlib.blake2b("{}\0{}\0{}\0pwg".format(seed, label, k).encode()).digest()
+    return int.from_bytes(d[:4], "little"), int.from_bytes(d[4:8], "little")
+
+
+def pwg_expected_shapes(geo):
+    """state-dict key -> shape of the generator with the sizes `geo`"""
+    R, G, S, A, ctx = geo["R"], geo["G"], geo["S"], geo["A"], geo["ctx"]
+    e = {"first_conv.weight": (R, 1, 1), "first_conv.bias": (R,), "upsample_net.conv_in.weight": (A, A, 2 * ctx + 1)}
+    for i, s in enumerate(geo["scales"]):
+        e[f"upsample_net.upsample.up_layers.{2 * i + 1}.weight"] = (1, 1, 1, 2 * s + 1)
+    for i in range(geo["layers"]):
+        q = f"conv_layers.{i}."
+        e.update({q + "conv.weight": (G, R, 3), q + "conv.bias": (G,), q + "conv1x1_aux.weight": (G, A, 1), q + "conv1x1_out.weight": (R, G // 2, 1),
+                  q + "conv1x1_out.bias": (R,), q + "conv1x1_skip.weight": (S, G // 2, 1), q + "conv1x1_skip.bias": (S,)})
+    e.update({"last_conv_layers.1.weight": (S, S, 1), "last_conv_layers.1.bias": (S,), "last_conv_layers.3.weight": (1, S, 1), "last_conv_layers.3.bias": (1,)})
+    return e
+
+
+def pwg_find_state_dict(obj):
+    """The generator's state dict inside what torch.load returned: at the top level or under `generator` / `Generator`, possibly inside `model`."""
+    for path in ((), ("generator",), ("Generator",), ("model",), ("model", "generator"), ("model", "Generator")):
+        d = obj
+        for k in path:
+            d = d.get(k) if isinstance(d, dict) else None
+        if isinstance(d, dict) and any(str(k).startswith("first_conv.") for k in d):
+            return d
+    raise ValueError("no Parallel WaveGAN generator state dict found (looked for `first_conv.*` at the top level, under generator / Generator and inside model)")
+
+
+def pwg_load(obj, geo):
+    """-> {key: float32 host tensor} with exactly the keys of `pwg_expected_shapes`: weight-norm pairs (`weight_g` / `weight_v`) are folded once, in float64;
+    a missing, surplus or wrongly shaped tensor raises a ValueError naming the key."""
+    sd = dict(pwg_find_state_dict(obj))
+    for kg in [k for k in sd if k.endswith(".weight_g")]:
+        base = kg[:-len("_g")]
+        if base + "_v" not in sd:
+            raise ValueError(f"vocoder checkpoint: {kg} has no {base}_v beside it")
+        if base in sd:
+            raise ValueError(f"vocoder checkpoint: {base} is given both plain and in weight-norm form")
+        g, v = sd.pop(kg).double(), sd.pop(base + "_v").double()
+        norm = v.reshape(v.shape[0], -1).norm(dim=1).reshape([-1] + [1] * (v.dim() - 1))
+        sd[base] = v * (g.reshape(norm.shape) / norm)
+    want = pwg_expected_shapes(geo)
+    for k in want:
+        if k not in sd:
+            raise ValueError(f"vocoder checkpoint: missing key {k}")
+    for k in sd:
+        if k not in want:
+            raise ValueError(f"vocoder checkpoint: surplus key {k} (not part of a generator of the Vocoder block's sizes)")
+    out = {}
+    for k, shape in want.items():
+        t = sd[k]
+        if not torch.is_tensor(t) or tuple(t.shape) != shape:
+            raise ValueError(f"vocoder checkpoint: {k} has shape {tuple(getattr(t, 'shape', ()))}, the Vocoder block's sizes need {shape}")
+        out[k] = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
+    return out
+
+
+class ParallelWaveGAN:
+    """ParallelWaveGAN(hp, device, state_dict=None)(mels [B, Mel, T], mel_lengths, seeds=None, noises=None) -> (wav [B, T * hop] fp32 on the device,
+    wav_lengths [B] int64).  state_dict None: `Vocoder.Checkpoint_Path` is loaded.  seeds [B, 2] (integer words, `pwg_seed_words`): z[t] is the counter hash
+    gauss(s0, s1, 0, t, 1) of csrc/gauss_hash.h evaluated in the first kernel; noises [B, T * hop]: the caller's z; neither: torch.randn on the device.
+    An utterance's waveform is bit-identical alone, in any batch, at any padding and from run to run (given its z)."""
+
+    def __init__(self, hp, device="cuda:0", state_dict=None):
+        self.geo = geo = pwg_geometry(hp)                           # before anything touches the device or the disk
+        if state_dict is None:
+            path = pwg_settings(hp)["Checkpoint_Path"]
+            if not path:
+                raise ValueError("Vocoder.Checkpoint_Path is not set: the neural vocoder needs a Parallel WaveGAN generator checkpoint")
+            state_dict = torch.load(path, map_location="cpu")
+        w = pwg_load(state_dict, geo)
+        if not _lib.lib().glowtts_pwg_supported(geo["R"], geo["G"], geo["S"], geo["A"], max(geo["dilations"])):
+            raise ValueError(f"the Vocoder block's sizes {geo} are not supported by the kernels")
+        self.device = torch.device(device)
+        self.sample_rate, self.n_mel, self.hop = int(hp.Sound.Sample_Rate), geo["A"], geo["hop"]
+        dev = lambda t: t.contiguous().to(self.device)
+        # weight images in the kernels' layouts (K-major: the MFMA B operand reads 16 consecutive output channels of one input row), built once
+        self.w_in = dev(w["upsample_net.conv_in.weight"].permute(2, 1, 0).reshape(-1, geo["A"]))
+        self.firs = dev(torch.cat([w[f"upsample_net.upsample.up_layers.{2 * i + 1}.weight"].reshape(-1) for i in range(len(geo["scales"]))]))
+        self.scales = (ctypes.c_int * len(geo["scales"]))(*geo["scales"])
+        self.first = (dev(w["first_conv.weight"].reshape(-1)), dev(w["first_conv.bias"]))
+        self.layer_weights = []
+        for i in range(geo["layers"]):
+            q = f"conv_layers.{i}."
+            w1 = torch.cat([w[q + "conv.weight"].permute(2, 1, 0).reshape(3 * geo["R"], geo["G"]), w[q + "conv1x1_aux.weight"][:, :, 0].t()], dim=0)
+            w2 = torch.cat([w[q + "conv1x1_out.weight"][:, :, 0].t(), w[q + "conv1x1_skip.weight"][:, :, 0].t()], dim=1)
+            b2 = torch.cat([w[q + "conv1x1_out.bias"], w[q + "conv1x1_skip.bias"]])
+            self.layer_weights.append((dev(w1), dev(w[q + "conv.bias"]), dev(w2), dev(b2)))
+        self.head = (dev(w["last_conv_layers.1.weight"][:, :, 0].t()), dev(w["last_conv_layers.1.bias"]), dev(w["last_conv_layers.3.weight"].reshape(-1)),
+                     dev(w["last_conv_layers.3.bias"]))
+        self._capacity, self._buffers = 0, None
+
+    def _work(self, B, L):
+        """Work buffers of a call (the two x, skips, c, the conditioning's intermediates): views of ONE set sized for the largest B x L (rounded up to
+        T_BUCKET frames) seen so far, like `GriffinLim._work`.  The kernels honour the lengths and write every row they later read."""
+        g = self.geo
+        frames = B * (-(-L // T_BUCKET) * T_BUCKET)
+        if frames > self._capacity:
+            self._buffers = None
+            f = lambda n: torch.empty(n, dtype=torch.float32, device=self.device)
+            rows = frames * g["hop"]
+            self._buffers = {"x": [f(rows * g["R"]), f(rows * g["R"])], "skips": f(rows * g["S"]), "c": f(rows * g["A"]),
+                             "cond": f(2 * frames * g["A"] * (g["hop"] // g["scales"][-1]))}
+            self._capacity = frames
+        T, bf = L * g["hop"], self._buffers
+        return {"x": [v[:B * T * g["R"]].view(B, T, g["R"]) for v in bf["x"]], "skips": bf["skips"][:B * T * g["S"]].view(B, T, g["S"]),
+                "c": bf["c"][:B * T * g["A"]].view(B, T, g["A"]), "cond": bf["cond"][:2 * B * L * g["A"] * (g["hop"] // g["scales"][-1])]}
+
+    def _lengths(self, lengths, B, L):
+        n = torch.as_tensor(lengths).to(device=self.device, dtype=torch.int32).reshape(B).contiguous()
+        return n.clamp(min=0, max=L)
+
+    def condition(self, mels, mel_lengths, out=None, work=None):
+        """mels [B, Mel, L] -> the conditioning rows c [B, L * hop, Mel] (rows beyond an utterance's own L * hop are not written)."""
+        if not mels.is_cuda:
+            raise _lib.GlowTTSHipError("expected a device tensor (the HIP path has no CPU fallback)")
+        mels = mels.to(device=self.device, dtype=torch.float32).contiguous()
+        B, Mel, L = mels.shape
+        if Mel != self.n_mel:
+            raise ValueError(f"mels have {Mel} channels, Sound.Mel_Dim = {self.n_mel}")
+        g = self.geo
+        c = out if out is not None else torch.zeros(B, L * g["hop"], Mel, dtype=torch.float32, device=self.device)
+        work = work if work is not None else torch.empty(2 * B * L * Mel * (g["hop"] // g["scales"][-1]), dtype=torch.float32, device=self.device)
+        ops.pwg_condition(mels, self._lengths(mel_lengths, B, L), self.w_in, self.firs, self.scales, work, c, g["ctx"])
+        return c
+
+    def layer(self, i, x, c, x_out, skips, frame_lengths, accumulate=True):
+        """Layer i alone on rows x [B, T, R], c [B, T, A] -> x_out, skips (tests)."""
+        B, T, _ = x.shape
+        L = T // self.geo["hop"]
+        ops.pwg_layer(x, c, *self.layer_weights[i], x_out, skips, self._lengths(frame_lengths, B, L), L, self.geo["hop"], self.geo["dilations"][i], accumulate)
+
+    @torch.no_grad()
+    def __call__(self, mels, mel_lengths, seeds=None, noises=None):
+        if seeds is not None and noises is not None:
+            raise ValueError("`seeds` and `noises` both given: the noise is either drawn in the kernel from the seed words or the caller's")
+        g = self.geo
+        B, _, L = mels.shape
+        T = L * g["hop"]
+        wk = self._work(B, L)
+        c = self.condition(mels, mel_lengths, out=wk["c"], work=wk["cond"])
+        lengths = self._lengths(mel_lengths, B, L)
+        if seeds is not None:
+            from .alignment import seed_words
+            seeds = seed_words(seeds, B, self.device)
+        else:
+            if noises is None:
+                noises = torch.randn(B, T, dtype=torch.float32, device=self.device)
+            noises = noises.to(device=self.device, dtype=torch.float32).reshape(B, -1).contiguous()
+            if tuple(noises.shape) != (B, T):
+                raise ValueError(f"noises have shape {tuple(noises.shape)}, expected {(B, T)} (or [B, 1, T])")
+        x, xn = wk["x"]
+        ops.pwg_first(noises, seeds, lengths, *self.first, x, L, g["hop"])
+        for i, (lw, d) in enumerate(zip(self.layer_weights, g["dilations"])):
+            ops.pwg_layer(x, c, *lw, xn, wk["skips"], lengths, L, g["hop"], d, i > 0)
+            x, xn = xn, x
+        wav = torch.empty(B, T, dtype=torch.float32, device=self.device)
+        ops.pwg_head(wk["skips"], lengths, *self.head, wav, L, g["hop"], math.sqrt(1.0 / g["layers"]))
+        return wav, lengths.to(torch.int64) * g["hop"]
+
+    def to_host(self, wav, wav_lengths):
+        """Device waveforms -> list of float32 numpy arrays clipped to [-1, 1] (what `audio.write_wav` takes).  No de-emphasis: the vocoder was trained on
+        final audio."""
+        wav, n = wav.cpu().numpy(), wav_lengths.cpu().tolist()
+        return [np.clip(w[:m], -1.0, 1.0).astype(np.float32) for w, m in zip(wav, n)]

@@ -874,6 +874,32 @@ int glowtts_yin_f32(const float *wav, const int32_t *wav_lengths, float *pitch, 
 int glowtts_prior_sample(const float *mean, const float *log_std, const float *dur, const int64_t *mel_lengths, const uint32_t *seeds,
                          const float *noise_scales, float *z, int32_t *idx, float *attn, int B, int C, int Tx, int Tmax, void *stream);
 
+/* ---- neural vocoder: Parallel WaveGAN generator (csrc/pwg_ops.hip; inference, f32; additions, the ABI version stays) ----
+ * Rows are samples, channels-last: x [B][Lmax hop][R], c [B][Lmax hop][A], skips [B][Lmax hop][S]; frame_lengths [B] i32 (device) are the utterances'
+ * frame counts L <= Lmax, an utterance owns rows [0, L hop) of its slab and only those are read or written (the waveform is zero beyond them).  Every
+ * value depends on its own utterance and a fixed summation order only.  All matrix products: v_mfma_f32_16x16x4_f32.
+ * Supported (glowtts_pwg_supported, else GLOWTTS_E_ARG): R, S multiples of 16 and A a multiple of 4, all <= 256; G == 2 R; dilation in [1, 1024]; the
+ * layer's LDS tile within 160 KB; 1 <= B <= 65535, 1 <= hop <= 65536, Lmax hop <= 2^30; at most 8 scales, each in [1, 16]; 0 <= ctx <= 16.
+ * glowtts_pwg_condition: mel [B][A][Lmax] -> c.  w_in [(2 ctx + 1) A][A] (row = tap * A + input channel) is conv_in, whose replicate padding uses the
+ *   utterance's own first / last frame; then per scale s: nearest-neighbour repeat and the (2 s + 1)-tap FIR (firs: the scales' taps one after another),
+ *   zero beyond the utterance's own ends.  scales is a HOST array.  work: 2 * B * Lmax * A * (hop / last scale) floats.  Logged as `pwg_cond_in` and one
+ *   `pwg_upsample` per scale.
+ * glowtts_pwg_first: x = first_conv(z), w / bias [R]; z[t] = noises [B][Lmax hop] or, noises NULL, gauss(seeds[b][0], seeds[b][1], 0, t, 1) of
+ *   csrc/gauss_hash.h evaluated in the kernel (seeds [B][2] u32 on the device); exactly one of the two is given.
+ * glowtts_pwg_layer: one WaveNet layer in one launch.  w1 [3 R + A][2 R]: rows x(t - d) | x(t) | x(t + d) | aux channels, columns tanh half | sigmoid
+ *   half, b1 [2 R];  w2 [R][R + S]: columns conv1x1_out | conv1x1_skip, b2 [R + S].  x_out = (out + x) sqrt(0.5) (x_out != x: neighbours read x);
+ *   skips = skip (accumulate == 0) or skips + skip.
+ * glowtts_pwg_head: wav [B][Lmax hop] = w2 . relu(w1^T relu(skips * scale) + b1) + b2;  w1 [S][S] (row = input channel), w2 [S], b2 [1]. */
+int glowtts_pwg_supported(int R, int G, int S, int A, int max_dilation);
+int glowtts_pwg_condition(const float *mel, const int32_t *frame_lengths, const float *w_in, const float *firs, const int *scales, int n_scales,
+                          float *work, float *c, int B, int A, int Lmax, int ctx, void *stream);
+int glowtts_pwg_first(const float *noises, const uint32_t *seeds, const int32_t *frame_lengths, const float *w, const float *bias, float *x, int B,
+                      int Lmax, int hop, int R, void *stream);
+int glowtts_pwg_layer(const float *x, const float *c, const float *w1, const float *b1, const float *w2, const float *b2, float *x_out, float *skips,
+                      const int32_t *frame_lengths, int B, int Lmax, int hop, int R, int S, int A, int dilation, int accumulate, void *stream);
+int glowtts_pwg_head(const float *skips, const int32_t *frame_lengths, const float *w1, const float *b1, const float *w2, const float *b2, float *wav,
+                     int B, int Lmax, int hop, int S, float scale, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
