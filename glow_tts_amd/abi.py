@@ -25,6 +25,7 @@ SUM_MAX_SEGS = 12
 C2D_MAX_LAYERS = 8
 SAMPLE_SCAN_CHUNK = 1024
 SAMPLE_TILE = 64
+GE2E_MAX_MEL, GE2E_MAX_H, GE2E_MAX_STACKS, GE2E_MAX_E = 512, 768, 8, 1024
 
 # ---- struct mirrors: `c_name` is the C struct whose layout the class restates ------------------------------------------------------------
 I, L, F, U, P = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_uint32, ctypes.c_void_p
@@ -266,4 +267,9 @@ SIGNATURES = {
     "glowtts_pwg_first": (I, [P] * 6 + [I] * 4 + [P]),
     "glowtts_pwg_layer": (I, [P] * 9 + [I] * 8 + [P]),
     "glowtts_pwg_head": (I, [P] * 7 + [I] * 4 + [F, P]),
+    "glowtts_ge2e_supported": (I, [I] * 4),
+    "glowtts_ge2e_image_floats": (L, [I] * 3),
+    "glowtts_ge2e_work_floats": (L, [L] + [I] * 3),
+    "glowtts_ge2e_pack": (I, [P] * 6 + [I] * 4 + [P]),
+    "glowtts_ge2e_forward": (I, [P] * 9 + [I] * 7 + [P]),
 }

@@ -5,7 +5,9 @@ where the mode allows it), one `.npy` mel per utterance (`Inference.py:213-220`;
 `WAV/<label>.wav` next to it from the active vocoder: Griffin-Lim (`vocoder.GriffinLim`: a baseline vocoder, not a neural one) or, with the yaml block
 `Vocoder` / `vocoder='pwg'` and a checkpoint, the Parallel WaveGAN generator (`vocoder.ParallelWaveGAN`).  `references` are either
 `.npy` files / arrays holding mels [T, Mel] (what `Pattern_Generator.Pattern_Generate` produces) or wav files, which go through
-`glow_tts_amd.audio` (librosa-free restatement of `Audio.py`; resampling is not implemented: the wav must be at hp.Sound.Sample_Rate)."""
+`glow_tts_amd.audio` (librosa-free restatement of `Audio.py`; resampling is not implemented: the wav must be at hp.Sound.Sample_Rate).
+With `Speaker_Embedding.Type: 'GE2E'` the speaker is given by `speaker_references` (wav files, mels or ready d-vectors), which go through
+`data.mels_for_ge2e` and the GE2E speaker encoder (`speaker_encoder.GE2E`; the reference runs it inside `GlowTTS.inference`, Modules.py:154-156)."""
 import hashlib
 import logging
 import os
@@ -26,11 +28,14 @@ def utterance_seed_words(seed, label, k=0):
 
 
 class Inferencer:
-    def __init__(self, checkpoint_path, hp=None, device="cuda:0", device_frontend=False, vocoder=None, vocoder_checkpoint=None):
+    def __init__(self, checkpoint_path, hp=None, device="cuda:0", device_frontend=False, vocoder=None, vocoder_checkpoint=None, speaker_encoder=None):
         """device_frontend: wav references and wav voice-conversion sources are analysed on the device (`frontend.Analyzer`) instead of the host's
         `audio.pattern_from_wav`; decoding, trimming and normalisation stay `audio.audio_prep` either way.
         vocoder: 'pwg' (the neural vocoder), 'griffin_lim' (forces the baseline) or None: 'pwg' when the yaml has the `Vocoder` block or
-        `vocoder_checkpoint` (overrides `Vocoder.Checkpoint_Path`) is given, Griffin-Lim otherwise."""
+        `vocoder_checkpoint` (overrides `Vocoder.Checkpoint_Path`) is given, Griffin-Lim otherwise.
+        speaker_encoder: GE2E mode only - a callable mapping a slice stack [B * Samples, Mel, Slice] to unit d-vectors [B, Embedding_Size].  None: the
+        `speaker_encoder.GE2E` of `Speaker_Embedding.GE2E.Checkpoint_Path`, else the one the GlowTTS checkpoint carries under `layer_Dict.GE2E.*` (keys of
+        another layout: a warning, and they are dropped), else none - then only ready d-vectors can be given."""
         self.hp = hp if hp is not None else get_hp()
         if vocoder not in (None, "pwg", "griffin_lim"):
             raise ValueError("vocoder must be 'pwg', 'griffin_lim' or None, got {!r}".format(vocoder))
@@ -41,6 +46,8 @@ class Inferencer:
         self.token_Dict = data.load_token_dict(self.hp.Token_Path)
         self.last_wav_files = []                                                 # the wav files the last Inference / Voice_Conversion / Vocode call wrote
         self._vocoder = None
+        self.ge2e_mode = self.hp.Mode.upper() in ("SE", "GR") and self.hp.Speaker_Embedding.Type.upper() == "GE2E"
+        self.speaker_encoder = speaker_encoder
         self.Model_Generate()
         self.Load_Checkpoint(checkpoint_path)
 
@@ -56,6 +63,11 @@ class Inferencer:
 
     def Load_Checkpoint(self, checkpoint_path):                                  # Inference.py:258-275
         state_Dict = torch.load(checkpoint_path, map_location="cpu")
+        if self.ge2e_mode and self.speaker_encoder is None:
+            from . import speaker_encoder
+            path = getattr(self.hp.Speaker_Embedding.GE2E, "Checkpoint_Path", None)
+            self.speaker_encoder = speaker_encoder.GE2E.from_checkpoint(self.hp, self.device, path) if path else \
+                speaker_encoder.from_glowtts_checkpoint(self.hp, self.device, state_Dict["Model"])
         self.model_Dict["GlowTTS"].load_state_dict(state_Dict["Model"])
         for flow in self.model_Dict["GlowTTS"].layer_Dict["Decoder"].layer_Dict["Flows"]:
             flow.layers[0].initialized = True      # Activation_Norm is already initialized when checkpoint is loaded.
@@ -121,6 +133,36 @@ class Inferencer:
             return self._analyzer([audio.audio_prep(ref, self.hp.Sound.Sample_Rate, 30)], with_pitch=gr)[0]
         return audio.pattern_from_wav(ref, self.hp, with_pitch=gr)
 
+    def D_Vectors(self, references, rngs=None):
+        """GE2E mode: one speaker reference per utterance -> d-vectors, np.ndarray [n, Embedding_Size].  A reference is a wav path, a `.npy` path or an array
+        [T, Mel] holding a mel, or a 1-D array [Embedding_Size] taken as a d-vector as it is.  Mels are cut into slices by `data.mels_for_ge2e`
+        (Datasets.py:41-65) - rngs: one generator per reference for its random offset, None: `np.random` as in the reference - and go through the speaker
+        encoder in one batch."""
+        hp = self.hp
+        ge, E = hp.Speaker_Embedding.GE2E.Inference, int(hp.Speaker_Embedding.Embedding_Size)
+        out = np.zeros((len(references), E), np.float32)
+        stacks, where = [], []
+        for i, ref in enumerate(references):
+            if torch.is_tensor(ref):
+                ref = ref.detach().cpu().numpy()
+            if isinstance(ref, np.ndarray) and ref.ndim == 1:
+                if ref.shape[0] != E:
+                    raise ValueError("speaker reference {}: a 1-D array is taken as a d-vector and must have Speaker_Embedding.Embedding_Size = {} elements, got {}"
+                                     .format(i, E, ref.shape[0]))
+                out[i] = ref
+                continue
+            mel = self._reference(ref)[0]
+            stacks.append(data.mels_for_ge2e([mel], int(ge.Samples), int(ge.Slice_Length), int(ge.Overlap_Length), rng=rngs[i] if rngs is not None else np.random))
+            where.append(i)
+        if stacks:
+            if self.speaker_encoder is None:
+                raise ValueError("GE2E mode: wav / mel speaker references need a speaker encoder - set Speaker_Embedding.GE2E.Checkpoint_Path, pass "
+                                 "Inferencer(speaker_encoder=...) or give ready d-vectors [Embedding_Size]")
+            x = torch.from_numpy(np.concatenate(stacks).astype(np.float32)).transpose(2, 1).contiguous().to(self.device)
+            with torch.no_grad():
+                out[where] = self.speaker_encoder(x).detach().float().cpu().numpy()
+        return out
+
     @torch.no_grad()
     def Inference_Step(self, tokens, token_lengths, prosodies, prosody_lengths, speakers, ge2es, pitches, pitch_lengths, length_scales, labels, texts,
                        start_index=0, tag_index=False, inference_path="./inference", noise_scale=1.0, wav=False, seeds=None, sample_index=None, vocoder_seeds=None):
@@ -157,12 +199,15 @@ class Inferencer:
             files.append(path)
         return files
 
-    def Inference(self, labels, texts, scales, speakers=None, references=None, inference_path="./inference", noise_scale=1.0, wav=False, seed=None, samples=1):
+    def Inference(self, labels, texts, scales, speakers=None, references=None, inference_path="./inference", noise_scale=1.0, wav=False, seed=None, samples=1,
+                  speaker_references=None):
         """Inference.py:225-256.  wav: also WAV/<label>.wav per utterance (paths in `last_wav_files`; the returned list stays the .npy files).
         seed (an int): reproducible sampling - every utterance draws its noise from `utterance_seed_words(seed, label, k)`, so its mel depends on the seed, its
         label and the sample number k only, not on the order of the prompts or Inference_Batch_Size; None: the unseeded draw.  noise_scale: the sampling
         temperature, a float or - seeded only - one float per utterance.  samples = N > 1: N takes of every prompt, written as <label>.S<k>.npy (and .wav),
-        k < N; samples = 1 keeps the plain names."""
+        k < N; samples = 1 keeps the plain names.
+        speaker_references (GE2E mode, required there): one per utterance, see `D_Vectors`.  The slices' random offset comes from `np.random` as in the
+        reference or, with `seed`, from an `np.random.RandomState` of the first word of `utterance_seed_words(seed, label)`: a seeded run repeats."""
         logging.info("Start inference.")
         self.last_wav_files = []
         hp = self.hp
@@ -177,6 +222,9 @@ class Inferencer:
         bs = hp.Inference_Batch_Size or hp.Train.Batch_Size
         speakers = speakers or [None] * len(texts)
         references = references or [None] * len(texts)
+        if self.ge2e_mode and (speaker_references is None or len(speaker_references) != len(texts) or any(r is None for r in speaker_references)):
+            raise ValueError("Speaker_Embedding.Type 'GE2E': `speaker_references` must give every utterance a wav, a mel or a d-vector (and wavs / mels need a "
+                             "speaker encoder: Speaker_Embedding.GE2E.Checkpoint_Path or Inferencer(speaker_encoder=...))")
         files = []
         for s in range(0, len(texts), bs):
             sl = slice(s, s + bs)
@@ -198,15 +246,20 @@ class Inferencer:
                     pit = torch.zeros(len(mp), int(pitl.max()))
                     for b, (_, p) in enumerate(mp):
                         pit[b, :p.shape[0]] = torch.from_numpy(p)
-            spk = None if any(x is None for x in speakers[sl]) else torch.tensor(speakers[sl], dtype=torch.int64)
+            # (GE2E mode: the speaker is the d-vector; speaker indices, which `main` passes in every SE / GR mode, are not read)
+            spk = None if self.ge2e_mode or any(x is None for x in speakers[sl]) else torch.tensor(speakers[sl], dtype=torch.int64)
             ns = torch.tensor([float(x) for x in noise_scale[sl]], dtype=torch.float32) if per_utterance else noise_scale
+            ge2es = None
+            if self.ge2e_mode:
+                rngs = None if seed is None else [np.random.RandomState(utterance_seed_words(seed, label)[0]) for label in labels[sl]]
+                ge2es = torch.from_numpy(self.D_Vectors(speaker_references[sl], rngs))
             for k in range(samples):
                 seeds = None if seed is None else torch.tensor([utterance_seed_words(seed, label, k) for label in labels[sl]], dtype=torch.int64)
                 vseeds = None
                 if seed is not None and wav and self.vocoder_kind == "pwg":
                     from .vocoder import pwg_seed_words
                     vseeds = torch.tensor([pwg_seed_words(seed, label, k) for label in labels[sl]], dtype=torch.int64)
-                files += self.Inference_Step(tokens, tl, pros, pl, spk, None, pit, pitl, torch.tensor(scales[sl], dtype=torch.float32), labels[sl], texts[sl],
+                files += self.Inference_Step(tokens, tl, pros, pl, spk, ge2es, pit, pitl, torch.tensor(scales[sl], dtype=torch.float32), labels[sl], texts[sl],
                                              start_index=s, inference_path=inference_path, noise_scale=ns, wav=wav, seeds=seeds,
                                              sample_index=k if samples > 1 else None, vocoder_seeds=vseeds)
         return files
@@ -244,7 +297,7 @@ class Inferencer:
                          wav=False):
         """Voice conversion through the invertible decoder (GlowTTS.voice_conversion): `sources` - recorded mels as .npy files / arrays [T, Mel]
         or wav files (GR: a wav also gives the YIN pitch track the flows read; (mel, pitch) pairs are taken as they are) - go through the flows
-        forward under their own conditioning and back under the target's.  SE-LUT: speaker indices; SE-GE2E: d-vectors [E]; PE / GR:
+        forward under their own conditioning and back under the target's.  SE-LUT: speaker indices; SE-GE2E: d-vectors [E], wav files or mels (`D_Vectors`); PE / GR:
         `target_references` (same formats as `sources`) give the target prosody vector (GR: plus the target speaker).  A None target takes
         the source's value.  Batches of Inference_Batch_Size; one NPY/<label>.npy [T, Mel] per utterance (wav: and WAV/<label>.wav, paths in
         `last_wav_files`); returns the written .npy files."""
@@ -267,7 +320,9 @@ class Inferencer:
                 return None
             if lut:
                 return torch.tensor([int(v) for v in vals], dtype=torch.int64, device=dev)
-            return torch.from_numpy(np.stack([np.asarray(v, np.float32) for v in vals])).to(dev)      # GE2E: d-vectors
+            if not self.ge2e_mode:
+                return torch.from_numpy(np.stack([np.asarray(v, np.float32) for v in vals])).to(dev)
+            return torch.from_numpy(self.D_Vectors([v if isinstance(v, str) or torch.is_tensor(v) else np.asarray(v, np.float32) for v in vals])).to(dev)
 
         files = []
         for s in range(0, n, bs):
@@ -295,7 +350,8 @@ class Inferencer:
 
 def read_convert_list(path):
     """The --convert TSV: label, source path, source speaker, target speaker and, optionally, a target reference path, tab-separated; an
-    optional header line whose first column is `Label`.  Empty speaker / reference columns are None."""
+    optional header line whose first column is `Label`.  Empty speaker / reference columns are None; a speaker column that is not an integer is kept as a
+    string: the path of a wav or `.npy` mel (GE2E mode)."""
     out = []
     with open(path, "r", encoding="utf-8") as f:
         for i, line in enumerate(f.read().splitlines()):
@@ -306,7 +362,13 @@ def read_convert_list(path):
                 continue
             if len(cols) < 4:
                 raise ValueError("{}:{}: expected label, source, source speaker, target speaker[, target reference]".format(path, i + 1))
-            spk = lambda x: int(x) if x else None
+            def spk(x):
+                if not x:
+                    return None
+                try:
+                    return int(x)
+                except ValueError:
+                    return x
             out.append({"label": cols[0], "source": cols[1], "source_speaker": spk(cols[2]), "target_speaker": spk(cols[3]),
                         "target_reference": (cols[4] or None) if len(cols) > 4 else None})
     return out
@@ -362,12 +424,15 @@ def main(argv=None):
                                               [r["target_speaker"] for r in recs], [r["target_reference"] for r in recs], args.out, wav=args.wav)
                         + inf.last_wav_files))
         return
+    speaker_references = None
     if args.prompts:
         recs = [r for r in data.read_inference_prompts(args.prompts) if r["text"] is not None]
         labels, texts, scales, speakers = [r["label"] for r in recs], [r["text"] for r in recs], [r["length_scale"] for r in recs], [r["speaker"] for r in recs]
+        if inf.ge2e_mode:                                                          # Inference.py:84-100: the prompt's wav for GE2E
+            speaker_references = [r["wav_for_ge2e"] for r in recs]
     else:                                                                         # Inference.py:290-301
         labels, texts, scales, speakers = ["Alpha", "Bravo"], ["Birds of a feather flock together.",
                                                                "A creative artist works on his next composition because he was not satisfied with his previous one."], [1.0, 0.9], [0, 1]
     mode = inf.hp.Mode.upper()
     print("\n".join(inf.Inference(labels, texts, scales, speakers if mode in ("SE", "GR") else None, None, args.out, wav=args.wav, seed=args.seed,
-                                  noise_scale=args.noise_scale, samples=args.samples) + inf.last_wav_files))
+                                  noise_scale=args.noise_scale, samples=args.samples, speaker_references=speaker_references) + inf.last_wav_files))

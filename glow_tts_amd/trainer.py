@@ -58,7 +58,8 @@ def mel_bucket_step(hp):
 class Trainer:
     def __init__(self, steps=0, hp=None, speaker_encoder=None, use_graph=True, workers=None):
         """speaker_encoder: GE2E mode only - a callable mapping the collater's slice stack [B * Samples, Mel, Slice] to L2-normalised d-vectors
-        [B, Embedding_Size] (the reference's pre-trained GE2E network is an un-vendored submodule: DESIGN.md)."""
+        [B, Embedding_Size].  None with `Speaker_Embedding.GE2E.Checkpoint_Path` set: the `speaker_encoder.GE2E` of that checkpoint (the reference's pre-trained
+        GE2E network is an un-vendored submodule; DESIGN.md "GE2E speaker encoder" states this package's own)."""
         self.hp = hp if hp is not None else get_hp()
         self.steps, self.epochs = steps, 0
         self.speaker_encoder, self.use_graph, self.workers = speaker_encoder, use_graph, workers       # workers: overrides hp.Train.Num_Workers
@@ -71,6 +72,10 @@ class Trainer:
         self.dp = gd.is_dist()                                                 # (also a one-rank group under distributed.SINGLE_RANK_IS_DIST: the RCCL path on one GPU)
         self.Datset_Generate()
         self.Model_Generate()
+        ge2e_path = getattr(self.hp.Speaker_Embedding.GE2E, "Checkpoint_Path", None)
+        if self.hp.Mode.upper() in ("SE", "GR") and self.hp.Speaker_Embedding.Type.upper() == "GE2E" and self.speaker_encoder is None and ge2e_path:
+            from .speaker_encoder import GE2E
+            self.speaker_encoder = GE2E.from_checkpoint(self.hp, self.device, ge2e_path)
         self.scalar_Dict = {"Train": defaultdict(float), "Evaluation": defaultdict(float)}
         self.Load_Checkpoint()
 

@@ -900,6 +900,37 @@ int glowtts_pwg_layer(const float *x, const float *c, const float *w1, const flo
 int glowtts_pwg_head(const float *skips, const int32_t *frame_lengths, const float *w1, const float *b1, const float *w2, const float *b2, float *wav,
                      int B, int Lmax, int hop, int S, float scale, void *stream);
 
+/* ---- GE2E speaker encoder: stacked LSTM -> linear -> d-vector (csrc/ge2e_ops.hip; inference, f32; additions, the ABI version stays) ----
+ * torch.nn.LSTM's definition (gates i, f, g, o; bias b_ih + b_hh; h0 = c0 = 0), then e = W h_{T-1}^{top} + b per slice, w = e / max(|e|, 1e-12),
+ * d = normalize(mean over an utterance's Samples consecutive slices of w).  Every product runs on v_mfma_f32_16x16x4_f32; a sequence's values depend on
+ * that sequence and a fixed summation order only (bit-identical alone and in any batch).  No kernel waits on another workgroup.
+ * Supported (glowtts_ge2e_supported, else GLOWTTS_E_ARG): Mel a multiple of 4, <= GLOWTTS_GE2E_MAX_MEL; H a multiple of 16, <= GLOWTTS_GE2E_MAX_H;
+ * 1 <= Stacks <= GLOWTTS_GE2E_MAX_STACKS; 1 <= E <= GLOWTTS_GE2E_MAX_E; T >= 1 (<= 2^20); N >= 1 a multiple of Samples, N <= 16 * 65535.
+ * Layouts (all f32, device):
+ *   x       [N][Mel][T]                 the slice stack, channels first (read in place)
+ *   images  glowtts_ge2e_image_floats() floats: layer 0 [Mel + H][4 H], then layers 1.. [2 H][4 H] each; K-major: rows are the layer's input channels
+ *           followed by its own hidden units (W_ih | W_hh as one K range); column 64 s + 4 u + g holds gate g (i, f, g, o) of hidden unit 16 s + u
+ *   biases  [Stacks][4 H], b_ih + b_hh in the images' column order
+ *   head_w  [E][H], head_b [E]          torch.nn.Linear's own tensors
+ *   work    glowtts_ge2e_work_floats(N, T, H, Stacks) = Stacks N H (T + 1) floats: c [Stacks][N][H] (updated in place), then the hidden states; with hs
+ *           given they go there instead and the first Stacks N H floats suffice
+ *   hs      [Stacks][N][T][H] or NULL   all hidden states (tests); e [N][E] or NULL: the raw embeddings; d [N / Samples][E]: unit-norm d-vectors
+ * glowtts_ge2e_pack packs ONE layer's torch tensors (w_ih [4 H][in], w_hh [4 H][H], b_ih, b_hh [4 H]) into its place in images / biases: call it once
+ * per layer at load and again only when the parameters change.  Logged as `ge2e_pack`.
+ * glowtts_ge2e_forward allocates nothing and takes only pointers and a stream: T + Stacks - 1 launches `ge2e_cell` (launch d: every cell
+ * (layer k, step d - k), which reads only what launch d - 1 wrote; grid (H / 16, ceil(N / 16), cells on the diagonal)) and one `ge2e_head`. */
+#define GLOWTTS_GE2E_MAX_MEL 512
+#define GLOWTTS_GE2E_MAX_H 768
+#define GLOWTTS_GE2E_MAX_STACKS 8
+#define GLOWTTS_GE2E_MAX_E 1024
+int glowtts_ge2e_supported(int Mel, int H, int Stacks, int E);
+int64_t glowtts_ge2e_image_floats(int Mel, int H, int Stacks);
+int64_t glowtts_ge2e_work_floats(int64_t N, int T, int H, int Stacks);
+int glowtts_ge2e_pack(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, float *images, float *biases, int layer, int Mel, int H,
+                      int Stacks, void *stream);
+int glowtts_ge2e_forward(const float *x, const float *images, const float *biases, const float *head_w, const float *head_b, float *work, float *hs,
+                         float *e, float *d, int N, int Samples, int Mel, int T, int H, int Stacks, int E, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
