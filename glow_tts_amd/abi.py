@@ -272,4 +272,13 @@ SIGNATURES = {
     "glowtts_ge2e_work_floats": (L, [L] + [I] * 3),
     "glowtts_ge2e_pack": (I, [P] * 6 + [I] * 4 + [P]),
     "glowtts_ge2e_forward": (I, [P] * 9 + [I] * 7 + [P]),
+    "glowtts_ge2e_train_image_floats": (L, [I] * 2),
+    "glowtts_ge2e_train_keep_floats": (L, [L] + [I] * 3),
+    "glowtts_ge2e_train_loss_work_floats": (L, [L] + [I] * 2),
+    "glowtts_ge2e_train_work_floats": (L, [L] + [I] * 4),
+    "glowtts_ge2e_train_pack": (I, [P] * 3 + [I] * 3 + [P]),
+    "glowtts_ge2e_train_forward": (I, [P] * 7 + [I] * 6 + [P]),
+    "glowtts_ge2e_train_loss": (I, [P] * 6 + [I] * 3 + [P]),
+    "glowtts_ge2e_train_backward": (I, [P] * 8 + [I] * 5 + [P]),
+    "glowtts_ge2e_train_wgrad": (I, [P] * 8 + [I] * 6 + [P]),
 }

@@ -2,7 +2,8 @@
 layer to `Speaker_Embedding.Embedding_Size`, L2 normalisation per slice, the mean over an utterance's slices, L2 normalisation again - the d-vector `GlowTTS`
 takes as `mels_for_ge2e`.  The reference runs a pre-trained network of this kind inside `GlowTTS.forward` / `inference` (Modules.py:29-35, 75-77, 154-156); its
 source is an un-vendored submodule, so the network is restated here as this project's own contract and the checkpoint layout is NOT pinned against a real file:
-CHECKPOINT_NAMES is the one place a differently named checkpoint is mapped.  Forward only (csrc/ge2e_ops.hip), device only, no CPU fallback."""
+CHECKPOINT_NAMES is the one place a differently named checkpoint is mapped.  Device only, no CPU fallback: the inference forward is csrc/ge2e_ops.hip;
+`GE2E(..., trainable=True).embed` and `GE2ELoss` are the training path (csrc/ge2e_train_ops.hip, DESIGN.md "Training the GE2E speaker encoder")."""
 import logging
 
 import torch
@@ -120,9 +121,10 @@ def ge2e_load(obj, sizes):
 class GE2E(torch.nn.Module):
     """hp: the Hyper_Parameters namespace; state_dict: a checkpoint object for `ge2e_load` (None: torch's default initialisation).  Calling it maps the slice stack
     [B * Samples, Mel, Slice] to unit-norm d-vectors [B, Embedding_Size] under no_grad through `glowtts_ge2e_forward` alone.  The parameters live in a
-    torch.nn.LSTM + torch.nn.Linear (their names are the state dict's) that is never called."""
+    torch.nn.LSTM + torch.nn.Linear (their names are the state dict's) that is never called.  trainable=True: the parameters require gradients and
+    `embed` maps a slice stack to the raw embeddings e [N, Embedding_Size] with a backward (`_Embed`); the plain call stays the frozen inference path."""
 
-    def __init__(self, hp, device, state_dict=None):
+    def __init__(self, hp, device, state_dict=None, trainable=False):
         super().__init__()
         self.sizes = ge2e_sizes(hp)
         ge2e_check_sizes(self.sizes)
@@ -136,8 +138,12 @@ class GE2E(torch.nn.Module):
         self.linear = torch.nn.Linear(s["H"], s["E"])
         if loaded is not None:
             torch.nn.Module.load_state_dict(self, loaded, strict=True)
-        self.to(device).requires_grad_(False).eval()
-        self._images = self._biases = self._packed_sig = None
+        self.trainable = bool(trainable)
+        if self.trainable:
+            self.to(device).requires_grad_(True)
+        else:
+            self.to(device).requires_grad_(False).eval()
+        self._images = self._biases = self._images_t = self._packed_sig = None
 
     @classmethod
     def from_checkpoint(cls, hp, device, path):
@@ -160,7 +166,34 @@ class GE2E(torch.nn.Module):
         for k, layer in enumerate(params):
             _lib.check(L.glowtts_ge2e_pack(*[_lib.ptr(p) for p in layer], _lib.ptr(self._images), _lib.ptr(self._biases), k, s["Mel"], s["H"], s["Stacks"],
                                            _lib.stream()), "glowtts_ge2e_pack")
+        if self.trainable:                                                  # the backward's transposed images: re-packed exactly when the forward's are
+            if self._images_t is None or self._images_t.device != dev:
+                self._images_t = torch.empty(L.glowtts_ge2e_train_image_floats(s["H"], s["Stacks"]), dtype=torch.float32, device=dev)
+            for k, layer in enumerate(params):
+                above = _lib.ptr(params[k + 1][0]) if k + 1 < s["Stacks"] else None
+                _lib.check(L.glowtts_ge2e_train_pack(_lib.ptr(layer[1]), above, _lib.ptr(self._images_t), k, s["H"], s["Stacks"], _lib.stream()),
+                           "glowtts_ge2e_train_pack")
         self._packed_sig = sig
+
+    def invalidate_images(self):
+        """The parameters were written behind torch's version counters (the `optim` kernels update them through raw pointers): pack again at the next call."""
+        self._packed_sig = None
+
+    def _check_stack(self, stack):
+        s = self.sizes
+        if stack.dim() != 3 or stack.shape[1] != s["Mel"] or stack.shape[0] < 1 or stack.shape[2] < 1:
+            raise ValueError("GE2E: expected a slice stack [N, {}, Slice], got {}".format(s["Mel"], list(stack.shape)))
+        if stack.dtype != torch.float32 or not stack.is_cuda:
+            raise _lib.GlowTTSHipError("GE2E: expected an fp32 device tensor (the HIP path has no CPU fallback)")
+
+    def embed(self, stack):
+        """stack [N, Mel, T] fp32 on the device -> the raw embeddings e [N, E] (before any normalisation), differentiable in the parameters.  After an
+        optimizer step of `optim.RAdam` call `invalidate_images()` (torch's own in-place ops are seen without it)."""
+        if not self.trainable:
+            raise _lib.GlowTTSHipError("GE2E.embed is the training path: construct the encoder with trainable=True")
+        self._check_stack(stack)
+        flat = [p for layer in self._lstm_params() for p in layer] + [self.linear.weight, self.linear.bias]
+        return _Embed.apply(self, stack.detach().contiguous(), *flat)
 
     @torch.no_grad()
     def forward_all(self, stack, samples=None, hidden=False, raw=False):
@@ -186,6 +219,102 @@ class GE2E(torch.nn.Module):
 
     def forward(self, stack, samples=None):
         return self.forward_all(stack, samples)[2]
+
+
+def train_forward(enc, x):
+    """-> (keep, e): `glowtts_ge2e_train_forward` of a trainable encoder on x [N, Mel, T] (contiguous)"""
+    s, L = enc.sizes, _lib.lib()
+    enc._pack()
+    N, _, T = x.shape
+    keep = torch.empty(L.glowtts_ge2e_train_keep_floats(N, T, s["H"], s["Stacks"]), dtype=torch.float32, device=x.device)
+    e = torch.empty(N, s["E"], dtype=torch.float32, device=x.device)
+    _lib.check(L.glowtts_ge2e_train_forward(_lib.ptr(x), _lib.ptr(enc._images), _lib.ptr(enc._biases), _lib.ptr(enc.linear.weight), _lib.ptr(enc.linear.bias),
+                                            _lib.ptr(keep), _lib.ptr(e), N, s["Mel"], T, s["H"], s["Stacks"], s["E"], _lib.stream()), "glowtts_ge2e_train_forward")
+    return keep, e
+
+
+def train_backward(enc, x, keep, de, da=None):
+    """-> {parameter name: gradient} (and da [Stacks, N, T, 4 H] is filled when given): `glowtts_ge2e_train_backward`, then `glowtts_ge2e_train_wgrad`
+    per layer.  The images are those of the forward (`_pack` ran there)."""
+    s, L = enc.sizes, _lib.lib()
+    N, _, T = x.shape
+    dev = x.device
+    if da is None:
+        da = torch.empty(s["Stacks"], N, T, 4 * s["H"], dtype=torch.float32, device=dev)
+    work = torch.empty(L.glowtts_ge2e_train_work_floats(N, T, s["Mel"], s["H"], s["Stacks"]), dtype=torch.float32, device=dev)
+    grads = {name: torch.empty(shape, dtype=torch.float32, device=dev) for name, shape in ge2e_shapes(s).items()}
+    _lib.check(L.glowtts_ge2e_train_backward(_lib.ptr(enc._images_t), _lib.ptr(keep), _lib.ptr(enc.linear.weight), _lib.ptr(de), _lib.ptr(da), _lib.ptr(work),
+                                             _lib.ptr(grads["linear.weight"]), _lib.ptr(grads["linear.bias"]), N, T, s["H"], s["Stacks"], s["E"], _lib.stream()),
+               "glowtts_ge2e_train_backward")
+    for k in range(s["Stacks"]):
+        g = [grads["lstm.{}_l{}".format(n, k)] for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+        _lib.check(L.glowtts_ge2e_train_wgrad(_lib.ptr(x), _lib.ptr(keep), _lib.ptr(da), _lib.ptr(work), *[_lib.ptr(t) for t in g], k, N, s["Mel"], T, s["H"],
+                                              s["Stacks"], _lib.stream()), "glowtts_ge2e_train_wgrad")
+    return grads
+
+
+class _Embed(torch.autograd.Function):
+    """e = GE2E.embed(stack): forward and backward are the HIP launches of csrc/ge2e_train_ops.hip; the gradient of the input is not computed."""
+
+    @staticmethod
+    def forward(ctx, enc, x, *flat):
+        keep, e = train_forward(enc, x)
+        ctx.enc, ctx.x, ctx.keep = enc, x, keep
+        return e
+
+    @staticmethod
+    def backward(ctx, de):
+        enc = ctx.enc
+        grads = train_backward(enc, ctx.x, ctx.keep, de.contiguous())
+        ctx.keep = None
+        order = ["lstm.{}_l{}".format(n, k) for k in range(enc.sizes["Stacks"]) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+        return (None, None) + tuple(grads[n] for n in order + ["linear.weight", "linear.bias"])
+
+
+def ge2e_loss_launch(e, w, S, M):
+    """-> (loss [1], de [N, E], dw [1]) of `glowtts_ge2e_train_loss` for e [S M, E] (row j M + i: speaker j's utterance i) and the device scalar w"""
+    L = _lib.lib()
+    N, E = e.shape
+    dev = e.device
+    work = torch.empty(L.glowtts_ge2e_train_loss_work_floats(N, S, E), dtype=torch.float32, device=dev)
+    loss, dw, de = torch.empty(1, dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.float32, device=dev), torch.empty_like(e)
+    _lib.check(L.glowtts_ge2e_train_loss(_lib.ptr(e), _lib.ptr(w), _lib.ptr(work), _lib.ptr(loss), _lib.ptr(de), _lib.ptr(dw), S, M, E, _lib.stream()),
+               "glowtts_ge2e_train_loss")
+    return loss, de, dw
+
+
+class _Loss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, e, w, S, M):
+        loss, de, dw = ge2e_loss_launch(e.detach().contiguous(), w.detach(), S, M)
+        ctx.save_for_backward(de, dw)
+        ctx.w_shape = w.shape
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        de, dw = ctx.saved_tensors
+        return de * g, (dw * g).reshape(ctx.w_shape), None, None
+
+
+class GE2ELoss(torch.nn.Module):
+    """The GE2E softmax loss (Wan et al. 2018, eq. 6 with the exclusive centroid of eq. 8-9) over raw embeddings e [speakers * utterances, E], speaker-major.
+    Invariant to a bias on the scores, so its one parameter is the scale `w`."""
+
+    def __init__(self, init_w=10.0):
+        super().__init__()
+        self.w = torch.nn.Parameter(torch.tensor(float(init_w)))
+
+    def forward(self, e, speakers, utterances):
+        S, M = int(speakers), int(utterances)
+        if S < 2 or M < 2 or e.dim() != 2 or e.shape[0] != S * M:
+            raise ValueError("GE2ELoss: expected e [speakers * utterances, E] with speakers >= 2 and utterances >= 2, got {} for {} x {}".format(
+                list(e.shape), S, M))
+        if e.shape[1] > abi.GE2E_MAX_E:
+            raise ValueError("GE2ELoss: {} = {} (at most {})".format(KEYS["E"], e.shape[1], abi.GE2E_MAX_E))
+        if e.dtype != torch.float32 or not e.is_cuda or not self.w.is_cuda:
+            raise _lib.GlowTTSHipError("GE2ELoss: expected fp32 device tensors (the HIP path has no CPU fallback)")
+        return _Loss.apply(e, self.w, S, M)
 
 
 def from_glowtts_checkpoint(hp, device, model_state):

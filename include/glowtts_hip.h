@@ -931,6 +931,42 @@ int glowtts_ge2e_pack(const float *w_ih, const float *w_hh, const float *b_ih, c
 int glowtts_ge2e_forward(const float *x, const float *images, const float *biases, const float *head_w, const float *head_b, float *work, float *hs,
                          float *e, float *d, int N, int Samples, int Mel, int T, int H, int Stacks, int E, void *stream);
 
+/* ---- Training the GE2E speaker encoder (csrc/ge2e_train_ops.hip; f32; additions, the ABI version stays) ----
+ * The forward's rules hold: launch order on the stream is the only synchronisation, no float atomics, every sum has a fixed partition and order (every
+ * result is bit-identical from run to run), the stack's products run on v_mfma_f32_16x16x4_f32.  None of these functions allocates.
+ * Layouts (all f32, device; N, Mel, T, H, Stacks, E, x, images, biases, head_w, head_b as for glowtts_ge2e_forward; N T < 2^31):
+ *   keep      glowtts_ge2e_train_keep_floats() = 6 Stacks N T H floats: hs [Stacks][N][T][H] | c [Stacks][N][T][H] | the activated gates
+ *             [Stacks][N][T][4 H] in the images' column order (column 64 s + 4 u + g: gate g (i, f, g, o) of hidden unit 16 s + u)
+ *   images_t  glowtts_ge2e_train_image_floats() = (8 Stacks - 4) H H floats: layer k at 8 k H H: W_hh^k as [4 H][H] with the rows in that column order,
+ *             then (all layers but the top one) W_ih^{k+1} likewise
+ *   da        [Stacks][N][T][4 H]: the gradients of the pre-activations, in the same column order
+ *   work      glowtts_ge2e_train_work_floats(): scratch shared by glowtts_ge2e_train_backward and glowtts_ge2e_train_wgrad
+ *   loss work glowtts_ge2e_train_loss_work_floats(N, S, E)
+ * glowtts_ge2e_train_pack    `ge2e_pack_bwd`: one layer's part of images_t from w_hh [4 H][H] of that layer and w_ih [4 H][H] of the layer above (NULL for
+ *                            the top layer, and only for it); call it whenever glowtts_ge2e_pack is called.
+ * glowtts_ge2e_train_forward T + Stacks - 1 `ge2e_cell` (the inference forward's arithmetic in its order: hs and e are bit-identical to
+ *                            glowtts_ge2e_forward's) and one `ge2e_head_fwd`: e [N][E].
+ * glowtts_ge2e_train_loss    the GE2E softmax loss over e [S M][E], row j M + i = speaker j's utterance i (S >= 2, M >= 2): u = e / max(|e|, 1e-12),
+ *                            s_{ji,k} = w cos(u_ji, c_k) with c_k the mean of speaker k's u and, for k = j, the mean without u_ji,
+ *                            L = mean_ji [logsumexp_k s_{ji,k} - s_{ji,j}].  w: one device float.  Writes loss [1], de [N][E], dw [1].
+ *                            `ge2e_loss_norm`, `_centroid`, `_scores`, `_dcent`, `_du`, `_final`.
+ * glowtts_ge2e_train_backward `ge2e_head_bwd` (dhead_w [E][H], dhead_b [E], the top layer's dh) and T + Stacks - 1 `ge2e_cell_bwd` (launch d, descending: every
+ *                            cell (layer k, step d - k)); fills da.  The gradient of x is not computed.
+ * glowtts_ge2e_train_wgrad   two `ge2e_wgrad` launches for ONE layer, after glowtts_ge2e_train_backward: dw_ih [4 H][in], dw_hh [4 H][H],
+ *                            db_ih = db_hh [4 H] in torch's row order (overwritten, not accumulated). */
+int64_t glowtts_ge2e_train_image_floats(int H, int Stacks);
+int64_t glowtts_ge2e_train_keep_floats(int64_t N, int T, int H, int Stacks);
+int64_t glowtts_ge2e_train_loss_work_floats(int64_t N, int S, int E);
+int64_t glowtts_ge2e_train_work_floats(int64_t N, int T, int Mel, int H, int Stacks);
+int glowtts_ge2e_train_pack(const float *w_hh, const float *w_ih_next, float *images_t, int layer, int H, int Stacks, void *stream);
+int glowtts_ge2e_train_forward(const float *x, const float *images, const float *biases, const float *head_w, const float *head_b, float *keep, float *e,
+                               int N, int Mel, int T, int H, int Stacks, int E, void *stream);
+int glowtts_ge2e_train_loss(const float *e, const float *w, float *work, float *loss, float *de, float *dw, int S, int M, int E, void *stream);
+int glowtts_ge2e_train_backward(const float *images_t, const float *keep, const float *head_w, const float *de, float *da, float *work, float *dhead_w,
+                                float *dhead_b, int N, int T, int H, int Stacks, int E, void *stream);
+int glowtts_ge2e_train_wgrad(const float *x, const float *keep, const float *da, float *work, float *dw_ih, float *dw_hh, float *db_ih, float *db_hh,
+                             int layer, int N, int Mel, int T, int H, int Stacks, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
