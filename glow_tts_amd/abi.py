@@ -281,4 +281,18 @@ SIGNATURES = {
     "glowtts_ge2e_train_loss": (I, [P] * 6 + [I] * 3 + [P]),
     "glowtts_ge2e_train_backward": (I, [P] * 8 + [I] * 5 + [P]),
     "glowtts_ge2e_train_wgrad": (I, [P] * 8 + [I] * 6 + [P]),
+    "glowtts_pwg_train_supported": (I, [I] * 4),
+    "glowtts_pwg_train_work_floats": (L, [I] * 6),
+    "glowtts_pwg_train_head_bwd": (I, [P] * 11 + [I] * 4 + [F, P]),
+    "glowtts_pwg_train_head_wgrad": (I, [P] * 10 + [I] * 4 + [P]),
+    "glowtts_pwg_train_layer_bwd": (I, [P] * 14 + [I] * 8 + [P]),
+    "glowtts_pwg_train_layer_wgrad": (I, [P] * 15 + [I] * 7 + [P]),
+    "glowtts_pwg_train_first_bwd": (I, [P] * 7 + [I] * 4 + [P]),
+    "glowtts_pwg_train_upsample_bwd": (I, [P] * 7 + [I] * 5 + [P]),
+    "glowtts_pwg_train_cond_in_bwd": (I, [P] * 4 + [I] * 4 + [P]),
+    "glowtts_stft_loss_supported": (I, [I] * 4),
+    "glowtts_stft_loss_keep_floats": (L, [I] * 4),
+    "glowtts_stft_loss_work_floats": (L, [I] * 4),
+    "glowtts_stft_loss_forward": (I, [P] * 8 + [I] * 5 + [F, I, P]),
+    "glowtts_stft_loss_backward": (I, [P] * 7 + [I] * 5 + [F, I, P]),
 }

@@ -277,14 +277,153 @@ def pwg_load(obj, geo):
     return out
 
 
+def pwg_init(geo, seed=0):
+    """A fresh generator's state dict (the names and shapes of `pwg_expected_shapes`, plain weights): torch.nn.Conv1d's default rule per tensor - uniform
+    in +- 1 / sqrt(fan_in), weights and biases alike - drawn in the order of `pwg_expected_shapes` on a host generator seeded with `seed`; the FIR of
+    scale s starts as the moving average 1 / (2 s + 1)."""
+    g = torch.Generator().manual_seed(int(seed))
+    shapes, sd = pwg_expected_shapes(geo), {}
+    for k, shape in shapes.items():
+        if ".up_layers." in k:
+            sd[k] = torch.full(shape, 1.0 / shape[-1], dtype=torch.float32)
+            continue
+        fan_in = math.prod(shapes[k[:-len("bias")] + "weight"][1:]) if k.endswith(".bias") else math.prod(shape[1:])
+        sd[k] = (torch.rand(shape, generator=g, dtype=torch.float32) * 2.0 - 1.0) / math.sqrt(fan_in)
+    return sd
+
+
+def pwg_train_geometry(geo):
+    """Raises ValueError naming the yaml keys when the backward's LDS tiles (larger than the forward's) do not fit; construction with trainable=True only."""
+    R, S, A = geo["R"], geo["S"], geo["A"]
+    K = 3 * R + A
+    gate, data = 4 * PWG_TILE * ((K if (K // 4) % 2 else K + 4) + R + S + 4), 4 * PWG_TILE * (6 * R + 4)
+    if max(gate, data) > PWG_LDS:
+        raise ValueError(f"Vocoder.Residual_Channels = {R} with Vocoder.Skip_Channels = {S} and Sound.Mel_Dim = {A}: training needs tiles of {gate} and {data} "
+                         f"bytes, more than the {PWG_LDS} bytes of LDS (inference supports these sizes, trainable=True does not)")
+
+
+def pwg_condition_stages(voc, mels, lengths, c):
+    """Fills c [B, L * hop, A] and returns the input of every upsampling scale (`stages[k]` [B, L * prod(scales[:k]), A]): the conditioning's own entry point
+    run on prefixes of the scale list (the identity FIR of a scale 1 for conv_in's output), so every stage is the forward's bit for bit."""
+    g = voc.geo
+    B, A, L = mels.shape
+    f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=mels.device)
+    work = f(2 * B * L * A * max(g["hop"] // g["scales"][-1], 1))
+    stages = [f(B, L, A)]
+    ops.pwg_condition(mels, lengths, voc.w_in, torch.tensor([0.0, 1.0, 0.0], device=mels.device), (ctypes.c_int * 1)(1), work, stages[0], g["ctx"])
+    mult = 1
+    for k in range(1, len(g["scales"])):
+        mult *= g["scales"][k - 1]
+        stages.append(f(B, L * mult, A))
+        ops.pwg_condition(mels, lengths, voc.w_in, voc.firs, (ctypes.c_int * k)(*g["scales"][:k]), work, stages[k], g["ctx"])
+    ops.pwg_condition(mels, lengths, voc.w_in, voc.firs, voc.scales, work, c, g["ctx"])
+    return stages
+
+
+def pwg_condition_backward(voc, mels, lengths, stages, dc, work, grads):
+    """d c [B, L * hop, A] -> the FIRs' and conv_in's gradients into `grads` (torch's layouts): `pwg_upsample_bwd` per scale, last to first, then `pwg_cond_in_bwd`."""
+    g, lib, P, st = voc.geo, _lib.lib(), _lib.ptr, _lib.stream()
+    B, A, L = mels.shape
+    dcur, mult, off = dc, g["hop"], sum(2 * s + 1 for s in g["scales"])
+    for k in reversed(range(len(g["scales"]))):
+        s = g["scales"][k]
+        mult //= s
+        off -= 2 * s + 1
+        din = torch.empty(B, L * mult, A, dtype=torch.float32, device=mels.device)
+        _lib.check(lib.glowtts_pwg_train_upsample_bwd(P(dcur), P(stages[k]), P(voc.firs[off:]), P(lengths), P(work), P(din),
+                                                      P(grads[f"upsample_net.upsample.up_layers.{2 * k + 1}.weight"]), B, A, L, mult, s, st),
+                   "glowtts_pwg_train_upsample_bwd")
+        dcur = din
+    _lib.check(lib.glowtts_pwg_train_cond_in_bwd(P(mels), P(dcur), P(lengths), P(grads["upsample_net.conv_in.weight"]), B, A, L, g["ctx"], st),
+               "glowtts_pwg_train_cond_in_bwd")
+
+
+def pwg_train_forward(voc, mels, lengths, seeds, noises):
+    """The inference forward's launches with every layer's input kept -> dict(wav, keep [Layers + 1, B, T, R], skips, c, stages): `stages[k]` is the input of
+    upsampling scale k, recomputed by running the conditioning's own entry point on prefixes of the scale list (the identity FIR of a scale 1 for
+    conv_in's output), so every stage is the forward's bit for bit."""
+    g = voc.geo
+    B, A, L = mels.shape
+    T, dev = L * g["hop"], mels.device
+    f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    keep, skips, c, wav = f(g["layers"] + 1, B, T, g["R"]), f(B, T, g["S"]), f(B, T, g["A"]), f(B, T)
+    stages = pwg_condition_stages(voc, mels, lengths, c)
+    ops.pwg_first(noises, seeds, lengths, *voc.first, keep[0], L, g["hop"])
+    for i, (lw, d) in enumerate(zip(voc.layer_weights, g["dilations"])):
+        ops.pwg_layer(keep[i], c, *lw, keep[i + 1], skips, lengths, L, g["hop"], d, i > 0)
+    ops.pwg_head(skips, lengths, *voc.head, wav, L, g["hop"], math.sqrt(1.0 / g["layers"]))
+    return {"wav": wav, "keep": keep, "skips": skips, "c": c, "stages": stages}
+
+
+def pwg_train_backward(voc, mels, lengths, seeds, noises, fwd, dwav):
+    """-> {name: gradient in torch's layout} for every name of `pwg_expected_shapes`, from what `pwg_train_forward` kept and d wav [B, T]."""
+    g, lib = voc.geo, _lib.lib()
+    B, A, L = mels.shape
+    hop, R, G, S = g["hop"], g["R"], g["G"], g["S"]
+    T, dev, P, st = L * hop, mels.device, _lib.ptr, _lib.stream()
+    f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    grads = {k: f(*shape) for k, shape in pwg_expected_shapes(g).items()}
+    work = f(lib.glowtts_pwg_train_work_floats(B, L, hop, R, S, A))
+    keep, skips, c = fwd["keep"], fwd["skips"], fwd["c"]
+    dwav = dwav.to(torch.float32).contiguous()
+    y, h, dh, dskips = f(B, T, S), f(B, T, S), f(B, T, S), f(B, T, S)
+    w1, b1, w2, b2 = voc.head
+    _lib.check(lib.glowtts_pwg_train_head_bwd(P(skips), P(lengths), P(w1), P(voc.head_w1t), P(b1), P(w2), P(dwav), P(y), P(h), P(dh), P(dskips), B, L, hop, S,
+                                              math.sqrt(1.0 / g["layers"]), st), "glowtts_pwg_train_head_bwd")
+    _lib.check(lib.glowtts_pwg_train_head_wgrad(P(y), P(h), P(dh), P(dwav), P(lengths), P(work), P(grads["last_conv_layers.1.weight"]),
+                                                P(grads["last_conv_layers.1.bias"]), P(grads["last_conv_layers.3.weight"]), P(grads["last_conv_layers.3.bias"]),
+                                                B, L, hop, S, st), "glowtts_pwg_train_head_wgrad")
+    del y, h, dh
+    gate, dpre, dc = f(B, T, R), f(B, T, G), f(B, T, A)
+    dxp, dx = torch.zeros(B, T, R, dtype=torch.float32, device=dev), f(B, T, R)        # nothing reads the last layer's x': its gradient is zero
+    for i in reversed(range(g["layers"])):
+        (lw1, lb1, _, _), (w2t, w1t, wauxt), d, q = voc.layer_weights[i], voc.layer_weights_t[i], g["dilations"][i], f"conv_layers.{i}."
+        _lib.check(lib.glowtts_pwg_train_layer_bwd(P(keep[i]), P(c), P(lw1), P(lb1), P(w2t), P(w1t), P(wauxt), P(dxp), P(dskips), P(gate), P(dpre), P(dx), P(dc),
+                                                   P(lengths), B, L, hop, R, S, A, d, int(i == g["layers"] - 1), st), "glowtts_pwg_train_layer_bwd")
+        _lib.check(lib.glowtts_pwg_train_layer_wgrad(P(keep[i]), P(c), P(gate), P(dpre), P(dxp), P(dskips), P(lengths), P(work), P(grads[q + "conv.weight"]),
+                                                     P(grads[q + "conv.bias"]), P(grads[q + "conv1x1_aux.weight"]), P(grads[q + "conv1x1_out.weight"]),
+                                                     P(grads[q + "conv1x1_out.bias"]), P(grads[q + "conv1x1_skip.weight"]), P(grads[q + "conv1x1_skip.bias"]),
+                                                     B, L, hop, R, S, A, d, st), "glowtts_pwg_train_layer_wgrad")
+        dxp, dx = dx, dxp
+    _lib.check(lib.glowtts_pwg_train_first_bwd(P(noises), P(seeds), P(dxp), P(lengths), P(work), P(grads["first_conv.weight"]), P(grads["first_conv.bias"]),
+                                               B, L, hop, R, st), "glowtts_pwg_train_first_bwd")
+    pwg_condition_backward(voc, mels, lengths, fwd["stages"], dc, work, grads)
+    grads["dx0"] = dxp
+    return grads
+
+
+class _Generate(torch.autograd.Function):
+    """wav = ParallelWaveGAN.generate(...): forward and backward are HIP launches (csrc/pwg_ops.hip, csrc/pwg_train_ops.hip); the mel gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, voc, mels, lengths, seeds, noises, *params):
+        voc._build_images({k: t.detach() for k, t in zip(voc.params, params)})
+        fwd = pwg_train_forward(voc, mels, lengths, seeds, noises)
+        ctx.voc, ctx.args, ctx.fwd = voc, (mels, lengths, seeds, noises), fwd
+        return fwd["wav"]
+
+    @staticmethod
+    def backward(ctx, dwav):
+        grads = pwg_train_backward(ctx.voc, *ctx.args, ctx.fwd, dwav)
+        ctx.fwd = None
+        return (None,) * 5 + tuple(grads[k] for k in ctx.voc.params)
+
+
 class ParallelWaveGAN:
     """ParallelWaveGAN(hp, device, state_dict=None)(mels [B, Mel, T], mel_lengths, seeds=None, noises=None) -> (wav [B, T * hop] fp32 on the device,
     wav_lengths [B] int64).  state_dict None: `Vocoder.Checkpoint_Path` is loaded.  seeds [B, 2] (integer words, `pwg_seed_words`): z[t] is the counter hash
     gauss(s0, s1, 0, t, 1) of csrc/gauss_hash.h evaluated in the first kernel; noises [B, T * hop]: the caller's z; neither: torch.randn on the device.
-    An utterance's waveform is bit-identical alone, in any batch, at any padding and from run to run (given its z)."""
+    An utterance's waveform is bit-identical alone, in any batch, at any padding and from run to run (given its z).
+    trainable=True (DESIGN.md "Training the Parallel WaveGAN generator"): `params` holds float32 device leaves in `pwg_expected_shapes`' names - from
+    `state_dict` or, without one, `pwg_init(geo, seed)` - and `generate` returns the same waveform with a backward (csrc/pwg_train_ops.hip)."""
 
-    def __init__(self, hp, device="cuda:0", state_dict=None):
+    def __init__(self, hp, device="cuda:0", state_dict=None, trainable=False, seed=0):
         self.geo = geo = pwg_geometry(hp)                           # before anything touches the device or the disk
+        self.trainable = bool(trainable)
+        if self.trainable:
+            pwg_train_geometry(geo)
+        if state_dict is None and self.trainable:
+            state_dict = pwg_init(geo, seed)
         if state_dict is None:
             path = pwg_settings(hp)["Checkpoint_Path"]
             if not path:
@@ -295,11 +434,21 @@ class ParallelWaveGAN:
             raise ValueError(f"the Vocoder block's sizes {geo} are not supported by the kernels")
         self.device = torch.device(device)
         self.sample_rate, self.n_mel, self.hop = int(hp.Sound.Sample_Rate), geo["A"], geo["hop"]
+        self.scales = (ctypes.c_int * len(geo["scales"]))(*geo["scales"])
+        self._capacity, self._buffers = 0, None
+        if self.trainable:                                          # float32 device leaves in pwg_expected_shapes' names; the images follow them (`_build_images`)
+            self.params = {k: t.to(self.device).requires_grad_(True) for k, t in w.items()}
+            w = {k: t.detach() for k, t in self.params.items()}
+        self._build_images(w)
+
+    def _build_images(self, w):
+        """The weight images in the kernels' layouts (K-major: the MFMA B operand reads 16 consecutive output channels of one input row) from the tensors `w`
+        (host or device): built once for a frozen generator; a trainable one rebuilds them on the device at every `generate`, with the transposed images of
+        the backward."""
+        geo = self.geo
         dev = lambda t: t.contiguous().to(self.device)
-        # weight images in the kernels' layouts (K-major: the MFMA B operand reads 16 consecutive output channels of one input row), built once
         self.w_in = dev(w["upsample_net.conv_in.weight"].permute(2, 1, 0).reshape(-1, geo["A"]))
         self.firs = dev(torch.cat([w[f"upsample_net.upsample.up_layers.{2 * i + 1}.weight"].reshape(-1) for i in range(len(geo["scales"]))]))
-        self.scales = (ctypes.c_int * len(geo["scales"]))(*geo["scales"])
         self.first = (dev(w["first_conv.weight"].reshape(-1)), dev(w["first_conv.bias"]))
         self.layer_weights = []
         for i in range(geo["layers"]):
@@ -310,7 +459,16 @@ class ParallelWaveGAN:
             self.layer_weights.append((dev(w1), dev(w[q + "conv.bias"]), dev(w2), dev(b2)))
         self.head = (dev(w["last_conv_layers.1.weight"][:, :, 0].t()), dev(w["last_conv_layers.1.bias"]), dev(w["last_conv_layers.3.weight"].reshape(-1)),
                      dev(w["last_conv_layers.3.bias"]))
-        self._capacity, self._buffers = 0, None
+        if self.trainable:
+            R, G = geo["R"], geo["G"]
+            self.layer_weights_t = [(dev(w2.t()), dev(w1[:3 * R].view(3, R, G).permute(0, 2, 1).reshape(3 * G, R)), dev(w1[3 * R:].t()))
+                                    for w1, _, w2, _ in self.layer_weights]
+            self.head_w1t = dev(w["last_conv_layers.1.weight"][:, :, 0])
+
+    def _refresh(self):
+        """A trainable generator's images follow its parameters: rebuilt before every call that reads them (an optimizer step writes the leaves in place)."""
+        if self.trainable:
+            self._build_images({k: t.detach() for k, t in self.params.items()})
 
     def _work(self, B, L):
         """Work buffers of a call (the two x, skips, c, the conditioning's intermediates): views of ONE set sized for the largest B x L (rounded up to
@@ -336,6 +494,7 @@ class ParallelWaveGAN:
         """mels [B, Mel, L] -> the conditioning rows c [B, L * hop, Mel] (rows beyond an utterance's own L * hop are not written)."""
         if not mels.is_cuda:
             raise _lib.GlowTTSHipError("expected a device tensor (the HIP path has no CPU fallback)")
+        self._refresh()
         mels = mels.to(device=self.device, dtype=torch.float32).contiguous()
         B, Mel, L = mels.shape
         if Mel != self.n_mel:
@@ -348,6 +507,7 @@ class ParallelWaveGAN:
 
     def layer(self, i, x, c, x_out, skips, frame_lengths, accumulate=True):
         """Layer i alone on rows x [B, T, R], c [B, T, A] -> x_out, skips (tests)."""
+        self._refresh()
         B, T, _ = x.shape
         L = T // self.geo["hop"]
         ops.pwg_layer(x, c, *self.layer_weights[i], x_out, skips, self._lengths(frame_lengths, B, L), L, self.geo["hop"], self.geo["dilations"][i], accumulate)
@@ -380,8 +540,148 @@ class ParallelWaveGAN:
         ops.pwg_head(wk["skips"], lengths, *self.head, wav, L, g["hop"], math.sqrt(1.0 / g["layers"]))
         return wav, lengths.to(torch.int64) * g["hop"]
 
+    def generate(self, mels, mel_lengths, seeds=None, noises=None):
+        """The training forward: `__call__`'s arithmetic term for term (the same launches, so the waveform is bit-identical) -> (wav [B, T * hop], wav_lengths)
+        with a backward that fills `.grad` of every tensor of `self.params`.  Only for `trainable=True`."""
+        if not self.trainable:
+            raise _lib.GlowTTSHipError("ParallelWaveGAN.generate needs a generator constructed with trainable=True (this one holds frozen weight images only)")
+        if seeds is not None and noises is not None:
+            raise ValueError("`seeds` and `noises` both given: the noise is either drawn in the kernel from the seed words or the caller's")
+        if not mels.is_cuda:
+            raise _lib.GlowTTSHipError("expected a device tensor (the HIP path has no CPU fallback)")
+        mels = mels.to(device=self.device, dtype=torch.float32).contiguous()
+        B, Mel, L = mels.shape
+        if Mel != self.n_mel:
+            raise ValueError(f"mels have {Mel} channels, Sound.Mel_Dim = {self.n_mel}")
+        T = L * self.geo["hop"]
+        lengths = self._lengths(mel_lengths, B, L)
+        if seeds is not None:
+            from .alignment import seed_words
+            seeds = seed_words(seeds, B, self.device)
+        else:
+            if noises is None:
+                noises = torch.randn(B, T, dtype=torch.float32, device=self.device)
+            noises = noises.to(device=self.device, dtype=torch.float32).reshape(B, -1).contiguous()
+            if tuple(noises.shape) != (B, T):
+                raise ValueError(f"noises have shape {tuple(noises.shape)}, expected {(B, T)} (or [B, 1, T])")
+        names = list(self.params)
+        wav = _Generate.apply(self, mels, lengths, seeds, noises, *[self.params[k] for k in names])
+        return wav, lengths.to(torch.int64) * self.geo["hop"]
+
     def to_host(self, wav, wav_lengths):
         """Device waveforms -> list of float32 numpy arrays clipped to [-1, 1] (what `audio.write_wav` takes).  No de-emphasis: the vocoder was trained on
         final audio."""
         wav, n = wav.cpu().numpy(), wav_lengths.cpu().tolist()
         return [np.clip(w[:m], -1.0, 1.0).astype(np.float32) for w, m in zip(wav, n)]
+
+
+# ================================================================================================================================================
+# Multi-resolution STFT loss (Yamamoto et al. 2020, eq. 4-6) on the kernels of csrc/stft_loss_ops.hip: stage one of the Parallel WaveGAN recipe trains the
+# generator with it alone.  The contract is frozen in DESIGN.md ("STFT loss"); tests/pwg_train_ref.py restates it with the library STFT.
+# ================================================================================================================================================
+STFT_RESOLUTIONS = [(1024, 120, 600), (2048, 240, 1200), (512, 50, 240)]            # (n_fft, hop, win); the recipe's, restated from memory: this project's contract
+STFT_KEY = "Vocoder.Train.STFT_Resolutions"
+
+
+def stft_loss_geometry(resolutions=None, T=None):
+    """[(n_fft, hop, win), ...] as ints; raises ValueError naming the yaml keys when the kernels do not support a resolution or, with `T` given, when the
+    segment of T samples is too short for its reflect padding."""
+    res = STFT_RESOLUTIONS if resolutions is None else resolutions
+    try:
+        res = [tuple(int(v) for v in r) for r in res]
+    except (TypeError, ValueError):
+        res = None
+    if not res or any(len(r) != 3 for r in res):
+        raise ValueError(f"{STFT_KEY} must be a non-empty list of [n_fft, hop, win] triples, got {resolutions!r}")
+    for n_fft, hop, win in res:
+        if n_fft < 256 or n_fft > 4096 or n_fft & (n_fft - 1):
+            raise ValueError(f"{STFT_KEY}: n_fft = {n_fft} of {[n_fft, hop, win]} must be a power of two in [256, 4096]")
+        if win < 1 or win > n_fft:
+            raise ValueError(f"{STFT_KEY}: win = {win} of {[n_fft, hop, win]} must lie in [1, n_fft = {n_fft}]")
+        if hop < 1 or hop > win:
+            raise ValueError(f"{STFT_KEY}: hop = {hop} of {[n_fft, hop, win]} must lie in [1, win = {win}] (every sample is covered by a frame)")
+        if T is not None and T <= n_fft // 2:
+            raise ValueError(f"{STFT_KEY}: n_fft = {n_fft} of {[n_fft, hop, win]} needs segments longer than n_fft / 2 = {n_fft // 2} samples for its reflect "
+                             f"padding, got {T} (Vocoder.Train.Segment_Frames * Sound.Frame_Shift)")
+    return res
+
+
+def stft_loss_forward(loss_fn, pred, target):
+    """The forward launches of every resolution -> (loss [1], terms [n, 3] = (L_sc, L_mag, the backward's coefficient) per resolution, keeps): the entry
+    points' own outputs, for `_STFTLoss` and the tests."""
+    B, T = pred.shape
+    L, dev, n = _lib.lib(), pred.device, len(loss_fn.resolutions)
+    loss, terms, keeps = torch.empty(1, dtype=torch.float32, device=dev), torch.empty(n, 3, dtype=torch.float32, device=dev), []
+    for i, ((n_fft, hop, win), (window, twiddle)) in enumerate(zip(loss_fn.resolutions, loss_fn.tables)):
+        keep = torch.empty(L.glowtts_stft_loss_keep_floats(B, T, n_fft, hop), dtype=torch.float32, device=dev)
+        work = loss_fn._work(L.glowtts_stft_loss_work_floats(B, T, win, hop))
+        _lib.check(L.glowtts_stft_loss_forward(_lib.ptr(pred), _lib.ptr(target), _lib.ptr(window), _lib.ptr(twiddle), _lib.ptr(keep), _lib.ptr(work),
+                                               _lib.ptr(terms[i]), _lib.ptr(loss), B, T, n_fft, win, hop, 1.0 / n, int(i > 0), _lib.stream()),
+                   "glowtts_stft_loss_forward")
+        keeps.append(keep)
+    return loss, terms, keeps
+
+
+def stft_loss_backward(loss_fn, keeps, terms, grad_out, B, T):
+    """The backward launches of every resolution -> d pred [B, T] = grad_out * dL/dpred (grad_out: one device float)."""
+    L, dev, n = _lib.lib(), terms.device, len(loss_fn.resolutions)
+    dpred = torch.empty(B, T, dtype=torch.float32, device=dev)
+    for i, ((n_fft, hop, win), (window, twiddle)) in enumerate(zip(loss_fn.resolutions, loss_fn.tables)):
+        work = loss_fn._work(L.glowtts_stft_loss_work_floats(B, T, win, hop))
+        _lib.check(L.glowtts_stft_loss_backward(_lib.ptr(keeps[i]), _lib.ptr(terms[i]), _lib.ptr(grad_out), _lib.ptr(window), _lib.ptr(twiddle), _lib.ptr(work),
+                                                _lib.ptr(dpred), B, T, n_fft, win, hop, 1.0 / n, int(i > 0), _lib.stream()), "glowtts_stft_loss_backward")
+    return dpred
+
+
+class _STFTLoss(torch.autograd.Function):
+    """loss = MultiResolutionSTFTLoss(pred, target): forward and backward are the HIP launches of csrc/stft_loss_ops.hip; the target gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, loss_fn, pred, target):
+        loss, terms, keeps = stft_loss_forward(loss_fn, pred, target)
+        ctx.loss_fn, ctx.keeps, ctx.terms, ctx.shape = loss_fn, keeps, terms, tuple(pred.shape)
+        loss_fn.terms = terms[:, :2]
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        dpred = stft_loss_backward(ctx.loss_fn, ctx.keeps, ctx.terms, g.to(torch.float32).reshape(1).contiguous(), *ctx.shape)
+        ctx.keeps = None
+        return None, dpred, None
+
+
+class MultiResolutionSTFTLoss:
+    """MultiResolutionSTFTLoss(resolutions=None, device)(pred [B, T], target [B, T]) -> the scalar loss, the mean over the resolutions of
+    L_sc + L_mag, with a backward that yields d pred (a second loss term of the caller's adds into the same tensor through autograd).  `.terms` [n, 2]
+    holds (L_sc, L_mag) per resolution of the last call.  Every row is of the full length T: training segments are of one length, so `lengths` that
+    differ from T raise.  Bit-identical from run to run."""
+
+    def __init__(self, resolutions=None, device="cuda:0"):
+        self.resolutions = stft_loss_geometry(resolutions)         # before anything touches the device
+        self.device = torch.device(device)
+        self.tables = []
+        for n_fft, hop, win in self.resolutions:
+            tw, w = fft_tables(n_fft, win)
+            self.tables.append(tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device) for a in (w, tw)))
+        self.terms, self._scratch = None, None
+
+    def _work(self, floats):
+        """One scratch buffer (the frames' sums, the backward's frame gradients) that grows to the largest request; a launch rewrites what it later reads."""
+        if self._scratch is None or self._scratch.numel() < floats:
+            self._scratch = None
+            self._scratch = torch.empty(floats, dtype=torch.float32, device=self.device)
+        return self._scratch
+
+    def __call__(self, pred, target, lengths=None):
+        if pred.dim() != 2 or tuple(pred.shape) != tuple(target.shape):
+            raise ValueError(f"MultiResolutionSTFTLoss: expected pred and target [B, T] of one shape, got {list(pred.shape)} and {list(target.shape)}")
+        if pred.dtype != torch.float32 or target.dtype != torch.float32 or not pred.is_cuda or not target.is_cuda:
+            raise _lib.GlowTTSHipError("MultiResolutionSTFTLoss: expected fp32 device tensors (the HIP path has no CPU fallback)")
+        B, T = pred.shape
+        if lengths is not None and any(int(n) != T for n in torch.as_tensor(lengths).reshape(-1).tolist()):
+            raise ValueError(f"MultiResolutionSTFTLoss: ragged input (lengths {torch.as_tensor(lengths).reshape(-1).tolist()} of T = {T}): every row must be of "
+                             "the full length, training segments are of one length (Vocoder.Train.Segment_Frames)")
+        stft_loss_geometry(self.resolutions, T)
+        if B < 1 or B > 65535 or B * T >= 2 ** 31:
+            raise ValueError(f"MultiResolutionSTFTLoss: batch of {B} x {T} samples is outside 1 <= B <= 65535, B T < 2^31 (Vocoder.Train.Batch_Size)")
+        return _STFTLoss.apply(self, pred.contiguous(), target.detach().contiguous())

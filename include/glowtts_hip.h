@@ -967,6 +967,72 @@ int glowtts_ge2e_train_backward(const float *images_t, const float *keep, const 
 int glowtts_ge2e_train_wgrad(const float *x, const float *keep, const float *da, float *work, float *dw_ih, float *dw_hh, float *db_ih, float *db_hh,
                              int layer, int N, int Mel, int T, int H, int Stacks, void *stream);
 
+/* ---- Training the Parallel WaveGAN generator (csrc/pwg_train_ops.hip; f32; additions, the ABI version stays) ----
+ * The training forward is the inference forward: the glowtts_pwg_* entry points above, with every layer's input x kept in its own slab (layer i reads
+ * slab i and writes slab i + 1), so the waveform is bit-identical.  The gate is recomputed here.  Rows, lengths and layouts as for glowtts_pwg_layer; nothing
+ * beyond an utterance's own rows is read or written.  No float atomics, no kernel waits on another workgroup, fixed partitions and orders: every gradient
+ * is bit-identical from run to run.  All matrix products: v_mfma_f32_16x16x4_f32.  None of these functions allocates.  The gradient of the mel is not computed.
+ * Supported (glowtts_pwg_train_supported, else GLOWTTS_E_ARG): glowtts_pwg_supported, and the backward's LDS tiles within 160 KB:
+ * 64 (stride(3 R + A) + R + S + 4) floats (gate launch) and 64 (6 R + 4) floats (data launch); B * ceil(Lmax hop / 1024) <= 65535.
+ *   work   glowtts_pwg_train_work_floats() floats, 8-byte aligned: the weight gradients' splits (one per utterance and 1024 rows), the FIR gradient's block sums
+ * glowtts_pwg_train_head_bwd    `pwg_head_bwd`: skips, dwav [B][Lmax hop] -> dskips [B][Lmax hop][S] (the same tensor for every layer) and, for the weight
+ *                               gradients, y = relu(scale skips), h = relu(W1 y + b1), dh, all [B][Lmax hop][S].  w1 [S][S] row = input channel (the forward's
+ *                               image), w1t [S][S] row = output channel (torch's tensor).
+ * glowtts_pwg_train_head_wgrad  `pwg_wgrad` + `pwg_wgrad_sum`: dw1 [S][S] (torch's [out][in]), db1 [S], dw2 [S], db2 [1]; overwritten.
+ * glowtts_pwg_train_layer_bwd   `pwg_layer_bwd_gate` (recomputes the gate from x, c, w1, b1; dgate = [sqrt(1/2) dxp | dskips] w2t^T-wise, w2t [R + S][R] =
+ *                               the forward's w2 transposed; writes gate [B][Lmax hop][R] and dpre [B][Lmax hop][2 R]) and `pwg_layer_bwd_data`
+ *                               (dx = sqrt(1/2) dxp + sum over the taps of dpre(t -+ d) W1_tap^T, w1t [3 * 2 R][R]: row = tap * 2 R + gate column;
+ *                               dc (+)= dpre wauxt, wauxt [2 R][A]; first != 0 overwrites dc).  dxp: the gradient of the layer's output x', dx: of its input.
+ * glowtts_pwg_train_layer_wgrad `pwg_wgrad` + `pwg_wgrad_sum` for ONE layer, after glowtts_pwg_train_layer_bwd: conv.weight [2 R][R][3], conv.bias [2 R],
+ *                               conv1x1_aux.weight [2 R][A], conv1x1_out.weight [R][R], .bias [R], conv1x1_skip.weight [S][R], .bias [S] in torch's layouts;
+ *                               overwritten.
+ * glowtts_pwg_train_first_bwd   `pwg_first_bwd` + `pwg_wgrad_sum`: first_conv's dw [R], db [R] from dx0 and z (noises or seeds as for glowtts_pwg_first).
+ * glowtts_pwg_train_upsample_bwd `pwg_upsample_bwd`, `pwg_upsample_bwd_fir` and `pwg_upsample_bwd_sum` for ONE scale s: dout [B][Lmax mult s][A], the stage's input in
+ *                               [B][Lmax mult][A], fir [2 s + 1] -> din [B][Lmax mult][A], dfir [2 s + 1].
+ * glowtts_pwg_train_cond_in_bwd `pwg_cond_in_bwd`: mel [B][A][Lmax], dcond [B][Lmax][A] -> dw [A][A][2 ctx + 1] (torch's layout). */
+int glowtts_pwg_train_supported(int R, int S, int A, int max_dilation);
+int64_t glowtts_pwg_train_work_floats(int B, int Lmax, int hop, int R, int S, int A);
+int glowtts_pwg_train_head_bwd(const float *skips, const int32_t *frame_lengths, const float *w1, const float *w1t, const float *b1, const float *w2,
+                               const float *dwav, float *y, float *h, float *dh, float *dskips, int B, int Lmax, int hop, int S, float scale, void *stream);
+int glowtts_pwg_train_head_wgrad(const float *y, const float *h, const float *dh, const float *dwav, const int32_t *frame_lengths, float *work, float *dw1,
+                                 float *db1, float *dw2, float *db2, int B, int Lmax, int hop, int S, void *stream);
+int glowtts_pwg_train_layer_bwd(const float *x, const float *c, const float *w1, const float *b1, const float *w2t, const float *w1t, const float *wauxt,
+                                const float *dxp, const float *dskips, float *gate, float *dpre, float *dx, float *dc, const int32_t *frame_lengths, int B,
+                                int Lmax, int hop, int R, int S, int A, int dilation, int first, void *stream);
+int glowtts_pwg_train_layer_wgrad(const float *x, const float *c, const float *gate, const float *dpre, const float *dxp, const float *dskips,
+                                  const int32_t *frame_lengths, float *work, float *dconv_w, float *dconv_b, float *daux_w, float *dout_w, float *dout_b,
+                                  float *dskip_w, float *dskip_b, int B, int Lmax, int hop, int R, int S, int A, int dilation, void *stream);
+int glowtts_pwg_train_first_bwd(const float *noises, const uint32_t *seeds, const float *dx0, const int32_t *frame_lengths, float *work, float *dw, float *db,
+                                int B, int Lmax, int hop, int R, void *stream);
+int glowtts_pwg_train_upsample_bwd(const float *dout, const float *in, const float *fir, const int32_t *frame_lengths, float *work, float *din, float *dfir,
+                                   int B, int A, int Lmax, int mult, int s, void *stream);
+int glowtts_pwg_train_cond_in_bwd(const float *mel, const float *dcond, const int32_t *frame_lengths, float *dw, int B, int A, int Lmax, int ctx, void *stream);
+
+/* ---- Multi-resolution STFT loss of vocoder training (csrc/stft_loss_ops.hip; f32 signals, float64 sums; additions, the ABI version stays) ----
+ * ONE resolution (n_fft, hop, win_length) per call; vocoder.MultiResolutionSTFTLoss calls once per resolution.  pred, target [B][T], every row of the full
+ * length T.  X = STFT with center = True, reflect padding by n_fft / 2, the periodic Hann window of win_length centred in n_fft (the tables of
+ * glowtts_stft_f32), NF = 1 + T / hop frames, F = n_fft / 2 + 1 bins;  |X| = sqrt(max(re^2 + im^2, 1e-7));  L_sc = ||Y| - |X||_F / ||Y||_F over the whole
+ * batch, L_mag = mean |log |Y| - log |X||  (Y: target, X: pred).  No atomics, fixed summation orders: bit-identical from run to run.
+ * Supported (glowtts_stft_loss_supported, else GLOWTTS_E_ARG): n_fft a power of two in [256, 4096], 1 <= hop <= win_length <= n_fft,
+ * n_fft / 2 < T <= 2^29; also 1 <= B <= 65535, B T < 2^31, B NF <= 2^24.  None of these functions allocates.
+ *   keep   glowtts_stft_loss_keep_floats() = 4 B NF F floats (8-byte aligned): pred's spectrum [B NF][F][2] | |X| [B NF][F] | |Y| [B NF][F]
+ *   work   glowtts_stft_loss_work_floats() = B NF (6 + win_length) floats (8-byte aligned): per-frame sums [B NF][3] f64 | the backward's windowed
+ *          frame gradients [B NF][win_length]
+ *   terms  [3]: L_sc, L_mag and the backward's coefficient 1 / (||Y| - |X||_F ||Y||_F) (0 when the magnitudes are equal)
+ * glowtts_stft_loss_forward   `stft_loss_fwd` (per frame: both signals through the LDS FFT, magnitudes and pred's spectrum into keep, the frame's sums)
+ *                             and `stft_loss_reduce` (one workgroup): fills terms and loss[0] = weight (L_sc + L_mag), added to loss[0] when accumulate.
+ * glowtts_stft_loss_backward  `stft_loss_bwd_frames` (per frame: dL/d|X| in closed form times X / |X|, zero where the clamp is active, the transposed real
+ *                             DFT in LDS, the window) and `stft_loss_bwd_fold` (per sample: gather of the ceil(win_length / hop) covering frames in ascending
+ *                             order at the sample's own padded position and the at most two that reflect onto it):
+ *                             dpred [B][T] = grad_out[0] weight dL/dpred (grad_out: one device float), added to dpred when accumulate. */
+int glowtts_stft_loss_supported(int n_fft, int win_length, int hop, int T);
+int64_t glowtts_stft_loss_keep_floats(int B, int T, int n_fft, int hop);
+int64_t glowtts_stft_loss_work_floats(int B, int T, int win_length, int hop);
+int glowtts_stft_loss_forward(const float *pred, const float *target, const float *window, const float *twiddle, float *keep, float *work, float *terms,
+                              float *loss, int B, int T, int n_fft, int win_length, int hop, float weight, int accumulate, void *stream);
+int glowtts_stft_loss_backward(const float *keep, const float *terms, const float *grad_out, const float *window, const float *twiddle, float *work,
+                               float *dpred, int B, int T, int n_fft, int win_length, int hop, float weight, int accumulate, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
