@@ -1,5 +1,6 @@
 // Analysis front end on the device (what Pattern_Generator.py and the wav references of Inference.py need): wav -> normalised mel in ONE launch, and the
-// YIN pitch track of GR mode.  The arithmetic is glow_tts_amd/audio.py's (`mel_generate`, `yin_pitch`) in fp32; the LDS FFT is the vocoder's (vocoder_fft.h).
+// YIN pitch track of GR mode.  The arithmetic is glow_tts_amd/audio.py's (`mel_generate`, `yin_pitch`) in fp32; the LDS FFT and the framing around it (LDS layout,
+// frame packer, real-input split) are vocoder_fft.h's, shared with the vocoder and the STFT loss; the pre-emphasis is this file's sample lambda.
 //
 // mel_analysis_kernel, one 256-thread workgroup per frame at a time, workgroups stride over the B * T frames; window and twiddles are staged in LDS once:
 //   HBM -> LDS   the win_length samples under the window, gathered with the pre-emphasis applied on the fly: y[s] = x[s] - p x[s-1], y[0] = x[0]; the reflect
@@ -56,16 +57,13 @@ __global__ __launch_bounds__(VOC_NT) void mel_analysis_kernel(const mel_args a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char fe_smem[];
     const int N = 1 << a.logN, M = N >> 1, logM = a.logN - 1, F = M + 1;
-    float2* const tw = reinterpret_cast<float2*>(fe_smem);                     // [M]
-    float2* const X = tw + M;                                                  // [voc_pad(M) + 1]
-    float* const wnd = reinterpret_cast<float*>(X + voc_pad(M) + 1);           // [win]
-    float* const mag = wnd + a.win;                                            // [F]
-    float* const row = mag + F;                                                // [Mel]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lpad = (N - a.win) >> 1;
-    for (int i = tid; i < M; i += VOC_NT) tw[i] = a.twiddle[i];
-    for (int i = tid; i < a.win; i += VOC_NT) wnd[i] = a.window[i];
-    __syncthreads();
+    const voc_lds lds = voc_lds_stage(fe_smem, a.twiddle, a.window, M, a.win);
+    float2* const X = lds.X;
+    const float2* const tw = lds.tw;
+    float* const mag = lds.rest;                                               // [F]
+    float* const row = mag + F;                                                // [Mel]
     const int total = a.B * a.T;
     for (int f = blockIdx.x; f < total; f += gridDim.x) {
         const int b = f / a.T, t = f - b * a.T;
@@ -77,24 +75,9 @@ __global__ __launch_bounds__(VOC_NT) void mel_analysis_kernel(const mel_args a)
             for (int j = tid; j < a.Mel; j += VOC_NT) out[j] = -a.max_abs;
             continue;
         }
-        // ---- gather with pre-emphasis + window + pack, bit-reversed ----
+        // ---- the frame, with the pre-emphasis applied to the reflected index ----
         const float* xb = a.x + (int64_t)b * a.ldx;
-        for (int m = tid; m < M; m += VOC_NT) {
-            float v[2];
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const int n = 2 * m + e, j = n - lpad;
-                v[e] = 0.f;
-                if (j >= 0 && j < a.win) {
-                    const int s = voc_reflect(t * a.hop + n - M, L);
-                    float y = xb[s];
-                    if (s > 0) y = y - a.p * xb[s - 1];
-                    v[e] = y * wnd[j];
-                }
-            }
-            X[voc_pad((int)(__brev((unsigned)m) >> (32 - logM)))] = make_float2(v[0], v[1]);
-        }
-        __syncthreads();
+        voc_pack_frame(lds, M, logM, lpad, a.win, t * a.hop - M, L, [&](int s) { return s > 0 ? xb[s] - a.p * xb[s - 1] : xb[s]; });
         voc_fft<false>(X, tw, logM, a.logN, tid);
         // ---- split: |Y_k| of the real-input spectrum, bin pairs (k, M - k) ----
         for (int k = tid; k <= (M >> 1); k += VOC_NT) {
@@ -104,12 +87,8 @@ __global__ __launch_bounds__(VOC_NT) void mel_analysis_kernel(const mel_args a)
                 mag[M] = fabsf(z.x - z.y);
                 continue;
             }
-            const float2 w = tw[k];
-            const float2 za = X[voc_pad(k)], zb = X[voc_pad(M - k)];
-            const float2 e = make_float2(0.5f * (za.x + zb.x), 0.5f * (za.y - zb.y));              // (Z[k] + conj Z[M-k]) / 2
-            const float2 d = make_float2(0.5f * (za.x - zb.x), 0.5f * (za.y + zb.y));              // (Z[k] - conj Z[M-k]) / 2
-            const float2 wo = voc_mul(make_float2(d.y, -d.x), w);                                  // W^k O,  O = d / i
-            const float2 yk = voc_add(e, wo), ymk = voc_sub(e, wo);
+            float2 yk, ymk;
+            voc_split_pair(X, tw, k, M, yk, ymk);
             mag[k] = sqrtf(yk.x * yk.x + yk.y * yk.y);
             mag[M - k] = sqrtf(ymk.x * ymk.x + ymk.y * ymk.y);
         }
@@ -223,7 +202,6 @@ __global__ __launch_bounds__(256) void yin_kernel(const yin_args a)
     }
 }
 
-int fe_log2(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
 bool fe_bad_batch(int B, int T, int ldx) { return B < 1 || B > 65535 || T < 1 || ldx < 1 || (int64_t)B * T > (int64_t)1 << 30; }
 
 }  // namespace
@@ -233,14 +211,13 @@ extern "C" int glowtts_mel_analysis_f32(const float* wav, const int32_t* wav_len
                                         float pre_emphasis, float min_db, float max_abs, void* stream)
 {
     if (!wav || !wav_lengths || !window || !twiddle || !fb_index || !fb_weight || !mel || fe_bad_batch(B, T, ldx) || Mel < 1 || Mel > 1024 || n_weights < 1 ||
-        n_fft < 256 || n_fft > 4096 || (n_fft & (n_fft - 1)) || win_length < 1 || win_length > n_fft || hop < 1 || !(max_abs > 0.f) || !(min_db < 0.f))
+        !voc_fft_supported(n_fft, win_length) || hop < 1 || !(max_abs > 0.f) || !(min_db < 0.f))
         return GLOWTTS_E_ARG;
     mel_args a = {};
     a.x = wav; a.lengths = wav_lengths; a.window = window; a.twiddle = reinterpret_cast<const float2*>(twiddle); a.fb_index = fb_index; a.fb_weight = fb_weight;
     a.mel = mel; a.p = pre_emphasis; a.min_db = min_db; a.max_abs = max_abs;
-    a.B = B; a.T = T; a.ldx = ldx; a.Mel = Mel; a.nw = n_weights; a.logN = fe_log2(n_fft); a.win = win_length; a.hop = hop;
-    const int M = n_fft / 2;
-    const size_t lds = (size_t)(M + M + (M >> 5) + 1) * 8 + (size_t)(win_length + M + 1 + Mel) * 4;      // <= 60.5 KiB at 4096 / 4096 / 1024
+    a.B = B; a.T = T; a.ldx = ldx; a.Mel = Mel; a.nw = n_weights; a.logN = voc_log2(n_fft); a.win = win_length; a.hop = hop;
+    const size_t lds = voc_lds_bytes(n_fft, win_length, n_fft / 2 + 1 + Mel);  // + magnitudes [F] | mel row [Mel]: <= 60.5 KiB at 4096 / 4096 / 1024
     const int frames = B * T, grid = frames < 1536 ? frames : 1536;            // 6 resident workgroups (by LDS at n_fft = 2048) on each of 256 CUs
     GLOWTTS_NOTE_STATIC("frontend_mel_analysis");
     hipLaunchKernelGGL(mel_analysis_kernel, dim3(grid), dim3(VOC_NT), lds, static_cast<hipStream_t>(stream), a);

@@ -2,9 +2,9 @@
 // backward, for gfx950, f32.  The rules are the forward's (ge2e_ops.hip): no kernel waits on another workgroup, no float atomics, every sum has a fixed
 // partition and a fixed order, every matrix product of the stack runs on v_mfma_f32_16x16x4_f32.
 //
-//   ge2e_cell (training)  the forward's diagonal wavefront and arithmetic, term for term; keeps c whole [Stacks][N][T][H] and the activated gates
-//                         [Stacks][N][T][4 H] in the image's column order (64 s + 4 u + g: one 16-byte store per unit).
-//   ge2e_head_fwd         e = W h_{T-1}^{top} + b, the inference head's sum (a wave per output, lanes over H, the same shuffle tree).
+//   ge2e_cell (training)  ge2e_common.h's cell kernel with KEEP = true (the inference runs the same text with KEEP = false): keeps c whole
+//                         [Stacks][N][T][H] and the activated gates [Stacks][N][T][4 H] in the image's column order.
+//   ge2e_head_fwd         e = W h_{T-1}^{top} + b for every sequence: ge2e_common.h's head projection, which the inference head calls too.
 //   ge2e_loss_*           six small launches: unit vectors, speaker sums and norms, scores + softmax, centroid gradients, du -> de, the two scalars.
 //   ge2e_head_bwd         dh_top = de W, dW_lin = de^T h_top (MFMA, one wave per 16 x 16 tile, K serial), db_lin = sum de.
 //   ge2e_pack_bwd         per layer the transposed image [W_hh^k ; W_ih^{k+1}] with rows in da's packed column order and columns = hidden units of layer k.
@@ -15,43 +15,20 @@
 //   ge2e_wgrad            per layer [4 H x N T] . [N T x (in + H + 1)] (the last column is the constant 1: the bias gradient): 64 x 64 output tiles, rows
 //                         staged 16 at a time, the reduction split in fixed chunks of rows; a second launch adds the chunks in order and writes torch's
 //                         gate-major rows.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/glowtts_hip.h"
-#include "launch_log.h"
+#include "ge2e_common.h"
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-constexpr int TM = 16, TU = 16;                           // as in ge2e_ops.hip
-constexpr int THREADS = 256, WAVES = THREADS / 64;
-constexpr int RED_FLOATS = WAVES * 4 * TM * TU;
 constexpr int BWD_CHUNK = 512;                            // floats of the K range per row and staging step of ge2e_cell_bwd
 constexpr int BWD_AS = BWD_CHUNK + 4;                     // (stride / 4) odd
 constexpr int WG_TILE = 64, WG_ROWS = 16, WG_LD = 80;     // ge2e_wgrad: output tile, rows per staging step, LDS stride (16 q + r: 64 distinct banks)
 constexpr int WG_MAX_SPLITS = 8, WG_SPLIT_ROWS = 256;
 constexpr float EPS = 1e-12f;
 
-__device__ __forceinline__ v4f mfma4(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
-__host__ __device__ __forceinline__ int as_stride_of(int K) { return ((K >> 2) & 1) ? K : K + 4; }
-__host__ __device__ __forceinline__ int64_t image_offset(int layer, int Mel, int H)
-{
-    return layer == 0 ? 0 : ((int64_t)(Mel + H) + (int64_t)(layer - 1) * 2 * H) * 4 * H;
-}
 __host__ __device__ __forceinline__ int64_t image_t_offset(int layer, int H) { return (int64_t)layer * 8 * H * H; }
-int cell_lds_bytes(int Mel, int H) { return (TM * as_stride_of(Mel > H ? Mel + H : 2 * H) + RED_FLOATS) * 4; }
 int wgrad_splits(int64_t rows) { const int64_t s = (rows + WG_SPLIT_ROWS - 1) / WG_SPLIT_ROWS; return (int)(s < 1 ? 1 : s > WG_MAX_SPLITS ? WG_MAX_SPLITS : s); }
 int64_t wgrad_chunk_rows(int64_t rows) { const int sp = wgrad_splits(rows); return ((rows + sp - 1) / sp + WG_ROWS - 1) / WG_ROWS * WG_ROWS; }
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
 // the sum over the workgroup in a fixed order (lanes: the shuffle tree; waves: 0 + 1 + 2 + 3); sc: WAVES floats of LDS; every thread gets the value
 __device__ __forceinline__ float block_sum(float v, float* sc)
 {
@@ -62,100 +39,13 @@ __device__ __forceinline__ float block_sum(float v, float* sc)
     return ((sc[0] + sc[1]) + sc[2]) + sc[3];
 }
 
-// ---- the training forward cell: ge2e_cell_kernel of ge2e_ops.hip with c and the gates kept ----------------------------------------------------------------
-__global__ __launch_bounds__(THREADS) void ge2e_cell_keep_kernel(const float* __restrict__ x, const float* __restrict__ images, const float* __restrict__ biases,
-                                                                 float* __restrict__ hs, float* __restrict__ cs, float* __restrict__ gates, int N, int Mel, int T,
-                                                                 int H, int d, int kmin)
-{
-    extern __shared__ __attribute__((aligned(16))) float ge2e_smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
-    const int k = kmin + blockIdx.z, t = d - k;
-    const int s = blockIdx.x, n0 = blockIdx.y * TM;
-    const int in = k == 0 ? Mel : H, K = in + H, G = 4 * H;
-    const int as = as_stride_of(K);
-    float* As = ge2e_smem;
-    float* red = ge2e_smem + TM * as_stride_of(Mel > H ? Mel + H : 2 * H);
-    const size_t layer_rows = (size_t)N * T;
-
-    if (k == 0) {
-        for (int e = tid; e < TM * Mel; e += THREADS) {
-            const int row = e / Mel, m = e - row * Mel, n = n0 + row;
-            As[row * as + m] = n < N ? x[((size_t)n * Mel + m) * T + t] : 0.f;
-        }
-    } else {
-        const int hq = H >> 2;
-        for (int e = tid; e < TM * hq; e += THREADS) {
-            const int row = e / hq, j4 = (e - row * hq) * 4, n = n0 + row;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (n < N) v = *reinterpret_cast<const float4*>(hs + (((size_t)(k - 1) * layer_rows + (size_t)n * T + t) * H + j4));
-            *reinterpret_cast<float4*>(As + row * as + j4) = v;
-        }
-    }
-    {
-        const int hq = H >> 2;
-        for (int e = tid; e < TM * hq; e += THREADS) {
-            const int row = e / hq, j4 = (e - row * hq) * 4, n = n0 + row;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (n < N && t > 0) v = *reinterpret_cast<const float4*>(hs + (((size_t)k * layer_rows + (size_t)n * T + (t - 1)) * H + j4));
-            *reinterpret_cast<float4*>(As + row * as + in + j4) = v;
-        }
-    }
-    __syncthreads();
-
-    const float* img = images + image_offset(k, Mel, H) + (size_t)s * 64 + r * 4;
-    const float* aa = As + r * as + q;
-    v4f acc[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) acc[g] = v4f{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-    for (int k0 = 4 * wave; k0 < K; k0 += 4 * WAVES) {
-        const float4 w = *reinterpret_cast<const float4*>(img + (size_t)(k0 + q) * G);
-        const float a = aa[k0];
-        acc[0] = mfma4(a, w.x, acc[0]);
-        acc[1] = mfma4(a, w.y, acc[1]);
-        acc[2] = mfma4(a, w.z, acc[2]);
-        acc[3] = mfma4(a, w.w, acc[3]);
-    }
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) red[((wave * 4 + g) * TM + q * 4 + i) * TU + r] = acc[g][i];
-    __syncthreads();
-
-    const int row = tid >> 4, u = tid & 15, n = n0 + row;
-    if (n >= N) return;
-    const int j = s * TU + u;
-    const float4 b = *reinterpret_cast<const float4*>(biases + (size_t)k * G + s * 64 + u * 4);
-    float pre[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) pre[g] += red[((w * 4 + g) * TM + row) * TU + u];
-    const size_t cell = (size_t)k * layer_rows + (size_t)n * T + t;
-    const float c_prev = t > 0 ? cs[(cell - 1) * H + j] : 0.f;
-    const float gi = sigmoidf_(pre[0]), gf = sigmoidf_(pre[1]), gg = tanhf(pre[2]), go = sigmoidf_(pre[3]);
-    const float c = fmaf(gf, c_prev, gi * gg);             // (the contraction the compiler chooses for the inference cell's `f c + i g`, spelled out)
-    cs[cell * H + j] = c;
-    hs[cell * H + j] = go * tanhf(c);
-    *reinterpret_cast<float4*>(gates + cell * G + s * 64 + u * 4) = make_float4(gi, gf, gg, go);
-}
-
 // ---- e = W h_{T-1}^{top} + b: grid (N), dynamic LDS hl [H] ----------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(THREADS) void ge2e_head_fwd_kernel(const float* __restrict__ h_top, const float* __restrict__ w, const float* __restrict__ bias,
                                                                 float* __restrict__ e_out, int T, int H, int E)
 {
     extern __shared__ __attribute__((aligned(16))) float ge2e_smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const size_t n = blockIdx.x;
-    float* hl = ge2e_smem;
-    for (int j = tid; j < H; j += THREADS) hl[j] = h_top[(n * T + (T - 1)) * H + j];
-    __syncthreads();
-    for (int j = wave; j < E; j += WAVES) {
-        float p = 0.f;
-        for (int kk = lane; kk < H; kk += 64) p = fmaf(w[(size_t)j * H + kk], hl[kk], p);
-        p = wave_sum(p) + bias[j];
-        if (lane == 0) e_out[n * E + j] = p;
-    }
+    ge2e_head_project(h_top + (n * T + (T - 1)) * H, w, bias, ge2e_smem, H, E, [&](int j, float p) { e_out[n * E + j] = p; });
 }
 
 // ---- the loss.  Scratch (loss_work_floats): u [N][E] | sums [S][E] | dcent [S][E] | g [N][S] | cosv [N][S] | norm_c [S] | norm_x [N] | row_l [N] | row_dw [N]
@@ -583,19 +473,7 @@ extern "C" int glowtts_ge2e_train_forward(const float* x, const float* images, c
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t cells = (size_t)Stacks * N * T * H;
     float *hs = keep, *cs = keep + cells, *gates = keep + 2 * cells;
-    const int lds = cell_lds_bytes(Mel, H);
-    static int allowed = 0;
-    if (lds > allowed) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ge2e_cell_keep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-            return GLOWTTS_E_LAUNCH;
-        allowed = lds;
-    }
-    for (int dg = 0; dg < T + Stacks - 1; ++dg) {
-        const int kmin = dg - (T - 1) > 0 ? dg - (T - 1) : 0, kmax = dg < Stacks - 1 ? dg : Stacks - 1;
-        hipLaunchKernelGGL(ge2e_cell_keep_kernel, dim3(H / TU, (N + TM - 1) / TM, kmax - kmin + 1), dim3(THREADS), (size_t)lds, s, x, images, biases, hs, cs, gates, N,
-                           Mel, T, H, dg, kmin);
-        GLOWTTS_NOTE_STATIC("ge2e_cell");
-    }
+    if (ge2e_launch_cells<true>(x, images, biases, hs, cs, gates, N, Mel, T, H, Stacks, s) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;
     hipLaunchKernelGGL(ge2e_head_fwd_kernel, dim3(N), dim3(THREADS), (size_t)H * 4, s, hs + (size_t)(Stacks - 1) * N * T * H, head_w, head_b, e, T, H, E);
     GLOWTTS_NOTE_STATIC("ge2e_head_fwd");
     return launched() ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;

@@ -18,29 +18,17 @@
 //   pwg_head       skips sqrt(1 / Layers), ReLU, S x S 1x1 (MFMA), ReLU, S -> 1 as a fixed-order dot product; zeros beyond the utterance
 // Tiles start at the utterance's own sample 0 and every sum has one fixed order, so a row's value depends on its utterance alone: the waveform is
 // bit-identical alone, in any batch, at any padding and from run to run.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
+// The constants, the layer's row gather (step 1) and the head's first stage live in pwg_common.h, which the backward (pwg_train_ops.hip) shares.
 #include <algorithm>
 
-#include "../../include/glowtts_hip.h"
 #include "gauss_hash.h"
 #include "launch_log.h"
+#include "pwg_common.h"
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-constexpr int TM = 64;                                    // samples (rows) per workgroup: four 16-row MFMA tiles
-constexpr int THREADS = 256, WAVES = THREADS / 64;
-constexpr int MAX_LDS = 160 * 1024;
 constexpr int PF = 4;                                     // k steps of GEMM 1 whose weights are prefetched into registers
-constexpr int MAX_DILATION = 1024, MAX_SCALE = 16, MAX_SCALES = 8, MAX_CHANNELS = 256;
-
-__device__ __forceinline__ v4f mfma4(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
-
-__host__ __device__ __forceinline__ int xs_stride_of(int K) { return ((K >> 2) & 1) ? K : K + 4; }      // (stride / 4) odd: 16 rows x 4 k hit 64 distinct dwords mod 32 pairs
+constexpr int MAX_DILATION = 1024, MAX_SCALES = 8;
 
 // ---- conditioning ---------------------------------------------------------------------------------------------------------------------------
 // grid (ceil(Lmax / 64), B); a wave owns 16 frames and walks the column tiles.  w: [(2 ctx + 1) A][A], row = tap * A + input channel.
@@ -126,24 +114,11 @@ __global__ __launch_bounds__(THREADS) void pwg_layer_kernel(const float* __restr
     float* Xs = pwg_smem;
     float* Gs = pwg_smem + gs_off;
 
-    // 1. gather: 16 bytes per access, coalesced along the channels
-    const int kq = KA >> 2;
-    for (int e = tid; e < TM * kq; e += THREADS) {
-        const int row = e / kq, k4 = (e - row * kq) * 4, t = t0 + row;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (t < T) {
-            if (k4 < 3 * R) {
-                const int j = k4 / R, ci = k4 - j * R, ts = t + (j - 1) * d;
-                if (ts >= 0 && ts < T) v = *reinterpret_cast<const float4*>(x + (row0 + ts) * R + ci);
-            } else {
-                v = *reinterpret_cast<const float4*>(c + (row0 + t) * A + (k4 - 3 * R));
-            }
-        }
-        *reinterpret_cast<float4*>(Xs + row * xs + k4) = v;
-    }
+    // 1. gather
+    pwg_gather_rows(x, c, Xs, row0, t0, T, R, A, d, xs);
     __syncthreads();
 
-    // 2. GEMM 1 + gate
+    // 2. GEMM 1 + gate.  (pwg_layer_bwd_gate_kernel runs this sum without the prefetch; both start from the bias and take k ascending in steps of 4)
     const bool alias = gs_off == 0;                        // then R / 16 <= WAVES: at most one column pair per wave
     v4f gate[4];
     int pending = -1;
@@ -223,7 +198,7 @@ __global__ __launch_bounds__(THREADS) void pwg_layer_kernel(const float* __restr
                 const int t = t0 + rt * 16 + q * 4 + i;
                 if (t >= T) continue;
                 if (res) {
-                    xo[(row0 + t) * R + col] = (acc[rt][i] + x[(row0 + t) * R + col]) * 0.70710678118654752440f;
+                    xo[(row0 + t) * R + col] = (acc[rt][i] + x[(row0 + t) * R + col]) * RSQRT2;
                 } else {
                     float* sp = skips + (row0 + t) * S + (col - R);
                     *sp = accumulate ? *sp + acc[rt][i] : acc[rt][i];
@@ -249,29 +224,11 @@ __global__ __launch_bounds__(THREADS) void pwg_head_kernel(const float* __restri
     const int st = S + 4;
     float* Ys = pwg_smem;
     float* Hs = pwg_smem + TM * st;
-    const int kq = S >> 2;
-    for (int e = tid; e < TM * kq; e += THREADS) {
-        const int row = e / kq, k4 = (e - row * kq) * 4, t = t0 + row;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (t < T) {
-            v = *reinterpret_cast<const float4*>(skips + (row0 + t) * S + k4);
-            v.x = fmaxf(v.x * scale, 0.f); v.y = fmaxf(v.y * scale, 0.f); v.z = fmaxf(v.z * scale, 0.f); v.w = fmaxf(v.w * scale, 0.f);
-        }
-        *reinterpret_cast<float4*>(Ys + row * st + k4) = v;
-    }
-    __syncthreads();
+    pwg_head_stage(skips, Ys, row0, t0, T, S, scale, [](size_t, float4) {});
     for (int n = wave; n < S / 16; n += WAVES) {
         const int col = n * 16 + r;
-        const float bv = b1[col];
         v4f acc[4];
-#pragma unroll
-        for (int rt = 0; rt < 4; ++rt) acc[rt] = v4f{bv, bv, bv, bv};
-        const float* ya = Ys + r * st + q;
-        for (int k0 = 0; k0 < S; k0 += 4) {
-            const float wk = w1[(size_t)(k0 + q) * S + col];
-#pragma unroll
-            for (int rt = 0; rt < 4; ++rt) acc[rt] = mfma4(ya[rt * 16 * st + k0], wk, acc[rt]);
-        }
+        pwg_head_w1(Ys, w1, b1, S, col, acc);
 #pragma unroll
         for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
@@ -296,16 +253,6 @@ int layer_lds_bytes(int R, int A, int* xs, int* gs_off)
     if (xs) *xs = stride;
     if (gs_off) *gs_off = alias ? 0 : TM * stride;
     return (TM * stride + (alias ? 0 : TM * (R + 4))) * 4;
-}
-
-bool bad_batch(int B, int Lmax, int hop)
-{
-    return B < 1 || B > 65535 || Lmax < 1 || hop < 1 || hop > (1 << 16) || (int64_t)Lmax * hop > ((int64_t)1 << 30);
-}
-
-template <typename K> int allow_lds(K kernel, int bytes)
-{
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
 }
 
 }  // namespace
@@ -368,11 +315,7 @@ extern "C" int glowtts_pwg_layer(const float* x, const float* c, const float* w1
         return GLOWTTS_E_ARG;
     int xs, gs_off;
     const int lds = layer_lds_bytes(R, A, &xs, &gs_off);
-    static int allowed = 0;                                // (grows monotonically; a racing second caller sets the same or a larger value)
-    if (lds > allowed) {
-        if (allow_lds(&pwg_layer_kernel, lds) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;
-        allowed = lds;
-    }
+    if (allow_lds<&pwg_layer_kernel>(lds) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;
     const int Tmax = Lmax * hop;
     hipLaunchKernelGGL(pwg_layer_kernel, dim3((Tmax + TM - 1) / TM, B), dim3(THREADS), (size_t)lds, static_cast<hipStream_t>(stream), x, c, w1, b1, w2, b2, x_out, skips,
                        frame_lengths, Lmax, hop, R, S, A, dilation, accumulate, xs, gs_off);
@@ -385,11 +328,7 @@ extern "C" int glowtts_pwg_head(const float* skips, const int32_t* frame_lengths
 {
     if (!skips || !frame_lengths || !w1 || !b1 || !w2 || !b2 || !wav || bad_batch(B, Lmax, hop) || S < 16 || S > MAX_CHANNELS || S % 16) return GLOWTTS_E_ARG;
     const int lds = 2 * TM * (S + 4) * 4;
-    static int allowed = 0;
-    if (lds > allowed) {
-        if (allow_lds(&pwg_head_kernel, lds) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;
-        allowed = lds;
-    }
+    if (allow_lds<&pwg_head_kernel>(lds) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;
     const int Tmax = Lmax * hop;
     hipLaunchKernelGGL(pwg_head_kernel, dim3((Tmax + TM - 1) / TM, B), dim3(THREADS), (size_t)lds, static_cast<hipStream_t>(stream), skips, frame_lengths, w1, b1, w2, b2,
                        wav, Lmax, hop, S, scale);

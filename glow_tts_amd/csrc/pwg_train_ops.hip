@@ -2,12 +2,12 @@
 // points, so the waveform is bit-identical); it differs only in where it writes: every layer's input x gets its own slab [Layers + 1][B][Tmax][R] (the
 // ping-pong buffers do not survive 30 layers), the gate is recomputed here.  Rows are samples, channels-last, as in the forward; an utterance owns rows
 // [0, L hop) of its slab, tiles are counted from its own sample 0 and nothing beyond those rows is read or written.  Every matrix product runs on
-// v_mfma_f32_16x16x4_f32 (operand layout: see pwg_ops.hip).  No float atomics, no kernel waits on another workgroup, every sum has a fixed partition and
-// order: every gradient is bit-identical from run to run.
+// v_mfma_f32_16x16x4_f32 (operand layout: see pwg_ops.hip).  The layer's row gather and the head's first stage are the forward's own (pwg_common.h).
+// No float atomics, no kernel waits on another workgroup, every sum has a fixed partition and order: every gradient is bit-identical from run to run.
 //
 //   pwg_head_bwd        per 64-row tile: y = relu(scale skips), h' = W1 y + b1 (MFMA), dh = dwav w2 [h' > 0], dy = W1^T dh (MFMA), dskips = scale dy [y > 0];
 //                       y, h = relu(h'), dh go to HBM for the weight gradients.  dskips is the same tensor for every layer (skips is a plain sum).
-//   pwg_layer_bwd_gate  per 64-row tile of one layer: the forward's gather and GEMM 1 again (tanh / sigmoid halves stay in the accumulators), dgate =
+//   pwg_layer_bwd_gate  per 64-row tile of one layer: the forward's gather (pwg_common.h) and GEMM 1 again (tanh / sigmoid halves stay in the accumulators), dgate =
 //                       [sqrt(1/2) dx' | dskips] W2^T (K = R + S, MFMA, same column ownership), dpre = dgate (sigma (1 - tanh^2) | tanh sigma (1 - sigma));
 //                       gate [rows][R] and dpre [rows][G] go to HBM - the dilated taps reach across tiles, so dpre must exist before dx can be formed.
 //   pwg_layer_bwd_data  per 64-row tile: dx(t) = sqrt(1/2) dx'(t) + [dpre(t + d) | dpre(t) | dpre(t - d)] W1_taps^T (K = 3 G, zero outside the utterance,
@@ -20,29 +20,17 @@
 //   pwg_upsample_bwd    per scale, descending: the gradient of the coarser rows (gather form of repeat + FIR); `pwg_upsample_bwd_fir`: the FIR's gradient
 //                       as per-block float64 sums in a fixed order; `pwg_upsample_bwd_sum`: their ordered sum.
 //   pwg_cond_in_bwd     dW_in, one thread per weight over all frames in ascending order (float64 sum); the gradient of the mel is not computed.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include <algorithm>
 
-#include "../../include/glowtts_hip.h"
 #include "gauss_hash.h"
 #include "launch_log.h"
+#include "pwg_common.h"
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-constexpr int TM = 64, THREADS = 256, WAVES = THREADS / 64;
-constexpr int MAX_LDS = 160 * 1024, MAX_CHANNELS = 256, MAX_SCALE = 16;
 constexpr int WG_ROWS = 1024;                             // rows of one split of the weight-gradient partition
 constexpr int WG_MAX_JOBS = 8;
 constexpr int FIR_ROWS = 256;                             // output rows of one block of the FIR gradient
-constexpr float RSQRT2 = 0.70710678118654752440f;
-
-__device__ __forceinline__ v4f mfma4(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
-__host__ __device__ __forceinline__ int xs_stride_of(int K) { return ((K >> 2) & 1) ? K : K + 4; }
 
 // ---- head: grid (ceil(Tmax / 64), B), LDS Ys [64][S + 4] | DHs [64][S + 4].  w1 [S][S] row = input channel (the forward's image), w1t [S][S] row = output
 // channel (torch's own tensor) ----
@@ -60,30 +48,12 @@ __global__ __launch_bounds__(THREADS) void pwg_head_bwd_kernel(const float* __re
     const int st = S + 4;
     float* Ys = pwt_smem;
     float* DHs = pwt_smem + TM * st;
-    const int kq = S >> 2;
-    for (int e = tid; e < TM * kq; e += THREADS) {
-        const int row = e / kq, k4 = (e - row * kq) * 4, t = t0 + row;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (t < T) {
-            v = *reinterpret_cast<const float4*>(skips + (row0 + t) * S + k4);
-            v.x = fmaxf(v.x * scale, 0.f); v.y = fmaxf(v.y * scale, 0.f); v.z = fmaxf(v.z * scale, 0.f); v.w = fmaxf(v.w * scale, 0.f);
-            *reinterpret_cast<float4*>(y + (row0 + t) * S + k4) = v;
-        }
-        *reinterpret_cast<float4*>(Ys + row * st + k4) = v;
-    }
-    __syncthreads();
+    pwg_head_stage(skips, Ys, row0, t0, T, S, scale, [&](size_t off, float4 v) { *reinterpret_cast<float4*>(y + off) = v; });
     for (int n = wave; n < S / 16; n += WAVES) {
         const int col = n * 16 + r;
-        const float bv = b1[col], w2v = w2[col];
+        const float w2v = w2[col];
         v4f acc[4];
-#pragma unroll
-        for (int rt = 0; rt < 4; ++rt) acc[rt] = v4f{bv, bv, bv, bv};
-        const float* ya = Ys + r * st + q;
-        for (int k0 = 0; k0 < S; k0 += 4) {
-            const float wk = w1[(size_t)(k0 + q) * S + col];
-#pragma unroll
-            for (int rt = 0; rt < 4; ++rt) acc[rt] = mfma4(ya[rt * 16 * st + k0], wk, acc[rt]);
-        }
+        pwg_head_w1(Ys, w1, b1, S, col, acc);
 #pragma unroll
         for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
@@ -135,20 +105,7 @@ __global__ __launch_bounds__(THREADS) void pwg_layer_bwd_gate_kernel(const float
     const size_t row0 = (size_t)b * Lmax * hop;
     float* Xs = pwt_smem;
     float* Dy = pwt_smem + TM * xs;
-    const int kq = KA >> 2;
-    for (int e = tid; e < TM * kq; e += THREADS) {         // the forward's gather
-        const int row = e / kq, k4 = (e - row * kq) * 4, t = t0 + row;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (t < T) {
-            if (k4 < 3 * R) {
-                const int j = k4 / R, ci = k4 - j * R, ts = t + (j - 1) * d;
-                if (ts >= 0 && ts < T) v = *reinterpret_cast<const float4*>(x + (row0 + ts) * R + ci);
-            } else {
-                v = *reinterpret_cast<const float4*>(c + (row0 + t) * A + (k4 - 3 * R));
-            }
-        }
-        *reinterpret_cast<float4*>(Xs + row * xs + k4) = v;
-    }
+    pwg_gather_rows(x, c, Xs, row0, t0, T, R, A, d, xs);
     const int nq = N2 >> 2;
     for (int e = tid; e < TM * nq; e += THREADS) {         // [sqrt(1/2) dx' | dskips]
         const int row = e / nq, k4 = (e - row * nq) * 4, t = t0 + row;
@@ -172,6 +129,7 @@ __global__ __launch_bounds__(THREADS) void pwg_layer_bwd_gate_kernel(const float
 #pragma unroll
         for (int rt = 0; rt < 4; ++rt) { at[rt] = v4f{bt, bt, bt, bt}; as[rt] = v4f{bs, bs, bs, bs}; dg[rt] = v4f{0.f, 0.f, 0.f, 0.f}; }
         const float* xa = Xs + r * xs + q;
+        // (pwg_layer_kernel runs this sum with a weight prefetch; both start from the bias and take k ascending in steps of 4)
         for (int k0 = 0; k0 < KA; k0 += 4) {
             const float wtk = wt[(size_t)(k0 + q) * G], wsk = wt[(size_t)(k0 + q) * G + R];
 #pragma unroll
@@ -412,21 +370,11 @@ __global__ __launch_bounds__(THREADS) void pwg_cond_in_bwd_kernel(const float* _
 }
 
 // ---- host side ----
-bool bad_batch(int B, int Lmax, int hop)
-{
-    return B < 1 || B > 65535 || Lmax < 1 || hop < 1 || hop > (1 << 16) || (int64_t)Lmax * hop > ((int64_t)1 << 30) ||
-           (int64_t)B * ((Lmax * (int64_t)hop + WG_ROWS - 1) / WG_ROWS) > 65535;
-}
+// the forward's limits, and the weight gradient's splits fit one grid dimension
+bool bad_train_batch(int B, int Lmax, int hop) { return bad_batch(B, Lmax, hop) || (int64_t)B * ((Lmax * (int64_t)hop + WG_ROWS - 1) / WG_ROWS) > 65535; }
 int gate_lds(int R, int S, int A) { return TM * (xs_stride_of(3 * R + A) + R + S + 4) * 4; }
 int data_lds(int R) { return TM * (6 * R + 4) * 4; }
 int head_lds(int S) { return 2 * TM * (S + 4) * 4; }
-
-// (the callers remember the largest size they allowed in a process-wide static, as pwg_ops.hip does: one device per process is assumed, and a racing second
-// caller sets the same or a larger value)
-template <typename K> int allow_lds(K kernel, int bytes)
-{
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
-}
 
 int tiles16(int n) { return (n + 15) / 16; }
 
@@ -469,7 +417,7 @@ extern "C" int glowtts_pwg_train_supported(int R, int S, int A, int max_dilation
 
 extern "C" int64_t glowtts_pwg_train_work_floats(int B, int Lmax, int hop, int R, int S, int A)
 {
-    if (bad_batch(B, Lmax, hop) || R < 1 || S < 1 || A < 1) return 0;
+    if (bad_train_batch(B, Lmax, hop) || R < 1 || S < 1 || A < 1) return 0;
     const int64_t T = (int64_t)Lmax * hop, splits = B * ((T + WG_ROWS - 1) / WG_ROWS);
     const int64_t head = 256 * ((int64_t)tiles16(S + 1) * tiles16(S) + (int64_t)tiles16(S + 1)), first = 256 * (int64_t)tiles16(R);
     const int64_t wg = splits * std::max(layer_elems(R, S, A), std::max(head, first));
@@ -480,15 +428,11 @@ extern "C" int64_t glowtts_pwg_train_work_floats(int B, int Lmax, int hop, int R
 extern "C" int glowtts_pwg_train_head_bwd(const float* skips, const int32_t* frame_lengths, const float* w1, const float* w1t, const float* b1, const float* w2,
                                           const float* dwav, float* y, float* h, float* dh, float* dskips, int B, int Lmax, int hop, int S, float scale, void* stream)
 {
-    if (!skips || !frame_lengths || !w1 || !w1t || !b1 || !w2 || !dwav || !y || !h || !dh || !dskips || bad_batch(B, Lmax, hop) || S < 16 || S > MAX_CHANNELS || S % 16 ||
+    if (!skips || !frame_lengths || !w1 || !w1t || !b1 || !w2 || !dwav || !y || !h || !dh || !dskips || bad_train_batch(B, Lmax, hop) || S < 16 || S > MAX_CHANNELS || S % 16 ||
         head_lds(S) > MAX_LDS)
         return GLOWTTS_E_ARG;
     const int lds = head_lds(S);
-    static int allowed = 0;
-    if (lds > allowed) {
-        if (allow_lds(&pwg_head_bwd_kernel, lds) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;
-        allowed = lds;
-    }
+    if (allow_lds<&pwg_head_bwd_kernel>(lds) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;
     GLOWTTS_NOTE_STATIC("pwg_head_bwd");
     hipLaunchKernelGGL(pwg_head_bwd_kernel, dim3((Lmax * hop + TM - 1) / TM, B), dim3(THREADS), (size_t)lds, static_cast<hipStream_t>(stream), skips, frame_lengths, w1,
                        w1t, b1, w2, dwav, y, h, dh, dskips, Lmax, hop, S, scale);
@@ -498,7 +442,7 @@ extern "C" int glowtts_pwg_train_head_bwd(const float* skips, const int32_t* fra
 extern "C" int glowtts_pwg_train_head_wgrad(const float* y, const float* h, const float* dh, const float* dwav, const int32_t* frame_lengths, float* work, float* dw1,
                                             float* db1, float* dw2, float* db2, int B, int Lmax, int hop, int S, void* stream)
 {
-    if (!y || !h || !dh || !dwav || !frame_lengths || !work || !dw1 || !db1 || !dw2 || !db2 || bad_batch(B, Lmax, hop) || S < 16 || S > MAX_CHANNELS || S % 16)
+    if (!y || !h || !dh || !dwav || !frame_lengths || !work || !dw1 || !db1 || !dw2 || !db2 || bad_train_batch(B, Lmax, hop) || S < 16 || S > MAX_CHANNELS || S % 16)
         return GLOWTTS_E_ARG;
     wg_args a = {};
     add_job(a, y, S, S, 0, dh, S, S, dw1, 1, S, db1, 1.f);                  // last_conv_layers.1.weight [out][in]
@@ -510,19 +454,11 @@ extern "C" int glowtts_pwg_train_layer_bwd(const float* x, const float* c, const
                                            const float* dxp, const float* dskips, float* gate, float* dpre, float* dx, float* dc, const int32_t* frame_lengths, int B,
                                            int Lmax, int hop, int R, int S, int A, int dilation, int first, void* stream)
 {
-    if (!x || !c || !w1 || !b1 || !w2t || !w1t || !wauxt || !dxp || !dskips || !gate || !dpre || !dx || !dc || !frame_lengths || bad_batch(B, Lmax, hop) ||
+    if (!x || !c || !w1 || !b1 || !w2t || !w1t || !wauxt || !dxp || !dskips || !gate || !dpre || !dx || !dc || !frame_lengths || bad_train_batch(B, Lmax, hop) ||
         !glowtts_pwg_train_supported(R, S, A, dilation))
         return GLOWTTS_E_ARG;
     const int lds1 = gate_lds(R, S, A), lds2 = data_lds(R);
-    static int allowed1 = 0, allowed2 = 0;
-    if (lds1 > allowed1) {
-        if (allow_lds(&pwg_layer_bwd_gate_kernel, lds1) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;
-        allowed1 = lds1;
-    }
-    if (lds2 > allowed2) {
-        if (allow_lds(&pwg_layer_bwd_data_kernel, lds2) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;
-        allowed2 = lds2;
-    }
+    if (allow_lds<&pwg_layer_bwd_gate_kernel>(lds1) != GLOWTTS_OK || allow_lds<&pwg_layer_bwd_data_kernel>(lds2) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;
     const dim3 grid((Lmax * hop + TM - 1) / TM, B);
     hipStream_t s = static_cast<hipStream_t>(stream);
     GLOWTTS_NOTE_STATIC("pwg_layer_bwd_gate");
@@ -538,7 +474,7 @@ extern "C" int glowtts_pwg_train_layer_wgrad(const float* x, const float* c, con
                                              float* dskip_w, float* dskip_b, int B, int Lmax, int hop, int R, int S, int A, int dilation, void* stream)
 {
     if (!x || !c || !gate || !dpre || !dxp || !dskips || !frame_lengths || !work || !dconv_w || !dconv_b || !daux_w || !dout_w || !dout_b || !dskip_w || !dskip_b ||
-        bad_batch(B, Lmax, hop) || !glowtts_pwg_train_supported(R, S, A, dilation))
+        bad_train_batch(B, Lmax, hop) || !glowtts_pwg_train_supported(R, S, A, dilation))
         return GLOWTTS_E_ARG;
     const int G = 2 * R;
     wg_args a = {};
@@ -553,7 +489,7 @@ extern "C" int glowtts_pwg_train_layer_wgrad(const float* x, const float* c, con
 extern "C" int glowtts_pwg_train_first_bwd(const float* noises, const uint32_t* seeds, const float* dx0, const int32_t* frame_lengths, float* work, float* dw, float* db,
                                            int B, int Lmax, int hop, int R, void* stream)
 {
-    if ((!noises) == (!seeds) || !dx0 || !frame_lengths || !work || !dw || !db || bad_batch(B, Lmax, hop) || R < 16 || R > MAX_CHANNELS || R % 16) return GLOWTTS_E_ARG;
+    if ((!noises) == (!seeds) || !dx0 || !frame_lengths || !work || !dw || !db || bad_train_batch(B, Lmax, hop) || R < 16 || R > MAX_CHANNELS || R % 16) return GLOWTTS_E_ARG;
     wg_args a = {};
     a.seeds = seeds; a.noise = noises;
     add_job(a, nullptr, 1, 1, 0, dx0, R, R, dw, 0, 1, db, 1.f);              // first_conv.weight [R][1][1]

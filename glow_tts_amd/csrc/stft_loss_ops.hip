@@ -20,6 +20,8 @@
 //                     taken at the sample's own position and at the at most two padded positions that reflect onto it (left edge first).
 // No atomics, no workgroup waits on another: every value is bit-identical from run to run.  LDS per workgroup at n_fft = 2048, win 1200: 8 KiB twiddles +
 // 8.3 KiB spectrum + 4.7 KiB window + 6 KiB reduction tree = 27 KiB.
+// The LDS layout, the frame packer, the split and its inverse and the frame unpack are vocoder_fft.h's, shared with vocoder_ops.hip and frontend_ops.hip; this
+// file keeps the magnitudes with their float64 sums, the gradient per bin and the fold.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/glowtts_hip.h"
@@ -64,14 +66,11 @@ __global__ __launch_bounds__(VOC_NT) void stft_loss_fwd_kernel(const sl_args a)
     extern __shared__ __attribute__((aligned(16))) unsigned char sl_smem[];
     __shared__ double red[3][VOC_NT];
     const int N = 1 << a.logN, M = N >> 1, logM = a.logN - 1, F = M + 1;
-    float2* const tw = reinterpret_cast<float2*>(sl_smem);                     // [M]
-    float2* const X = tw + M;                                                  // [voc_pad(M) + 1]
-    float* const wnd = reinterpret_cast<float*>(X + voc_pad(M) + 1);           // [win]
     const int tid = threadIdx.x;
     const int lpad = (N - a.win) >> 1;
-    for (int i = tid; i < M; i += VOC_NT) tw[i] = a.twiddle[i];
-    for (int i = tid; i < a.win; i += VOC_NT) wnd[i] = a.window[i];
-    __syncthreads();
+    const voc_lds lds = voc_lds_stage(sl_smem, a.twiddle, a.window, M, a.win);
+    float2* const X = lds.X;
+    const float2* const tw = lds.tw;
     const int total = a.B * a.NF;
     for (int f = blockIdx.x; f < total; f += gridDim.x) {
         const int b = f / a.NF, t = f - b * a.NF;
@@ -82,17 +81,7 @@ __global__ __launch_bounds__(VOC_NT) void stft_loss_fwd_kernel(const sl_args a)
 #pragma unroll 1
         for (int pass = 0; pass < 2; ++pass) {
             const float* xb = (pass ? a.pred : a.target) + (int64_t)b * a.T;
-            for (int m = tid; m < M; m += VOC_NT) {
-                float v[2];
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const int n = 2 * m + e, j = n - lpad;
-                    v[e] = 0.f;
-                    if (j >= 0 && j < a.win) v[e] = xb[voc_reflect(t * a.hop + n - M, a.T)] * wnd[j];
-                }
-                X[voc_pad((int)(__brev((unsigned)m) >> (32 - logM)))] = make_float2(v[0], v[1]);
-            }
-            __syncthreads();
+            voc_pack_frame(lds, M, logM, lpad, a.win, t * a.hop - M, a.T, [&](int s) { return xb[s]; });
             voc_fft<false>(X, tw, logM, a.logN, tid);
             // one bin: the target's magnitude goes out; the prediction's is set beside the target's, which this very thread wrote in pass 0
             auto bin = [&](int k, float2 y) {
@@ -112,17 +101,10 @@ __global__ __launch_bounds__(VOC_NT) void stft_loss_fwd_kernel(const sl_args a)
                     bin(M, make_float2(z.x - z.y, 0.f));
                     continue;
                 }
-                const float2 w = tw[k];
-                const float2 za = X[voc_pad(k)], zb = X[voc_pad(M - k)];
-                const float2 e = make_float2(0.5f * (za.x + zb.x), 0.5f * (za.y - zb.y));              // (Z[k] + conj Z[M-k]) / 2
-                const float2 d = make_float2(0.5f * (za.x - zb.x), 0.5f * (za.y + zb.y));              // (Z[k] - conj Z[M-k]) / 2
-                const float2 wo = voc_mul(make_float2(d.y, -d.x), w);                                  // W^k O,  O = d / i
-                bin(k, voc_add(e, wo));
-                if (M - k != k) {
-                    float2 ymk = voc_sub(e, wo);
-                    ymk.y = -ymk.y;                                                                    // Y[M-k] = conj(E - W^k O)
-                    bin(M - k, ymk);
-                }
+                float2 yk, ymk;
+                voc_split_pair(X, tw, k, M, yk, ymk);
+                bin(k, yk);
+                if (M - k != k) bin(M - k, ymk);
             }
             __syncthreads();                                                   // the spectrum is read: the next gather may overwrite it
         }
@@ -163,14 +145,11 @@ __global__ __launch_bounds__(VOC_NT) void stft_loss_bwd_frames_kernel(const sl_a
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char sl_smem[];
     const int N = 1 << a.logN, M = N >> 1, logM = a.logN - 1, F = M + 1;
-    float2* const tw = reinterpret_cast<float2*>(sl_smem);
-    float2* const X = tw + M;
-    float* const wnd = reinterpret_cast<float*>(X + voc_pad(M) + 1);
     const int tid = threadIdx.x;
     const int lpad = (N - a.win) >> 1;
-    for (int i = tid; i < M; i += VOC_NT) tw[i] = a.twiddle[i];
-    for (int i = tid; i < a.win; i += VOC_NT) wnd[i] = a.window[i];
-    __syncthreads();
+    const voc_lds lds = voc_lds_stage(sl_smem, a.twiddle, a.window, M, a.win);
+    float2* const X = lds.X;
+    const float2* const tw = lds.tw;
     const int total = a.B * a.NF;
     const float g = a.grad_out[0] * a.weight, coef = a.terms[2], inv_n = (float)(1.0 / ((double)total * (double)F));
     for (int f = blockIdx.x; f < total; f += gridDim.x) {
@@ -192,23 +171,12 @@ __global__ __launch_bounds__(VOC_NT) void stft_loss_bwd_frames_kernel(const sl_a
                 X[0] = make_float2(g0 + gm, g0 - gm);
                 continue;
             }
-            const int ik = voc_pad(k), imk = voc_pad(M - k);
-            const float2 w = tw[k];
-            const float2 yk = grad(k), ymk = grad(M - k);
-            const float2 e = make_float2(0.5f * (yk.x + ymk.x), 0.5f * (yk.y - ymk.y));
-            const float2 o = voc_mulc(make_float2(0.5f * (yk.x - ymk.x), 0.5f * (yk.y + ymk.y)), w);
-            X[ik] = make_float2(e.x - o.y, e.y + o.x);                                                 // Z[k] = E + i O
-            X[imk] = make_float2(e.x + o.y, o.x - e.y);                                                // Z[M-k] = conj(E - i O)
+            voc_unsplit_pair(X, tw, k, M, grad(k), grad(M - k));
         }
         __syncthreads();
         voc_fft<true>(X, tw, logM, a.logN, tid);
         float* fr = a.dframes + (int64_t)f * a.win;
-        for (int j = tid; j < a.win; j += VOC_NT) {
-            const int n = lpad + j;
-            const float2 z = X[voc_pad((int)(__brev((unsigned)(n >> 1)) >> (32 - logM)))];
-            fr[j] = ((n & 1) ? z.y : z.x) * wnd[j];
-        }
-        __syncthreads();
+        voc_unpack_frame(X, logM, lpad, a.win, [&](int j, float y) { fr[j] = y * lds.wnd[j]; });
     }
 }
 
@@ -238,8 +206,6 @@ __global__ __launch_bounds__(256) void stft_loss_bwd_fold_kernel(const float* __
     *out = accumulate ? *out + r : r;
 }
 
-int sl_log2(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
-size_t sl_lds_bytes(int n_fft, int win) { const int M = n_fft / 2; return (size_t)(M + M + (M >> 5) + 1) * 8 + (size_t)win * 4; }
 int sl_grid(int frames) { return frames < 1280 ? frames : 1280; }              // 5 resident workgroups (by LDS at n_fft = 2048) on each of 256 CUs; more frames: strided
 bool sl_bad_dims(int B, int T, int n_fft, int win, int hop)
 {
@@ -251,8 +217,7 @@ bool sl_bad_dims(int B, int T, int n_fft, int win, int hop)
 
 extern "C" int glowtts_stft_loss_supported(int n_fft, int win_length, int hop, int T)
 {
-    return n_fft >= 256 && n_fft <= 4096 && (n_fft & (n_fft - 1)) == 0 && win_length >= 1 && win_length <= n_fft && hop >= 1 && hop <= win_length && T > n_fft / 2 &&
-           T <= (1 << 29);
+    return voc_fft_supported(n_fft, win_length) && hop >= 1 && hop <= win_length && T > n_fft / 2 && T <= (1 << 29);
 }
 
 extern "C" int64_t glowtts_stft_loss_keep_floats(int B, int T, int n_fft, int hop)
@@ -278,9 +243,9 @@ extern "C" int glowtts_stft_loss_forward(const float* pred, const float* target,
     sl_args a = {};
     a.pred = pred; a.target = target; a.window = window; a.twiddle = reinterpret_cast<const float2*>(twiddle);
     a.spec = keep; a.mag_x = keep + frames * F * 2; a.mag_y = keep + frames * F * 3; a.partial = reinterpret_cast<double*>(work);
-    a.weight = weight; a.B = B; a.T = T; a.NF = NF; a.logN = sl_log2(n_fft); a.win = win_length; a.hop = hop;
+    a.weight = weight; a.B = B; a.T = T; a.NF = NF; a.logN = voc_log2(n_fft); a.win = win_length; a.hop = hop;
     GLOWTTS_NOTE_STATIC("stft_loss_fwd");
-    hipLaunchKernelGGL(stft_loss_fwd_kernel, dim3(sl_grid((int)frames)), dim3(VOC_NT), sl_lds_bytes(n_fft, win_length), static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(stft_loss_fwd_kernel, dim3(sl_grid((int)frames)), dim3(VOC_NT), voc_lds_bytes(n_fft, win_length, 0), static_cast<hipStream_t>(stream), a);
     if (hipGetLastError() != hipSuccess) return GLOWTTS_E_LAUNCH;
     GLOWTTS_NOTE_STATIC("stft_loss_reduce");
     hipLaunchKernelGGL(stft_loss_reduce_kernel, dim3(1), dim3(VOC_NT), 0, static_cast<hipStream_t>(stream), a.partial, terms, loss, (int)frames, F, weight, accumulate);
@@ -299,9 +264,9 @@ extern "C" int glowtts_stft_loss_backward(const float* keep, const float* terms,
     a.window = window; a.twiddle = reinterpret_cast<const float2*>(twiddle);
     a.spec = const_cast<float*>(keep); a.mag_x = a.spec + frames * F * 2; a.mag_y = a.spec + frames * F * 3;
     a.terms = terms; a.grad_out = grad_out; a.dframes = work + frames * 6;
-    a.weight = weight; a.B = B; a.T = T; a.NF = NF; a.logN = sl_log2(n_fft); a.win = win_length; a.hop = hop;
+    a.weight = weight; a.B = B; a.T = T; a.NF = NF; a.logN = voc_log2(n_fft); a.win = win_length; a.hop = hop;
     GLOWTTS_NOTE_STATIC("stft_loss_bwd_frames");
-    hipLaunchKernelGGL(stft_loss_bwd_frames_kernel, dim3(sl_grid((int)frames)), dim3(VOC_NT), sl_lds_bytes(n_fft, win_length), static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(stft_loss_bwd_frames_kernel, dim3(sl_grid((int)frames)), dim3(VOC_NT), voc_lds_bytes(n_fft, win_length, 0), static_cast<hipStream_t>(stream), a);
     if (hipGetLastError() != hipSuccess) return GLOWTTS_E_LAUNCH;
     GLOWTTS_NOTE_STATIC("stft_loss_bwd_fold");
     hipLaunchKernelGGL(stft_loss_bwd_fold_kernel, dim3((T + 255) / 256, B), dim3(256), 0, static_cast<hipStream_t>(stream), a.dframes, dpred, T, NF, n_fft, win_length, hop,

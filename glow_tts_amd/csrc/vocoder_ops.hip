@@ -22,6 +22,8 @@
 // Lengths: an utterance whose length exceeds what the signal buffer holds (wav_lengths[b] > ldx, or hop (frame_lengths[b] - 1) > ldx) is a caller error that
 // the host cannot see without a synchronisation; the kernels never read beyond ldx, so such an utterance comes out as zeros (STFT) or is left unwritten
 // (inverse STFT, step).  vocoder.GriffinLim derives lengths and buffers from the same shapes, so the product path cannot reach this.
+// The LDS layout, the frame packer, the split and its inverse, the frame unpack and the FFT itself are vocoder_fft.h's, shared with frontend_ops.hip and
+// stft_loss_ops.hip; this file keeps the projection, the MODE template, the overlap-add and the mel inversion.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/glowtts_hip.h"
@@ -57,14 +59,11 @@ __global__ __launch_bounds__(VOC_NT) void vocoder_frame_kernel(const voc_args a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char voc_smem[];
     const int N = 1 << a.logN, M = N >> 1, logM = a.logN - 1, F = M + 1;
-    float2* const tw = reinterpret_cast<float2*>(voc_smem);                    // [M]
-    float2* const X = tw + M;                                                  // [voc_pad(M) + 1]
-    float* const wnd = reinterpret_cast<float*>(X + voc_pad(M) + 1);           // [win]
     const int tid = threadIdx.x;
     const int lpad = (N - a.win) >> 1;
-    for (int i = tid; i < M; i += VOC_NT) tw[i] = a.twiddle[i];
-    for (int i = tid; i < a.win; i += VOC_NT) wnd[i] = a.window[i];
-    __syncthreads();
+    const voc_lds lds = voc_lds_stage(voc_smem, a.twiddle, a.window, M, a.win);
+    float2* const X = lds.X;
+    const float2* const tw = lds.tw;
     const int total = a.B * a.T;
     for (int f = blockIdx.x; f < total; f += gridDim.x) {
         const int b = f / a.T, t = f - b * a.T;
@@ -79,25 +78,12 @@ __global__ __launch_bounds__(VOC_NT) void vocoder_frame_kernel(const voc_args a)
         }
         if (MODE != MODE_STFT && (t >= Tb || L < 1 || L > a.ldx)) continue;   // (uniform over the workgroup)
         if (MODE != MODE_ISTFT) {
-            // ---- gather + window + pack, bit-reversed ----
             const float* xb = a.x + (int64_t)b * a.ldx;
             const float* xpb = MODE == MODE_STEP ? a.xp + (int64_t)b * a.ldx : nullptr;
-            for (int m = tid; m < M; m += VOC_NT) {
-                float v[2];
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const int n = 2 * m + e, j = n - lpad;
-                    v[e] = 0.f;
-                    if (j >= 0 && j < a.win) {
-                        const int s = voc_reflect(t * a.hop + n - M, L);
-                        float y = xb[s];
-                        if (MODE == MODE_STEP) y = y + a.alpha * (y - xpb[s]);
-                        v[e] = y * wnd[j];
-                    }
-                }
-                X[voc_pad((int)(__brev((unsigned)m) >> (32 - logM)))] = make_float2(v[0], v[1]);
-            }
-            __syncthreads();
+            voc_pack_frame(lds, M, logM, lpad, a.win, t * a.hop - M, L, [&](int s) {
+                const float y = xb[s];
+                return MODE == MODE_STEP ? y + a.alpha * (y - xpb[s]) : y;
+            });
             voc_fft<false>(X, tw, logM, a.logN, tid);
         }
         // ---- split (real-input spectrum from the packed one), projection, inverse split: bin pairs (k, M - k) ----
@@ -119,27 +105,16 @@ __global__ __launch_bounds__(VOC_NT) void vocoder_frame_kernel(const voc_args a)
                     X[0] = make_float2(0.5f * (y0 + ym), 0.5f * (y0 - ym));
                     continue;
                 }
-                const int ik = voc_pad(k), imk = voc_pad(M - k);
-                const float2 w = tw[k];
                 float2 yk, ymk;
                 if (MODE == MODE_ISTFT) {
                     yk = make_float2(sp[2 * k], sp[2 * k + 1]);
                     ymk = make_float2(sp[2 * (M - k)], sp[2 * (M - k) + 1]);
                 } else {
-                    const float2 za = X[ik], zb = X[imk];
-                    const float2 e = make_float2(0.5f * (za.x + zb.x), 0.5f * (za.y - zb.y));          // (Z[k] + conj Z[M-k]) / 2
-                    const float2 d = make_float2(0.5f * (za.x - zb.x), 0.5f * (za.y + zb.y));          // (Z[k] - conj Z[M-k]) / 2
-                    const float2 wo = voc_mul(make_float2(d.y, -d.x), w);                              // W^k O,  O = d / i
-                    yk = voc_add(e, wo);
-                    ymk = voc_sub(e, wo);
-                    ymk.y = -ymk.y;                                                                    // Y[M-k] = conj(E - W^k O)
+                    voc_split_pair(X, tw, k, M, yk, ymk);
                 }
                 if (MODE == MODE_STFT) { out[k] = yk; out[M - k] = ymk; continue; }
                 if (MODE == MODE_STEP) { yk = voc_project(yk, mg[k]); ymk = voc_project(ymk, mg[M - k]); }
-                const float2 e = make_float2(0.5f * (yk.x + ymk.x), 0.5f * (yk.y - ymk.y));
-                const float2 o = voc_mulc(make_float2(0.5f * (yk.x - ymk.x), 0.5f * (yk.y + ymk.y)), w);
-                X[ik] = make_float2(e.x - o.y, e.y + o.x);                                             // Z[k] = E + i O
-                X[imk] = make_float2(e.x + o.y, o.x - e.y);                                            // Z[M-k] = conj(E - i O)
+                voc_unsplit_pair(X, tw, k, M, yk, ymk);
             }
             __syncthreads();
         }
@@ -148,12 +123,7 @@ __global__ __launch_bounds__(VOC_NT) void vocoder_frame_kernel(const voc_args a)
             // ---- the samples under the window, windowed again: this frame's overlap-add contribution ----
             float* fr = a.frames + (int64_t)f * a.win;
             const float scale = 1.f / (float)M;
-            for (int j = tid; j < a.win; j += VOC_NT) {
-                const int n = lpad + j;
-                const float2 z = X[voc_pad((int)(__brev((unsigned)(n >> 1)) >> (32 - logM)))];
-                fr[j] = ((n & 1) ? z.y : z.x) * scale * wnd[j];
-            }
-            __syncthreads();
+            voc_unpack_frame(X, logM, lpad, a.win, [&](int j, float y) { fr[j] = y * scale * lds.wnd[j]; });
         }
     }
 }
@@ -225,14 +195,12 @@ __global__ __launch_bounds__(256) void vocoder_mel_to_linear_kernel(const float*
     }
 }
 
-int voc_log2(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
-size_t voc_lds_bytes(int n_fft, int win) { const int M = n_fft / 2; return (size_t)(M + M + (M >> 5) + 1) * 8 + (size_t)win * 4; }
 int voc_grid(int frames) { return frames < 1792 ? frames : 1792; }             // 7 resident workgroups (by LDS at n_fft = 2048) on each of 256 CUs: one wave; more frames: strided
 
 template <int MODE>
 int voc_launch(const voc_args& a, int n_fft, void* stream)
 {
-    hipLaunchKernelGGL(vocoder_frame_kernel<MODE>, dim3(voc_grid(a.B * a.T)), dim3(VOC_NT), voc_lds_bytes(n_fft, a.win), static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(vocoder_frame_kernel<MODE>, dim3(voc_grid(a.B * a.T)), dim3(VOC_NT), voc_lds_bytes(n_fft, a.win, 0), static_cast<hipStream_t>(stream), a);
     return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
 }
 int voc_ola(const float* frames, const int32_t* lengths, const float* window, float* wav, int B, int T, int ldx, int n_fft, int win, int hop, void* stream)
@@ -249,7 +217,7 @@ bool voc_bad_dims(int B, int T, int ldx, int n_fft, int win, int hop)
 
 extern "C" int glowtts_vocoder_supported(int n_fft, int win_length, int hop)
 {
-    return n_fft >= 256 && n_fft <= 4096 && (n_fft & (n_fft - 1)) == 0 && win_length >= 1 && win_length <= n_fft && hop >= 1 && win_length % hop == 0;
+    return voc_fft_supported(n_fft, win_length) && hop >= 1 && win_length % hop == 0;
 }
 
 extern "C" int glowtts_mel_to_linear_f32(const float* mels, const int32_t* frame_lengths, const float* basis, float* mag, int B, int Mel, int T, int F, float max_abs,
