@@ -295,4 +295,14 @@ SIGNATURES = {
     "glowtts_stft_loss_work_floats": (L, [I] * 4),
     "glowtts_stft_loss_forward": (I, [P] * 8 + [I] * 5 + [F, I, P]),
     "glowtts_stft_loss_backward": (I, [P] * 7 + [I] * 5 + [F, I, P]),
+    "glowtts_pwg_disc_supported": (I, [I] * 3),
+    "glowtts_pwg_disc_work_floats": (L, [I] * 3),
+    "glowtts_pwg_disc_first": (I, [P] * 4 + [I] * 3 + [F, P]),
+    "glowtts_pwg_disc_layer": (I, [P] * 4 + [I] * 4 + [F, P]),
+    "glowtts_pwg_disc_last": (I, [P] * 4 + [I] * 3 + [P]),
+    "glowtts_pwg_disc_mse": (I, [P] * 4 + [L] * 2 + [F] * 3 + [P]),
+    "glowtts_pwg_disc_last_bwd": (I, [P] * 3 + [I] * 3 + [P]),
+    "glowtts_pwg_disc_layer_bwd": (I, [P] * 5 + [I] * 4 + [F, P]),
+    "glowtts_pwg_disc_first_bwd": (I, [P] * 5 + [I] * 3 + [F, P]),
+    "glowtts_pwg_disc_wgrad": (I, [P] * 6 + [I] * 5 + [P]),
 }

@@ -39,6 +39,19 @@ template <auto Kernel> int allow_lds(int bytes)
     return GLOWTTS_OK;
 }
 
+// The sum of `v` over the workgroup's 256 threads in a fixed tree order (red: 256 doubles of LDS); every thread gets it.
+__device__ __forceinline__ double block_sum(double v, double* red, int tid)
+{
+    __syncthreads();
+    red[tid] = v;
+    __syncthreads();
+    for (int h = THREADS >> 1; h > 0; h >>= 1) {
+        if (tid < h) red[tid] += red[tid + h];
+        __syncthreads();
+    }
+    return red[0];
+}
+
 // The layer's rows: [x(t - d) | x(t) | x(t + d) | c(t)] of samples t0 .. t0 + 63 of the utterance whose slab starts at row0 and holds T samples, zero outside
 // it, into Xs [64][xs]; K = 3 R + A floats per row, 16 bytes per access, coalesced along the channels.  No barrier.
 __device__ __forceinline__ void pwg_gather_rows(const float* __restrict__ x, const float* __restrict__ c, float* Xs, size_t row0, int t0, int T, int R, int A, int d,

@@ -12,7 +12,7 @@
 //                       gate [rows][R] and dpre [rows][G] go to HBM - the dilated taps reach across tiles, so dpre must exist before dx can be formed.
 //   pwg_layer_bwd_data  per 64-row tile: dx(t) = sqrt(1/2) dx'(t) + [dpre(t + d) | dpre(t) | dpre(t - d)] W1_taps^T (K = 3 G, zero outside the utterance,
 //                       mirroring the forward gather) and dc(t) (+)= dpre(t) W_aux^T; the first layer processed overwrites dc.
-//   pwg_wgrad           every weight gradient is a product A^T B over the rows.  A job names A (with a row shift for the dilated taps, or the noise hash for
+//   pwg_wgrad           (pwg_wgrad.h, shared with the discriminator's backward) every weight gradient is a product A^T B over the rows.  A job names A (with a row shift for the dilated taps, or the noise hash for
 //                       first_conv, and an optional constant-one column that yields the bias), B and where the result goes in torch's layout.  One wave owns
 //                       a 16 x 16 output tile of one job over one split of the rows; the split partition is fixed: per utterance, chunks of 1024 rows.
 //   pwg_wgrad_sum       adds the splits in ascending order, scales, writes torch's layout (overwrites).
@@ -25,11 +25,10 @@
 #include "gauss_hash.h"
 #include "launch_log.h"
 #include "pwg_common.h"
+#include "pwg_wgrad.h"
 
 namespace {
 
-constexpr int WG_ROWS = 1024;                             // rows of one split of the weight-gradient partition
-constexpr int WG_MAX_JOBS = 8;
 constexpr int FIR_ROWS = 256;                             // output rows of one block of the FIR gradient
 
 // ---- head: grid (ceil(Tmax / 64), B), LDS Ys [64][S + 4] | DHs [64][S + 4].  w1 [S][S] row = input channel (the forward's image), w1t [S][S] row = output
@@ -214,76 +213,6 @@ __global__ __launch_bounds__(THREADS) void pwg_layer_bwd_data_kernel(const float
     }
 }
 
-// ---- weight gradients: out[i][n] = scale sum_rows A[row + shift][i] B[row][n], rows of every utterance's own [0, T_b) ----
-struct wg_job {
-    const float* a;            // [B][Tmax][lda], or NULL: the noise z (seeds given: the counter hash, else `noise` [B][Tmax])
-    const float* b;            // [B][Tmax][ldb]
-    float* dst;                // out[i][n] -> dst[i * dst_i + n * dst_n]
-    float* dbias;              // ones: out[ka][n] -> dbias[n]
-    int lda, ka, shift, ldb, n, dst_i, dst_n, ones, tiles_i, tiles_n, tile0, off;
-    float scale;
-};
-struct wg_args {
-    wg_job job[WG_MAX_JOBS];
-    const int32_t* lengths;
-    const uint32_t* seeds;
-    const float* noise;
-    float* partial;            // [splits][total_elems]
-    int njobs, total_tiles, total_elems, Lmax, hop, nchunk;
-};
-
-// grid (total_tiles, B * nchunk), one wave: a 16 x 16 output tile of one job over rows [chunk * 1024, (chunk + 1) * 1024) of utterance b
-__global__ __launch_bounds__(64) void pwg_wgrad_kernel(const wg_args a)
-{
-    const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
-    int j = 0;
-    while (j + 1 < a.njobs && (int)blockIdx.x >= a.job[j + 1].tile0) ++j;
-    const wg_job& J = a.job[j];
-    const int tile = blockIdx.x - J.tile0, ti = tile / J.tiles_n, tn = tile - ti * J.tiles_n;
-    const int b = blockIdx.y / a.nchunk, chunk = blockIdx.y - b * a.nchunk;
-    const int Tmax = a.Lmax * a.hop, T = min(a.lengths[b], a.Lmax) * a.hop;
-    const int i = ti * 16 + r, n = tn * 16 + r;
-    const size_t row0 = (size_t)b * Tmax;
-    const int t_end = min((chunk + 1) * WG_ROWS, T);
-    const bool a_ok = i < J.ka, a_one = J.ones && i == J.ka, n_ok = n < J.n;
-    v4f acc = {0.f, 0.f, 0.f, 0.f};
-    for (int t = chunk * WG_ROWS + q; t < t_end + 3; t += 4) {      // (t - q < t_end for every lane of the wave: the MFMA is issued by all 64)
-        if (t - q >= t_end) break;
-        float av = 0.f, bv = 0.f;
-        if (t < t_end) {
-            if (a_ok) {
-                const int ts = t + J.shift;
-                if (ts >= 0 && ts < T) {
-                    if (J.a) av = J.a[(row0 + ts) * J.lda + i];
-                    else av = a.noise ? a.noise[row0 + ts] : gauss_hash::gauss(a.seeds[2 * b], a.seeds[2 * b + 1], 0u, (uint32_t)ts, 1u);
-                }
-            } else if (a_one) av = 1.f;
-            if (n_ok) bv = J.b[(row0 + t) * J.ldb + n];
-        }
-        acc = mfma4(av, bv, acc);
-    }
-    float* out = a.partial + (size_t)blockIdx.y * a.total_elems + J.off;
-    const int npad = J.tiles_n * 16;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) out[(ti * 16 + q * 4 + k) * npad + tn * 16 + r] = acc[k];
-}
-
-__global__ __launch_bounds__(THREADS) void pwg_wgrad_sum_kernel(const wg_args a, int splits)
-{
-    const int e = blockIdx.x * THREADS + threadIdx.x;
-    if (e >= a.total_elems) return;
-    int j = 0;
-    while (j + 1 < a.njobs && e >= a.job[j + 1].off) ++j;
-    const wg_job& J = a.job[j];
-    const int npad = J.tiles_n * 16, local = e - J.off, i = local / npad, n = local - i * npad;
-    if (n >= J.n || i > J.ka || (i == J.ka && !J.ones)) return;
-    float s = 0.f;
-    for (int k = 0; k < splits; ++k) s += a.partial[(size_t)k * a.total_elems + e];
-    s *= J.scale;
-    if (i < J.ka) J.dst[(size_t)i * J.dst_i + (size_t)n * J.dst_n] = s;
-    else J.dbias[n] = s;
-}
-
 // ---- conditioning chain ----
 // d in[u] = sum_{v in [u s, u s + s)} sum_j fir[j] d out[v - j + s]: grid (ceil(Lmax mult A / 4 / 256), B)
 __global__ __launch_bounds__(THREADS) void pwg_upsample_bwd_kernel(const float* __restrict__ dout, const int32_t* __restrict__ lengths, const float* __restrict__ fir,
@@ -306,18 +235,6 @@ __global__ __launch_bounds__(THREADS) void pwg_upsample_bwd_kernel(const float* 
             acc.x = fmaf(wj, g.x, acc.x); acc.y = fmaf(wj, g.y, acc.y); acc.z = fmaf(wj, g.z, acc.z); acc.w = fmaf(wj, g.w, acc.w);
         }
     *reinterpret_cast<float4*>(din + ((size_t)b * Lmax * mult + u) * A + a) = acc;
-}
-
-__device__ __forceinline__ double block_sum(double v, double* red, int tid)
-{
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    for (int h = THREADS >> 1; h > 0; h >>= 1) {
-        if (tid < h) red[tid] += red[tid + h];
-        __syncthreads();
-    }
-    return red[0];
 }
 
 // d fir[j] of one block of 256 output rows: grid (nblk, B) -> partial [B nblk][2 s + 1] (float64)
@@ -370,36 +287,9 @@ __global__ __launch_bounds__(THREADS) void pwg_cond_in_bwd_kernel(const float* _
 }
 
 // ---- host side ----
-// the forward's limits, and the weight gradient's splits fit one grid dimension
-bool bad_train_batch(int B, int Lmax, int hop) { return bad_batch(B, Lmax, hop) || (int64_t)B * ((Lmax * (int64_t)hop + WG_ROWS - 1) / WG_ROWS) > 65535; }
 int gate_lds(int R, int S, int A) { return TM * (xs_stride_of(3 * R + A) + R + S + 4) * 4; }
 int data_lds(int R) { return TM * (6 * R + 4) * 4; }
 int head_lds(int S) { return 2 * TM * (S + 4) * 4; }
-
-int tiles16(int n) { return (n + 15) / 16; }
-
-// appends a job and lays out its tiles and partial sums
-void add_job(wg_args& a, const float* A_, int lda, int ka, int shift, const float* B_, int ldb, int n, float* dst, int dst_i, int dst_n, float* dbias, float scale)
-{
-    wg_job& J = a.job[a.njobs++];
-    J.a = A_; J.b = B_; J.dst = dst; J.dbias = dbias; J.lda = lda; J.ka = ka; J.shift = shift; J.ldb = ldb; J.n = n; J.dst_i = dst_i; J.dst_n = dst_n;
-    J.ones = dbias != nullptr; J.tiles_i = tiles16(ka + (J.ones ? 1 : 0)); J.tiles_n = tiles16(n); J.tile0 = a.total_tiles; J.off = a.total_elems; J.scale = scale;
-    a.total_tiles += J.tiles_i * J.tiles_n;
-    a.total_elems += J.tiles_i * J.tiles_n * 256;
-}
-
-int wgrad_launch(wg_args& a, const int32_t* lengths, float* work, int B, int Lmax, int hop, const char* name, void* stream)
-{
-    a.lengths = lengths; a.partial = work; a.Lmax = Lmax; a.hop = hop;
-    a.nchunk = (int)(((int64_t)Lmax * hop + WG_ROWS - 1) / WG_ROWS);
-    const int splits = B * a.nchunk;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    glowtts_note_launch(name);
-    hipLaunchKernelGGL(pwg_wgrad_kernel, dim3(a.total_tiles, splits), dim3(64), 0, s, a);
-    hipLaunchKernelGGL(pwg_wgrad_sum_kernel, dim3((a.total_elems + THREADS - 1) / THREADS), dim3(THREADS), 0, s, a, splits);
-    GLOWTTS_NOTE_STATIC("pwg_wgrad_sum");
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
-}
 
 int64_t layer_elems(int R, int S, int A)
 {
@@ -447,7 +337,7 @@ extern "C" int glowtts_pwg_train_head_wgrad(const float* y, const float* h, cons
     wg_args a = {};
     add_job(a, y, S, S, 0, dh, S, S, dw1, 1, S, db1, 1.f);                  // last_conv_layers.1.weight [out][in]
     add_job(a, h, S, S, 0, dwav, 1, 1, dw2, 1, S, db2, 1.f);                // last_conv_layers.3.weight [1][in]
-    return wgrad_launch(a, frame_lengths, work, B, Lmax, hop, "pwg_wgrad", stream);
+    return wgrad_launch(a, frame_lengths, work, B, Lmax, hop, "pwg_wgrad", "pwg_wgrad_sum", stream);
 }
 
 extern "C" int glowtts_pwg_train_layer_bwd(const float* x, const float* c, const float* w1, const float* b1, const float* w2t, const float* w1t, const float* wauxt,
@@ -483,7 +373,7 @@ extern "C" int glowtts_pwg_train_layer_wgrad(const float* x, const float* c, con
     add_job(a, c, A, A, 0, dpre, G, G, daux_w, 1, A, nullptr, 1.f);          // conv1x1_aux.weight [G][A]
     add_job(a, gate, R, R, 0, dxp, R, R, dout_w, 1, R, dout_b, RSQRT2);      // conv1x1_out.weight [R][G / 2]
     add_job(a, gate, R, R, 0, dskips, S, S, dskip_w, 1, R, dskip_b, 1.f);    // conv1x1_skip.weight [S][G / 2]
-    return wgrad_launch(a, frame_lengths, work, B, Lmax, hop, "pwg_wgrad", stream);
+    return wgrad_launch(a, frame_lengths, work, B, Lmax, hop, "pwg_wgrad", "pwg_wgrad_sum", stream);
 }
 
 extern "C" int glowtts_pwg_train_first_bwd(const float* noises, const uint32_t* seeds, const float* dx0, const int32_t* frame_lengths, float* work, float* dw, float* db,
@@ -493,7 +383,7 @@ extern "C" int glowtts_pwg_train_first_bwd(const float* noises, const uint32_t* 
     wg_args a = {};
     a.seeds = seeds; a.noise = noises;
     add_job(a, nullptr, 1, 1, 0, dx0, R, R, dw, 0, 1, db, 1.f);              // first_conv.weight [R][1][1]
-    return wgrad_launch(a, frame_lengths, work, B, Lmax, hop, "pwg_first_bwd", stream);
+    return wgrad_launch(a, frame_lengths, work, B, Lmax, hop, "pwg_first_bwd", "pwg_wgrad_sum", stream);
 }
 
 extern "C" int glowtts_pwg_train_upsample_bwd(const float* dout, const float* in, const float* fir, const int32_t* frame_lengths, float* work, float* din, float* dfir,

@@ -1,5 +1,7 @@
-"""Trainer of the Parallel WaveGAN generator, stage one of its recipe (DESIGN.md "Training the Parallel WaveGAN generator"): the generator alone under the
-multi-resolution STFT loss - `python Train_PWG.py -hp <yaml> -s <steps>`.
+"""Trainer of the Parallel WaveGAN vocoder - `python Train_PWG.py -hp <yaml> -s <steps>`.  Stage one of its recipe (DESIGN.md "Training the Parallel WaveGAN
+generator"): the generator alone under the multi-resolution STFT loss.  With the optional yaml block `Vocoder.Train.Discriminator`, stage two from its
+`Start_Step` on (DESIGN.md "Training the Parallel WaveGAN discriminator"): the least-squares adversarial term joins the generator's loss and the
+discriminator `vocoder.PWGDiscriminator` is trained beside it, with a clipping and a RAdam of its own.
 
 Reads the pattern directories `Pattern_Generator.py` writes (through METADATA.PICKLE: `File_List`, `Mel_Length_Dict`, `Audio_Length_Dict`): every pattern
 holds the raw `Audio` beside its `Mel`, frame f centred on sample f * Frame_Shift.  Draws seeded batches of mel segments with the audio under them, and steps
@@ -17,7 +19,8 @@ import torch
 
 from . import optim
 from .hparams import Recursive_Parse, get_hp, load_yaml
-from .vocoder import STFT_RESOLUTIONS, MultiResolutionSTFTLoss, ParallelWaveGAN, pwg_geometry, pwg_load, stft_loss_geometry
+from .vocoder import (STFT_RESOLUTIONS, MultiResolutionSTFTLoss, ParallelWaveGAN, PWGDiscriminator, adversarial_mse, pwg_disc_load, pwg_disc_settings, pwg_geometry,
+                      pwg_load, plain_block, stft_loss_geometry)
 
 TRAIN_KEY = "Vocoder.Train"
 DEFAULTS = {"Batch_Size": 8, "Segment_Frames": 100, "Learning_Rate": 1.0e-4, "Epsilon": 1.0e-6, "Gradient_Norm": 10.0,
@@ -25,14 +28,11 @@ DEFAULTS = {"Batch_Size": 8, "Segment_Frames": 100, "Learning_Rate": 1.0e-4, "Ep
             "Checkpoint_Save_Interval": 5000, "Evaluation_Interval": 1000, "Checkpoint_Path": "./pwg_results"}
 
 
-def _plain(v):
-    return {k: _plain(x) for k, x in vars(v).items()} if isinstance(v, argparse.Namespace) else v
-
-
 def train_settings(hp):
-    """The optional yaml block `Vocoder.Train` over DEFAULTS (absent block or key: the default), checked: a ValueError names every bad key."""
-    given = _plain(getattr(getattr(hp, "Vocoder", None), "Train", None)) or {}
-    unknown = sorted(set(given) - set(DEFAULTS))
+    """The optional yaml block `Vocoder.Train` over DEFAULTS (absent block or key: the default), checked: a ValueError names every bad key.  The optional
+    sub-block `Discriminator` (`vocoder.pwg_disc_settings`) appears in the result only when the yaml has it."""
+    given = plain_block(getattr(getattr(hp, "Vocoder", None), "Train", None)) or {}
+    unknown = sorted(set(given) - set(DEFAULTS) - {"Discriminator"})
     if unknown:
         raise ValueError("unknown key {}.{} (known: {})".format(TRAIN_KEY, unknown[0], ", ".join(DEFAULTS)))
     s = dict(DEFAULTS, **given)
@@ -50,6 +50,8 @@ def train_settings(hp):
     if bad:
         raise ValueError("the vocoder trainer does not support " + "; ".join(bad))
     s["STFT_Resolutions"] = stft_loss_geometry(s["STFT_Resolutions"], int(s["Segment_Frames"]) * int(hp.Sound.Frame_Shift))
+    if "Discriminator" in given:
+        s["Discriminator"] = pwg_disc_settings(hp)
     return s
 
 
@@ -125,6 +127,12 @@ class PWG_Trainer:
         self.criterion = MultiResolutionSTFTLoss(s["STFT_Resolutions"], self.device)
         self.params = list(self.model.params.values())
         self.optimizer = optim.RAdam(self.params, lr=float(s["Learning_Rate"]), eps=float(s["Epsilon"]))
+        # stage two (optional block Vocoder.Train.Discriminator): initialised from the seed at construction, untouched before Start_Step
+        self.disc_set, self.discriminator, self.disc_steps = s.get("Discriminator"), None, 0
+        if self.disc_set is not None:
+            self.discriminator = PWGDiscriminator(self.hp, self.device, trainable=True, seed=self.seed)
+            self.disc_params = list(self.discriminator.params.values())
+            self.disc_optimizer = optim.RAdam(self.disc_params, lr=float(self.disc_set["Learning_Rate"]), eps=float(self.disc_set["Epsilon"]))
         self.last = {}
         if self.steps > 0:
             self.Load_Checkpoint()
@@ -140,14 +148,32 @@ class PWG_Trainer:
     def seeds(self, step, B):
         return torch.tensor([noise_seed_words(self.seed, step, i) for i in range(B)], dtype=torch.int64)
 
-    def forward(self, mel, target, step):
+    def disc_learning_rate(self, updates):
+        """The discriminator's step decay counts its own updates: Learning_Rate * Gamma^(updates // Step)"""
+        d = self.disc_set["Learning_Rate_Decay"]
+        return float(self.disc_set["Learning_Rate"]) * float(d["Gamma"]) ** (int(updates) // int(d["Step"]))
+
+    def adversarial(self, step):
+        return self.disc_set is not None and int(step) >= int(self.disc_set["Start_Step"])
+
+    def forward(self, mel, target, step, adversarial=False):
+        """-> L_stft, or with `adversarial` (L_G = L_stft + Lambda_Adversarial L_adv, L_D, the unscaled (L_adv, real term, fake term) [3]): one discriminator
+        forward over [target; wav]; L_G's backward reaches the generator alone, L_D's the discriminator alone."""
         mel, target = mel.to(self.device, non_blocking=True), target.to(self.device, non_blocking=True)
         B, _, L = mel.shape
         wav, _ = self.model.generate(mel, [L] * B, seeds=self.seeds(step, B))
-        return self.criterion(wav, target)
+        stft = self.criterion(wav, target)
+        if not adversarial:
+            return stft
+        both, p_fake = self.discriminator.score_pair(target, wav)
+        adv, adv_terms = adversarial_mse(p_fake, 1.0, float(self.disc_set["Lambda_Adversarial"]))
+        d_loss, d_terms = adversarial_mse(both, (1.0, 0.0))
+        return stft + adv, d_loss, torch.cat([adv_terms[:1], d_terms]), stft
 
     def Train_Step(self, mel, target):
-        """One step on a host or device batch (mel [B, Mel, frames], target [B, frames * hop]); returns the loss (0-d device tensor)."""
+        """One step on a host or device batch (mel [B, Mel, frames], target [B, frames * hop]); returns the generator's loss (0-d device tensor)."""
+        if self.adversarial(self.steps):
+            return self.Adversarial_Step(mel, target)
         loss = self.forward(mel, target, self.steps)
         for p in self.params:
             p.grad = None
@@ -160,20 +186,51 @@ class PWG_Trainer:
         self.last = {"Loss": loss.detach(), "Terms": self.criterion.terms, "Gradient_Norm": norm}
         return loss.detach()
 
+    def Adversarial_Step(self, mel, target):
+        """A step of stage two: both updates are computed from the state before the step (the discriminator's forward and both backwards precede both updates)."""
+        loss, d_loss, adv_terms, stft = self.forward(mel, target, self.steps, adversarial=True)
+        for p in self.params + self.disc_params:
+            p.grad = None
+        loss.backward()                                                                    # the generator alone: the fake rows' data chain, no weight gradients
+        d_loss.backward()                                                                  # the discriminator alone
+        norm = optim.clip_grad_norm_(self.params, float(self.set["Gradient_Norm"]), _table_key=("pwg", id(self)))
+        d_norm = optim.clip_grad_norm_(self.disc_params, float(self.disc_set["Gradient_Norm"]), _table_key=("pwg_disc", id(self)))
+        for group in self.optimizer.param_groups:
+            group["lr"] = self.learning_rate(self.steps)
+        for group in self.disc_optimizer.param_groups:
+            group["lr"] = self.disc_learning_rate(self.disc_steps)
+        self.optimizer.step()
+        self.disc_optimizer.step()
+        self.steps += 1
+        self.disc_steps += 1
+        self.last = {"Loss": loss.detach(), "Terms": self.criterion.terms, "Gradient_Norm": norm, "STFT_Loss": stft.detach(), "Discriminator_Loss": d_loss.detach(),
+                     "L_adv": adv_terms[0], "Real_Term": adv_terms[1], "Fake_Term": adv_terms[2], "Discriminator_Gradient_Norm": d_norm}
+        return loss.detach()
+
     @torch.no_grad()
     def Evaluation(self, batches=4):
-        """-> (mean loss, mean (L_sc, L_mag) per resolution [n, 2]) over `batches` batches of the evaluation set"""
+        """-> (mean loss, mean (L_sc, L_mag) per resolution [n, 2]) over `batches` batches of the evaluation set; with the discriminator block, a third
+        element: the mean (L_adv, real term, fake term) [3] of the current discriminator on the generated and the target segments."""
         if "Eval" not in self.sampler:
             return None
-        losses, terms = [], []
+        losses, terms, adv = [], [], []
         for b in range(batches):
-            losses.append(float(self.forward(*self.sampler["Eval"].batch(b), step=-1 - b)))
+            if self.discriminator is None:
+                losses.append(float(self.forward(*self.sampler["Eval"].batch(b), step=-1 - b)))
+            else:
+                out = self.forward(*self.sampler["Eval"].batch(b), step=-1 - b, adversarial=True)
+                losses.append(float(out[3]))
+                adv.append(out[2].cpu().double())
             terms.append(self.criterion.terms.cpu().double())
-        return float(np.mean(losses)), torch.stack(terms).mean(0)
+        ev = float(np.mean(losses)), torch.stack(terms).mean(0)
+        return ev if self.discriminator is None else ev + (torch.stack(adv).mean(0),)
 
     def Save_Checkpoint(self):
         os.makedirs(self.set["Checkpoint_Path"], exist_ok=True)
         state = {"generator": {k: v.detach().cpu() for k, v in self.model.params.items()}, "Optimizer": self.optimizer.state_dict(), "Steps": self.steps}
+        if self.discriminator is not None:
+            state.update(discriminator={k: v.detach().cpu() for k, v in self.discriminator.params.items()},
+                         Discriminator_Optimizer=self.disc_optimizer.state_dict(), Discriminator_Steps=self.disc_steps)
         torch.save(state, self.checkpoint_file(self.steps))
         logging.info("Checkpoint saved at %d steps.", self.steps)
         return self.checkpoint_file(self.steps)
@@ -185,6 +242,14 @@ class PWG_Trainer:
                 self.model.params[k].copy_(v)
         self.optimizer.load_state_dict(state["Optimizer"])
         self.steps = int(state["Steps"])
+        if self.discriminator is not None:
+            if "discriminator" not in state:
+                raise ValueError("{} holds no discriminator: it was written without the block {}.Discriminator".format(self.checkpoint_file(self.steps), TRAIN_KEY))
+            with torch.no_grad():
+                for k, v in pwg_disc_load(state["discriminator"], self.discriminator.geo).items():
+                    self.discriminator.params[k].copy_(v)
+            self.disc_optimizer.load_state_dict(state["Discriminator_Optimizer"])
+            self.disc_steps = int(state["Discriminator_Steps"])
 
     def Train(self):
         s = self.set
@@ -193,6 +258,11 @@ class PWG_Trainer:
             if self.steps % int(s["Evaluation_Interval"]) == 0:
                 ev = self.Evaluation()
                 logging.info("Step %d: loss %.4f%s", self.steps, float(loss), "" if ev is None else ", evaluation loss {:.4f}, terms {}".format(ev[0], ev[1].tolist()))
+                if ev is not None and len(ev) > 2:
+                    logging.info("Step %d: evaluation L_adv %.4f, real term %.4f, fake term %.4f", self.steps, *ev[2].tolist())
+                if "L_adv" in self.last:
+                    logging.info("Step %d: L_adv %.4f, real term %.4f, fake term %.4f, discriminator loss %.4f", self.steps, float(self.last["L_adv"]),
+                                 float(self.last["Real_Term"]), float(self.last["Fake_Term"]), float(self.last["Discriminator_Loss"]))
             if self.steps % int(s["Checkpoint_Save_Interval"]) == 0:
                 self.Save_Checkpoint()
         if not os.path.exists(self.checkpoint_file(self.steps)):

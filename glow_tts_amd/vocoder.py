@@ -10,6 +10,7 @@ Frame_Shift, Slaney mel filterbank, dB normalisation to +- Max_Abs_Mel), so a ge
 Fast Griffin-Lim with the momentum applied to the SIGNAL (the STFT is linear): y = x_n + alpha (x_n - x_n-1), x_n+1 = istft(|S| * Y / max(|Y|, 1e-8)) with
 Y = stft(y); two signals are kept, never a previous spectrogram, and the complex spectrum of an iteration never leaves LDS.  The waveform is still
 pre-emphasised: `audio.deemphasis` undoes that on the host before the samples are written."""
+import argparse
 import ctypes
 import hashlib
 import math
@@ -685,3 +686,300 @@ class MultiResolutionSTFTLoss:
         if B < 1 or B > 65535 or B * T >= 2 ** 31:
             raise ValueError(f"MultiResolutionSTFTLoss: batch of {B} x {T} samples is outside 1 <= B <= 65535, B T < 2^31 (Vocoder.Train.Batch_Size)")
         return _STFTLoss.apply(self, pred.contiguous(), target.detach().contiguous())
+
+
+# ================================================================================================================================================
+# The Parallel WaveGAN discriminator and the least-squares adversarial loss on the kernels of csrc/pwg_disc_ops.hip: stage two of the recipe.  The
+# contract (DESIGN.md "Training the Parallel WaveGAN discriminator") restates the most widely used implementation from memory and is UNPINNED.
+# ================================================================================================================================================
+DISC_KEY = "Vocoder.Train.Discriminator"
+DISC_DEFAULTS = {"Start_Step": 100000, "Lambda_Adversarial": 4.0, "Learning_Rate": 5.0e-5, "Epsilon": 1.0e-6, "Gradient_Norm": 1.0,
+                 "Learning_Rate_Decay": {"Step": 200000, "Gamma": 0.5}, "Layers": 10, "Channels": 64, "Negative_Slope": 0.2}
+DISC_MAX_LAYERS = 16
+
+
+def plain_block(v):
+    """A parsed yaml block (nested Namespaces) as plain dicts"""
+    return {k: plain_block(x) for k, x in vars(v).items()} if isinstance(v, argparse.Namespace) else v
+
+
+def pwg_disc_settings(hp):
+    """The optional yaml block `Vocoder.Train.Discriminator` over DISC_DEFAULTS (absent block: None), checked: a ValueError names every unknown or bad key."""
+    block = getattr(getattr(getattr(hp, "Vocoder", None), "Train", None), "Discriminator", None)
+    if block is None:
+        return None
+    given = plain_block(block) or {}
+    if not isinstance(given, dict):
+        raise ValueError(f"{DISC_KEY} must be a mapping, got {given!r}")
+    unknown = sorted(set(given) - set(DISC_DEFAULTS))
+    if unknown:
+        raise ValueError("unknown key {}.{} (known: {})".format(DISC_KEY, unknown[0], ", ".join(DISC_DEFAULTS)))
+    decay = given.get("Learning_Rate_Decay") or {}
+    if not isinstance(decay, dict) or set(decay) - {"Step", "Gamma"}:
+        bad_sub = sorted(set(decay) - {"Step", "Gamma"})[0] if isinstance(decay, dict) else decay
+        raise ValueError("unknown key {}.Learning_Rate_Decay.{} (known: Step, Gamma)".format(DISC_KEY, bad_sub))
+    s = dict(DISC_DEFAULTS, **given)
+    s["Learning_Rate_Decay"] = dict(DISC_DEFAULTS["Learning_Rate_Decay"], **decay)
+
+    def ok(fn, v):
+        try:
+            return bool(fn(v))
+        except (TypeError, ValueError):
+            return False
+    bad = []
+    if not ok(lambda v: int(v) == v and int(v) >= 0, s["Start_Step"]):
+        bad.append("{}.Start_Step = {} (an integer, at least 0)".format(DISC_KEY, s["Start_Step"]))
+    if not ok(lambda v: float(v) >= 0, s["Lambda_Adversarial"]):
+        bad.append("{}.Lambda_Adversarial = {} (not negative)".format(DISC_KEY, s["Lambda_Adversarial"]))
+    for k in ("Learning_Rate", "Epsilon", "Gradient_Norm"):
+        if not ok(lambda v: float(v) > 0, s[k]):
+            bad.append("{}.{} = {} (positive)".format(DISC_KEY, k, s[k]))
+    d = s["Learning_Rate_Decay"]
+    if not ok(lambda v: int(v["Step"]) >= 1 and 0 < float(v["Gamma"]) <= 1, d):
+        bad.append("{}.Learning_Rate_Decay = {{Step: {}, Gamma: {}}} (Step >= 1, 0 < Gamma <= 1)".format(DISC_KEY, d.get("Step"), d.get("Gamma")))
+    if not ok(lambda v: int(v) == v and 3 <= int(v) <= DISC_MAX_LAYERS, s["Layers"]):
+        bad.append("{}.Layers = {} (an integer in [3, {}])".format(DISC_KEY, s["Layers"], DISC_MAX_LAYERS))
+    if not ok(lambda v: int(v) == v and int(v) >= 16 and int(v) % 16 == 0 and pwg_disc_lds(int(v)) <= PWG_LDS and int(v) <= PWG_MAX_CHANNELS, s["Channels"]):
+        bad.append("{}.Channels = {} (a multiple of 16 in [16, {}]: a tile of 64 rows x 3 Channels floats must fit the {} bytes of LDS)".format(
+            DISC_KEY, s["Channels"], pwg_disc_max_channels(), PWG_LDS))
+    if not ok(lambda v: 0 <= float(v) < 1, s["Negative_Slope"]):
+        bad.append("{}.Negative_Slope = {} (in [0, 1): the backward reads the LeakyReLU mask from the layer's output)".format(DISC_KEY, s["Negative_Slope"]))
+    if bad:
+        raise ValueError("the vocoder trainer does not support " + "; ".join(bad))
+    return s
+
+
+def pwg_disc_lds(C):
+    """Bytes of LDS of a middle layer's tile, forward and backward alike: 64 rows of 3 C floats at a stride whose quarter is odd."""
+    K = 3 * C
+    return 4 * PWG_TILE * (K if (K // 4) % 2 else K + 4)
+
+
+def pwg_disc_max_channels():
+    return max(c for c in range(16, PWG_MAX_CHANNELS + 1, 16) if pwg_disc_lds(c) <= PWG_LDS)
+
+
+def pwg_disc_geometry(hp):
+    """The discriminator's sizes as a dict (layers, C, slope, dilations) from the block `Vocoder.Train.Discriminator` (absent: the defaults); raises ValueError
+    naming the offending yaml keys when the kernels do not support them."""
+    s = pwg_disc_settings(hp) or DISC_DEFAULTS
+    layers, C = int(s["Layers"]), int(s["Channels"])
+    return {"layers": layers, "C": C, "slope": float(s["Negative_Slope"]), "dilations": [1] + list(range(1, layers - 1)) + [1]}
+
+
+def pwg_disc_expected_shapes(geo):
+    """state-dict key -> shape of the discriminator with the sizes `geo`"""
+    n, C, e = geo["layers"], geo["C"], {}
+    for i in range(n):
+        e[f"conv_layers.{i}.weight"] = (1 if i == n - 1 else C, 1 if i == 0 else C, 3)
+        e[f"conv_layers.{i}.bias"] = (1 if i == n - 1 else C,)
+    return e
+
+
+def pwg_disc_init(geo, seed=0):
+    """A fresh discriminator's state dict: torch.nn.Conv1d's default rule per tensor - uniform in +- 1 / sqrt(fan_in), weights and biases alike - drawn in
+    the order of `pwg_disc_expected_shapes` on a host generator seeded with `seed` (the pattern of `pwg_init`)."""
+    g = torch.Generator().manual_seed(int(seed))
+    shapes, sd = pwg_disc_expected_shapes(geo), {}
+    for k, shape in shapes.items():
+        fan_in = math.prod(shapes[k[:-len("bias")] + "weight"][1:]) if k.endswith(".bias") else math.prod(shape[1:])
+        sd[k] = (torch.rand(shape, generator=g, dtype=torch.float32) * 2.0 - 1.0) / math.sqrt(fan_in)
+    return sd
+
+
+def pwg_disc_find_state_dict(obj):
+    """The discriminator's state dict inside what torch.load returned: under `discriminator` / `Discriminator`, possibly inside `model`, or at the top level."""
+    for path in (("discriminator",), ("Discriminator",), ("model", "discriminator"), ("model", "Discriminator"), (), ("model",)):
+        d = obj
+        for k in path:
+            d = d.get(k) if isinstance(d, dict) else None
+        if isinstance(d, dict) and any(str(k).startswith("conv_layers.0.weight") for k in d) and not any(str(k).startswith("first_conv.") for k in d):
+            return d
+    raise ValueError("no Parallel WaveGAN discriminator state dict found (looked for `conv_layers.0.weight*` under discriminator / Discriminator, inside model "
+                     "and at the top level)")
+
+
+def pwg_disc_load(obj, geo):
+    """-> {key: float32 host tensor} with exactly the keys of `pwg_disc_expected_shapes`: weight-norm pairs (`weight_g` / `weight_v`) are folded once, in
+    float64, exactly as `pwg_load` folds them; a missing, surplus or wrongly shaped tensor raises a ValueError naming the key."""
+    sd = dict(pwg_disc_find_state_dict(obj))
+    for kg in [k for k in sd if k.endswith(".weight_g")]:
+        base = kg[:-len("_g")]
+        if base + "_v" not in sd:
+            raise ValueError(f"discriminator checkpoint: {kg} has no {base}_v beside it")
+        if base in sd:
+            raise ValueError(f"discriminator checkpoint: {base} is given both plain and in weight-norm form")
+        g, v = sd.pop(kg).double(), sd.pop(base + "_v").double()
+        norm = v.reshape(v.shape[0], -1).norm(dim=1).reshape([-1] + [1] * (v.dim() - 1))
+        sd[base] = v * (g.reshape(norm.shape) / norm)
+    want = pwg_disc_expected_shapes(geo)
+    for k in want:
+        if k not in sd:
+            raise ValueError(f"discriminator checkpoint: missing key {k}")
+    for k in sd:
+        if k not in want:
+            raise ValueError(f"discriminator checkpoint: surplus key {k} (not part of a discriminator of the {DISC_KEY} block's sizes)")
+    out = {}
+    for k, shape in want.items():
+        t = sd[k]
+        if not torch.is_tensor(t) or tuple(t.shape) != shape:
+            raise ValueError(f"discriminator checkpoint: {k} has shape {tuple(getattr(t, 'shape', ()))}, the {DISC_KEY} block's sizes need {shape}")
+        out[k] = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
+    return out
+
+
+def pwg_disc_forward(disc, wav, alloc=None):
+    """The forward launches on wav [B, T] (fp32, contiguous, on the device) -> dict(wav, scores [B, T], keep: the Layers - 1 hidden outputs [B, T, C] - C floats
+    per row and layer, all the backward needs: the output of a LeakyReLU carries its mask).  alloc(*shape): the caller's buffers (tests)."""
+    g, lib, P, st = disc.geo, _lib.lib(), _lib.ptr, _lib.stream()
+    B, T = wav.shape
+    C, slope = g["C"], g["slope"]
+    f = alloc or (lambda *shape: torch.empty(*shape, dtype=torch.float32, device=wav.device))
+    keep, scores = [f(B, T, C) for _ in range(g["layers"] - 1)], f(B, T)
+    _lib.check(lib.glowtts_pwg_disc_first(P(wav), P(disc.first[0]), P(disc.first[1]), P(keep[0]), B, T, C, slope, st), "glowtts_pwg_disc_first")
+    for i in range(1, g["layers"] - 1):
+        w, b, _ = disc.middle[i - 1]
+        _lib.check(lib.glowtts_pwg_disc_layer(P(keep[i - 1]), P(w), P(b), P(keep[i]), B, T, C, g["dilations"][i], slope, st), "glowtts_pwg_disc_layer")
+    _lib.check(lib.glowtts_pwg_disc_last(P(keep[-1]), P(disc.last[0]), P(disc.last[1]), P(scores), B, T, C, st), "glowtts_pwg_disc_last")
+    return {"wav": wav, "scores": scores, "keep": keep}
+
+
+def pwg_disc_backward(disc, fwd, dscores, freeze=False, alloc=None):
+    """d scores [B, T] -> (d wav [B, T], {name: gradient in torch's layout} or None when `freeze`) from what `pwg_disc_forward` kept (or the views of some of
+    its batch rows).  freeze: the data chain alone - no dpre is written and no weight-gradient launch is made."""
+    g, lib, P, st = disc.geo, _lib.lib(), _lib.ptr, _lib.stream()
+    wav, keep = fwd["wav"], fwd["keep"]
+    B, T = wav.shape
+    C, slope, n, dev = g["C"], g["slope"], g["layers"], wav.device
+    f = alloc or (lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev))
+    dscores = dscores.to(torch.float32).contiguous()
+    grads = work = lengths = dpre = None
+    if not freeze:
+        grads = {k: f(*shape) for k, shape in pwg_disc_expected_shapes(g).items()}
+        work, lengths, dpre = f(lib.glowtts_pwg_disc_work_floats(B, T, C)), torch.full((B,), T, dtype=torch.int32, device=dev), f(B, T, C)
+
+    def wgrad(i, a, d_out, cin, cout):
+        _lib.check(lib.glowtts_pwg_disc_wgrad(P(a), P(d_out), P(lengths), P(work), P(grads[f"conv_layers.{i}.weight"]), P(grads[f"conv_layers.{i}.bias"]), B, T, cin,
+                                              cout, g["dilations"][i], st), "glowtts_pwg_disc_wgrad")
+    dout, dx = f(B, T, C), f(B, T, C)
+    _lib.check(lib.glowtts_pwg_disc_last_bwd(P(dscores), P(disc.last[0]), P(dout), B, T, C, st), "glowtts_pwg_disc_last_bwd")
+    if not freeze:
+        wgrad(n - 1, keep[-1], dscores, C, 1)
+    for i in reversed(range(1, n - 1)):
+        _lib.check(lib.glowtts_pwg_disc_layer_bwd(P(dout), P(keep[i]), P(disc.middle[i - 1][2]), P(dx), P(dpre), B, T, C, g["dilations"][i], slope, st),
+                   "glowtts_pwg_disc_layer_bwd")
+        if not freeze:
+            wgrad(i, keep[i - 1], dpre, C, C)
+        dout, dx = dx, dout
+    dwav = f(B, T)
+    _lib.check(lib.glowtts_pwg_disc_first_bwd(P(dout), P(keep[0]), P(disc.first[0]), P(dwav), P(dpre), B, T, C, slope, st), "glowtts_pwg_disc_first_bwd")
+    if not freeze:
+        wgrad(0, wav, dpre, 1, C)
+    return dwav, grads
+
+
+class _Score(torch.autograd.Function):
+    """scores = PWGDiscriminator.score(wav): forward and backward are the HIP launches of csrc/pwg_disc_ops.hip.  `shared`: a forward that was already run on
+    this waveform with these parameters (`PWGDiscriminator.score_pair`) - no forward launch is made then.  freeze: no parameter gradients."""
+
+    @staticmethod
+    def forward(ctx, disc, wav, freeze, shared, *params):
+        if shared is None:
+            disc._build_images({k: t.detach() for k, t in zip(disc.params, params)})
+            shared = pwg_disc_forward(disc, wav.detach())
+        ctx.disc, ctx.fwd, ctx.freeze, ctx.n = disc, shared, bool(freeze), len(params)
+        return shared["scores"].clone()
+
+    @staticmethod
+    def backward(ctx, dscores):
+        dwav, grads = pwg_disc_backward(ctx.disc, ctx.fwd, dscores, ctx.freeze)
+        ctx.fwd = None
+        return (None, dwav, None, None) + (tuple(grads[k] for k in ctx.disc.params) if not ctx.freeze else (None,) * ctx.n)
+
+
+class PWGDiscriminator:
+    """PWGDiscriminator(hp, device, state_dict=None, trainable=True, seed=0).score(wav [B, T], freeze=False) -> scores [B, T], one per sample, every row of
+    the full length T.  The sizes come from the yaml block `Vocoder.Train.Discriminator` (absent: the defaults).  `params` holds float32 device leaves in
+    `pwg_disc_expected_shapes`' names - from `state_dict` (`pwg_disc_load`) or, without one, `pwg_disc_init(geo, seed)`; the packed and transposed weight
+    images are rebuilt from them at every call (an optimizer step writes the leaves in place).  The backward yields d wav and, unless `freeze`, the
+    parameter gradients.  A row's scores and its d wav are bit-identical alone, in any batch and from run to run."""
+
+    def __init__(self, hp, device="cuda:0", state_dict=None, trainable=True, seed=0):
+        self.geo = geo = pwg_disc_geometry(hp)                      # before anything touches the device
+        self.trainable = bool(trainable)
+        w = pwg_disc_load(state_dict, geo) if state_dict is not None else pwg_disc_init(geo, seed)
+        if not _lib.lib().glowtts_pwg_disc_supported(geo["C"], geo["layers"], max(geo["dilations"])):
+            raise ValueError(f"the {DISC_KEY} block's sizes {geo} are not supported by the kernels")
+        self.device = torch.device(device)
+        self.params = {k: t.to(self.device).requires_grad_(self.trainable) for k, t in w.items()}
+        self._build_images({k: t.detach() for k, t in self.params.items()})
+
+    def _build_images(self, w):
+        """The weight images in the kernels' layouts: first and last [3][C] (row = tap); a middle layer's forward image [3 C][C] (row = tap * C + input
+        channel) and its backward image [3 C][C] (row = tap * C + output channel)."""
+        n, C = self.geo["layers"], self.geo["C"]
+        dev = lambda t: t.contiguous().to(self.device)
+        self.first = (dev(w["conv_layers.0.weight"][:, 0, :].t()), dev(w["conv_layers.0.bias"]))
+        self.middle = [(dev(w[f"conv_layers.{i}.weight"].permute(2, 1, 0).reshape(3 * C, C)), dev(w[f"conv_layers.{i}.bias"]),
+                        dev(w[f"conv_layers.{i}.weight"].permute(2, 0, 1).reshape(3 * C, C))) for i in range(1, n - 1)]
+        self.last = (dev(w[f"conv_layers.{n - 1}.weight"][0].t()), dev(w[f"conv_layers.{n - 1}.bias"]))
+
+    def _check(self, wav):
+        if wav.dim() != 2 or wav.dtype != torch.float32 or not wav.is_cuda:
+            raise _lib.GlowTTSHipError(f"PWGDiscriminator: expected an fp32 device tensor [B, T] (the HIP path has no CPU fallback), got {list(wav.shape)} {wav.dtype}")
+        B, T = wav.shape
+        if B < 1 or T < 1 or not _lib.lib().glowtts_pwg_disc_work_floats(B, T, self.geo["C"]):
+            raise ValueError(f"PWGDiscriminator: a batch of {B} x {T} samples is outside 1 <= B, 1 <= T, B T < 2^31, B ceil(T / 1024) <= 65535")
+
+    def score(self, wav, freeze=False):
+        self._check(wav)
+        return _Score.apply(self, wav.contiguous(), freeze, None, *self.params.values())
+
+    def score_pair(self, real, fake):
+        """ONE forward over [real; fake] (2 B rows) -> (scores [2 B, T] whose backward yields the parameter gradients alone, p_fake [B, T] = scores[B:] whose
+        backward yields d fake alone: the data chain over the fake rows, no weight-gradient launch).  The two backwards share what the forward kept."""
+        self._check(fake)
+        if tuple(real.shape) != tuple(fake.shape):
+            raise ValueError(f"PWGDiscriminator.score_pair: real {list(real.shape)} and fake {list(fake.shape)} differ in shape")
+        B = fake.shape[0]
+        both = torch.cat([real.detach().to(device=self.device, dtype=torch.float32), fake.detach()]).contiguous()
+        self._check(both)
+        self._build_images({k: t.detach() for k, t in self.params.items()})
+        fwd = pwg_disc_forward(self, both)
+        half = {"wav": both[B:], "scores": fwd["scores"][B:], "keep": [k[B:] for k in fwd["keep"]]}
+        return _Score.apply(self, both, False, fwd, *self.params.values()), _Score.apply(self, fake.contiguous(), True, half)
+
+
+class _AdversarialMSE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, split, v0, v1, factor):
+        lib, P, N = _lib.lib(), _lib.ptr, scores.numel()
+        dp, loss = torch.empty_like(scores), torch.empty(3, dtype=torch.float32, device=scores.device)
+        work = torch.empty(4 * (-(-N // 4096)), dtype=torch.float32, device=scores.device)
+        _lib.check(lib.glowtts_pwg_disc_mse(P(scores), P(dp), P(work), P(loss), N, split, v0, v1, factor, _lib.stream()), "glowtts_pwg_disc_mse")
+        ctx.dp = dp
+        terms = loss[1:].clone()
+        ctx.mark_non_differentiable(terms)
+        return loss[0].reshape(()), terms
+
+    @staticmethod
+    def backward(ctx, g, _):
+        return ctx.dp * g.to(torch.float32), None, None, None, None
+
+
+def adversarial_mse(scores, value, factor=1.0):
+    """The least-squares adversarial loss on `pwg_disc_mse`: factor * mean((scores - value)^2) over all scores, with a backward (d scores = factor 2 (scores -
+    value) / count).  value = (v0, v1): the first half of the batch rows is held against v0, the second against v1, and the loss is the sum of the two halves'
+    means (L_D on [real; fake] with (1, 0)).  -> (loss, terms [2]: the unscaled mean of each part, the second 0 for a single value)."""
+    if scores.dim() != 2 or scores.dtype != torch.float32 or not scores.is_cuda:
+        raise _lib.GlowTTSHipError("adversarial_mse: expected fp32 device scores [B, T] (the HIP path has no CPU fallback)")
+    N = scores.numel()
+    if N < 1 or N >= 2 ** 31:
+        raise ValueError(f"adversarial_mse: {N} scores are outside 1 <= B T < 2^31")
+    if isinstance(value, (tuple, list)):
+        if len(value) != 2 or scores.shape[0] % 2:
+            raise ValueError("adversarial_mse: a pair of values needs a batch of an even number of rows ([real; fake])")
+        split, v0, v1 = N // 2, float(value[0]), float(value[1])
+    else:
+        split, v0, v1 = N, float(value), 0.0
+    return _AdversarialMSE.apply(scores.contiguous(), split, v0, v1, float(factor))

@@ -1033,6 +1033,42 @@ int glowtts_stft_loss_forward(const float *pred, const float *target, const floa
 int glowtts_stft_loss_backward(const float *keep, const float *terms, const float *grad_out, const float *window, const float *twiddle, float *work,
                                float *dpred, int B, int T, int n_fft, int win_length, int hop, float weight, int accumulate, void *stream);
 
+/* ---- The Parallel WaveGAN discriminator and the adversarial loss (csrc/pwg_disc_ops.hip; f32; additions, the ABI version stays) ----
+ * `layers` 1-D convolutions of kernel size 3 over wav [B][T], "same" zero padding, bias, LeakyReLU(slope) after all but the last: 1 -> C (dilation 1),
+ * C -> C with dilation i for i = 1 .. layers - 2, C -> 1 (dilation 1).  Activations are rows [B][T][C]; EVERY batch row is of the full length T, tiles are
+ * counted from a row's own sample 0 and every tap is masked by the row's own [0, T): a row's result does not depend on the batch around it, and nothing
+ * beyond the B T rows is read or written.  Matrix products: v_mfma_f32_16x16x4_f32.  No float atomics, fixed partitions and orders: bit-identical from run
+ * to run.  None of these functions allocates.
+ * Supported (glowtts_pwg_disc_supported, else GLOWTTS_E_ARG): C a multiple of 16 in [16, 256] whose tile of 64 stride(3 C) floats fits 160 KB (C <= 208),
+ * 3 <= layers <= 16, dilation in [1, 1024]; 1 <= B <= 65535, 1 <= T <= 2^30, B T < 2^31, B ceil(T / 1024) <= 65535.
+ *   work   glowtts_pwg_disc_work_floats() floats, 8-byte aligned: the weight gradients' splits (one per batch row and 1024 samples), the loss's block sums
+ * glowtts_pwg_disc_first      `pwg_disc_first`: wav -> out [B][T][C]; w [3][C] (row = tap), bias [C].
+ * glowtts_pwg_disc_layer      `pwg_disc_layer`: x -> out (out != x), both [B][T][C]; w [3 C][C]: row = tap * C + input channel, column = output channel.
+ * glowtts_pwg_disc_last       `pwg_disc_last`: x [B][T][C] -> scores [B][T]; w [3][C] (row = tap), bias [1].
+ * glowtts_pwg_disc_mse        `pwg_disc_mse` + `pwg_disc_mse_sum`: p, dp [N]; the scores before `split` (1 <= split <= N) are held against v0, the others
+ *                             against v1: m0 = mean (p - v0)^2 over the first part, m1 = mean (p - v1)^2 over the second (0 when split == N), float64 block
+ *                             sums added in ascending order; loss [3] = factor (m0 + m1), m0, m1; dp = factor 2 (p - v) / (the size of its part).
+ * glowtts_pwg_disc_last_bwd   `pwg_disc_last_bwd`: dp [B][T] -> dh [B][T][C], the gradient of the last hidden layer's output; w as for glowtts_pwg_disc_last.
+ * glowtts_pwg_disc_layer_bwd  `pwg_disc_layer_bwd`: dout, out [B][T][C] (the gradient of a middle layer's output, and that output: it carries the LeakyReLU
+ *                             mask) -> dx [B][T][C], the gradient of the layer's input (dx != dout); wt [3 C][C]: row = tap * C + output channel, column =
+ *                             input channel.  dpre [B][T][C] (or NULL: not wanted) receives dout (out > 0 ? 1 : slope) for the weight gradient (dpre != dout).
+ * glowtts_pwg_disc_first_bwd  `pwg_disc_first_bwd`: dout, out of layer 0 -> dwav [B][T]; dpre as above; w as for glowtts_pwg_disc_first.
+ * glowtts_pwg_disc_wgrad      `pwg_disc_wgrad` + `pwg_disc_wgrad_sum` (the kernels of glowtts_pwg_train_layer_wgrad) for ONE layer: a [B][T][Cin] its input,
+ *                             dpre [B][T][Cout], lengths [B] int32 all equal to T -> dw [Cout][Cin][3], db [Cout] in torch's layouts; overwritten.
+ *                             Cin == 1 (the first layer, a = wav) or Cout == 1 (the last, dpre = d scores) or both supported widths. */
+int glowtts_pwg_disc_supported(int C, int layers, int max_dilation);
+int64_t glowtts_pwg_disc_work_floats(int B, int T, int C);
+int glowtts_pwg_disc_first(const float *wav, const float *w, const float *bias, float *out, int B, int T, int C, float slope, void *stream);
+int glowtts_pwg_disc_layer(const float *x, const float *w, const float *bias, float *out, int B, int T, int C, int dilation, float slope, void *stream);
+int glowtts_pwg_disc_last(const float *x, const float *w, const float *bias, float *scores, int B, int T, int C, void *stream);
+int glowtts_pwg_disc_mse(const float *p, float *dp, float *work, float *loss, int64_t N, int64_t split, float v0, float v1, float factor, void *stream);
+int glowtts_pwg_disc_last_bwd(const float *dp, const float *w, float *dh, int B, int T, int C, void *stream);
+int glowtts_pwg_disc_layer_bwd(const float *dout, const float *out, const float *wt, float *dx, float *dpre, int B, int T, int C, int dilation, float slope,
+                               void *stream);
+int glowtts_pwg_disc_first_bwd(const float *dout, const float *out, const float *w, float *dwav, float *dpre, int B, int T, int C, float slope, void *stream);
+int glowtts_pwg_disc_wgrad(const float *a, const float *dpre, const int32_t *lengths, float *work, float *dw, float *db, int B, int T, int Cin, int Cout,
+                           int dilation, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
