@@ -10,7 +10,6 @@ Frame_Shift, Slaney mel filterbank, dB normalisation to +- Max_Abs_Mel), so a ge
 Fast Griffin-Lim with the momentum applied to the SIGNAL (the STFT is linear): y = x_n + alpha (x_n - x_n-1), x_n+1 = istft(|S| * Y / max(|Y|, 1e-8)) with
 Y = stft(y); two signals are kept, never a previous spectrogram, and the complex spectrum of an iteration never leaves LDS.  The waveform is still
 pre-emphasised: `audio.deemphasis` undoes that on the host before the samples are written."""
-import argparse
 import ctypes
 import hashlib
 import math
@@ -19,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib, audio, ops
+from .hparams import overlay_settings, plain_block  # noqa: F401 (plain_block: for the callers that look for it here)
 
 DEFAULT_ITERATIONS, DEFAULT_MOMENTUM = 60, 0.99
 T_BUCKET = 64                                                       # frames: the work buffers are sized for T_max rounded up to a multiple of it
@@ -167,13 +167,77 @@ class GriffinLim:
 
 
 # ================================================================================================================================================
-# Neural vocoder: the Parallel WaveGAN generator (Yamamoto et al. 2020), inference only, f32.  The network, the launch plan and the noise contract are
-# written down in DESIGN.md ("Neural vocoder"); the checkpoint layout restates the most widely used implementation's names and is UNPINNED (no such
-# checkpoint was at hand when this was written).
+# Neural vocoder: the Parallel WaveGAN generator (Yamamoto et al. 2020), f32: the frozen inference path and, with trainable=True, the training forward
+# and backward (DESIGN.md "Neural vocoder", "Training the Parallel WaveGAN generator").  The network, the launch plan and the noise contract are written
+# down there; the checkpoint layout restates the most widely used implementation's names and is UNPINNED (no such checkpoint was at hand when this was
+# written).  The state-dict finder, the weight-norm fold, the checked load and the Conv1d-default initialiser just below serve the generator and the
+# discriminator (further down) alike.
 # ================================================================================================================================================
 PWG_DEFAULTS = {"Type": "PWG", "Checkpoint_Path": None, "Layers": 30, "Stacks": 3, "Residual_Channels": 64, "Gate_Channels": 128, "Skip_Channels": 64,
                 "Aux_Context_Window": 2, "Upsample_Scales": [4, 4, 4, 4]}
 PWG_TILE, PWG_MAX_CHANNELS, PWG_MAX_DILATION, PWG_MAX_SCALE, PWG_MAX_SCALES, PWG_MAX_CTX, PWG_LDS = 64, 256, 1024, 16, 8, 16, 160 * 1024
+
+
+def lds_row_stride(K):
+    """The stride in floats of an LDS row of K floats whose quarter is odd (`xs_stride_of` of csrc/pwg_common.h)"""
+    return K if (K // 4) % 2 else K + 4
+
+
+def find_state_dict(obj, paths, mine, error):
+    """The first dict for which `mine` holds among those that the key paths `paths` reach inside `obj` (what torch.load returned); none: ValueError(error)."""
+    for path in paths:
+        d = obj
+        for k in path:
+            d = d.get(k) if isinstance(d, dict) else None
+        if isinstance(d, dict) and mine(d):
+            return d
+    raise ValueError(error)
+
+
+def fold_weight_norm(sd, noun):
+    """Folds the weight-norm pairs (`weight_g` / `weight_v`) of the state dict `sd` in place into plain `weight`s, in float64"""
+    for kg in [k for k in sd if k.endswith(".weight_g")]:
+        base = kg[:-len("_g")]
+        if base + "_v" not in sd:
+            raise ValueError(f"{noun} checkpoint: {kg} has no {base}_v beside it")
+        if base in sd:
+            raise ValueError(f"{noun} checkpoint: {base} is given both plain and in weight-norm form")
+        g, v = sd.pop(kg).double(), sd.pop(base + "_v").double()
+        norm = v.reshape(v.shape[0], -1).norm(dim=1).reshape([-1] + [1] * (v.dim() - 1))
+        sd[base] = v * (g.reshape(norm.shape) / norm)
+
+
+def checked_load(found, want, noun, model, block):
+    """-> {key: float32 host tensor} with exactly the keys of `want` (key -> shape) from the state dict `found` of a `model` (weight-norm pairs are folded
+    once); a missing, surplus or wrongly shaped tensor raises a ValueError naming the key.  `noun` names the checkpoint, `block` the yaml block of the sizes."""
+    sd = dict(found)
+    fold_weight_norm(sd, noun)
+    for k in want:
+        if k not in sd:
+            raise ValueError(f"{noun} checkpoint: missing key {k}")
+    for k in sd:
+        if k not in want:
+            raise ValueError(f"{noun} checkpoint: surplus key {k} (not part of a {model} of the {block} block's sizes)")
+    out = {}
+    for k, shape in want.items():
+        t = sd[k]
+        if not torch.is_tensor(t) or tuple(t.shape) != shape:
+            raise ValueError(f"{noun} checkpoint: {k} has shape {tuple(getattr(t, 'shape', ()))}, the {block} block's sizes need {shape}")
+        out[k] = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
+    return out
+
+
+def conv_default_init(shapes, seed, constant=lambda k, shape: None):
+    """A fresh state dict of the names and shapes `shapes`: torch.nn.Conv1d's default rule per tensor - uniform in +- 1 / sqrt(fan_in), weights and biases
+    alike - drawn in the order of `shapes` on a host generator seeded with `seed`; a tensor that `constant(key, shape)` gives is taken as it is, undrawn."""
+    g = torch.Generator().manual_seed(int(seed))
+    sd = {}
+    for k, shape in shapes.items():
+        sd[k] = constant(k, shape)
+        if sd[k] is None:
+            fan_in = math.prod(shapes[k[:-len("bias")] + "weight"][1:]) if k.endswith(".bias") else math.prod(shape[1:])
+            sd[k] = (torch.rand(shape, generator=g, dtype=torch.float32) * 2.0 - 1.0) / math.sqrt(fan_in)
+    return sd
 
 
 def pwg_settings(hp):
@@ -211,7 +275,7 @@ def pwg_geometry(hp):
     if math.prod(scales) != hop:
         raise ValueError(f"Vocoder.Upsample_Scales = {scales} multiply to {math.prod(scales)}, Sound.Frame_Shift is {hop}: the vocoder must produce one hop per frame")
     K = 3 * R + A
-    lds = 4 * PWG_TILE * ((K if (K // 4) % 2 else K + 4) + (0 if R <= 64 else R + 4))
+    lds = 4 * PWG_TILE * (lds_row_stride(K) + (0 if R <= 64 else R + 4))
     if lds > PWG_LDS:
         raise ValueError(f"Vocoder.Residual_Channels = {R} with Sound.Mel_Dim = {A}: a layer's tile of {lds} bytes exceeds the {PWG_LDS} bytes of LDS")
     return {"layers": layers, "stacks": stacks, "R": R, "G": G, "S": S, "A": A, "ctx": ctx, "scales": scales, "hop": hop, "dilations": dilations}
@@ -240,64 +304,28 @@ def pwg_expected_shapes(geo):
 
 def pwg_find_state_dict(obj):
     """The generator's state dict inside what torch.load returned: at the top level or under `generator` / `Generator`, possibly inside `model`."""
-    for path in ((), ("generator",), ("Generator",), ("model",), ("model", "generator"), ("model", "Generator")):
-        d = obj
-        for k in path:
-            d = d.get(k) if isinstance(d, dict) else None
-        if isinstance(d, dict) and any(str(k).startswith("first_conv.") for k in d):
-            return d
-    raise ValueError("no Parallel WaveGAN generator state dict found (looked for `first_conv.*` at the top level, under generator / Generator and inside model)")
+    return find_state_dict(obj, ((), ("generator",), ("Generator",), ("model",), ("model", "generator"), ("model", "Generator")),
+                           lambda d: any(str(k).startswith("first_conv.") for k in d),
+                           "no Parallel WaveGAN generator state dict found (looked for `first_conv.*` at the top level, under generator / Generator and inside model)")
 
 
 def pwg_load(obj, geo):
-    """-> {key: float32 host tensor} with exactly the keys of `pwg_expected_shapes`: weight-norm pairs (`weight_g` / `weight_v`) are folded once, in float64;
-    a missing, surplus or wrongly shaped tensor raises a ValueError naming the key."""
-    sd = dict(pwg_find_state_dict(obj))
-    for kg in [k for k in sd if k.endswith(".weight_g")]:
-        base = kg[:-len("_g")]
-        if base + "_v" not in sd:
-            raise ValueError(f"vocoder checkpoint: {kg} has no {base}_v beside it")
-        if base in sd:
-            raise ValueError(f"vocoder checkpoint: {base} is given both plain and in weight-norm form")
-        g, v = sd.pop(kg).double(), sd.pop(base + "_v").double()
-        norm = v.reshape(v.shape[0], -1).norm(dim=1).reshape([-1] + [1] * (v.dim() - 1))
-        sd[base] = v * (g.reshape(norm.shape) / norm)
-    want = pwg_expected_shapes(geo)
-    for k in want:
-        if k not in sd:
-            raise ValueError(f"vocoder checkpoint: missing key {k}")
-    for k in sd:
-        if k not in want:
-            raise ValueError(f"vocoder checkpoint: surplus key {k} (not part of a generator of the Vocoder block's sizes)")
-    out = {}
-    for k, shape in want.items():
-        t = sd[k]
-        if not torch.is_tensor(t) or tuple(t.shape) != shape:
-            raise ValueError(f"vocoder checkpoint: {k} has shape {tuple(getattr(t, 'shape', ()))}, the Vocoder block's sizes need {shape}")
-        out[k] = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
-    return out
+    """-> {key: float32 host tensor} with exactly the keys of `pwg_expected_shapes`: weight-norm pairs are folded once, in float64 (`fold_weight_norm`);
+    a missing, surplus or wrongly shaped tensor raises a ValueError naming the key (`checked_load`)."""
+    return checked_load(pwg_find_state_dict(obj), pwg_expected_shapes(geo), "vocoder", "generator", "Vocoder")
 
 
 def pwg_init(geo, seed=0):
-    """A fresh generator's state dict (the names and shapes of `pwg_expected_shapes`, plain weights): torch.nn.Conv1d's default rule per tensor - uniform
-    in +- 1 / sqrt(fan_in), weights and biases alike - drawn in the order of `pwg_expected_shapes` on a host generator seeded with `seed`; the FIR of
-    scale s starts as the moving average 1 / (2 s + 1)."""
-    g = torch.Generator().manual_seed(int(seed))
-    shapes, sd = pwg_expected_shapes(geo), {}
-    for k, shape in shapes.items():
-        if ".up_layers." in k:
-            sd[k] = torch.full(shape, 1.0 / shape[-1], dtype=torch.float32)
-            continue
-        fan_in = math.prod(shapes[k[:-len("bias")] + "weight"][1:]) if k.endswith(".bias") else math.prod(shape[1:])
-        sd[k] = (torch.rand(shape, generator=g, dtype=torch.float32) * 2.0 - 1.0) / math.sqrt(fan_in)
-    return sd
+    """A fresh generator's state dict (the names and shapes of `pwg_expected_shapes`, plain weights): `conv_default_init`; the FIR of scale s starts as the
+    moving average 1 / (2 s + 1)."""
+    return conv_default_init(pwg_expected_shapes(geo), seed, lambda k, shape: torch.full(shape, 1.0 / shape[-1], dtype=torch.float32) if ".up_layers." in k else None)
 
 
 def pwg_train_geometry(geo):
     """Raises ValueError naming the yaml keys when the backward's LDS tiles (larger than the forward's) do not fit; construction with trainable=True only."""
     R, S, A = geo["R"], geo["S"], geo["A"]
     K = 3 * R + A
-    gate, data = 4 * PWG_TILE * ((K if (K // 4) % 2 else K + 4) + R + S + 4), 4 * PWG_TILE * (6 * R + 4)
+    gate, data = 4 * PWG_TILE * (lds_row_stride(K) + R + S + 4), 4 * PWG_TILE * (6 * R + 4)
     if max(gate, data) > PWG_LDS:
         raise ValueError(f"Vocoder.Residual_Channels = {R} with Vocoder.Skip_Channels = {S} and Sound.Mel_Dim = {A}: training needs tiles of {gate} and {data} "
                          f"bytes, more than the {PWG_LDS} bytes of LDS (inference supports these sizes, trainable=True does not)")
@@ -698,61 +726,29 @@ DISC_DEFAULTS = {"Start_Step": 100000, "Lambda_Adversarial": 4.0, "Learning_Rate
 DISC_MAX_LAYERS = 16
 
 
-def plain_block(v):
-    """A parsed yaml block (nested Namespaces) as plain dicts"""
-    return {k: plain_block(x) for k, x in vars(v).items()} if isinstance(v, argparse.Namespace) else v
-
-
 def pwg_disc_settings(hp):
     """The optional yaml block `Vocoder.Train.Discriminator` over DISC_DEFAULTS (absent block: None), checked: a ValueError names every unknown or bad key."""
     block = getattr(getattr(getattr(hp, "Vocoder", None), "Train", None), "Discriminator", None)
     if block is None:
         return None
-    given = plain_block(block) or {}
-    if not isinstance(given, dict):
-        raise ValueError(f"{DISC_KEY} must be a mapping, got {given!r}")
-    unknown = sorted(set(given) - set(DISC_DEFAULTS))
-    if unknown:
-        raise ValueError("unknown key {}.{} (known: {})".format(DISC_KEY, unknown[0], ", ".join(DISC_DEFAULTS)))
-    decay = given.get("Learning_Rate_Decay") or {}
-    if not isinstance(decay, dict) or set(decay) - {"Step", "Gamma"}:
-        bad_sub = sorted(set(decay) - {"Step", "Gamma"})[0] if isinstance(decay, dict) else decay
-        raise ValueError("unknown key {}.Learning_Rate_Decay.{} (known: Step, Gamma)".format(DISC_KEY, bad_sub))
-    s = dict(DISC_DEFAULTS, **given)
-    s["Learning_Rate_Decay"] = dict(DISC_DEFAULTS["Learning_Rate_Decay"], **decay)
+    whole = lambda v: int(v) == v
 
-    def ok(fn, v):
-        try:
-            return bool(fn(v))
-        except (TypeError, ValueError):
-            return False
-    bad = []
-    if not ok(lambda v: int(v) == v and int(v) >= 0, s["Start_Step"]):
-        bad.append("{}.Start_Step = {} (an integer, at least 0)".format(DISC_KEY, s["Start_Step"]))
-    if not ok(lambda v: float(v) >= 0, s["Lambda_Adversarial"]):
-        bad.append("{}.Lambda_Adversarial = {} (not negative)".format(DISC_KEY, s["Lambda_Adversarial"]))
-    for k in ("Learning_Rate", "Epsilon", "Gradient_Norm"):
-        if not ok(lambda v: float(v) > 0, s[k]):
-            bad.append("{}.{} = {} (positive)".format(DISC_KEY, k, s[k]))
-    d = s["Learning_Rate_Decay"]
-    if not ok(lambda v: int(v["Step"]) >= 1 and 0 < float(v["Gamma"]) <= 1, d):
-        bad.append("{}.Learning_Rate_Decay = {{Step: {}, Gamma: {}}} (Step >= 1, 0 < Gamma <= 1)".format(DISC_KEY, d.get("Step"), d.get("Gamma")))
-    if not ok(lambda v: int(v) == v and 3 <= int(v) <= DISC_MAX_LAYERS, s["Layers"]):
-        bad.append("{}.Layers = {} (an integer in [3, {}])".format(DISC_KEY, s["Layers"], DISC_MAX_LAYERS))
-    if not ok(lambda v: int(v) == v and int(v) >= 16 and int(v) % 16 == 0 and pwg_disc_lds(int(v)) <= PWG_LDS and int(v) <= PWG_MAX_CHANNELS, s["Channels"]):
-        bad.append("{}.Channels = {} (a multiple of 16 in [16, {}]: a tile of 64 rows x 3 Channels floats must fit the {} bytes of LDS)".format(
-            DISC_KEY, s["Channels"], pwg_disc_max_channels(), PWG_LDS))
-    if not ok(lambda v: 0 <= float(v) < 1, s["Negative_Slope"]):
-        bad.append("{}.Negative_Slope = {} (in [0, 1): the backward reads the LeakyReLU mask from the layer's output)".format(DISC_KEY, s["Negative_Slope"]))
-    if bad:
-        raise ValueError("the vocoder trainer does not support " + "; ".join(bad))
-    return s
+    def rules(s, need):
+        need("Start_Step", lambda v: whole(v) and int(v) >= 0, "an integer, at least 0")
+        need("Lambda_Adversarial", lambda v: float(v) >= 0, "not negative")
+        for k in ("Learning_Rate", "Epsilon", "Gradient_Norm"):
+            need(k, lambda v: float(v) > 0, "positive")
+        need("Learning_Rate_Decay", lambda v: int(v["Step"]) >= 1 and 0 < float(v["Gamma"]) <= 1, "Step >= 1, 0 < Gamma <= 1")
+        need("Layers", lambda v: whole(v) and 3 <= int(v) <= DISC_MAX_LAYERS, "an integer in [3, {}]".format(DISC_MAX_LAYERS))
+        need("Channels", lambda v: whole(v) and int(v) >= 16 and int(v) % 16 == 0 and pwg_disc_lds(int(v)) <= PWG_LDS and int(v) <= PWG_MAX_CHANNELS,
+             "a multiple of 16 in [16, {}]: a tile of 64 rows x 3 Channels floats must fit the {} bytes of LDS".format(pwg_disc_max_channels(), PWG_LDS))
+        need("Negative_Slope", lambda v: 0 <= float(v) < 1, "in [0, 1): the backward reads the LeakyReLU mask from the layer's output")
+    return overlay_settings(block, DISC_DEFAULTS, DISC_KEY, "vocoder", rules)
 
 
 def pwg_disc_lds(C):
     """Bytes of LDS of a middle layer's tile, forward and backward alike: 64 rows of 3 C floats at a stride whose quarter is odd."""
-    K = 3 * C
-    return 4 * PWG_TILE * (K if (K // 4) % 2 else K + 4)
+    return 4 * PWG_TILE * lds_row_stride(3 * C)
 
 
 def pwg_disc_max_channels():
@@ -779,53 +775,20 @@ def pwg_disc_expected_shapes(geo):
 def pwg_disc_init(geo, seed=0):
     """A fresh discriminator's state dict: torch.nn.Conv1d's default rule per tensor - uniform in +- 1 / sqrt(fan_in), weights and biases alike - drawn in
     the order of `pwg_disc_expected_shapes` on a host generator seeded with `seed` (the pattern of `pwg_init`)."""
-    g = torch.Generator().manual_seed(int(seed))
-    shapes, sd = pwg_disc_expected_shapes(geo), {}
-    for k, shape in shapes.items():
-        fan_in = math.prod(shapes[k[:-len("bias")] + "weight"][1:]) if k.endswith(".bias") else math.prod(shape[1:])
-        sd[k] = (torch.rand(shape, generator=g, dtype=torch.float32) * 2.0 - 1.0) / math.sqrt(fan_in)
-    return sd
+    return conv_default_init(pwg_disc_expected_shapes(geo), seed)
 
 
 def pwg_disc_find_state_dict(obj):
     """The discriminator's state dict inside what torch.load returned: under `discriminator` / `Discriminator`, possibly inside `model`, or at the top level."""
-    for path in (("discriminator",), ("Discriminator",), ("model", "discriminator"), ("model", "Discriminator"), (), ("model",)):
-        d = obj
-        for k in path:
-            d = d.get(k) if isinstance(d, dict) else None
-        if isinstance(d, dict) and any(str(k).startswith("conv_layers.0.weight") for k in d) and not any(str(k).startswith("first_conv.") for k in d):
-            return d
-    raise ValueError("no Parallel WaveGAN discriminator state dict found (looked for `conv_layers.0.weight*` under discriminator / Discriminator, inside model "
-                     "and at the top level)")
+    return find_state_dict(obj, (("discriminator",), ("Discriminator",), ("model", "discriminator"), ("model", "Discriminator"), (), ("model",)),
+                           lambda d: any(str(k).startswith("conv_layers.0.weight") for k in d) and not any(str(k).startswith("first_conv.") for k in d),
+                           "no Parallel WaveGAN discriminator state dict found (looked for `conv_layers.0.weight*` under discriminator / Discriminator, inside model "
+                           "and at the top level)")
 
 
 def pwg_disc_load(obj, geo):
-    """-> {key: float32 host tensor} with exactly the keys of `pwg_disc_expected_shapes`: weight-norm pairs (`weight_g` / `weight_v`) are folded once, in
-    float64, exactly as `pwg_load` folds them; a missing, surplus or wrongly shaped tensor raises a ValueError naming the key."""
-    sd = dict(pwg_disc_find_state_dict(obj))
-    for kg in [k for k in sd if k.endswith(".weight_g")]:
-        base = kg[:-len("_g")]
-        if base + "_v" not in sd:
-            raise ValueError(f"discriminator checkpoint: {kg} has no {base}_v beside it")
-        if base in sd:
-            raise ValueError(f"discriminator checkpoint: {base} is given both plain and in weight-norm form")
-        g, v = sd.pop(kg).double(), sd.pop(base + "_v").double()
-        norm = v.reshape(v.shape[0], -1).norm(dim=1).reshape([-1] + [1] * (v.dim() - 1))
-        sd[base] = v * (g.reshape(norm.shape) / norm)
-    want = pwg_disc_expected_shapes(geo)
-    for k in want:
-        if k not in sd:
-            raise ValueError(f"discriminator checkpoint: missing key {k}")
-    for k in sd:
-        if k not in want:
-            raise ValueError(f"discriminator checkpoint: surplus key {k} (not part of a discriminator of the {DISC_KEY} block's sizes)")
-    out = {}
-    for k, shape in want.items():
-        t = sd[k]
-        if not torch.is_tensor(t) or tuple(t.shape) != shape:
-            raise ValueError(f"discriminator checkpoint: {k} has shape {tuple(getattr(t, 'shape', ()))}, the {DISC_KEY} block's sizes need {shape}")
-        out[k] = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
-    return out
+    """-> {key: float32 host tensor} with exactly the keys of `pwg_disc_expected_shapes`, as `pwg_load` gives the generator's (`checked_load`)."""
+    return checked_load(pwg_disc_find_state_dict(obj), pwg_disc_expected_shapes(geo), "discriminator", "discriminator", DISC_KEY)
 
 
 def pwg_disc_forward(disc, wav, alloc=None):

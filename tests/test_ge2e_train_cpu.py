@@ -167,7 +167,9 @@ def test_yaml_defaults_apply_when_the_block_is_absent():
     for k, v in DEFAULTS.items():
         assert "#     {}:".format(k) in text, k
     for bad, key in (({"Speakers": 1}, "Train.Speakers"), ({"Utterances": 1}, "Train.Utterances"), ({"Slice_Length": {"Min": 9, "Max": 3}}, "Train.Slice_Length"),
-                     ({"Learning_Rate": 0}, "Train.Learning_Rate"), ({"Speaker": 3}, "Train.Speaker")):
+                     ({"Learning_Rate": 0}, "Train.Learning_Rate"), ({"Speaker": 3}, "Train.Speaker"),
+                     ({"Learning_Rate": "fast"}, r"Speaker_Embedding\.GE2E\.Train\.Learning_Rate = fast"),             # a wrongly typed value is a bad value
+                     ({"Slice_Length": {"Bogus": 1}}, r"unknown key Speaker_Embedding\.GE2E\.Train\.Slice_Length\.Bogus")):
         d["Speaker_Embedding"]["GE2E"]["Train"] = bad
         with pytest.raises(ValueError, match=key):
             train_settings(Recursive_Parse(copy.deepcopy(d)))

@@ -166,7 +166,9 @@ def test_train_settings_defaults_and_bad_settings():
     for train, word in (({"Batch_Size": 0}, "Vocoder.Train.Batch_Size"), ({"Learning_Rate": -1.0}, "Vocoder.Train.Learning_Rate"),
                         ({"Learning_Rate_Decay": {"Gamma": 2.0}}, "Vocoder.Train.Learning_Rate_Decay"), ({"Bogus": 1}, "Vocoder.Train.Bogus"),
                         ({"Segment_Frames": 40}, "Vocoder.Train.STFT_Resolutions"),                     # 600 samples: too short for n_fft = 2048
-                        ({"Segment_Frames": 40, "STFT_Resolutions": [[300, 50, 240]]}, "Vocoder.Train.STFT_Resolutions")):
+                        ({"Segment_Frames": 40, "STFT_Resolutions": [[300, 50, 240]]}, "Vocoder.Train.STFT_Resolutions"),
+                        ({"Learning_Rate": "fast"}, "Vocoder.Train.Learning_Rate = fast"),                  # a wrongly typed value is a bad value
+                        ({"Learning_Rate_Decay": {"Bogus": 1}}, "unknown key Vocoder.Train.Learning_Rate_Decay.Bogus")):
         with pytest.raises(ValueError) as e:
             T.train_settings(_hp(train))
         assert word in str(e.value), (train, str(e.value))
