@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include "../../include/glowtts_hip.h"
 #include "launch_log.h"
+#include "device_common.h"
 
 extern "C" int glowtts_abi_version(void) { return GLOWTTS_ABI_VERSION; }
 
@@ -89,14 +90,12 @@ extern "C" int glowtts_launch_log_dump(char* buf, int buflen)
 
 // ---- sustained matrix clock (measurement aid for bench.py's roofline, see include/glowtts_hip.h) ----
 namespace {
-typedef float probe_f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 probe_bf16x8 __attribute__((ext_vector_type(8)));
 __global__ __launch_bounds__(256) void mfma_clock_probe_kernel(long long* out, int iters)
 {
     // four independent accumulators per wave, one wave per SIMD: the matrix pipe issues back to back (32 clk per MFMA), operands are
     // pseudo-random bf16 (zero operands draw less power and clock higher)
-    probe_f32x16 acc[4] = {};
-    probe_bf16x8 a, b;
+    f32x16 acc[4] = {};
+    bf16x8 a, b;
     uint32_t h = threadIdx.x * 0x9E3779B1u + blockIdx.x * 0x85EBCA6Bu + 12345u;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -125,7 +124,7 @@ extern "C" int glowtts_debug_stamp(long long* slot, void* stream)
 {
     if (!slot) return GLOWTTS_E_ARG;
     hipLaunchKernelGGL(stamp_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), slot);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 // One 31-bit dropout seed word per training step from a counter in device memory (see glowtts_step_seed in the header)
@@ -135,7 +134,7 @@ __global__ void step_seed_kernel(uint32_t* state, uint32_t* out)
         const uint32_t c = state[0] + 1u;
         state[0] = c;
         uint32_t h = state[1] + c * 0x9E3779B9u;
-        h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+        h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;      // fmix (device_common.h) spelled out: the call compiles to other machine code here
         out[0] = h & 0x7FFFFFFFu;
     }
 }
@@ -144,7 +143,7 @@ extern "C" int glowtts_step_seed(uint32_t* state, uint32_t* out, void* stream)
 {
     if (!state || !out) return GLOWTTS_E_ARG;
     hipLaunchKernelGGL(step_seed_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), state, out);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_mfma_clock_probe(long long* out, int nwg, int iters, int* wall_khz, void* stream)
@@ -157,5 +156,5 @@ extern "C" int glowtts_mfma_clock_probe(long long* out, int nwg, int iters, int*
     }
     GLOWTTS_NOTE_STATIC("mfma_clock_probe");
     hipLaunchKernelGGL(mfma_clock_probe_kernel, dim3(nwg), dim3(256), 0, static_cast<hipStream_t>(stream), out, iters);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }

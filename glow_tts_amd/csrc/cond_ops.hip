@@ -23,12 +23,6 @@ constexpr int CO_MAXD = 512;         // inputs per conv
 constexpr int CT_ROWS = 32;          // rows n per workgroup
 constexpr int CT_NT = 256;
 
-__device__ __forceinline__ float co_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // LDS layout shared by both kernels: sv [CT_ROWS][D + 4] (rows of v), svec [BP][D + 4] (zero rows past B), ssc [CT_ROWS] / sinv [CT_ROWS]
 // (row pitch D + 4 floats: consecutive rows start 4 banks apart, 16-byte reads of 8 consecutive rows are conflict-free)
 __device__ __forceinline__ void co_stage(const float* __restrict__ v, const float* __restrict__ vec, float* sv, float* svec, float* ssq, int n0, int N, int D, int B, int BP)
@@ -48,7 +42,7 @@ __device__ __forceinline__ void co_stage(const float* __restrict__ v, const floa
             *reinterpret_cast<float4*>(sv + r * P + 4 * q) = x;
             s += x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w;
         }
-        s = co_wave_sum(s);
+        s = wave_sum(s);
         if (lane == 0) ssq[r] = s;
     }
 }
@@ -231,7 +225,7 @@ extern "C" int glowtts_cond_linear_fwd(const float* v, const float* g, const flo
         case 5: CF_LAUNCH(5); break; case 6: CF_LAUNCH(6); break; case 7: CF_LAUNCH(7); break; default: CF_LAUNCH(8); break;
     }
 #undef CF_LAUNCH
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int64_t glowtts_cond_linear_bwd_scratch_floats(int N, int D, int B) { return (int64_t)((N + CT_ROWS - 1) / CT_ROWS) * B * D; }
@@ -257,7 +251,7 @@ extern "C" int glowtts_cond_linear_bwd(const float* dcond, int64_t ldd, const fl
         const int64_t n = (int64_t)B * D;
         hipLaunchKernelGGL(cond_dvec_kernel, dim3((int)((n + 63) / 64)), dim3(1024), 0, s, scratch, dvec, nwg, n);
     }
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 // The conditioning gradient's fixed-point accumulators (device_common.h fx_atomic_add) -> float; a poisoned accumulator (non-finite / out-of-range addend) reads NaN.
@@ -277,5 +271,5 @@ extern "C" int glowtts_fx_to_float(const int64_t* acc, float* out, int64_t n, vo
     const long g = (n + 255) / 256;
     GLOWTTS_NOTE_STATIC("fx_to_float");
     hipLaunchKernelGGL(fx_to_float_kernel, dim3((int)(g > 4096 ? 4096 : g)), dim3(256), 0, static_cast<hipStream_t>(stream), reinterpret_cast<const long long*>(acc), out, (long)n);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }

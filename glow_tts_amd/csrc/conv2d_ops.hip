@@ -270,7 +270,7 @@ template <typename CT, int NI, int WM, int NSUB>
 int c2d_launch(const c2d_args& a, int tiles, int ny, hipStream_t s)
 {
     hipLaunchKernelGGL((c2d_gemm_kernel<CT, NI, WM, NSUB>), dim3(tiles, ny), dim3(WM * 64), 0, s, a);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 template <typename CT>
@@ -671,7 +671,7 @@ extern "C" int glowtts_conv3x3s2_pack(const glowtts_c2d_pack_job* dev_jobs, int 
     GLOWTTS_NOTE_STATIC("conv3x3s2_pack");
     if (precision == GLOWTTS_BF16) hipLaunchKernelGGL(c2d_pack_kernel<__bf16>, dim3(total_blocks), dim3(256), 0, s, dev_jobs, njobs);
     else                           hipLaunchKernelGGL(c2d_pack_kernel<float>, dim3(total_blocks), dim3(256), 0, s, dev_jobs, njobs);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_conv3x3s2_fwd(const float* x, const float* w, const void* img_fwd, float* y, int B, int H, int W, int Ci, int Co, int relu,
@@ -685,7 +685,7 @@ extern "C" int glowtts_conv3x3s2_fwd(const float* x, const float* w, const void*
         GLOWTTS_NOTE_STATIC("conv3x3s2_first_fwd");
         const long threads = (long)B * Ho * Wo * (Co / 4);
         hipLaunchKernelGGL(c2d_first_fwd_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, x, w, y, B, H, W, Ho, Wo, Co, relu);
-        return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+        RET_LAUNCH();
     }
     if (!img_fwd) return GLOWTTS_E_ARG;
     const int KC = precision == GLOWTTS_BF16 ? 32 : 16;
@@ -752,7 +752,7 @@ extern "C" int glowtts_conv3x3s2_wgrad(const float* x, const float* dpre, float*
             done = true;
         }
         hipLaunchKernelGGL(c2d_first_wgrad_kernel, dim3(ns), dim3(512), 512 * 37 * sizeof(float), s, x, dpre, partial, B, H, W, Ho, Wo, Co);
-        return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+        RET_LAUNCH();
     }
     c2d_wgrad_args a;
     a.x = x; a.dpre = dpre; a.partial = partial;
@@ -772,7 +772,7 @@ extern "C" int glowtts_conv3x3s2_wgrad(const float* x, const float* dpre, float*
         default: return GLOWTTS_E_ARG;
     }
 #undef C2D_WG
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_conv3x3s2_wgrad_reduce(const glowtts_c2d_reduce_job* jobs /* host */, int njobs, void* stream)
@@ -789,5 +789,5 @@ extern "C" int glowtts_conv3x3s2_wgrad_reduce(const glowtts_c2d_reduce_job* jobs
     t.n = njobs;
     GLOWTTS_NOTE_STATIC("conv3x3s2_wgrad_reduce");
     hipLaunchKernelGGL(c2d_reduce_kernel, dim3(b0), dim3(256), 0, static_cast<hipStream_t>(stream), t);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }

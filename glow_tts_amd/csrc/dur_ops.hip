@@ -146,7 +146,6 @@ __global__ __launch_bounds__(256) void prior_split_bwd_kernel(const float* __res
     }
 }
 
-#define RET_LAUNCH() return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH
 }  // namespace
 
 extern "C" int glowtts_dur_proj_supported(int C) { return C >= 4 && C <= 256 * DP_MAXCH && (C & 3) == 0; }

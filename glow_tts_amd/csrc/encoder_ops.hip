@@ -8,24 +8,9 @@
 #include "../../include/glowtts_hip.h"
 #include "tunable.h"
 #include "launch_log.h"
+#include "device_common.h"
 
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float drop_scale(uint32_t seed, uint32_t id, float p, float inv_keep) {
-    uint32_t h = id * 0x9E3779B1u + seed;
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-    return ((h >> 8) * (1.0f / 16777216.0f) >= p) ? inv_keep : 0.f;
-}
 
 constexpr int LN_MAXK = 16;          // channels per lane: C <= 1024
 
@@ -33,8 +18,6 @@ constexpr int LN_MAXK = 16;          // channels per lane: C <= 1024
 // y = rowmask * dropout( relu?( LayerNorm(a + b) * gamma + beta ) ),  one wavefront per row.
 // Keeps s = a + b (when b is given) and (mean, rstd) per row for the backward.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint16_t f2bf(float v) { const __bf16 b = (__bf16)v; return *reinterpret_cast<const uint16_t*>(&b); }
-__device__ __forceinline__ float bf2f(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
 
 // KT > 0: C == 64 * KT exactly (192- and 256-channel rows: every row of the encoder): no per-element predicates, and EVERY load of the row -
 // a, b, gamma, beta, the row mask - is issued before the first use.  (The generic form below loads under `if (c < C)`: hipcc then branches
@@ -89,7 +72,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ a
             if (relu) o = fmaxf(o, 0.f);
             if (drop_p > 0.f) o *= drop_scale(seed, (uint32_t)(r * CC + c), drop_p, ik);
             y[r * CC + c] = o * m;
-            if (yb) yb[r * CC + c] = f2bf(o * m);          // the same rows as an MFMA operand (LDS-DMA convs read raw bf16)
+            if (yb) yb[r * CC + c] = bf16_bits(o * m);          // the same rows as an MFMA operand (LDS-DMA convs read raw bf16)
         }
         return;
     }
@@ -122,7 +105,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ a
         if (relu) o = fmaxf(o, 0.f);
         if (drop_p > 0.f) o *= drop_scale(seed, (uint32_t)(r * C + c), drop_p, ik);
         y[r * C + c] = o * m;
-        if (yb) yb[r * C + c] = f2bf(o * m);          // the same rows as an MFMA operand (LDS-DMA convs read raw bf16)
+        if (yb) yb[r * C + c] = bf16_bits(o * m);          // the same rows as an MFMA operand (LDS-DMA convs read raw bf16)
     }
 }
 
@@ -190,7 +173,7 @@ __global__ __launch_bounds__(LN_BWD_WAVES * 64) void ln_bwd_kernel(const float* 
             for (int k = 0; k < KT; ++k) {
                 const float g = rstd * (dz[k] - s1 - xh[k] * s2);
                 ds[o + 64 * k] = g;
-                if (dsb) dsb[o + 64 * k] = f2bf(gout ? (gv[k] != 0.f ? g * gate_scale : 0.f) : g);
+                if (dsb) dsb[o + 64 * k] = bf16_bits(gout ? (gv[k] != 0.f ? g * gate_scale : 0.f) : g);
             }
         }
     } else
@@ -223,7 +206,7 @@ __global__ __launch_bounds__(LN_BWD_WAVES * 64) void ln_bwd_kernel(const float* 
                 ds[r * C + c] = g;
                 // bf16 copy for the conv that produced the LayerNorm input: as is, or already through that conv's dropout / relu gate
                 // (d(pre-activation) = ds * (out != 0 ? 1 / keep : 0): saves the separate gate pass over the rows)
-                if (dsb) dsb[r * C + c] = f2bf(gate_out ? (gate_out[r * C + c] != 0.f ? g * gate_scale : 0.f) : g);
+                if (dsb) dsb[r * C + c] = bf16_bits(gate_out ? (gate_out[r * C + c] != 0.f ? g * gate_scale : 0.f) : g);
             }
         }
     }
@@ -265,13 +248,13 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const void* __restrict__ 
         const long r = (i * 4) / C;
         const float m = (rowmask ? rowmask[r] : 1.f) * scale;
         float4 d, o;
-        if (DYB) { const ushort4 t = reinterpret_cast<const ushort4*>(dy_)[i]; d = make_float4(bf2f(t.x), bf2f(t.y), bf2f(t.z), bf2f(t.w)); }
+        if (DYB) { const ushort4 t = reinterpret_cast<const ushort4*>(dy_)[i]; d = make_float4(bf16_to_f32(t.x), bf16_to_f32(t.y), bf16_to_f32(t.z), bf16_to_f32(t.w)); }
         else d = reinterpret_cast<const float4*>(dy_)[i];
         if (!out_) o = make_float4(1.f, 1.f, 1.f, 1.f);       // (no gate: the row mask alone - the backward of a conv whose output is only masked)
-        else if (OUTB) { const ushort4 t = reinterpret_cast<const ushort4*>(out_)[i]; o = make_float4(bf2f(t.x), bf2f(t.y), bf2f(t.z), bf2f(t.w)); }
+        else if (OUTB) { const ushort4 t = reinterpret_cast<const ushort4*>(out_)[i]; o = make_float4(bf16_to_f32(t.x), bf16_to_f32(t.y), bf16_to_f32(t.z), bf16_to_f32(t.w)); }
         else o = reinterpret_cast<const float4*>(out_)[i];
         const float4 z = make_float4(o.x != 0.f ? d.x * m : 0.f, o.y != 0.f ? d.y * m : 0.f, o.z != 0.f ? d.z * m : 0.f, o.w != 0.f ? d.w * m : 0.f);
-        if (DZB) { ushort4 t; t.x = f2bf(z.x); t.y = f2bf(z.y); t.z = f2bf(z.z); t.w = f2bf(z.w); reinterpret_cast<ushort4*>(dz_)[i] = t; }
+        if (DZB) { ushort4 t; t.x = bf16_bits(z.x); t.y = bf16_bits(z.y); t.z = bf16_bits(z.z); t.w = bf16_bits(z.w); reinterpret_cast<ushort4*>(dz_)[i] = t; }
         else reinterpret_cast<float4*>(dz_)[i] = z;
     }
 }
@@ -579,7 +562,6 @@ __global__ __launch_bounds__(128) void attn_bwd_rel_kernel(const float* __restri
 }
 
 inline int grid_for(long total, int per = 256, int cap = 2048) { long g = (total + per - 1) / per; return (int)(g > cap ? cap : (g < 1 ? 1 : g)); }
-#define RET_LAUNCH() return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH
 
 }  // namespace
 
@@ -702,8 +684,6 @@ extern "C" int glowtts_embedding_bwd(const int64_t* tokens, const float* drows, 
 // of a half-wave then hit 32 different banks whether they walk rows (A / K-as-B operands) or columns (V-as-B operand).
 // P stores the probabilities BEFORE dropout (the backward regenerates the keep mask from the same hash).
 // ------------------------------------------------------------------------------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 at_bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int AT_TP = 128, AT_LDP = AT_TP + 1;
 
 // BF (bf16 precision only): the same contractions on v_mfma_f32_32x32x16_bf16.  The LDS tiles stay fp32; a lane gathers the 8 consecutive
@@ -711,12 +691,12 @@ constexpr int AT_TP = 128, AT_LDP = AT_TP + 1;
 // bf16 in registers, fp32 accumulate, softmax and all element-wise arithmetic unchanged.  One bf16 MFMA does the work of 8 fp32 ones in
 // half the matrix-pipe time: the fp32 form spends 64 clk per 4096 FLOP and made these kernels matrix-pipe bound.
 template <bool BF> struct AtOp { typedef float T; static constexpr int KSTEP = 2, UNR = 4; };
-template <> struct AtOp<true> { typedef at_bf16x8 T; static constexpr int KSTEP = 16, UNR = 2; };
+template <> struct AtOp<true> { typedef bf16x8 T; static constexpr int KSTEP = 16, UNR = 2; };
 template <bool BF, class F>
 __device__ __forceinline__ typename AtOp<BF>::T at_frag(F&& f)
 {
     if constexpr (BF) {
-        at_bf16x8 v;
+        bf16x8 v;
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = (__bf16)f(e);
         return v;
@@ -753,7 +733,6 @@ __device__ __forceinline__ float half_sum(float v) {
     v += dpp_mov<DPP_ROW_MIRROR>(v);
     return v + __shfl_xor(v, 16, 64);
 }
-__device__ __forceinline__ int acc_row(int reg, int lhi) { return (reg & 3) + 8 * (reg >> 2) + 4 * lhi; }
 
 // rows [0, nrows) x D floats of a [*, ld]-strided global tile -> LDS [ROWS][LD] (rows >= nrows zero), NT threads (a workgroup, or one
 // wave with NT = 64).  The loads of a pass are issued TOGETHER, unconditionally (rows past the end re-read row 0 and are zeroed on the way to

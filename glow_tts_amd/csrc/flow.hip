@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include "../../include/glowtts_hip.h"
 #include "tunable.h"
+#include "launch_log.h"
 
 namespace {
 
@@ -117,7 +118,7 @@ int copy_half(const float* src, float* dst, long rows, int C, int n, void* s) {
     if (n & 3) return GLOWTTS_E_ARG;
     long g = (rows * (n / 4) + 255) / 256; if (g > 2048) g = 2048;
     hipLaunchKernelGGL(copy_half_kernel, dim3((int)g), dim3(256), 0, static_cast<hipStream_t>(s), src, dst, rows, C, n);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 template <typename XT>
@@ -142,7 +143,7 @@ int utt_colsum(const float* x, int64_t ldx, float* out, int64_t ldout, int B, in
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (x_bf16) hipLaunchKernelGGL(utt_colsum_kernel<__bf16>, grid, dim3(256), 0, s, reinterpret_cast<const __bf16*>(x), (long)ldx, out, (long)ldout, rows_per_utt, n, perm, perm_h);
     else hipLaunchKernelGGL(utt_colsum_kernel<float>, grid, dim3(256), 0, s, x, (long)ldx, out, (long)ldout, rows_per_utt, n, perm, perm_h);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 }  // namespace

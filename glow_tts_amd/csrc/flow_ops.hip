@@ -9,6 +9,7 @@
 #include "launch_log.h"
 #include "tunable.h"
 #include "actnorm_math.h"
+#include "device_common.h"
 
 namespace {
 
@@ -113,12 +114,6 @@ __global__ void inv4x4_kernel(const float* __restrict__ W, float* __restrict__ o
 // ActNorm + invertible 1x1, forward and inverse, one pass over the rows.
 // thread = (row, group g): channels {2g, 2g+1, C/2+2g, C/2+2g+1} <-> split index 0..3  (Modules.py:738-740)
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t an_pack_bf16x2(float lo, float hi) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    bf16x2 v; v[0] = (__bf16)lo; v[1] = (__bf16)hi;
-    return *reinterpret_cast<uint32_t*>(&v);
-}
-
 template <bool REVERSE>
 __global__ __launch_bounds__(256) void actnorm_inv_kernel(const float* __restrict__ xin, float* __restrict__ xout,
                                                           const float* __restrict__ logs, const float* __restrict__ bias,
@@ -157,7 +152,7 @@ __global__ __launch_bounds__(256) void actnorm_inv_kernel(const float* __restric
         *reinterpret_cast<float2*>(xout + r * C + 2 * g) = make_float2(o[0], o[1]);
         *reinterpret_cast<float2*>(xout + r * C + C2 + 2 * g) = make_float2(o[2], o[3]);
         if (!REVERSE && xpass) *reinterpret_cast<float2*>(xpass + r * C + 2 * g) = make_float2(o[0], o[1]);
-        if (!REVERSE && xa_bf) xa_bf[(r * C2 + 2 * g) >> 1] = an_pack_bf16x2(o[0], o[1]);      // x_a as bf16 rows [rows][C/2] (Start conv weight gradient operand)
+        if (!REVERSE && xa_bf) xa_bf[(r * C2 + 2 * g) >> 1] = pack_bf16x2(o[0], o[1]);      // x_a as bf16 rows [rows][C/2] (Start conv weight gradient operand)
     }
 }
 
@@ -551,7 +546,6 @@ __global__ void logdet_final_kernel(const float* __restrict__ part, float* __res
 }
 
 inline int grid_for(long total, int per = 256, int cap = 2048) { long g = (total + per - 1) / per; return (int)(g > cap ? cap : (g < 1 ? 1 : g)); }
-#define RET_LAUNCH() return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH
 
 }  // namespace
 

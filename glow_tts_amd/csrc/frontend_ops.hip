@@ -30,16 +30,10 @@
 #include <stdint.h>
 #include "../../include/glowtts_hip.h"
 #include "launch_log.h"
+#include "device_common.h"
 #include "vocoder_fft.h"
 
 namespace {
-
-__device__ __forceinline__ float fe_wave_sum(float v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
 
 struct mel_args {
     const float* x;            // [B][ldx]
@@ -101,7 +95,7 @@ __global__ __launch_bounds__(VOC_NT) void mel_analysis_kernel(const mel_args a)
             if (cnt > a.nw - off) cnt = a.nw - off;
             float acc = 0.f;
             for (int i = lane; i < cnt; i += 64) acc = fmaf(a.fb_weight[off + i], mag[first + i], acc);
-            acc = fe_wave_sum(acc);
+            acc = wave_sum(acc);
             if (lane == 0) {
                 const float db = 20.f * log10f(acc + 1e-7f);
                 const float v = (2.f * a.max_abs) * (db - a.min_db) / (-a.min_db) - a.max_abs;
@@ -168,7 +162,7 @@ __global__ __launch_bounds__(256) void yin_kernel(const yin_args a)
             }
 #pragma unroll
             for (int i = 0; i < YIN_TG; ++i) {
-                const float s = fe_wave_sum(acc[i]);
+                const float s = wave_sum(acc[i]);
                 if (lane == 0 && t0 + i < a.tau_max) d[t0 + i] = s;
             }
         }
@@ -221,7 +215,7 @@ extern "C" int glowtts_mel_analysis_f32(const float* wav, const int32_t* wav_len
     const int frames = B * T, grid = frames < 1536 ? frames : 1536;            // 6 resident workgroups (by LDS at n_fft = 2048) on each of 256 CUs
     GLOWTTS_NOTE_STATIC("frontend_mel_analysis");
     hipLaunchKernelGGL(mel_analysis_kernel, dim3(grid), dim3(VOC_NT), lds, static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_yin_f32(const float* wav, const int32_t* wav_lengths, float* pitch, float* cmnd, int B, int ldx, int T, int w_len, int w_step, int tau_min,
@@ -236,5 +230,5 @@ extern "C" int glowtts_yin_f32(const float* wav, const int32_t* wav_lengths, flo
     const int frames = B * T, grid = frames < 2048 ? frames : 2048;            // 8 workgroups of 4 waves on each of 256 CUs; more frames: strided
     GLOWTTS_NOTE_STATIC("frontend_yin");
     hipLaunchKernelGGL(yin_kernel, dim3(grid), dim3(256), (size_t)(w_len + 2 * tau_max) * 4, static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }

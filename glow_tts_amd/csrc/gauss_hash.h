@@ -2,7 +2,7 @@
 // FROZEN: a seeded mel changes if anything below changes.  tests/prior_sample_ref.py restates it (integers bit for bit, the Gaussian in float64),
 // tests/test_prior_sample_cpu.py pins golden values, DESIGN.md ("Seeded sampling") states it in words.
 //
-//   keys      k0 = fmix(s0 ^ 0x243F6A88), k1 = fmix(s1 + k0), k0 = fmix(k0 ^ k1), k2 = fmix(k1 + 0x9E3779B9)      (fmix: the murmur3 finalizer)
+//   keys      k0 = fmix(s0 ^ 0x243F6A88), k1 = fmix(s1 + k0), k0 = fmix(k0 ^ k1), k2 = fmix(k1 + 0x9E3779B9)      (fmix: the murmur3 finalizer, device_common.h)
 //             - both seed words reach every key through full avalanche rounds, asymmetrically: (a, b) / (b, a), s / s + 1 and s / s + K
 //             (K the counter's multiplier) give unrelated keys, so no pair of seeds yields equal or shifted streams (the pitfall of `id * K + seed`)
 //   counter   two consecutive frames share one Box-Muller pair:  p = (t >> 1) * C + c   (uint32 arithmetic);  m = (p ^ k0) * 0x9E3779B1
@@ -15,11 +15,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "device_common.h"
+
 namespace gauss_hash {
 
 struct Keys { uint32_t k0, k1, k2; };
-
-__host__ __device__ __forceinline__ uint32_t fmix(uint32_t h) { h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16; return h; }
 
 __host__ __device__ __forceinline__ Keys keys(uint32_t s0, uint32_t s1)
 {

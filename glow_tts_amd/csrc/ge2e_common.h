@@ -1,38 +1,26 @@
-// What the GE2E speaker encoder's inference (ge2e_ops.hip) and training (ge2e_train_ops.hip) share: the tile constants, the packed image's geometry, the
-// fixed shuffle tree, ONE LSTM cell kernel and its diagonal launch loop, and the head projection.  The training forward is the inference forward bit for bit
+// What the GE2E speaker encoder's inference (ge2e_ops.hip) and training (ge2e_train_ops.hip) share: the tile constants, the packed image's geometry,
+// ONE LSTM cell kernel and its diagonal launch loop, and the head projection.  The training forward is the inference forward bit for bit
 // because both are instantiations of the text below: every arithmetic expression of the cell and of the head's sum is spelled exactly once.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/glowtts_hip.h"
+#include "device_common.h"
 #include "launch_log.h"
 
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int TM = 16;                                    // sequences (rows) per workgroup: one MFMA tile
 constexpr int TU = 16;                                    // hidden units per workgroup (x 4 gates = 64 image columns)
 constexpr int THREADS = 256, WAVES = THREADS / 64;
 constexpr int RED_FLOATS = WAVES * 4 * TM * TU;           // the waves' partial gate sums
 
-__device__ __forceinline__ v4f mfma4(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
-
-__host__ __device__ __forceinline__ int as_stride_of(int K) { return ((K >> 2) & 1) ? K : K + 4; }      // (stride / 4) odd: 16 rows x 4 k hit distinct banks
 __host__ __device__ __forceinline__ int64_t image_offset(int layer, int Mel, int H)
 {
     return layer == 0 ? 0 : ((int64_t)(Mel + H) + (int64_t)(layer - 1) * 2 * H) * 4 * H;
 }
-int cell_lds_bytes(int Mel, int H) { return (TM * as_stride_of(Mel > H ? Mel + H : 2 * H) + RED_FLOATS) * 4; }
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);      // a fixed tree: every lane ends with the same value
-    return v;
-}
+int cell_lds_bytes(int Mel, int H) { return (TM * lds_stride_of(Mel > H ? Mel + H : 2 * H) + RED_FLOATS) * 4; }
 
 // ---- one diagonal of cells.  dynamic LDS: As [16][as] | red [WAVES][4][16 x 16] ---------------------------------------------------------------------
 // KEEP selects only where c lives and whether the activated gates are stored:
@@ -48,9 +36,9 @@ __global__ __launch_bounds__(THREADS) void ge2e_cell_kernel(const float* __restr
     const int k = kmin + blockIdx.z, t = d - k;            // the cell (uniform over the workgroup)
     const int s = blockIdx.x, n0 = blockIdx.y * TM;
     const int in = k == 0 ? Mel : H, K = in + H, G = 4 * H;
-    const int as = as_stride_of(K);
+    const int as = lds_stride_of(K);
     float* As = ge2e_smem;
-    float* red = ge2e_smem + TM * as_stride_of(Mel > H ? Mel + H : 2 * H);      // (the same offset in every launch)
+    float* red = ge2e_smem + TM * lds_stride_of(Mel > H ? Mel + H : 2 * H);      // (the same offset in every launch)
     const size_t layer_rows = (size_t)N * T;               // rows of one layer of hs
 
     // 1. gather [input | h_prev] of the tile's rows; rows beyond N and h_{-1} are zero
@@ -82,9 +70,9 @@ __global__ __launch_bounds__(THREADS) void ge2e_cell_kernel(const float* __restr
     // 2. the four gates of 16 units for 16 rows; wave w owns the k steps w, w + 4, ...
     const float* img = images + image_offset(k, Mel, H) + (size_t)s * 64 + r * 4;
     const float* aa = As + r * as + q;
-    v4f acc[4];
+    f32x4 acc[4];
 #pragma unroll
-    for (int g = 0; g < 4; ++g) acc[g] = v4f{0.f, 0.f, 0.f, 0.f};
+    for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
     for (int k0 = 4 * wave; k0 < K; k0 += 4 * WAVES) {
         const float4 w = *reinterpret_cast<const float4*>(img + (size_t)(k0 + q) * G);

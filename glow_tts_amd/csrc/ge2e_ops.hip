@@ -120,7 +120,7 @@ extern "C" int glowtts_ge2e_pack(const float* w_ih, const float* w_hh, const flo
     hipLaunchKernelGGL(ge2e_pack_kernel, dim3((unsigned)((total + THREADS - 1) / THREADS)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), w_ih, w_hh, b_ih, b_hh,
                        images + image_offset(layer, Mel, H), biases + (size_t)layer * 4 * H, in, H);
     GLOWTTS_NOTE_STATIC("ge2e_pack");
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_ge2e_forward(const float* x, const float* images, const float* biases, const float* head_w, const float* head_b, float* work, float* hs,
@@ -136,5 +136,5 @@ extern "C" int glowtts_ge2e_forward(const float* x, const float* images, const f
     hipLaunchKernelGGL(ge2e_head_kernel, dim3(N / Samples), dim3(THREADS), (size_t)(H + E + 2) * 4, s, hbuf + (size_t)(Stacks - 1) * N * T * H, head_w, head_b, e, d,
                        Samples, T, H, E);
     GLOWTTS_NOTE_STATIC("ge2e_head");
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }

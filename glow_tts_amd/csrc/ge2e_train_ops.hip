@@ -258,7 +258,7 @@ __global__ __launch_bounds__(THREADS) void ge2e_head_bwd_kernel(const float* __r
     const int m0 = (tile / tiles_n) * 16, c0 = (tile % tiles_n) * 16;
     const size_t hstride = (size_t)T * H;
     const float* hl = h_top + (size_t)(T - 1) * H;
-    v4f acc = v4f{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int k0 = 0; k0 < K; k0 += 4) {
         const int kk = k0 + q, m = m0 + r;
         float a = 0.f, b = 0.f;
@@ -308,7 +308,7 @@ __global__ __launch_bounds__(THREADS) void ge2e_cell_bwd_kernel(const float* __r
     const size_t layer_rows = (size_t)N * T;
     const float* img = images_t + image_t_offset(k, H) + s * TU + r;
 
-    v4f acc = v4f{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int seg = 0; seg < 2; ++seg) {
         // seg 0: da^k_{t+1} against W_hh^k; seg 1: da^{k+1}_t against W_ih^{k+1}
         if (seg == 0 ? t + 1 >= T : k + 1 >= Stacks) continue;                 // (uniform over the workgroup)
@@ -361,9 +361,9 @@ __global__ __launch_bounds__(THREADS) void ge2e_wgrad_kernel(const float* __rest
     const int G = 4 * H, Ka = in + H + 1;
     const int m0 = blockIdx.x * WG_TILE, c0 = blockIdx.y * WG_TILE;
     const int64_t r0 = (int64_t)blockIdx.z * chunk, r1 = r0 + chunk < rows ? r0 + chunk : rows;
-    v4f acc[4];
+    f32x4 acc[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) acc[i] = v4f{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < 4; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int lrow = tid >> 4, lc4 = (tid & 15) * 4;
     for (int64_t rb = r0; rb < r1; rb += WG_ROWS) {
         __syncthreads();

@@ -109,13 +109,8 @@ template <> struct Prec<__bf16> { static constexpr int KC = 32; static constexpr
 
 constexpr int MAX_TAPS = 5;
 
-// compile-time loop: f(integral_constant<int, 0>) ... f(integral_constant<int, N-1>); the register-set selection below
-// must be resolved by `if constexpr`, not by a run-time select, or the sets are demoted to scratch memory
-template <int V> struct IC { static constexpr int value = V; };
-template <int N> struct StaticFor {
-    template <class F> __device__ __forceinline__ static void run(F&& f) { StaticFor<N - 1>::run(f); f(IC<N - 1>{}); }
-};
-template <> struct StaticFor<0> { template <class F> __device__ __forceinline__ static void run(F&&) {} };
+// StaticFor (device_common.h) is the compile-time loop of the kernels below: their register-set selection must be resolved by
+// `if constexpr`, not by a run-time select, or the sets are demoted to scratch memory
 
 
 // ------------------------------------------------------------------------------------------------
@@ -146,7 +141,6 @@ __device__ __forceinline__ void conv_epilogue(const glowtts_conv_args& p, f32x16
     constexpr uint32_t OOB = 0x80000000u;
     const int rb = m0 + wm * MI * 32 + 4 * lhi;               // row of (mi = 0, reg = 0)
     auto roff = [](int mi, int reg) { return mi * 32 + (reg & 3) + 8 * (reg >> 2); };
-    auto mk = [](const void* ptr, long bytes) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ptr), 0, (int)bytes, 0x00020000); };
     auto ld32 = [](Rsrc r, uint32_t vo, uint32_t so) { return __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, 0); };
     auto ldf = [&](Rsrc r, uint32_t vo, uint32_t so) { return __uint_as_float(ld32(r, vo, so)); };
     auto ldh = [](Rsrc r, uint32_t vo, uint32_t so) { return __uint_as_float((uint32_t)__builtin_amdgcn_raw_buffer_load_b16(r, vo, so, 0) << 16); };
@@ -156,12 +150,12 @@ __device__ __forceinline__ void conv_epilogue(const glowtts_conv_args& p, f32x16
         const __bf16 b = (__bf16)v;
         __builtin_amdgcn_raw_buffer_store_b16(*reinterpret_cast<const unsigned short*>(&b), r, vo, so, 0);
     };
-    const Rsrc rmk = mk(p.rowmask, (long)p.rows * 4);
+    const Rsrc rmk = mk_rsrc(p.rowmask, (long)p.rows * 4);
 
     if constexpr (EPI == GLOWTTS_EPI_LINEAR) {
         const uint32_t esz = out0_bf ? 2 : 4;
         const uint32_t eiz = in0_bf ? 2 : 4;
-        const Rsrc ro = mk(p.out0, (long)p.rows * p.ld0 * esz), ri = mk(p.in0, (long)p.rows * p.ldi0 * eiz);
+        const Rsrc ro = mk_rsrc(p.out0, (long)p.rows * p.ld0 * esz), ri = mk_rsrc(p.in0, (long)p.rows * p.ldi0 * eiz);
         const int ncv = (fl & GLOWTTS_F_COLMASK) ? p.ncols_valid[blockIdx.z] : 0x7FFFFFFF;
         uint32_t vo[NI], vi[NI], idn[NI]; float bs[NI]; bool cz[NI];
 #pragma unroll
@@ -255,7 +249,7 @@ __device__ __forceinline__ void conv_epilogue(const glowtts_conv_args& p, f32x16
         const bool last = (fl & GLOWTTS_F_LAST) != 0, first = (fl & GLOWTTS_F_FIRST) != 0;
         const bool copy_bf = last && out0_bf && (const void*)p.out0 != (const void*)p.out1;     // last layer: out0 = optional bf16 copy of the sum
         const uint32_t e0 = out0_bf ? 2 : 4, ei = in0_bf ? 2 : 4;
-        const Rsrc ro0 = mk(p.out0, (long)p.rows * p.ld0 * e0), rin = mk(p.in0, (long)p.rows * p.ldi0 * ei), ro1 = mk(p.out1, (long)p.rows * p.ld1 * 4);
+        const Rsrc ro0 = mk_rsrc(p.out0, (long)p.rows * p.ld0 * e0), rin = mk_rsrc(p.in0, (long)p.rows * p.ldi0 * ei), ro1 = mk_rsrc(p.out1, (long)p.rows * p.ld1 * 4);
         uint32_t v0[NI], vin[NI], v1[NI], vl0[NI]; float bs[NI]; bool anyres[NI], anyskip[NI];
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) {
@@ -327,15 +321,15 @@ __device__ __forceinline__ void conv_epilogue(const glowtts_conv_args& p, f32x16
         // the tanh half, 2*pi+1 the sigmoid half of 32 channels.  Output: interleaved (tanh, sigmoid) pairs.
         static_assert(NI % 2 == 0, "pair epilogues need NI even");
         const uint32_t esz = out0_bf ? 2 : 4;
-        const Rsrc ro = mk(p.out0, (long)p.rows * p.ld0 * esz);
+        const Rsrc ro = mk_rsrc(p.out0, (long)p.rows * p.ld0 * esz);
         // optional second output (bf16 storage only): acts = tanh * sigmoid as plain bf16 rows [rows][ld1], the A operand of the
         // Res_Skip conv and the X operand of its weight gradient (both then need no prologue).  No out1: zero-sized descriptor,
         // the stores are dropped by the bounds check.
-        const Rsrc ra = mk(p.out1, p.out1 ? (long)p.rows * p.ld1 * 2 : 0);
+        const Rsrc ra = mk_rsrc(p.out1, p.out1 ? (long)p.rows * p.ld1 * 2 : 0);
         // conditioning rows: one per utterance, or (GLOWTTS_F_COND_ROWS: per-frame conditioning, GR-mode pitch) one per activation row
         const int Tp = (fl & GLOWTTS_F_COND_ROWS) ? 1 : (p.rows_per_utt > 0 ? p.rows_per_utt : 1);
         const int nutt = p.rows / Tp;
-        const Rsrc rc = mk(p.cond, (long)nutt * p.ldcond * 4);
+        const Rsrc rc = mk_rsrc(p.cond, (long)nutt * p.ldcond * 4);
         const bool drop = p.drop_p > 0.f, cnd = p.cond != nullptr;
         const uint32_t thr = drop_threshold(p.drop_p);
         const float ik = drop_inv_keep(thr);
@@ -413,7 +407,7 @@ __device__ __forceinline__ void conv_epilogue(const glowtts_conv_args& p, f32x16
     } else if constexpr (EPI == GLOWTTS_EPI_DGATE) {
         // d gate pre-activations from d acts and the kept gates (autograd of Modules.py:885-887 and of the Dropout at :862)
         const uint32_t esz = out0_bf ? 2 : 4, ei = in0_bf ? 2 : 4;
-        const Rsrc ro = mk(p.out0, (long)p.rows * p.ld0 * esz), rg = mk(p.in0, (long)p.rows * p.ldi0 * ei);
+        const Rsrc ro = mk_rsrc(p.out0, (long)p.rows * p.ld0 * esz), rg = mk_rsrc(p.in0, (long)p.rows * p.ldi0 * ei);
         const bool drop = p.drop_p > 0.f;
         const uint32_t thr = drop_threshold(p.drop_p);
         const float ik = drop_inv_keep(thr);
@@ -442,7 +436,7 @@ __device__ __forceinline__ void conv_epilogue(const glowtts_conv_args& p, f32x16
         // sum_r (da, ds)[r][n] * pitch[r][j] - the Pitch_l conv's weight gradient, also taken before the keep mask
         const bool pit = PITCH && dcnd && p.cond && (fl & GLOWTTS_F_COND_ROWS);
         const int pns = pit ? (int)p.ldcond : 0;
-        const Rsrc rp = mk(p.cond, pit ? (long)p.rows * pns * 4 : 0);
+        const Rsrc rp = mk_rsrc(p.cond, pit ? (long)p.rows * pns * 4 : 0);
         float pa[2][NI], ps[2][NI];
 #pragma unroll
         for (int j = 0; j < 2; ++j)
@@ -581,7 +575,7 @@ __device__ __forceinline__ void conv_epilogue(const glowtts_conv_args& p, f32x16
         static_assert(EPI == GLOWTTS_EPI_COUPLE && NI % 2 == 0, "pair epilogues need NI even");
         const float* xsrc = p.in0 ? p.in0 : p.out0;           // x_b is read from the kept coupling input when given
         const long ldx = p.in0 ? p.ldi0 : p.ld0;
-        const Rsrc rx = mk(xsrc, (long)p.rows * ldx * 4), ro = mk(p.out0, (long)p.rows * p.ld0 * 4), rk = mk(p.out1, p.out1 ? (long)p.rows * p.ld1 * 4 : 0);
+        const Rsrc rx = mk_rsrc(xsrc, (long)p.rows * ldx * 4), ro = mk_rsrc(p.out0, (long)p.rows * p.ld0 * 4), rk = mk_rsrc(p.out1, p.out1 ? (long)p.rows * p.ld1 * 4 : 0);
         const bool rev = (fl & GLOWTTS_F_REVERSE) != 0;
         uint32_t vx[NI / 2], vo[NI / 2], vk[NI / 2]; float bm[NI / 2], bl[NI / 2];
 #pragma unroll
@@ -1208,11 +1202,9 @@ __global__ __launch_bounds__(CH_WN * CH_WM * 64) void conv_chain_kernel(const gl
     // ---------------- epilogue 1: values -> global (what later kernels need) and -> LDS tiles (A operand of GEMM 2) ----------------
     {
         const int rb = m0 + wm * 32 + 4 * lhi;
-        typedef __amdgpu_buffer_rsrc_t Rs;
-        auto mkr = [](const void* ptr, long bytes) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ptr), 0, (int)bytes, 0x00020000); };
-        const Rs rmk = mkr(p.rowmask, (long)p.rows * 4);
-        const Rs rold = mkr(p.out1, p.out1 ? (long)p.rows * p.ld1 * 4 : 0);          // RESSKIP: the fp32 skip sum of the earlier layers
-        const Rs rout = mkr(p.out0, (long)p.rows * p.ld0 * 2);                        // bf16 result rows [rows][ld0]
+        const Rsrc rmk = mk_rsrc(p.rowmask, (long)p.rows * 4);
+        const Rsrc rold = mk_rsrc(p.out1, p.out1 ? (long)p.rows * p.ld1 * 4 : 0);          // RESSKIP: the fp32 skip sum of the earlier layers
+        const Rsrc rout = mk_rsrc(p.out0, (long)p.rows * p.ld0 * 2);                        // bf16 result rows [rows][ld0]
         float mk[16];
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg)
@@ -1324,7 +1316,7 @@ int launch_skinny(const glowtts_conv_args& a, hipStream_t s)
 {
     GLOWTTS_NOTE_STATIC("conv_skinny<%d,%d%s>", KS16 * 16, NI * 32, ABF ? ",abf16" : "");
     hipLaunchKernelGGL((conv_skinny_kernel<KS16, NI, ABF>), dim3((a.rows + 31) / 32), dim3(64), 0, s, a);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1373,9 +1365,8 @@ __global__ __launch_bounds__(384) void proj_ln_kernel(const proj_ln_args p)
         bfr[k] = *reinterpret_cast<const Chunk16*>(wb + ((size_t)((k >> 1) * p.npad + wave * 32 + l31) * 64 + (size_t)((2 * (k & 1) + lhi) * 16)));
     // epilogue operands, asked for before the MFMAs: accumulator element reg: row = (reg & 3) + 8 (reg >> 2) + 4 lhi, column = 32 wave + l31; rows past the
     // end are dropped / read as zero by the descriptors' bounds check
-    auto mk = [](const void* ptr, long bytes) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ptr), 0, (int)bytes, 0x00020000); };
-    const Rsrc rx = mk(p.x, p.rows * C * 4), rs = mk(p.s, p.rows * C * 4), ry = mk(p.y, p.rows * C * 4), ryb = mk(p.yb, p.rows * C * 2);
-    const Rsrc rpj = mk(p.proj, p.proj ? p.rows * C * 4 : 0), rst = mk(p.stats, p.rows * 8), rmk = mk(p.rowmask, p.rows * 4);
+    const Rsrc rx = mk_rsrc(p.x, p.rows * C * 4), rs = mk_rsrc(p.s, p.rows * C * 4), ry = mk_rsrc(p.y, p.rows * C * 4), ryb = mk_rsrc(p.yb, p.rows * C * 2);
+    const Rsrc rpj = mk_rsrc(p.proj, p.proj ? p.rows * C * 4 : 0), rst = mk_rsrc(p.stats, p.rows * 8), rmk = mk_rsrc(p.rowmask, p.rows * 4);
     const int rb = m0 + 4 * lhi, col = wave * 32 + l31;
     auto rof = [](int reg) { return (reg & 3) + 8 * (reg >> 2); };
     float xin[16], mk16[16];
@@ -1490,9 +1481,8 @@ __global__ __launch_bounds__(384) void ln_qkv_kernel(const ln_qkv_args p)
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m0 = blockIdx.x * 32;
-    auto mk = [](const void* ptr, long bytes) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ptr), 0, (int)bytes, 0x00020000); };
-    const Rsrc ra = mk(p.a, p.rows * C * 4), rbb = mk(p.b, p.rows * C * 4), rs = mk(p.s, p.rows * C * 4), ry = mk(p.y, p.rows * C * 4);
-    const Rsrc ryb = mk(p.yb, p.rows * C * 2), rst = mk(p.stats, p.rows * 8), rmk = mk(p.rowmask, p.rows * 4), rq = mk(p.qkv, p.rows * N * 4);
+    const Rsrc ra = mk_rsrc(p.a, p.rows * C * 4), rbb = mk_rsrc(p.b, p.rows * C * 4), rs = mk_rsrc(p.s, p.rows * C * 4), ry = mk_rsrc(p.y, p.rows * C * 4);
+    const Rsrc ryb = mk_rsrc(p.yb, p.rows * C * 2), rst = mk_rsrc(p.stats, p.rows * 8), rmk = mk_rsrc(p.rowmask, p.rows * 4), rq = mk_rsrc(p.qkv, p.rows * N * 4);
     const int rb = m0 + 4 * lhi, col = wave * 32 + l31;
     auto rof = [](int reg) { return (reg & 3) + 8 * (reg >> 2); };
     // the loads up front: the LayerNorm's operands of this lane (element reg: row = rof(reg) + 4 lhi, column = 32 wave + l31) and half of the
@@ -1633,7 +1623,7 @@ int launch_chain(const glowtts_conv_args& a1, const glowtts_conv_args& a2, hipSt
     }
     GLOWTTS_NOTE_STATIC("conv_chain<%s,%s>", epi_name(EPI1), epi_name(EPI2));
     hipLaunchKernelGGL((conv_chain_kernel<EPI1, EPI2>), dim3((a1.rows + CH_BM - 1) / CH_BM), dim3(CH_WN * CH_WM * 64), lds, s, a1, a2);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 int num_cus()
@@ -1749,10 +1739,10 @@ int launch_dma(const glowtts_conv_args& a, hipStream_t s)
     dim3 grid(((a.rows + BM - 1) / BM) * gy);
     GLOWTTS_NOTE_STATIC("conv_dma<%s,%d>", epi_name(EPI), TAPS);
 #ifdef GLOWTTS_TOOLS
-    if (ks) { hipLaunchKernelGGL((conv_dma_kernel<EPI, TAPS, NI, NI == 2>), grid, dim3(best * 64), lds, s, a, nst, 0); return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH; }
+    if (ks) { hipLaunchKernelGGL((conv_dma_kernel<EPI, TAPS, NI, NI == 2>), grid, dim3(best * 64), lds, s, a, nst, 0); RET_LAUNCH(); }
 #endif
     hipLaunchKernelGGL((conv_dma_kernel<EPI, TAPS, NI, false>), grid, dim3((best + nload) * 64), lds, s, a, nload ? 2 : nst, nload);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 template <typename CT, int MI, int NI, int WM, int WN, int EPI, int TAPS, int APRO, bool ABF>
@@ -1762,7 +1752,7 @@ int launch_k(const glowtts_conv_args& a, hipStream_t s)
     dim3 grid(((a.rows + BM - 1) / BM) * ((a.npad + BN - 1) / BN), 1, a.batch > 1 ? a.batch : 1);
     GLOWTTS_NOTE_STATIC("conv_cl<%s,%d,%s%s>", epi_name(EPI), TAPS, sizeof(CT) == 2 ? "bf16" : "f32", ABF ? ",abf" : "");
     hipLaunchKernelGGL((conv_cl_kernel<CT, MI, NI, WM, WN, EPI, TAPS, APRO, ABF>), grid, dim3(WM * WN * 64), 0, s, a);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 template <typename CT, int EPI, int TAPS, int APRO, bool ABF = false>
@@ -1886,7 +1876,7 @@ int pack_batched(const float* w, int batch, int O, int I, int taps, int transpos
     else
         hipLaunchKernelGGL(pack_weight_kernel<float>, dim3(blocks, batch), dim3(256), 0, s, w, static_cast<float*>(packed), O, I, taps, transpose, perm, perm_h, N, kchunks * KC, npad, kchunks,
                            inner, outer_stride, inner_stride, w_stride);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 }  // namespace
 
@@ -1914,7 +1904,7 @@ extern "C" int glowtts_pack_weight_multi(const glowtts_pack_job* dev_jobs, int n
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (precision == GLOWTTS_BF16) hipLaunchKernelGGL(pack_weight_multi_kernel<__bf16>, dim3(total_blocks), dim3(256), 0, s, dev_jobs, njobs);
     else hipLaunchKernelGGL(pack_weight_multi_kernel<float>, dim3(total_blocks), dim3(256), 0, s, dev_jobs, njobs);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_pack_weight(const float* w, int O, int I, int taps, int transpose, int perm, int perm_h,
@@ -1990,7 +1980,7 @@ extern "C" int glowtts_proj_layernorm(const float* a, int64_t lda, const void* w
     p.rows = rows; p.eps = eps; p.drop_p = drop_p; p.seed = seed; p.seed_ptr = seed_ptr;
     GLOWTTS_NOTE_STATIC("proj_ln<%d>", 192);
     hipLaunchKernelGGL(proj_ln_kernel, dim3((unsigned)((rows + 31) / 32)), dim3(384), 0, static_cast<hipStream_t>(stream), p);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_layernorm_qkv(const float* a, const float* b, const float* gamma, const float* beta, const float* rowmask, float* s, float* stats,
@@ -2004,6 +1994,6 @@ extern "C" int glowtts_layernorm_qkv(const float* a, const float* b, const float
     p.w = wqkv; p.npad = npad; p.bias = bias; p.qkv = qkv; p.rows = rows; p.eps = eps;
     GLOWTTS_NOTE_STATIC("ln_qkv<%d>", 192);
     hipLaunchKernelGGL(ln_qkv_kernel, dim3((unsigned)((rows + 31) / 32)), dim3(384), 0, static_cast<hipStream_t>(stream), p);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 

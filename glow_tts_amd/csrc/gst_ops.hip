@@ -277,7 +277,7 @@ extern "C" int glowtts_gst_fwd(const float* hs, const int64_t* lengths, int stri
     hipLaunchKernelGGL(gst_tanh_kernel, dim3((I * NT + 255) / 256), dim3(256), 0, s, tokens, TT, I * NT);
     hipLaunchKernelGGL(gst_kv_kernel, dim3(C), dim3((NT + 63) / 64 * 64), 0, s, TT, Wk, bk, Wv, bv, K, V, I, NT);
     hipLaunchKernelGGL(gst_attn_fwd_kernel, dim3(B), dim3(C), (size_t)(G + 2 * C + H * NT) * sizeof(float), s, hs, lengths, Wq, bq, K, V, Wp, bp, out, keep, d);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_gst_bwd(const float* dout, const float* keep, const int64_t* lengths, int stride_prod, const float* tokens, const float* Wq, const float* Wk,
@@ -302,5 +302,5 @@ extern "C" int glowtts_gst_bwd(const float* dout, const float* keep, const int64
     if ((long)I * NT > m2) m2 = (long)I * NT;
     const float* TT = keep + (long)B * (2 * C + H * NT + G);
     hipLaunchKernelGGL(gst_grads2_kernel, dim3((unsigned)((m2 + 255) / 256), 3), dim3(256), 0, s, TT, Wk, Wv, dK, dV, dWk, dbk, dWv, dbv, dtokens, d);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }

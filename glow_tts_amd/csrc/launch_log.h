@@ -14,3 +14,6 @@ std::atomic<long long>* glowtts_launch_slot(const char* cls);     // never freed
 // the same for call sites whose class name depends only on template parameters: the slot is looked up once per instantiation
 #define GLOWTTS_NOTE_STATIC(...) do { static std::atomic<long long>* slot_ = [&] { char nm_[96]; snprintf(nm_, sizeof(nm_), __VA_ARGS__); \
                                           return glowtts_launch_slot(nm_); }(); if (slot_) slot_->fetch_add(1, std::memory_order_relaxed); } while (0)
+
+// how an entry point whose last act is a kernel launch ends
+#define RET_LAUNCH() return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH

@@ -319,7 +319,6 @@ __global__ __launch_bounds__(256) void mse_bwd_kernel(const float* __restrict__ 
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) da[i] = g * (a[i] - t[i]);
 }
 
-#define RET_LAUNCH() return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH
 }  // namespace
 
 // Operands of the log-prior GEMM (Modules.py:108-114) from the encoder's mean / log_std [B][Cm][Tx] in ONE launch (was 15 small

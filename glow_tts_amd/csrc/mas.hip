@@ -264,7 +264,7 @@ int launch_dp(const float* value, const int32_t* t_xs, const int32_t* t_ys, int3
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     GLOWTTS_NOTE("mas_dp<R%d,%s,%s,%s>", R, vec_used ? "vec" : "scalar", q_out ? "q" : "noq", transposed ? "t" : "n");
     hipLaunchKernelGGL(k, dim3(B), dim3(64), lds, s, value, t_xs, t_ys, idx_out, q_out, Tx, Ty, neg);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 int dispatch_dp(const float* value, const int32_t* t_xs, const int32_t* t_ys, int32_t* idx_out, float* q_out,
@@ -313,14 +313,14 @@ extern "C" int glowtts_mas_path_from_idx(const int32_t* idx, void* path, int B, 
         const unsigned int blocks = (unsigned int)std::min<uint64_t>((total4 + 255) / 256, 8192);
         if (out_dtype == 0) hipLaunchKernelGGL(mas_path_linear_kernel<int32_t>, dim3(blocks), dim3(256), 0, s, idx, static_cast<int32_t*>(path), Tx, Ty, (unsigned int)total4);
         else                hipLaunchKernelGGL(mas_path_linear_kernel<float>, dim3(blocks), dim3(256), 0, s, idx, static_cast<float*>(path), Tx, Ty, (unsigned int)total4);
-        return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+        RET_LAUNCH();
     }
     const int rpb = std::max(1, GLOWTTS_TUNABLE("GLOWTTS_PATH_ROWS", 8));
     dim3 grid((Tx + rpb - 1) / rpb, B);
     const int vec_ok = (Ty % 4 == 0) && ((reinterpret_cast<uintptr_t>(path) & 15) == 0) && ((reinterpret_cast<uintptr_t>(idx) & 15) == 0);
     if (out_dtype == 0) hipLaunchKernelGGL(mas_path_kernel<int32_t>, grid, dim3(256), 0, s, idx, static_cast<int32_t*>(path), Tx, Ty, vec_ok, rpb);
     else                hipLaunchKernelGGL(mas_path_kernel<float>, grid, dim3(256), 0, s, idx, static_cast<float*>(path), Tx, Ty, vec_ok, rpb);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_mas_f32(const float* value, int32_t* path, const int32_t* t_xs, const int32_t* t_ys,

@@ -7,6 +7,7 @@
 #include "../../include/glowtts_hip.h"
 #include "launch_log.h"
 #include "mas_common.h"
+#include "device_common.h"
 
 // tools/mas_lab.hip includes this file with its own stamp hook (phase timing of one workgroup); the library has none
 #ifndef MAS_LAB_STAMP
@@ -122,12 +123,11 @@ __global__ __launch_bounds__(64) void mas_dp2_kernel(const float* __restrict__ v
 
     // one column = one coalesced 8-byte load per lane through a buffer descriptor: lane offset in the VGPR, column offset in an SGPR
     // (soffset is not bounds-checked: columns are clamped to Ty - 1 where the look-ahead can pass the end of the tensor)
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(vb), 0, Tx * Ty * 4, 0x00020000);
+    const Rsrc rs = mk_rsrc(vb, Tx * Ty * 4);
     const uint32_t voff = (uint32_t)min(lane * 2, Tx - 2) * 4u;       // rows >= Tx are clamped: they are never inside the band
     const int rowbytes = Tx * 4, lastoff = (Ty - 1) * rowbytes;
-    typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
     auto load_col = [&](int soff) -> float2 {
-        const u32x2_t w = __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, 0);
+        const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, 0);
         return make_float2(__uint_as_float(w.x), __uint_as_float(w.y));
     };
 
@@ -193,5 +193,5 @@ int glowtts_detail::launch_mas_dp2(const float* value, const int32_t* t_xs, cons
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     GLOWTTS_NOTE("mas_dp2<%s>", q_out ? "q" : "noq");
     hipLaunchKernelGGL(k, dim3(B), dim3(64), lds, s, value, t_xs, t_ys, idx_out, q_out, Tx, Ty, neg);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }

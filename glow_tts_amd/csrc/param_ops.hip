@@ -7,14 +7,9 @@
 #include <string.h>
 #include "../../include/glowtts_hip.h"
 #include "launch_log.h"
+#include "device_common.h"
 
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 constexpr int WN_MAXK = 32;            // elements per lane kept in registers: cols <= 2048 (longer rows take the strided path)
 
@@ -139,7 +134,7 @@ extern "C" int glowtts_weightnorm_bwd_multi(const glowtts_wn_bwd_job* jobs, int 
     if (blocks >= (1L << 31)) return GLOWTTS_E_ARG;
     GLOWTTS_NOTE_STATIC("weightnorm_bwd_multi");
     hipLaunchKernelGGL(weightnorm_bwd_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), tab, njobs);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_weightnorm_fwd(const float* v, const float* g, float* w, float* inv_norm, int64_t rows, int cols, void* stream)
@@ -147,7 +142,7 @@ extern "C" int glowtts_weightnorm_fwd(const float* v, const float* g, float* w, 
     if (!v || !g || !w || !inv_norm || rows < 1 || cols < 1) return GLOWTTS_E_ARG;
     GLOWTTS_NOTE_STATIC("weightnorm_fwd");
     hipLaunchKernelGGL(weightnorm_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), v, g, w, inv_norm, (long)rows, cols);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_weightnorm_bwd(const float* dw, const float* v, const float* g, const float* inv_norm, float* dv, float* dg,
@@ -156,7 +151,7 @@ extern "C" int glowtts_weightnorm_bwd(const float* dw, const float* v, const flo
     if (!dw || !v || !g || !inv_norm || !dv || !dg || rows < 1 || cols < 1) return GLOWTTS_E_ARG;
     hipLaunchKernelGGL(weightnorm_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), dw, v, g, inv_norm, dv, dg,
                        (long)rows, cols);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -303,14 +298,14 @@ extern "C" int glowtts_multi_grad_norm(const glowtts_opt_job* dev_jobs, int njob
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(multi_sqnorm_kernel, dim3(total_blocks), dim3(256), 0, s, dev_jobs, njobs, partial);
     hipLaunchKernelGGL(norm_final_kernel, dim3(1), dim3(256), 0, s, partial, total_blocks, max_norm, norm_and_coef);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_multi_grad_scale(const glowtts_opt_job* dev_jobs, int njobs, int total_blocks, const float* coef, void* stream)
 {
     if (!dev_jobs || njobs < 1 || total_blocks < 1 || !coef) return GLOWTTS_E_ARG;
     hipLaunchKernelGGL(multi_scale_kernel, dim3(total_blocks), dim3(256), 0, static_cast<hipStream_t>(stream), dev_jobs, njobs, coef);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_radam_step(const glowtts_opt_job* dev_jobs, int njobs, int total_blocks, const float* hyper, const float* grad_scale,
@@ -318,7 +313,7 @@ extern "C" int glowtts_radam_step(const glowtts_opt_job* dev_jobs, int njobs, in
 {
     if (!dev_jobs || njobs < 1 || total_blocks < 1 || !hyper) return GLOWTTS_E_ARG;
     hipLaunchKernelGGL(radam_kernel, dim3(total_blocks), dim3(256), 0, static_cast<hipStream_t>(stream), dev_jobs, njobs, hyper, grad_scale);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_opt_chunk(void) { return OPT_CHUNK; }
@@ -341,7 +336,7 @@ extern "C" int glowtts_sum_slices(const float* partial, float* out, int S, int64
     const long n4 = n / 4;
     hipLaunchKernelGGL(sum_slices_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        reinterpret_cast<const float4*>(partial), reinterpret_cast<float4*>(out), S, n4);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 // The same for a partial image that is cut into up to GLOWTTS_SUM_MAX_SEGS destination tensors (the decoder's one-tap weight gradients: several classes, some of them
@@ -375,6 +370,6 @@ extern "C" int glowtts_sum_slices_seg(const float* partial, int S, int64_t strid
     const long n4 = end / 4;
     hipLaunchKernelGGL(sum_slices_seg_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        reinterpret_cast<const float4*>(partial), S, (long)(stride / 4), n4, tab, nseg);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 

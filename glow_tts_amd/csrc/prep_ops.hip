@@ -24,14 +24,6 @@ constexpr int PREP_TR = 16;                      // source rows (packed O indice
 constexpr int PREP_RP = 4;                       // rows of a wave in flight per pass
 constexpr int PREP_MAXPL = 16;                   // floats of a row per lane: I * taps <= 1024
 
-__device__ __forceinline__ float prep_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ unsigned short bf16_bits_prep(float v) { const __bf16 b = (__bf16)v; return *reinterpret_cast<const unsigned short*>(&b); }
-
 // The job table travels in the kernel's ARGUMENT segment (<= PREP_MAXJOBS x sizeof(glowtts_prep_job) = 24 x 120 bytes): inside a captured training step a device-side table would
 // need a host-to-device copy node in front of the launch, re-executed at every replay, on the critical path of the decoder's stream.
 constexpr int PREP_MAXJOBS = GLOWTTS_PREP_MAX_JOBS;
@@ -94,7 +86,7 @@ __device__ __forceinline__ void prep_body(const glowtts_prep_job& j, const int r
 #pragma unroll
                 for (int k = 0; k < 4; ++k) { const int c = c0 + lane + 64 * k; x[k] = vr[c < cols ? c : cols - 1]; }
 #pragma unroll
-                for (int k = 0; k < 4; ++k) { const int c = c0 + lane + 64 * k; if (c < cols) tile[r * pitch + c] = ok ? bf16_bits_prep(x[k]) : (unsigned short)0; }
+                for (int k = 0; k < 4; ++k) { const int c = c0 + lane + 64 * k; if (c < cols) tile[r * pitch + c] = ok ? bf16_bits(x[k]) : (unsigned short)0; }
             }
         }
     } else
@@ -160,7 +152,7 @@ __device__ __forceinline__ void prep_body(const glowtts_prep_job& j, const int r
 #pragma unroll
             for (int k = 0; k < PREP_MAXPL; ++k) {
                 const int c = lane + 64 * k;
-                if (k < nk && c < cols && !(abl & 2)) tile[r * pitch + c] = bf16_bits_prep(x[h][k] * sc);
+                if (k < nk && c < cols && !(abl & 2)) tile[r * pitch + c] = bf16_bits(x[h][k] * sc);
             }
         }
     }
@@ -298,7 +290,7 @@ extern "C" int glowtts_prep_launch_dev(const glowtts_prep_job* dev_jobs, int njo
     }
     GLOWTTS_NOTE_STATIC("prep_weights_dev");
     hipLaunchKernelGGL(prep_dev_kernel, dim3(total_blocks), dim3(PREP_NT), lds, static_cast<hipStream_t>(stream), dev_jobs, njobs);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_prep_launch(const glowtts_prep_job* host_jobs, int njobs, int total_blocks, int max_cols, void* stream)
@@ -315,7 +307,7 @@ extern "C" int glowtts_prep_launch(const glowtts_prep_job* host_jobs, int njobs,
     }
     GLOWTTS_NOTE_STATIC("prep_weights");
     hipLaunchKernelGGL(prep_kernel, dim3(total_blocks), dim3(PREP_NT), lds, static_cast<hipStream_t>(stream), tab, njobs, GLOWTTS_TUNABLE("GLOWTTS_PREP_ABL", 0));
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 // The jobs of the per-flow weight images of the fused coupling-network kernels: the same placement as glowtts_wavenet_pack_images /

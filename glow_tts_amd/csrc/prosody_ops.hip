@@ -8,10 +8,9 @@
 #include <algorithm>
 #include "../../include/glowtts_hip.h"
 #include "launch_log.h"
+#include "device_common.h"
 
 namespace {
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 // The same with the thread's row of W_hh held in REGISTERS for the whole recurrence (HH = H floats: 128 VGPRs at the GST encoder's size; the generic kernel
 // re-reads its row - 3 H^2 floats per workgroup - from L2 at every time step: 81 us for 13 steps, round 5 profile of config 5).
@@ -199,10 +198,10 @@ extern "C" int glowtts_gru_fwd(const float* gi, const float* w_hh, const float* 
     if (!gi || !w_hh || !b_hh || !hs || !keep || B < 1 || T < 1 || H < 1 || 3 * H > 1024) return GLOWTTS_E_ARG;
     if (H == 128 && (reinterpret_cast<uintptr_t>(w_hh) & 15) == 0) {
         hipLaunchKernelGGL(gru_fwd_reg_kernel<128>, dim3(B), dim3(384), 0, static_cast<hipStream_t>(stream), gi, w_hh, b_hh, hs, keep, T);
-        return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+        RET_LAUNCH();
     }
     hipLaunchKernelGGL(gru_fwd_kernel, dim3(B), dim3(3 * H), 4 * H * sizeof(float), static_cast<hipStream_t>(stream), gi, w_hh, b_hh, hs, keep, T, H);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_gru_bwd(const float* dhs, const float* hs, const float* keep, const float* w_hh, float* dgi, float* dgh,
@@ -211,8 +210,8 @@ extern "C" int glowtts_gru_bwd(const float* dhs, const float* hs, const float* k
     if (!dhs || !hs || !keep || !w_hh || !dgi || !dgh || B < 1 || T < 1 || H < 1 || 3 * H > 1024) return GLOWTTS_E_ARG;
     if (H == 128) {
         hipLaunchKernelGGL(gru_bwd_reg_kernel<128>, dim3(B), dim3(384), 0, static_cast<hipStream_t>(stream), dhs, hs, keep, w_hh, dgi, dgh, T);
-        return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+        RET_LAUNCH();
     }
     hipLaunchKernelGGL(gru_bwd_kernel, dim3(B), dim3(3 * H), 7 * H * sizeof(float), static_cast<hipStream_t>(stream), dhs, hs, keep, w_hh, dgi, dgh, T, H);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }

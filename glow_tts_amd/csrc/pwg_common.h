@@ -1,4 +1,4 @@
-// What the Parallel WaveGAN generator's forward (pwg_ops.hip) and backward (pwg_train_ops.hip) share: the tile constants, the MFMA wrapper, the host-side
+// What the Parallel WaveGAN generator's forward (pwg_ops.hip) and backward (pwg_train_ops.hip) share: the tile constants, the host-side
 // batch and LDS checks, the layer's row gather and the head's first stage.  The backward recomputes the gate and the head's hidden layer from rows and
 // sums that are this text, not a copy of it; what it must additionally keep in step with the forward is said at the two GEMM 1 loops.
 #pragma once
@@ -6,21 +6,15 @@
 #include <stdint.h>
 
 #include "../../include/glowtts_hip.h"
+#include "device_common.h"
 
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int TM = 64;                                    // samples (rows) per workgroup: four 16-row MFMA tiles
 constexpr int THREADS = 256, WAVES = THREADS / 64;
 constexpr int MAX_LDS = 160 * 1024;
 constexpr int MAX_SCALE = 16, MAX_CHANNELS = 256;
 constexpr float RSQRT2 = 0.70710678118654752440f;
-
-__device__ __forceinline__ v4f mfma4(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
-
-__host__ __device__ __forceinline__ int xs_stride_of(int K) { return ((K >> 2) & 1) ? K : K + 4; }      // (stride / 4) odd: 16 rows x 4 k hit 64 distinct dwords mod 32 pairs
 
 bool bad_batch(int B, int Lmax, int hop)
 {
@@ -94,12 +88,12 @@ __device__ __forceinline__ void pwg_head_stage(const float* __restrict__ skips, 
     __syncthreads();
 }
 // b. h' = W1 y + b1 for the wave's 16 columns (this lane's: col) and all four row tiles: bias-initialised, k ascending.  w1 [S][S], row = input channel.
-__device__ __forceinline__ void pwg_head_w1(const float* Ys, const float* __restrict__ w1, const float* __restrict__ b1, int S, int col, v4f (&acc)[4])
+__device__ __forceinline__ void pwg_head_w1(const float* Ys, const float* __restrict__ w1, const float* __restrict__ b1, int S, int col, f32x4 (&acc)[4])
 {
     const int lane = threadIdx.x & 63, st = S + 4;
     const float bv = b1[col];
 #pragma unroll
-    for (int rt = 0; rt < 4; ++rt) acc[rt] = v4f{bv, bv, bv, bv};
+    for (int rt = 0; rt < 4; ++rt) acc[rt] = f32x4{bv, bv, bv, bv};
     const float* ya = Ys + (lane & 15) * st + (lane >> 4);
     for (int k0 = 0; k0 < S; k0 += 4) {
         const float wk = w1[(size_t)(k0 + (lane >> 4)) * S + col];

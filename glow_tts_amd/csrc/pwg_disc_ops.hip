@@ -71,9 +71,9 @@ __global__ __launch_bounds__(THREADS) void pwg_disc_layer_kernel(const float* __
     for (int n = wave; n < C / 16; n += WAVES) {
         const int col = n * 16 + r;
         const float bv = bias[col];
-        v4f acc[4];
+        f32x4 acc[4];
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) acc[rt] = v4f{bv, bv, bv, bv};
+        for (int rt = 0; rt < 4; ++rt) acc[rt] = f32x4{bv, bv, bv, bv};
         const float* xa = Xs + r * xs + q;
         for (int k0 = 0; k0 < K; k0 += 4) {
             const float wk = w[(size_t)(k0 + q) * C + col];
@@ -187,9 +187,9 @@ __global__ __launch_bounds__(THREADS) void pwg_disc_layer_bwd_kernel(const float
     __syncthreads();
     for (int n = wave; n < C / 16; n += WAVES) {
         const int col = n * 16 + r;                        // input channel
-        v4f acc[4];
+        f32x4 acc[4];
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) acc[rt] = v4f{0.f, 0.f, 0.f, 0.f};
+        for (int rt = 0; rt < 4; ++rt) acc[rt] = f32x4{0.f, 0.f, 0.f, 0.f};
         const float* da = Ds + r * xs + q;
         for (int k0 = 0; k0 < K; k0 += 4) {
             const float wk = wt[(size_t)(k0 + q) * C + col];
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(THREADS) void pwg_disc_first_bwd_kernel(const float
 }
 
 // ---- host side ----
-int layer_lds(int C) { return TM * xs_stride_of(3 * C) * 4; }
+int layer_lds(int C) { return TM * lds_stride_of(3 * C) * 4; }
 bool bad_channels(int C) { return C < 16 || C > MAX_CHANNELS || C % 16 || layer_lds(C) > MAX_LDS; }
 // every batch row of the full length T: the generator's limits with one sample per "frame", B T < 2^31
 bool bad_rows(int B, int T) { return bad_train_batch(B, T, 1) || (int64_t)B * T >= ((int64_t)1 << 31); }
@@ -259,7 +259,7 @@ extern "C" int glowtts_pwg_disc_first(const float* wav, const float* w, const fl
     if (!wav || !w || !bias || !out || bad_rows(B, T) || bad_channels(C)) return GLOWTTS_E_ARG;
     GLOWTTS_NOTE_STATIC("pwg_disc_first");
     hipLaunchKernelGGL(pwg_disc_first_kernel, dim3(quad_blocks(T, C), B), dim3(THREADS), 0, static_cast<hipStream_t>(stream), wav, w, bias, out, T, C, slope);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_pwg_disc_layer(const float* x, const float* w, const float* bias, float* out, int B, int T, int C, int dilation, float slope, void* stream)
@@ -269,8 +269,8 @@ extern "C" int glowtts_pwg_disc_layer(const float* x, const float* w, const floa
     if (allow_lds<&pwg_disc_layer_kernel>(lds) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;
     GLOWTTS_NOTE_STATIC("pwg_disc_layer");
     hipLaunchKernelGGL(pwg_disc_layer_kernel, dim3((T + TM - 1) / TM, B), dim3(THREADS), (size_t)lds, static_cast<hipStream_t>(stream), x, w, bias, out, T, C, dilation,
-                       xs_stride_of(3 * C), slope);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+                       lds_stride_of(3 * C), slope);
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_pwg_disc_last(const float* x, const float* w, const float* bias, float* scores, int B, int T, int C, void* stream)
@@ -278,7 +278,7 @@ extern "C" int glowtts_pwg_disc_last(const float* x, const float* w, const float
     if (!x || !w || !bias || !scores || bad_rows(B, T) || bad_channels(C)) return GLOWTTS_E_ARG;
     GLOWTTS_NOTE_STATIC("pwg_disc_last");
     hipLaunchKernelGGL(pwg_disc_last_kernel, dim3((T + THREADS - 1) / THREADS, B), dim3(THREADS), 0, static_cast<hipStream_t>(stream), x, w, bias, scores, T, C);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_pwg_disc_mse(const float* p, float* dp, float* work, float* loss, int64_t N, int64_t split, float v0, float v1, float factor, void* stream)
@@ -290,7 +290,7 @@ extern "C" int glowtts_pwg_disc_mse(const float* p, float* dp, float* work, floa
     hipLaunchKernelGGL(pwg_disc_mse_kernel, dim3(blocks), dim3(THREADS), 0, s, p, dp, reinterpret_cast<double*>(work), N, split, v0, v1, factor);
     GLOWTTS_NOTE_STATIC("pwg_disc_mse_sum");
     hipLaunchKernelGGL(pwg_disc_mse_sum_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<const double*>(work), loss, blocks, N, split, factor);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_pwg_disc_last_bwd(const float* dp, const float* w, float* dh, int B, int T, int C, void* stream)
@@ -298,7 +298,7 @@ extern "C" int glowtts_pwg_disc_last_bwd(const float* dp, const float* w, float*
     if (!dp || !w || !dh || bad_rows(B, T) || bad_channels(C)) return GLOWTTS_E_ARG;
     GLOWTTS_NOTE_STATIC("pwg_disc_last_bwd");
     hipLaunchKernelGGL(pwg_disc_last_bwd_kernel, dim3(quad_blocks(T, C), B), dim3(THREADS), 0, static_cast<hipStream_t>(stream), dp, w, dh, T, C);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_pwg_disc_layer_bwd(const float* dout, const float* out, const float* wt, float* dx, float* dpre, int B, int T, int C, int dilation, float slope,
@@ -309,8 +309,8 @@ extern "C" int glowtts_pwg_disc_layer_bwd(const float* dout, const float* out, c
     if (allow_lds<&pwg_disc_layer_bwd_kernel>(lds) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;
     GLOWTTS_NOTE_STATIC("pwg_disc_layer_bwd");
     hipLaunchKernelGGL(pwg_disc_layer_bwd_kernel, dim3((T + TM - 1) / TM, B), dim3(THREADS), (size_t)lds, static_cast<hipStream_t>(stream), dout, out, wt, dx, dpre, T, C,
-                       dilation, xs_stride_of(3 * C), slope);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+                       dilation, lds_stride_of(3 * C), slope);
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_pwg_disc_first_bwd(const float* dout, const float* out, const float* w, float* dwav, float* dpre, int B, int T, int C, float slope, void* stream)
@@ -319,7 +319,7 @@ extern "C" int glowtts_pwg_disc_first_bwd(const float* dout, const float* out, c
     GLOWTTS_NOTE_STATIC("pwg_disc_first_bwd");
     hipLaunchKernelGGL(pwg_disc_first_bwd_kernel, dim3((T + THREADS - 1) / THREADS, B), dim3(THREADS), 0, static_cast<hipStream_t>(stream), dout, out, w, dwav, dpre, T, C,
                        slope);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_pwg_disc_wgrad(const float* a, const float* dpre, const int32_t* lengths, float* work, float* dw, float* db, int B, int T, int Cin, int Cout,

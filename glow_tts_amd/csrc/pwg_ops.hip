@@ -44,7 +44,7 @@ __global__ __launch_bounds__(THREADS) void pwg_cond_in_kernel(const float* __res
     const int f = f0 + r;
     for (int n0 = 0; n0 < A; n0 += 16) {
         const bool col_ok = n0 + r < A;
-        v4f acc = {0.f, 0.f, 0.f, 0.f};
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         for (int k0 = 0; k0 < K; k0 += 4) {
             const int k = k0 + q, j = k / A, ci = k - j * A;
             const int src = min(max(f + j - ctx, 0), L - 1);                  // replicate padding by the utterance's own first / last frame
@@ -120,14 +120,14 @@ __global__ __launch_bounds__(THREADS) void pwg_layer_kernel(const float* __restr
 
     // 2. GEMM 1 + gate.  (pwg_layer_bwd_gate_kernel runs this sum without the prefetch; both start from the bias and take k ascending in steps of 4)
     const bool alias = gs_off == 0;                        // then R / 16 <= WAVES: at most one column pair per wave
-    v4f gate[4];
+    f32x4 gate[4];
     int pending = -1;
     for (int p = wave; p < R / 16; p += WAVES) {
         const float* wt = w1 + p * 16 + r;                 // tanh column; its sigmoid column lies R further
         const float bt = b1[p * 16 + r], bs = b1[R + p * 16 + r];
-        v4f at[4], as[4];
+        f32x4 at[4], as[4];
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) { at[rt] = v4f{bt, bt, bt, bt}; as[rt] = v4f{bs, bs, bs, bs}; }
+        for (int rt = 0; rt < 4; ++rt) { at[rt] = f32x4{bt, bt, bt, bt}; as[rt] = f32x4{bs, bs, bs, bs}; }
         const float* xa = Xs + r * xs + q;
         float wtr[PF], wsr[PF];                            // the weights of the next PF k steps are in flight while the MFMAs of this one issue
 #pragma unroll
@@ -180,9 +180,9 @@ __global__ __launch_bounds__(THREADS) void pwg_layer_kernel(const float* __restr
     for (int n = wave; n < N2 / 16; n += WAVES) {
         const int col = n * 16 + r;
         const float bv = b2[col];
-        v4f acc[4];
+        f32x4 acc[4];
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) acc[rt] = v4f{bv, bv, bv, bv};
+        for (int rt = 0; rt < 4; ++rt) acc[rt] = f32x4{bv, bv, bv, bv};
         const float* ga = Gs + r * gst + q;
         const float* wc = w2 + col;
         for (int k0 = 0; k0 < R; k0 += 4) {
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(THREADS) void pwg_head_kernel(const float* __restri
     pwg_head_stage(skips, Ys, row0, t0, T, S, scale, [](size_t, float4) {});
     for (int n = wave; n < S / 16; n += WAVES) {
         const int col = n * 16 + r;
-        v4f acc[4];
+        f32x4 acc[4];
         pwg_head_w1(Ys, w1, b1, S, col, acc);
 #pragma unroll
         for (int rt = 0; rt < 4; ++rt)
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(THREADS) void pwg_head_kernel(const float* __restri
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------------
 int layer_lds_bytes(int R, int A, int* xs, int* gs_off)
 {
-    const int stride = xs_stride_of(3 * R + A);
+    const int stride = lds_stride_of(3 * R + A);
     const bool alias = R / 16 <= WAVES;
     if (xs) *xs = stride;
     if (gs_off) *gs_off = alias ? 0 : TM * stride;
@@ -293,7 +293,7 @@ extern "C" int glowtts_pwg_condition(const float* mel, const int32_t* frame_leng
         mult *= sc;
         fir += 2 * sc + 1;
     }
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_pwg_first(const float* noises, const uint32_t* seeds, const int32_t* frame_lengths, const float* w, const float* bias, float* x, int B,
@@ -304,7 +304,7 @@ extern "C" int glowtts_pwg_first(const float* noises, const uint32_t* seeds, con
     hipLaunchKernelGGL(pwg_first_kernel, dim3((unsigned)((quads + THREADS - 1) / THREADS), B), dim3(THREADS), 0, static_cast<hipStream_t>(stream), noises, seeds,
                        frame_lengths, w, bias, x, Lmax, hop, R);
     GLOWTTS_NOTE_STATIC("pwg_first");
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_pwg_layer(const float* x, const float* c, const float* w1, const float* b1, const float* w2, const float* b2, float* x_out, float* skips,
@@ -320,7 +320,7 @@ extern "C" int glowtts_pwg_layer(const float* x, const float* c, const float* w1
     hipLaunchKernelGGL(pwg_layer_kernel, dim3((Tmax + TM - 1) / TM, B), dim3(THREADS), (size_t)lds, static_cast<hipStream_t>(stream), x, c, w1, b1, w2, b2, x_out, skips,
                        frame_lengths, Lmax, hop, R, S, A, dilation, accumulate, xs, gs_off);
     GLOWTTS_NOTE_STATIC("pwg_layer");
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_pwg_head(const float* skips, const int32_t* frame_lengths, const float* w1, const float* b1, const float* w2, const float* b2, float* wav,
@@ -333,5 +333,5 @@ extern "C" int glowtts_pwg_head(const float* skips, const int32_t* frame_lengths
     hipLaunchKernelGGL(pwg_head_kernel, dim3((Tmax + TM - 1) / TM, B), dim3(THREADS), (size_t)lds, static_cast<hipStream_t>(stream), skips, frame_lengths, w1, b1, w2, b2,
                        wav, Lmax, hop, S, scale);
     GLOWTTS_NOTE_STATIC("pwg_head");
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }

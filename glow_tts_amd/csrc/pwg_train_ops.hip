@@ -51,7 +51,7 @@ __global__ __launch_bounds__(THREADS) void pwg_head_bwd_kernel(const float* __re
     for (int n = wave; n < S / 16; n += WAVES) {
         const int col = n * 16 + r;
         const float w2v = w2[col];
-        v4f acc[4];
+        f32x4 acc[4];
         pwg_head_w1(Ys, w1, b1, S, col, acc);
 #pragma unroll
         for (int rt = 0; rt < 4; ++rt)
@@ -70,9 +70,9 @@ __global__ __launch_bounds__(THREADS) void pwg_head_bwd_kernel(const float* __re
     __syncthreads();
     for (int n = wave; n < S / 16; n += WAVES) {
         const int col = n * 16 + r;                        // input channel
-        v4f acc[4];
+        f32x4 acc[4];
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) acc[rt] = v4f{0.f, 0.f, 0.f, 0.f};
+        for (int rt = 0; rt < 4; ++rt) acc[rt] = f32x4{0.f, 0.f, 0.f, 0.f};
         const float* da = DHs + r * st + q;
         for (int k0 = 0; k0 < S; k0 += 4) {
             const float wk = w1t[(size_t)(k0 + q) * S + col];
@@ -124,9 +124,9 @@ __global__ __launch_bounds__(THREADS) void pwg_layer_bwd_gate_kernel(const float
         const int col = p * 16 + r;
         const float* wt = w1 + col;                        // tanh column; its sigmoid column lies R further
         const float bt = b1[col], bs = b1[R + col];
-        v4f at[4], as[4], dg[4];
+        f32x4 at[4], as[4], dg[4];
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) { at[rt] = v4f{bt, bt, bt, bt}; as[rt] = v4f{bs, bs, bs, bs}; dg[rt] = v4f{0.f, 0.f, 0.f, 0.f}; }
+        for (int rt = 0; rt < 4; ++rt) { at[rt] = f32x4{bt, bt, bt, bt}; as[rt] = f32x4{bs, bs, bs, bs}; dg[rt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
         const float* xa = Xs + r * xs + q;
         // (pwg_layer_kernel runs this sum with a weight prefetch; both start from the bias and take k ascending in steps of 4)
         for (int k0 = 0; k0 < KA; k0 += 4) {
@@ -186,9 +186,9 @@ __global__ __launch_bounds__(THREADS) void pwg_layer_bwd_data_kernel(const float
         const bool res = n < nr;                           // (uniform over the wave)
         const int col = (res ? n : n - nr) * 16 + r;
         const bool ok = res || col < A;
-        v4f acc[4];
+        f32x4 acc[4];
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) acc[rt] = v4f{0.f, 0.f, 0.f, 0.f};
+        for (int rt = 0; rt < 4; ++rt) acc[rt] = f32x4{0.f, 0.f, 0.f, 0.f};
         const float* da = Ds + r * ds + q + (res ? 0 : G);
         const int K = res ? K3 : G, ldw = res ? R : A;
         const float* wsrc = res ? w1t : wauxt;
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(THREADS) void pwg_cond_in_bwd_kernel(const float* _
 }
 
 // ---- host side ----
-int gate_lds(int R, int S, int A) { return TM * (xs_stride_of(3 * R + A) + R + S + 4) * 4; }
+int gate_lds(int R, int S, int A) { return TM * (lds_stride_of(3 * R + A) + R + S + 4) * 4; }
 int data_lds(int R) { return TM * (6 * R + 4) * 4; }
 int head_lds(int S) { return 2 * TM * (S + 4) * 4; }
 
@@ -326,7 +326,7 @@ extern "C" int glowtts_pwg_train_head_bwd(const float* skips, const int32_t* fra
     GLOWTTS_NOTE_STATIC("pwg_head_bwd");
     hipLaunchKernelGGL(pwg_head_bwd_kernel, dim3((Lmax * hop + TM - 1) / TM, B), dim3(THREADS), (size_t)lds, static_cast<hipStream_t>(stream), skips, frame_lengths, w1,
                        w1t, b1, w2, dwav, y, h, dh, dskips, Lmax, hop, S, scale);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_pwg_train_head_wgrad(const float* y, const float* h, const float* dh, const float* dwav, const int32_t* frame_lengths, float* work, float* dw1,
@@ -353,10 +353,10 @@ extern "C" int glowtts_pwg_train_layer_bwd(const float* x, const float* c, const
     hipStream_t s = static_cast<hipStream_t>(stream);
     GLOWTTS_NOTE_STATIC("pwg_layer_bwd_gate");
     hipLaunchKernelGGL(pwg_layer_bwd_gate_kernel, grid, dim3(THREADS), (size_t)lds1, s, x, c, w1, b1, w2t, dxp, dskips, gate, dpre, frame_lengths, Lmax, hop, R, S, A,
-                       dilation, xs_stride_of(3 * R + A));
+                       dilation, lds_stride_of(3 * R + A));
     GLOWTTS_NOTE_STATIC("pwg_layer_bwd_data");
     hipLaunchKernelGGL(pwg_layer_bwd_data_kernel, grid, dim3(THREADS), (size_t)lds2, s, dpre, w1t, wauxt, dxp, dx, dc, frame_lengths, Lmax, hop, R, A, dilation, first);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_pwg_train_layer_wgrad(const float* x, const float* c, const float* gate, const float* dpre, const float* dxp, const float* dskips,
@@ -401,7 +401,7 @@ extern "C" int glowtts_pwg_train_upsample_bwd(const float* dout, const float* in
     hipLaunchKernelGGL(pwg_upsample_bwd_fir_kernel, dim3(nblk, B), dim3(THREADS), 0, st, dout, in, frame_lengths, reinterpret_cast<double*>(work), A, Lmax, mult, s);
     GLOWTTS_NOTE_STATIC("pwg_upsample_bwd_sum");
     hipLaunchKernelGGL(pwg_sum_parts_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<const double*>(work), dfir, B * nblk, 2 * s + 1);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_pwg_train_cond_in_bwd(const float* mel, const float* dcond, const int32_t* frame_lengths, float* dw, int B, int A, int Lmax, int ctx, void* stream)
@@ -410,5 +410,5 @@ extern "C" int glowtts_pwg_train_cond_in_bwd(const float* mel, const float* dcon
     GLOWTTS_NOTE_STATIC("pwg_cond_in_bwd");
     hipLaunchKernelGGL(pwg_cond_in_bwd_kernel, dim3((A * A * (2 * ctx + 1) + THREADS - 1) / THREADS), dim3(THREADS), 0, static_cast<hipStream_t>(stream), mel, dcond,
                        frame_lengths, dw, B, A, Lmax, ctx);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }

@@ -45,7 +45,7 @@ __global__ __launch_bounds__(64) void pwg_wgrad_kernel(const wg_args a)
     const size_t row0 = (size_t)b * Tmax;
     const int t_end = min((chunk + 1) * WG_ROWS, T);
     const bool a_ok = i < J.ka, a_one = J.ones && i == J.ka, n_ok = n < J.n;
-    v4f acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int t = chunk * WG_ROWS + q; t < t_end + 3; t += 4) {      // (t - q < t_end for every lane of the wave: the MFMA is issued by all 64)
         if (t - q >= t_end) break;
         float av = 0.f, bv = 0.f;
@@ -110,7 +110,7 @@ int wgrad_launch(wg_args& a, const int32_t* lengths, float* work, int B, int Lma
     hipLaunchKernelGGL(pwg_wgrad_kernel, dim3(a.total_tiles, splits), dim3(64), 0, s, a);
     hipLaunchKernelGGL(pwg_wgrad_sum_kernel, dim3((a.total_elems + THREADS - 1) / THREADS), dim3(THREADS), 0, s, a, splits);
     glowtts_note_launch(sum_name);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 }  // namespace

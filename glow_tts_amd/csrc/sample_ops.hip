@@ -160,5 +160,5 @@ extern "C" int glowtts_prior_sample(const float* mean, const float* log_std, con
     if (vec) hipLaunchKernelGGL(prior_sample_kernel<true>, grid, dim3(THREADS), 0, s, mean, log_std, dur, mel_lengths, seeds, noise_scales, z, idx, attn, C, Tx, Tmax);
     else     hipLaunchKernelGGL(prior_sample_kernel<false>, grid, dim3(THREADS), 0, s, mean, log_std, dur, mel_lengths, seeds, noise_scales, z, idx, attn, C, Tx, Tmax);
     GLOWTTS_NOTE_STATIC("prior_sample");
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }

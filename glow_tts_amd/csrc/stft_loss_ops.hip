@@ -249,7 +249,7 @@ extern "C" int glowtts_stft_loss_forward(const float* pred, const float* target,
     if (hipGetLastError() != hipSuccess) return GLOWTTS_E_LAUNCH;
     GLOWTTS_NOTE_STATIC("stft_loss_reduce");
     hipLaunchKernelGGL(stft_loss_reduce_kernel, dim3(1), dim3(VOC_NT), 0, static_cast<hipStream_t>(stream), a.partial, terms, loss, (int)frames, F, weight, accumulate);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_stft_loss_backward(const float* keep, const float* terms, const float* grad_out, const float* window, const float* twiddle, float* work,
@@ -271,5 +271,5 @@ extern "C" int glowtts_stft_loss_backward(const float* keep, const float* terms,
     GLOWTTS_NOTE_STATIC("stft_loss_bwd_fold");
     hipLaunchKernelGGL(stft_loss_bwd_fold_kernel, dim3((T + 255) / 256, B), dim3(256), 0, static_cast<hipStream_t>(stream), a.dframes, dpred, T, NF, n_fft, win_length, hop,
                        accumulate);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }

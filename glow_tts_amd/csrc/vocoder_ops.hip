@@ -201,12 +201,12 @@ template <int MODE>
 int voc_launch(const voc_args& a, int n_fft, void* stream)
 {
     hipLaunchKernelGGL(vocoder_frame_kernel<MODE>, dim3(voc_grid(a.B * a.T)), dim3(VOC_NT), voc_lds_bytes(n_fft, a.win, 0), static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 int voc_ola(const float* frames, const int32_t* lengths, const float* window, float* wav, int B, int T, int ldx, int n_fft, int win, int hop, void* stream)
 {
     hipLaunchKernelGGL(vocoder_ola_kernel, dim3((ldx + 255) / 256, B), dim3(256), 0, static_cast<hipStream_t>(stream), frames, lengths, window, wav, T, ldx, n_fft, win, hop);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 bool voc_bad_dims(int B, int T, int ldx, int n_fft, int win, int hop)
 {
@@ -227,7 +227,7 @@ extern "C" int glowtts_mel_to_linear_f32(const float* mels, const int32_t* frame
     GLOWTTS_NOTE_STATIC("vocoder_mel_to_linear");
     hipLaunchKernelGGL(vocoder_mel_to_linear_kernel, dim3((T + MTL_TF - 1) / MTL_TF, B), dim3(256), (size_t)MTL_TF * Mel * 4, static_cast<hipStream_t>(stream), mels,
                        frame_lengths, basis, mag, Mel, T, F, max_abs);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 extern "C" int glowtts_stft_f32(const float* wav, const int32_t* wav_lengths, const float* window, const float* twiddle, float* spec, int B, int ldx, int T, int n_fft,

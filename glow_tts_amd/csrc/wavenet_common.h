@@ -17,17 +17,7 @@ constexpr int WN_NT = WN_NW * 64;
 constexpr int WN_MAXL = GLOWTTS_WN_FUSED_MAX_LAYERS;
 constexpr int WN_SROWS = 96;                      // rows of the Start conv's operand tile (three fragments cover the 68 state rows)
 
-typedef __amdgpu_buffer_rsrc_t Rsrc;
-template <int V> struct IC { static constexpr int value = V; };
 constexpr uint32_t OOB = 0x80000000u;
-// f(IC<0>{}), f(IC<1>{}), ... f(IC<N - 1>{}): straight-line code over compile-time step numbers
-template <int N> struct StaticForN {
-    template <class F> __device__ __forceinline__ static void run(F&& f) { StaticForN<N - 1>::run(f); f(IC<N - 1>{}); }
-};
-template <> struct StaticForN<0> { template <class F> __device__ __forceinline__ static void run(F&&) {} };
-
-__device__ __forceinline__ Rsrc mk_rsrc(const void* ptr, long bytes) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ptr), 0, (int)bytes, 0x00020000); }
-__device__ __forceinline__ int frag_row(int reg) { return (reg & 3) + 8 * (reg >> 2); }       // + 4 * (lane >> 5): row of accumulator element `reg`
 template <bool ON = true>
 __device__ __forceinline__ f32x16 mfma_bf16(const Chunk16& a, const Chunk16& b, const f32x16& c) {
     if constexpr (!ON) { f32x16 r = c; r[0] += __uint_as_float(a[0] ^ b[0]); return r; }
@@ -57,7 +47,5 @@ template <int N> __device__ __forceinline__ void lgkm_wait(Chunk16 (&a)[2], Chun
 __device__ __forceinline__ uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) unsigned char*)p; }
 __device__ __forceinline__ Chunk16 lds16(const unsigned char* p) { return *reinterpret_cast<const Chunk16*>(p); }
 template <class T> __device__ __forceinline__ T pick4(T const (&a)[4], int l) { return l == 0 ? a[0] : (l == 1 ? a[1] : (l == 2 ? a[2] : a[3])); }   // (no dynamic indexing of kernel arguments)
-__device__ __forceinline__ unsigned short bf16_bits(float v) { const __bf16 b = (__bf16)v; return *reinterpret_cast<const unsigned short*>(&b); }
-
 
 }  // namespace

@@ -44,7 +44,7 @@ constexpr int WN_LDS = OFF_UT + WN_XR * 4;
 static_assert(WN_LDS <= 160 * 1024, "LDS budget");
 static_assert(SZ_AT >= 3 * WN_SROWS * 64, "the Start operand tile aliases the acts tile");
 
-typedef StaticForN<WN_TAPS * WN_KCH> StaticFor30;
+typedef StaticFor<WN_TAPS * WN_KCH> StaticFor30;
 
 struct wn_fwd_args {
     int rows, rows_per_utt, L, C2, reverse, keep, safe_waits;
@@ -373,7 +373,7 @@ __global__ __launch_bounds__(WN_NT) void wn_fwd_kernel(const wn_fwd_args p)
             int rb = rbw;
             asm volatile("" : "+v"(rb));                       // (opaque: the per-element invariants are not hoisted out of the layer loop - they spilled)
             const Rsrc rg = mk_rsrc(pick4(p.gates, l), keep ? (long)p.rows * (2 * WN_H * 2) : 0);
-            const uint32_t rk0 = (uint32_t)(t0 + rb) * 0x9E3779B1u + seed0 + (uint32_t)l;      // drop_rowkey(seed, row) = mix(row * M + seed)
+            const uint32_t rk0 = (uint32_t)(t0 + rb) * 0x9E3779B1u + seed0 + (uint32_t)l;      // drop_rowkey(seed, row) = fmix_head(row * M + seed)
             const uint32_t own0 = (uint32_t)(rb - halo);                                       // owned <=> (rb + c - halo) < lim (unsigned)
             unsigned char* const ac = AT + pi * (WN_WIN * 64) + rb * 64;
             const int* const ut = UT + rb + WN_PAD;
@@ -383,9 +383,7 @@ __global__ __launch_bounds__(WN_NT) void wn_fwd_kernel(const wn_fwd_args p)
                 for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        constexpr uint32_t M1 = 0x9E3779B1u;
-                        uint32_t x = rk0 + (uint32_t)(16 * rt + i) * M1; x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13;
-                        rkey[rt][i] = x;
+                        rkey[rt][i] = fmix_head(rk0 + (uint32_t)(16 * rt + i) * 0x9E3779B1u);
                     }
             }
 #pragma unroll
@@ -703,7 +701,7 @@ int launch_wn_fwd(const wn_fwd_args& k, dim3 grid, hipStream_t s)
     }
     GLOWTTS_NOTE_STATIC("wn_fwd<%s%s>", DROP ? "drop" : "nodrop", COND ? ",cond" : "");
     hipLaunchKernelGGL((wn_fwd_kernel<DROP, COND, KEEP, SAFE, ABL>), grid, dim3(WN_NT), WN_LDS, s, k);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 template <bool DROP, bool COND>

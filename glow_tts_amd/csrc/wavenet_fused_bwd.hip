@@ -310,7 +310,7 @@ __global__ __launch_bounds__(WN_NT) void wn_bwd_kernel(const wn_bwd_args p)
         // Behind slab 0's DMAs: the NG gate loads; behind slab 1's: those and the copy-out's stores; from slab 2 on all of them are older ----
         zero_acc();
         if constexpr (last) {
-            StaticForN<3>::run([&](auto J_) __attribute__((always_inline)) {
+            StaticFor<3>::run([&](auto J_) __attribute__((always_inline)) {
                 constexpr int j = decltype(J_)::value;
                 const unsigned char* slot = begin_step(IC<(j == 0 ? NGX : (j == 1 ? NGX + ((ABL & 4) ? 0 : XC) : 0))>{});
                 if constexpr (j == 0) copy_out(DS, WN_XR, halo + WN_PAD, p.dskip, WN_H * 2, 64, 0);            // d skip (kept: DY of the Res_Skip weight gradients)
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(WN_NT) void wn_bwd_kernel(const wn_bwd_args p)
                 end_step();
             });
         } else {
-            StaticForN<3>::run([&](auto J_) __attribute__((always_inline)) {      // K chunks 0..5: d x_{l+1} (window rows)
+            StaticFor<3>::run([&](auto J_) __attribute__((always_inline)) {      // K chunks 0..5: d x_{l+1} (window rows)
                 constexpr int j = decltype(J_)::value;
                 const unsigned char* slot = begin_step(IC<(j == 0 ? NGX : (j == 1 ? NGX + ((ABL & 4) ? 0 : XC) : 0))>{});
                 if constexpr (j == 0) copy_out(DX, WN_WIN, halo, pick4(p.dh, l + 1), WN_H * 2, 64, 0);           // d x_{l+1} (kept: DY of the Res_Skip weight gradient)
@@ -342,11 +342,8 @@ __global__ __launch_bounds__(WN_NT) void wn_bwd_kernel(const wn_bwd_args p)
             const int rb = rf * 32 + 4 * lqx;
             const int jch0 = cf * 32 + l15x;                    // (shadows the kernel-wide one)
             const int g0 = xr0 + roff + rb;                     // global row of accumulator row 0
-            const uint32_t rk0 = (uint32_t)g0 * 0x9E3779B1u + seed0 + (uint32_t)l;      // drop_rowkey(seed + l, row) = mix(row * M + seed + l)
-            auto rowkey = [&](int c) __attribute__((always_inline)) -> uint32_t {
-                uint32_t x = rk0 + (uint32_t)c * 0x9E3779B1u; x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13;
-                return x;
-            };
+            const uint32_t rk0 = (uint32_t)g0 * 0x9E3779B1u + seed0 + (uint32_t)l;      // drop_rowkey(seed + l, row) = fmix_head(row * M + seed + l)
+            auto rowkey = [&](int c) __attribute__((always_inline)) -> uint32_t { return fmix_head(rk0 + (uint32_t)c * 0x9E3779B1u); };
             // owned TILE rows [own_lo, own_hi): the conditioning gradient sums them per utterance
             const int own_lo = halo + WN_PAD, own_hi = own_lo + lim;
             const bool one_utt = COND && lim > 0 && UT[own_lo] == UT[own_lo + lim - 1];       // (wave-uniform) the rule: an utterance is hundreds of rows
@@ -489,7 +486,7 @@ __global__ __launch_bounds__(WN_NT) void wn_bwd_kernel(const wn_bwd_args p)
                 __builtin_amdgcn_sched_barrier(0);
                 end_step();
             };
-            StaticForN<30>::run([&](auto J_) __attribute__((always_inline)) { step(J_); });
+            StaticFor<30>::run([&](auto J_) __attribute__((always_inline)) { step(J_); });
             lgkm_wait<0>(fa[1], fb[1]);
             mma(IC<1>{});                                       // slab 29
         }
@@ -657,7 +654,7 @@ int launch_wn_bwd(const wn_bwd_args& k, dim3 grid, hipStream_t s)
     }
     GLOWTTS_NOTE_STATIC("wn_bwd<%s%s>", DROP ? "drop" : "nodrop", COND ? ",cond" : "");
     hipLaunchKernelGGL((wn_bwd_kernel<DROP, COND, ABL>), grid, dim3(WN_NT), BW_LDS, s, k);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 }  // namespace

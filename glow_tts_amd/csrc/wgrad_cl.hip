@@ -22,13 +22,12 @@
 #include "../../include/glowtts_hip.h"
 #include "tunable.h"
 #include "launch_log.h"
+#include "device_common.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BMO = 128;      // o per block
 constexpr int BNC = 64;       // c per block
@@ -45,40 +44,25 @@ constexpr int BK = 64;        // rows per step
 constexpr int NT = WGRAD_WAVES * 64;          // threads per workgroup: 8 waves = 4 (o) x 2 (c) wave tiles of 32 x 32 (x taps)
 constexpr int MI = WGRAD_WAVES == 8 ? 1 : 2; // 32-row fragments of o per wave
 
-__device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    bf16x2 v; v[0] = (__bf16)lo; v[1] = (__bf16)hi;
-    return *reinterpret_cast<uint32_t*>(&v);
-}
-
-template <int V> struct WIC { static constexpr int value = V; };
-template <int N> struct WStaticFor {
-    template <class F> __device__ __forceinline__ static void run(F&& f) { WStaticFor<N - 1>::run(f); f(WIC<N - 1>{}); }
-};
-template <> struct WStaticFor<0> { template <class F> __device__ __forceinline__ static void run(F&&) {} };
-
 struct WCommon { int rows, pad, accumulate, njobs, xcd; int phase = 0; };      // phase: tiles of the first phase (glowtts_wgrad_grouped_phased), 0 = one phase
 
 // pointers that come out of the device job table are "generic" to the compiler, which would emit flat_load (counted on
 // BOTH vmcnt and lgkmcnt, i.e. every LDS wait would also drain the prefetch).  They are global: say so.
-typedef float f32x4n __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 ldg4(const float* p) {
-    const f32x4n v = *(const f32x4n __attribute__((address_space(1)))*)(p);
+    const f32x4 v = *(const f32x4 __attribute__((address_space(1)))*)(p);
     return make_float4(v[0], v[1], v[2], v[3]);
 }
 
 // NW 32-bit words from a global byte address (8-byte aligned for NW == 2, 16-byte otherwise)
-typedef uint32_t u32x2n __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4n __attribute__((ext_vector_type(4)));
 template <int NW>
 __device__ __forceinline__ void ldgw(uint32_t* dst, const unsigned char* src) {
     if constexpr (NW == 2) {
-        const u32x2n v = *(const u32x2n __attribute__((address_space(1)))*)(src);
+        const u32x2 v = *(const u32x2 __attribute__((address_space(1)))*)(src);
         dst[0] = v[0]; dst[1] = v[1];
     } else {
 #pragma unroll
         for (int j = 0; j < NW / 4; ++j) {
-            const u32x4n v = *(const u32x4n __attribute__((address_space(1)))*)(src + 16 * j);
+            const u32x4 v = *(const u32x4 __attribute__((address_space(1)))*)(src + 16 * j);
             dst[4 * j] = v[0]; dst[4 * j + 1] = v[1]; dst[4 * j + 2] = v[2]; dst[4 * j + 3] = v[3];
         }
     }
@@ -198,7 +182,7 @@ __global__ __launch_bounds__(NT) void wgrad_kernel(const glowtts_wgrad_job singl
                 for (int e = 0; e < 4; ++e) {
                     const float a = ok ? __uint_as_float(rdy[it][2 * e]) : 0.f, b = ok ? __uint_as_float(rdy[it][2 * e + 1]) : 0.f;
                     bsum[2 * e] += a; bsum[2 * e + 1] += b;
-                    w[e] = pk_bf16(a, b);
+                    w[e] = pack_bf16x2(a, b);
                 }
                 *reinterpret_cast<uint4*>(dyb + row * LDY + c4 * 16) = make_uint4(w[0], w[1], w[2], w[3]);
             } else if constexpr (DYBF) {
@@ -210,7 +194,7 @@ __global__ __launch_bounds__(NT) void wgrad_kernel(const glowtts_wgrad_job singl
                 v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
                 bsum[0] += v.x; bsum[1] += v.y; bsum[2] += v.z; bsum[3] += v.w;
                 if constexpr (ES == 2) {
-                    uint2 w = make_uint2(pk_bf16(v.x, v.y), pk_bf16(v.z, v.w));
+                    uint2 w = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
                     *reinterpret_cast<uint2*>(dyb + row * LDY + c4 * 8) = w;
                 } else {
                     *reinterpret_cast<float4*>(dyb + row * LDY + c4 * 16) = v;
@@ -231,7 +215,7 @@ __global__ __launch_bounds__(NT) void wgrad_kernel(const glowtts_wgrad_job singl
                 uint32_t w[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    w[e] = ok ? pk_bf16(__uint_as_float(rx[it][2 * e]), __uint_as_float(rx[it][2 * e + 1])) : 0u;
+                    w[e] = ok ? pack_bf16x2(__uint_as_float(rx[it][2 * e]), __uint_as_float(rx[it][2 * e + 1])) : 0u;
                 *reinterpret_cast<uint4*>(xb + row * LDX + c4 * 16) = make_uint4(w[0], w[1], w[2], w[3]);
             } else if constexpr (XBF && XPRO == GLOWTTS_APRO_NONE) {
                 *reinterpret_cast<uint2*>(xb + row * LDX + c4 * 8) = make_uint2(ok ? rx[it][0] : 0u, ok ? rx[it][1] : 0u);
@@ -247,7 +231,7 @@ __global__ __launch_bounds__(NT) void wgrad_kernel(const glowtts_wgrad_job singl
                 }
                 v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
                 if constexpr (ES == 2) {
-                    uint2 w = make_uint2(pk_bf16(v.x, v.y), pk_bf16(v.z, v.w));
+                    uint2 w = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
                     *reinterpret_cast<uint2*>(xb + row * LDX + c4 * 8) = w;
                 } else {
                     *reinterpret_cast<float4*>(xb + row * LDX + c4 * 16) = v;
@@ -309,12 +293,12 @@ __global__ __launch_bounds__(NT) void wgrad_kernel(const glowtts_wgrad_job singl
 
     // NS steps per iteration so that the register sets are selected at compile time; every load is unconditional
     // (rows past the end are clamped, their contribution is masked to zero when stored)
-    WStaticFor<NS>::run([&](auto j) __attribute__((always_inline)) { gload(rdy[j.value], rx[j.value], rbeg + (long)j.value * BK); });
+    StaticFor<NS>::run([&](auto j) __attribute__((always_inline)) { gload(rdy[j.value], rx[j.value], rbeg + (long)j.value * BK); });
     sstore(rdy[0], rx[0], 0, rbeg);
     __syncthreads();
     for (int s = 0; s < nsteps; s += NS) {
         const long rs = rbeg + (long)s * BK;
-        WStaticFor<NS>::run([&](auto jc) __attribute__((always_inline)) {
+        StaticFor<NS>::run([&](auto jc) __attribute__((always_inline)) {
             constexpr int j = jc.value, jn = (j + 1) % NS;
             gload(rdy[j], rx[j], rs + (long)(j + NS) * BK);              // set j was stored for step s + j: refill it for step s + j + NS
             if (s + j < nsteps) compute(j & 1);
@@ -387,7 +371,6 @@ __global__ __launch_bounds__(NT) void wgrad_kernel(const glowtts_wgrad_job singl
 // Alone on the chip, the In_l group: 338 us (1.01 PFLOP/s, 216 workgroups) against 491-540 us for the staged kernel; MFMAs alone 216 us, DMAs
 // alone 155 us, reads alone 114 us (tools/bench_wgrad.py and its ablations).
 // ------------------------------------------------------------------------------------------------
-typedef float f32x4w __attribute__((ext_vector_type(4)));
 typedef int i32x4w __attribute__((ext_vector_type(4)));
 constexpr int DBK = 64, DBMO = 192, DNW = 4, DNT = DNW * 64;
 constexpr int DMO = 6;                                       // 16-channel o fragments of a wave tile; waves: 2 (o halves of 96) x 2 (c halves)
@@ -418,7 +401,7 @@ template <int TAPS> struct DCfg {
 
 // The 240 accumulator registers of a wave live in AGPRs BY CONSTRUCTION: left to the register allocator the 5-tap kernel came out with 428 v_accvgpr moves and
 // scratch reloads (each behind an s_waitcnt vmcnt(0) that also waits for the DMAs in flight) inside the step loop.
-static __device__ __forceinline__ void mfma_acc(f32x4w& c, const bf16x8& a, const bf16x8& b)
+static __device__ __forceinline__ void mfma_acc(f32x4& c, const bf16x8& a, const bf16x8& b)
 {
     asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
 }
@@ -499,7 +482,7 @@ __global__ __launch_bounds__(DNT) void wgrad_dma_kernel(const glowtts_wgrad_job*
         }
     };
 
-    f32x4w acc[DMO][DNC][TAPS];
+    f32x4 acc[DMO][DNC][TAPS];
     float bsum[DMO];                                         // dbias partial of this lane: DY column 64 wm + 16 mo + s16, the rows of its k group
 #pragma unroll
     for (int mo = 0; mo < DMO; ++mo) {
@@ -507,7 +490,7 @@ __global__ __launch_bounds__(DNT) void wgrad_dma_kernel(const glowtts_wgrad_job*
 #pragma unroll
         for (int nc = 0; nc < DNC; ++nc)
 #pragma unroll
-            for (int t = 0; t < TAPS; ++t) acc[mo][nc][t] = f32x4w{0.f, 0.f, 0.f, 0.f};
+            for (int t = 0; t < TAPS; ++t) acc[mo][nc][t] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     const bool want_bias = (p.dbias != nullptr) && tile_c == 0 && wn == 0;
 
@@ -640,7 +623,7 @@ int launch_wgrad_dma(const glowtts_wgrad_job* table, const WCommon& cm, dim3 gri
     }
     GLOWTTS_NOTE_STATIC("wgrad_dma<%d>/grouped", TAPS);
     hipLaunchKernelGGL((wgrad_dma_kernel<TAPS>), grid, dim3(DNT), DCfg<TAPS>::STAGES * DCfg<TAPS>::STAGE, s, table, cm);
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 
 template <typename CT, int XPRO, bool DYBF, bool XBF, bool WIDE = false>
@@ -654,7 +637,7 @@ int launch_x(const glowtts_wgrad_job& one, const glowtts_wgrad_job* table, const
         case 5: hipLaunchKernelGGL((wgrad_kernel<CT, 5, XPRO, DYBF, XBF, WIDE>), grid, dim3(NT), 0, s, one, table, cm); break;
         default: return GLOWTTS_E_ARG;
     }
-    return hipGetLastError() == hipSuccess ? GLOWTTS_OK : GLOWTTS_E_LAUNCH;
+    RET_LAUNCH();
 }
 // all jobs of one launch share the X prologue (`xpro`) and the storage types (`io`): grouped launches are formed per class.
 // bf16 storage combinations the Glow-TTS path uses: (DY, X) both bf16 with no prologue (In conv: gate gradients x WaveNet state)

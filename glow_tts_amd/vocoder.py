@@ -179,7 +179,7 @@ PWG_TILE, PWG_MAX_CHANNELS, PWG_MAX_DILATION, PWG_MAX_SCALE, PWG_MAX_SCALES, PWG
 
 
 def lds_row_stride(K):
-    """The stride in floats of an LDS row of K floats whose quarter is odd (`xs_stride_of` of csrc/pwg_common.h)"""
+    """The stride in floats of an LDS row of K floats whose quarter is odd (`lds_stride_of` of csrc/device_common.h)"""
     return K if (K // 4) % 2 else K + 4
 
 

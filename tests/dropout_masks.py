@@ -4,7 +4,7 @@ None of these masks is ever written to memory by the library: every kernel that 
 backward kernels re-derive it again (or recover it from `output != 0`).  A parity test restates the draw here and injects the result into
 the oracle (oracle/glowtts_ref.py `drop=` hooks), whose forward and torch.autograd backward then see the same network.
 
-  linear_keep / attention_keep   `drop_scale` of csrc/device_common.h and csrc/encoder_ops.hip: the text encoder's sites
+  linear_keep / attention_keep   `drop_scale` of csrc/device_common.h (the one definition every site calls): the text encoder's sites
   hip_keep_multipliers           `drop_rowkey` / `drop_colkey` / `drop_draw` of csrc/device_common.h: the WaveNet gate pre-activations
 """
 import numpy as np
