@@ -267,6 +267,8 @@ SIGNATURES = {
     "glowtts_pwg_first": (I, [P] * 6 + [I] * 4 + [P]),
     "glowtts_pwg_layer": (I, [P] * 9 + [I] * 8 + [P]),
     "glowtts_pwg_head": (I, [P] * 7 + [I] * 4 + [F, P]),
+    "glowtts_pwg_supported_bf16": (I, [I] * 5),
+    "glowtts_pwg_layer_bf16": (I, [P] * 9 + [I] * 8 + [P]),
     "glowtts_ge2e_supported": (I, [I] * 4),
     "glowtts_ge2e_image_floats": (L, [I] * 3),
     "glowtts_ge2e_work_floats": (L, [L] + [I] * 3),

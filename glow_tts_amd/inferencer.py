@@ -28,11 +28,14 @@ def utterance_seed_words(seed, label, k=0):
 
 
 class Inferencer:
-    def __init__(self, checkpoint_path, hp=None, device="cuda:0", device_frontend=False, vocoder=None, vocoder_checkpoint=None, speaker_encoder=None):
+    def __init__(self, checkpoint_path, hp=None, device="cuda:0", device_frontend=False, vocoder=None, vocoder_checkpoint=None, speaker_encoder=None,
+                 vocoder_precision=None):
         """device_frontend: wav references and wav voice-conversion sources are analysed on the device (`frontend.Analyzer`) instead of the host's
         `audio.pattern_from_wav`; decoding, trimming and normalisation stay `audio.audio_prep` either way.
         vocoder: 'pwg' (the neural vocoder), 'griffin_lim' (forces the baseline) or None: 'pwg' when the yaml has the `Vocoder` block or
         `vocoder_checkpoint` (overrides `Vocoder.Checkpoint_Path`) is given, Griffin-Lim otherwise.
+        vocoder_precision: 'f32', 'bf16' or None (the yaml's `Vocoder.Precision`, default 'f32') - the neural vocoder's layer arithmetic
+        (`vocoder.ParallelWaveGAN`); Griffin-Lim ignores it.
         speaker_encoder: GE2E mode only - a callable mapping a slice stack [B * Samples, Mel, Slice] to unit d-vectors [B, Embedding_Size].  None: the
         `speaker_encoder.GE2E` of `Speaker_Embedding.GE2E.Checkpoint_Path`, else the one the GlowTTS checkpoint carries under `layer_Dict.GE2E.*` (keys of
         another layout: a warning, and they are dropped), else none - then only ready d-vectors can be given."""
@@ -41,6 +44,9 @@ class Inferencer:
             raise ValueError("vocoder must be 'pwg', 'griffin_lim' or None, got {!r}".format(vocoder))
         self.vocoder_kind = vocoder or ("pwg" if vocoder_checkpoint or getattr(self.hp, "Vocoder", None) is not None else "griffin_lim")
         self.vocoder_checkpoint = vocoder_checkpoint
+        if vocoder_precision not in (None, "f32", "bf16"):
+            raise ValueError("vocoder_precision must be 'f32', 'bf16' or None, got {!r}".format(vocoder_precision))
+        self.vocoder_precision = vocoder_precision
         self.device = torch.device(device)
         self.device_frontend, self._analyzer = bool(device_frontend), None
         self.token_Dict = data.load_token_dict(self.hp.Token_Path)
@@ -84,7 +90,7 @@ class Inferencer:
             import copy
             hp = copy.copy(hp)
             hp.Vocoder = argparse.Namespace(**dict(vocoder.pwg_settings(hp), Checkpoint_Path=self.vocoder_checkpoint))
-        return vocoder.ParallelWaveGAN(hp, self.device)
+        return vocoder.ParallelWaveGAN(hp, self.device, precision=self.vocoder_precision)
 
     def _write_wavs(self, mels, mel_lengths, names, inference_path, seeds=None, vocoder_seeds=None):
         """The active vocoder on the mels as the model produced them ([B, Mel, T], on the device) -> WAV/<name>.wav, 16-bit, Sound.Sample_Rate.
@@ -402,6 +408,9 @@ def build_parser():
                     help="the vocoder behind --wav / --vocode: pwg = the neural vocoder (Parallel WaveGAN generator; needs a checkpoint), griffin_lim = the baseline; "
                          "default: pwg when the yaml has a `Vocoder` block or --vocoder-checkpoint is given, else griffin_lim")
     ap.add_argument("--vocoder-checkpoint", default=None, metavar="PATH", help="Parallel WaveGAN generator checkpoint (overrides Vocoder.Checkpoint_Path of the yaml)")
+    ap.add_argument("--vocoder-precision", choices=["f32", "bf16"], default=None,
+                    help="arithmetic of the neural vocoder's layers (overrides Vocoder.Precision of the yaml; default f32): bf16 rounds the layers' operands, "
+                         "weights and gate to bf16 - faster, and with --seed its own reproducible wav, not the f32 one")
     ap.add_argument("--vocode", default=None, metavar="LIST", help="vocode existing mels instead of synthesising: one label<TAB>mel.npy ([T, Mel]) per line")
     ap.add_argument("--device-frontend", action="store_true", help="analyse wav references / conversion sources on the device instead of the host")
     ap.add_argument("--seed", type=int, default=None, help="reproducible sampling: an utterance's mel depends on this seed, its label and the sample number only")
@@ -413,7 +422,8 @@ def build_parser():
 def main(argv=None):
     logging.basicConfig(level=logging.INFO)
     args = build_parser().parse_args(argv)
-    inf = Inferencer(checkpoint_path=args.checkpoint, device_frontend=args.device_frontend, vocoder=args.vocoder, vocoder_checkpoint=args.vocoder_checkpoint)
+    inf = Inferencer(checkpoint_path=args.checkpoint, device_frontend=args.device_frontend, vocoder=args.vocoder, vocoder_checkpoint=args.vocoder_checkpoint,
+                     vocoder_precision=args.vocoder_precision)
     if args.vocode:
         recs = read_vocode_list(args.vocode)
         print("\n".join(inf.Vocode([r[0] for r in recs], [r[1] for r in recs], args.out)))

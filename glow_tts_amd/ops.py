@@ -182,6 +182,17 @@ def pwg_layer(x, c, w1, b1, w2, b2, x_out, skips, frame_lengths, Lmax, hop, dila
                                             int(bool(accumulate)), _lib.stream()), "glowtts_pwg_layer")
 
 
+def pwg_layer_bf16(x, c, w1p, b1, w2p, b2, x_out, skips, frame_lengths, Lmax, hop, dilation, accumulate):
+    """One WaveNet layer with bf16 operands (glowtts_pwg_layer_bf16): as `pwg_layer`; w1p, w2p: the packed bf16 images of `vocoder.pwg_pack_bf16`."""
+    R, S, A = x.shape[2], skips.shape[2], c.shape[2]
+    if w1p.dtype != torch.bfloat16 or w2p.dtype != torch.bfloat16 or tuple(w1p.shape) != ((3 * R + A + 31) // 32 * 4, 2 * R, 8) or \
+            tuple(w2p.shape) != ((R + 31) // 32 * 4, R + S, 8):
+        raise _lib.GlowTTSHipError("glowtts_pwg_layer_bf16 needs the packed bf16 weight images of vocoder.pwg_pack_bf16 for these sizes")
+    _lib.check(_lib.lib().glowtts_pwg_layer_bf16(_lib.ptr(x), _lib.ptr(c), _lib.ptr(w1p), _lib.ptr(b1), _lib.ptr(w2p), _lib.ptr(b2), _lib.ptr(x_out), _lib.ptr(skips),
+                                                 _lib.ptr(frame_lengths), x.shape[0], int(Lmax), int(hop), R, S, A, int(dilation), int(bool(accumulate)),
+                                                 _lib.stream()), "glowtts_pwg_layer_bf16")
+
+
 def pwg_head(skips, frame_lengths, w1, b1, w2, b2, wav, Lmax, hop, scale):
     """skips [B, Lmax * hop, S] -> wav [B, Lmax * hop], zero beyond each utterance (glowtts_pwg_head)."""
     _lib.check(_lib.lib().glowtts_pwg_head(_lib.ptr(skips), _lib.ptr(frame_lengths), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(wav),

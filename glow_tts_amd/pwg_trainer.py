@@ -103,7 +103,7 @@ class PWG_Trainer(aux_trainer.Trainer):
         self.geo = pwg_geometry(hp)
         s = train_settings(hp)
         super().__init__(hp, s, steps, device, seed, Sampler, (s["Batch_Size"], s["Segment_Frames"], self.geo["hop"]))
-        self.model = ParallelWaveGAN(self.hp, self.device, trainable=True, seed=self.seed)
+        self.model = ParallelWaveGAN(self.hp, self.device, trainable=True, seed=self.seed, precision="f32")     # (Vocoder.Precision is a serving setting)
         self.criterion = MultiResolutionSTFTLoss(s["STFT_Resolutions"], self.device)
         self.params = list(self.model.params.values())
         self.optimizer = optim.RAdam(self.params, lr=float(s["Learning_Rate"]), eps=float(s["Epsilon"]))

@@ -174,13 +174,33 @@ class GriffinLim:
 # discriminator (further down) alike.
 # ================================================================================================================================================
 PWG_DEFAULTS = {"Type": "PWG", "Checkpoint_Path": None, "Layers": 30, "Stacks": 3, "Residual_Channels": 64, "Gate_Channels": 128, "Skip_Channels": 64,
-                "Aux_Context_Window": 2, "Upsample_Scales": [4, 4, 4, 4]}
+                "Aux_Context_Window": 2, "Upsample_Scales": [4, 4, 4, 4], "Precision": "f32"}
+PWG_PRECISIONS = ("f32", "bf16")
 PWG_TILE, PWG_MAX_CHANNELS, PWG_MAX_DILATION, PWG_MAX_SCALE, PWG_MAX_SCALES, PWG_MAX_CTX, PWG_LDS = 64, 256, 1024, 16, 8, 16, 160 * 1024
 
 
 def lds_row_stride(K):
     """The stride in floats of an LDS row of K floats whose quarter is odd (`lds_stride_of` of csrc/device_common.h)"""
     return K if (K // 4) % 2 else K + 4
+
+
+def pad32(K):
+    """K rounded up to a multiple of 32: the k step of the bf16 MFMA (`pad32` of csrc/pwg_bf16_ops.hip)"""
+    return (K + 31) // 32 * 32
+
+
+def pwg_pack_bf16(w):
+    """w [K, N] float32 (K-major: row = input channel) -> the bf16 image [Kp / 8, N, 8] of csrc/pwg_bf16_ops.hip: rounded to nearest even, zero rows from K to
+    Kp = pad32(K); element (k, n) lies at [k // 8, n, k % 8], so a lane's eight k values of one column are 16 consecutive bytes."""
+    K, N = w.shape
+    p = torch.zeros(pad32(K), N, dtype=torch.bfloat16, device=w.device)
+    p[:K] = w.to(torch.float32).to(torch.bfloat16)
+    return p.view(-1, 8, N).permute(0, 2, 1).contiguous()
+
+
+def pwg_unpack_bf16(image):
+    """The inverse of `pwg_pack_bf16`: image [Kp / 8, N, 8] bf16 -> [Kp, N] float32 (the rounded weights, then the zero rows)"""
+    return image.permute(0, 2, 1).reshape(-1, image.shape[1]).to(torch.float32)
 
 
 def find_state_dict(obj, paths, mine, error):
@@ -247,9 +267,12 @@ def pwg_settings(hp):
 
 
 def pwg_geometry(hp):
-    """The generator's sizes as a dict (layers, stacks, R, G, S, A, ctx, scales, hop, dilations); raises ValueError naming the offending yaml keys when the
-    kernels do not support them - the idiom of `geometry`."""
+    """The generator's sizes as a dict (layers, stacks, R, G, S, A, ctx, scales, hop, dilations, precision); raises ValueError naming the offending yaml keys
+    when the kernels do not support them - the idiom of `geometry`."""
     v = pwg_settings(hp)
+    precision = v["Precision"]
+    if precision not in PWG_PRECISIONS:
+        raise ValueError(f"Vocoder.Precision = {precision!r} must be 'f32' or 'bf16' (bf16: the layer launches' operands only, inference only)")
     if v["Type"] != "PWG":
         raise ValueError(f"Vocoder.Type = {v['Type']!r}: the only neural vocoder is 'PWG' (the Parallel WaveGAN generator)")
     layers, stacks, R, G, S, ctx = (int(v[k]) for k in ("Layers", "Stacks", "Residual_Channels", "Gate_Channels", "Skip_Channels", "Aux_Context_Window"))
@@ -278,7 +301,20 @@ def pwg_geometry(hp):
     lds = 4 * PWG_TILE * (lds_row_stride(K) + (0 if R <= 64 else R + 4))
     if lds > PWG_LDS:
         raise ValueError(f"Vocoder.Residual_Channels = {R} with Sound.Mel_Dim = {A}: a layer's tile of {lds} bytes exceeds the {PWG_LDS} bytes of LDS")
-    return {"layers": layers, "stacks": stacks, "R": R, "G": G, "S": S, "A": A, "ctx": ctx, "scales": scales, "hop": hop, "dilations": dilations}
+    geo = {"layers": layers, "stacks": stacks, "R": R, "G": G, "S": S, "A": A, "ctx": ctx, "scales": scales, "hop": hop, "dilations": dilations,
+           "precision": precision}
+    if precision == "bf16":
+        pwg_bf16_geometry(geo)
+    return geo
+
+
+def pwg_bf16_geometry(geo):
+    """Raises ValueError naming the yaml keys when the bf16 layer kernel's LDS tile (`layer_bf16_lds_bytes` of csrc/pwg_bf16_ops.hip) does not fit."""
+    R, A = geo["R"], geo["A"]
+    lds = 2 * PWG_TILE * (pad32(3 * R + A) + 8 + pad32(R) + 8)
+    if lds > PWG_LDS:
+        raise ValueError(f"Vocoder.Precision = 'bf16' with Vocoder.Residual_Channels = {R} and Sound.Mel_Dim = {A}: a layer's bf16 tile of {lds} bytes exceeds the "
+                         f"{PWG_LDS} bytes of LDS")
 
 
 def pwg_seed_words(seed, label, k=0):
@@ -443,12 +479,24 @@ class ParallelWaveGAN:
     wav_lengths [B] int64).  state_dict None: `Vocoder.Checkpoint_Path` is loaded.  seeds [B, 2] (integer words, `pwg_seed_words`): z[t] is the counter hash
     gauss(s0, s1, 0, t, 1) of csrc/gauss_hash.h evaluated in the first kernel; noises [B, T * hop]: the caller's z; neither: torch.randn on the device.
     An utterance's waveform is bit-identical alone, in any batch, at any padding and from run to run (given its z).
+    precision 'f32' / 'bf16' / None (the yaml's `Vocoder.Precision`, default 'f32'), readable as `.precision`: 'bf16' runs the layer launches with bf16 operands
+    (csrc/pwg_bf16_ops.hip; DESIGN.md "bf16 inference mode" has the contract) - inference only: with trainable=True an explicit 'bf16' raises and the yaml's
+    key is ignored (training is f32).
     trainable=True (DESIGN.md "Training the Parallel WaveGAN generator"): `params` holds float32 device leaves in `pwg_expected_shapes`' names - from
     `state_dict` or, without one, `pwg_init(geo, seed)` - and `generate` returns the same waveform with a backward (csrc/pwg_train_ops.hip)."""
 
-    def __init__(self, hp, device="cuda:0", state_dict=None, trainable=False, seed=0):
+    def __init__(self, hp, device="cuda:0", state_dict=None, trainable=False, seed=0, precision=None):
         self.geo = geo = pwg_geometry(hp)                           # before anything touches the device or the disk
         self.trainable = bool(trainable)
+        if precision is not None and precision not in PWG_PRECISIONS:
+            raise ValueError(f"precision = {precision!r} must be 'f32', 'bf16' or None (None: Vocoder.Precision of the yaml)")
+        if self.trainable and precision == "bf16":
+            raise ValueError("precision = 'bf16' with trainable=True: the bf16 mode is inference only, training stays f32")
+        # the argument over the yaml's key; a trainable generator is f32 whatever the yaml says (the key is a serving setting)
+        self.precision = "f32" if self.trainable else precision or geo["precision"]
+        if self.precision == "bf16":
+            pwg_bf16_geometry(geo)
+        self.geo = geo = dict(geo, precision=self.precision)        # the precision that runs
         if self.trainable:
             pwg_train_geometry(geo)
         if state_dict is None and self.trainable:
@@ -459,8 +507,10 @@ class ParallelWaveGAN:
                 raise ValueError("Vocoder.Checkpoint_Path is not set: the neural vocoder needs a Parallel WaveGAN generator checkpoint")
             state_dict = torch.load(path, map_location="cpu")
         w = pwg_load(state_dict, geo)
-        if not _lib.lib().glowtts_pwg_supported(geo["R"], geo["G"], geo["S"], geo["A"], max(geo["dilations"])):
+        supported = _lib.lib().glowtts_pwg_supported_bf16 if self.precision == "bf16" else _lib.lib().glowtts_pwg_supported
+        if not supported(geo["R"], geo["G"], geo["S"], geo["A"], max(geo["dilations"])):
             raise ValueError(f"the Vocoder block's sizes {geo} are not supported by the kernels")
+        self._layer_op = ops.pwg_layer_bf16 if self.precision == "bf16" else ops.pwg_layer
         self.device = torch.device(device)
         self.sample_rate, self.n_mel, self.hop = int(hp.Sound.Sample_Rate), geo["A"], geo["hop"]
         self.scales = (ctypes.c_int * len(geo["scales"]))(*geo["scales"])
@@ -473,8 +523,9 @@ class ParallelWaveGAN:
     def _build_images(self, w):
         """The weight images in the kernels' layouts (K-major: the MFMA B operand reads 16 consecutive output channels of one input row) from the tensors `w`
         (host or device): built once for a frozen generator; a trainable one rebuilds them on the device at every `generate`, with the transposed images of
-        the backward."""
+        the backward.  precision 'bf16': the layers' two matrices are the packed bf16 images of `pwg_pack_bf16` instead (biases stay float32)."""
         geo = self.geo
+        image = pwg_pack_bf16 if self.precision == "bf16" else lambda t: t
         dev = lambda t: t.contiguous().to(self.device)
         self.w_in = dev(w["upsample_net.conv_in.weight"].permute(2, 1, 0).reshape(-1, geo["A"]))
         self.firs = dev(torch.cat([w[f"upsample_net.upsample.up_layers.{2 * i + 1}.weight"].reshape(-1) for i in range(len(geo["scales"]))]))
@@ -485,7 +536,7 @@ class ParallelWaveGAN:
             w1 = torch.cat([w[q + "conv.weight"].permute(2, 1, 0).reshape(3 * geo["R"], geo["G"]), w[q + "conv1x1_aux.weight"][:, :, 0].t()], dim=0)
             w2 = torch.cat([w[q + "conv1x1_out.weight"][:, :, 0].t(), w[q + "conv1x1_skip.weight"][:, :, 0].t()], dim=1)
             b2 = torch.cat([w[q + "conv1x1_out.bias"], w[q + "conv1x1_skip.bias"]])
-            self.layer_weights.append((dev(w1), dev(w[q + "conv.bias"]), dev(w2), dev(b2)))
+            self.layer_weights.append((dev(image(w1)), dev(w[q + "conv.bias"]), dev(image(w2)), dev(b2)))
         self.head = (dev(w["last_conv_layers.1.weight"][:, :, 0].t()), dev(w["last_conv_layers.1.bias"]), dev(w["last_conv_layers.3.weight"].reshape(-1)),
                      dev(w["last_conv_layers.3.bias"]))
         if self.trainable:
@@ -539,7 +590,7 @@ class ParallelWaveGAN:
         self._refresh()
         B, T, _ = x.shape
         L = T // self.geo["hop"]
-        ops.pwg_layer(x, c, *self.layer_weights[i], x_out, skips, self._lengths(frame_lengths, B, L), L, self.geo["hop"], self.geo["dilations"][i], accumulate)
+        self._layer_op(x, c, *self.layer_weights[i], x_out, skips, self._lengths(frame_lengths, B, L), L, self.geo["hop"], self.geo["dilations"][i], accumulate)
 
     @torch.no_grad()
     def __call__(self, mels, mel_lengths, seeds=None, noises=None):
@@ -563,7 +614,7 @@ class ParallelWaveGAN:
         x, xn = wk["x"]
         ops.pwg_first(noises, seeds, lengths, *self.first, x, L, g["hop"])
         for i, (lw, d) in enumerate(zip(self.layer_weights, g["dilations"])):
-            ops.pwg_layer(x, c, *lw, xn, wk["skips"], lengths, L, g["hop"], d, i > 0)
+            self._layer_op(x, c, *lw, xn, wk["skips"], lengths, L, g["hop"], d, i > 0)
             x, xn = xn, x
         wav = torch.empty(B, T, dtype=torch.float32, device=self.device)
         ops.pwg_head(wk["skips"], lengths, *self.head, wav, L, g["hop"], math.sqrt(1.0 / g["layers"]))

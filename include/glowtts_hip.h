@@ -900,6 +900,18 @@ int glowtts_pwg_layer(const float *x, const float *c, const float *w1, const flo
 int glowtts_pwg_head(const float *skips, const int32_t *frame_lengths, const float *w1, const float *b1, const float *w2, const float *b2, float *wav,
                      int B, int Lmax, int hop, int S, float scale, void *stream);
 
+/* ---- neural vocoder, bf16 inference mode (csrc/pwg_bf16_ops.hip; additions, the ABI version stays) ----
+ * glowtts_pwg_layer_bf16 is glowtts_pwg_layer with bf16 operands on v_mfma_f32_16x16x32_bf16, logged as `pwg_layer_bf16`: the gathered rows
+ * x(t - d) | x(t) | x(t + d) | c(t), the weights and the gate tanh * sigmoid are rounded to bf16 (nearest even); the accumulators, the biases, tanh / sigmoid,
+ * the residual (which adds the unrounded x), the skip sum and x, x_out, skips in memory stay f32.  Rows, lengths, ownership and bit-identity as for
+ * glowtts_pwg_layer.  The weights come as packed bf16 images [Kp / 8][N][8] - element (k, n) at ((k / 8) N + n) 8 + k % 8, Kp = K rounded up to a multiple of
+ * 32, zero rows beyond K:  w1p packs w1 (K = 3 R + A, N = 2 R), w2p packs w2 (K = R, N = R + S); b1, b2 as for glowtts_pwg_layer.
+ * Supported (glowtts_pwg_supported_bf16, else GLOWTTS_E_ARG): glowtts_pwg_supported, and the bf16 LDS tile 128 (Kp(3 R + A) + Kp(R) + 16) bytes within 160 KB. */
+int glowtts_pwg_supported_bf16(int R, int G, int S, int A, int max_dilation);
+int glowtts_pwg_layer_bf16(const float *x, const float *c, const uint16_t *w1p, const float *b1, const uint16_t *w2p, const float *b2, float *x_out,
+                           float *skips, const int32_t *frame_lengths, int B, int Lmax, int hop, int R, int S, int A, int dilation, int accumulate,
+                           void *stream);
+
 /* ---- GE2E speaker encoder: stacked LSTM -> linear -> d-vector (csrc/ge2e_ops.hip; inference, f32; additions, the ABI version stays) ----
  * torch.nn.LSTM's definition (gates i, f, g, o; bias b_ih + b_hh; h0 = c0 = 0), then e = W h_{T-1}^{top} + b per slice, w = e / max(|e|, 1e-12),
  * d = normalize(mean over an utterance's Samples consecutive slices of w).  Every product runs on v_mfma_f32_16x16x4_f32; a sequence's values depend on
