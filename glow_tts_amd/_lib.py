@@ -1,9 +1,15 @@
 """ctypes binding of libglowtts_hip.so (C ABI in include/glowtts_hip.h).
 
 The product path has no CPU fallback: if the HIP library is missing or a call fails, this module
-raises.  PyTorch is used only for device memory and streams (tensor.data_ptr(), current stream)."""
+raises.  PyTorch is used only for device memory and streams (tensor.data_ptr(), current stream).
+
+Two handles onto the same symbols, both bound from abi.SIGNATURES in one pass:
+  api()  what the package and the tools call: an entry point that returns a status raises GlowTTSHipError, naming the symbol, when that status is
+         not GLOWTTS_OK (ctypes' `errcheck`) - a call site is the call and nothing else: `_lib.api().glowtts_expand_fwd(..., _lib.stream())`;
+  lib()  the raw CDLL, whose functions return the status: for bench.py and for the tests that assert one (`== abi.E_ARG`)."""
 import ctypes
 import os
+import types
 
 import torch
 
@@ -15,7 +21,7 @@ LIB_PATH = os.path.join(_HERE, "libglowtts_hip.so")
 # GLOWTTS_* switches are live; the product library above has them compiled to their defaults and reads no environment variable.
 if os.environ.get("GLOWTTS_LIB_PATH"):
     LIB_PATH = os.environ["GLOWTTS_LIB_PATH"]
-_lib = None
+_lib = _api = None
 ABI_VERSION = abi.ABI_VERSION
 
 c_int, c_float, c_void_p = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
@@ -32,10 +38,18 @@ def _symbol(L, name):
         raise GlowTTSHipError(f"{LIB_PATH} does not export {name}, which include/glowtts_hip.h of ABI version {ABI_VERSION} declares: rebuild it") from None
 
 
+def _raise_on_status(rc, fn, args):
+    """`errcheck` of the checked handle's status-returning entry points (the status is passed on, so a check() around such a call is harmless)."""
+    if rc != 0:
+        raise GlowTTSHipError(f"{fn.__name__} failed with code {rc}")
+    return rc
+
+
 def lib():
     """Loads the shared library (once) and binds every entry point of the C ABI as abi.SIGNATURES states it - callers never declare a signature.
-    Raises if the library has not been built (python __graft_entry__.py), is of another ABI version or lacks an entry point."""
-    global _lib
+    Raises if the library has not been built (python __graft_entry__.py), is of another ABI version or lacks an entry point.
+    The functions of this handle return the C status unchecked; api() is the handle whose functions raise on a failing one."""
+    global _lib, _api
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise GlowTTSHipError(
@@ -45,11 +59,24 @@ def lib():
         version = _symbol(L, "glowtts_abi_version")()    # (int (void): ctypes' defaults) - the struct mirrors of abi.py are the layouts of exactly this version
         if version != ABI_VERSION:
             raise GlowTTSHipError(f"{LIB_PATH} has ABI version {version}, this package binds version {ABI_VERSION}: rebuild it")
+        A = types.SimpleNamespace()
         for name, (restype, argtypes) in abi.SIGNATURES.items():
             fn = _symbol(L, name)
             fn.restype, fn.argtypes = restype, argtypes
-        _lib = L
+            checked = L[name]                             # (L[name] makes a second function object for the symbol; L.name is the cached one just bound)
+            checked.restype, checked.argtypes = restype, argtypes
+            if restype is c_int and name not in abi.VALUE_RETURNING:
+                checked.errcheck = _raise_on_status
+            setattr(A, name, checked)
+        _lib, _api = L, A
     return _lib
+
+
+def api():
+    """The checked handle (see the module's docstring): one attribute per name of abi.SIGNATURES, loaded in the same pass as lib()."""
+    if _api is None:
+        lib()
+    return _api
 
 
 def check(rc, what):

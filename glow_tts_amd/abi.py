@@ -308,3 +308,12 @@ SIGNATURES = {
     "glowtts_pwg_disc_first_bwd": (I, [P] * 5 + [I] * 3 + [F, P]),
     "glowtts_pwg_disc_wgrad": (I, [P] * 6 + [I] * 5 + [P]),
 }
+
+# ---- the entry points above whose `int` result is a VALUE (a version, a chunk size, a yes / no), not a GLOWTTS_OK / _E_ARG / _E_LAUNCH status: `_lib.api()`
+# raises on a non-zero result of every other `int` entry point (int64_t results - *_floats, *_blocks, *_rows, glowtts_launch_count - are never statuses) ----
+VALUE_RETURNING = frozenset({
+    "glowtts_abi_version", "glowtts_opt_chunk",
+    "glowtts_cond_linear_supported", "glowtts_gst_supported", "glowtts_conv3x3s2_supported", "glowtts_dur_proj_supported", "glowtts_vocoder_supported",
+    "glowtts_pwg_supported", "glowtts_pwg_supported_bf16", "glowtts_ge2e_supported", "glowtts_pwg_train_supported", "glowtts_stft_loss_supported",
+    "glowtts_pwg_disc_supported",
+})

@@ -19,19 +19,17 @@ def log_prior_prepare(mean, log_std, token_lengths, mel_lengths, Ty, mel_multipl
     (sigma^-2 | mu sigma^-2) weight image, the per-token constant, the frame mask and the int32 lengths.  `GlowTTS.forward` calls it on the encoder's stream, right
     behind the projection - off the chain between the flow decoder's last launch and its backward - and hands the result to `log_prior_t`."""
     B, Cm, Tx = mean.shape
-    L = _lib.lib()
+    L = _lib.api()
     dev = mean.device
     mean, log_std = mean.contiguous(), log_std.contiguous()
     npad, kch = ctypes.c_int(0), ctypes.c_int(0)
-    _lib.check(L.glowtts_logprior_prep(None, None, None, None, None, None, None, None, None, B, Cm, Tx, Ty, int(mel_multiple), ctypes.byref(npad), ctypes.byref(kch), None),
-               "glowtts_logprior_prep(size)")
+    L.glowtts_logprior_prep(None, None, None, None, None, None, None, None, None, B, Cm, Tx, Ty, int(mel_multiple), ctypes.byref(npad), ctypes.byref(kch), None)
     stride = kch.value * npad.value * 64                                     # bytes per utterance of the packed (sigma^-2 | mu sigma^-2) image
     packed = torch.empty(B * stride, dtype=torch.uint8, device=dev)
     cb, fmask = torch.empty(B, Tx, device=dev), torch.empty(B, Ty, device=dev)
     tx, ty = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
-    _lib.check(L.glowtts_logprior_prep(_lib.ptr(mean), _lib.ptr(log_std), _lib.ptr(token_lengths.contiguous()), _lib.ptr(mel_lengths.contiguous()),
-                                       _lib.ptr(packed), _lib.ptr(cb), _lib.ptr(fmask), _lib.ptr(tx), _lib.ptr(ty), B, Cm, Tx, Ty, int(mel_multiple), None, None,
-                                       _lib.stream()), "glowtts_logprior_prep")
+    L.glowtts_logprior_prep(_lib.ptr(mean), _lib.ptr(log_std), _lib.ptr(token_lengths.contiguous()), _lib.ptr(mel_lengths.contiguous()),
+                            _lib.ptr(packed), _lib.ptr(cb), _lib.ptr(fmask), _lib.ptr(tx), _lib.ptr(ty), B, Cm, Tx, Ty, int(mel_multiple), None, None, _lib.stream())
     return {"packed": packed, "cb": cb, "fmask": fmask, "tx": tx, "ty": ty, "npad": npad.value, "kch": kch.value, "stride": stride, "dims": (B, Cm, Tx, Ty)}
 
 
@@ -71,7 +69,7 @@ def log_prior_t(mean, log_std, z, token_lengths, mel_lengths, mel_multiple=1, re
     a.batch, a.a_bstride, a.w_bstride, a.bias_bstride, a.out_bstride, a.mask_bstride = B, zt_bstride, stride, Tx, Ty * Tx, Ty
     a.ncols_valid = tx.data_ptr()
     a.rows_per_utt = Ty
-    _lib.check(_lib.lib().glowtts_conv_cl(ctypes.byref(a), _lib.stream()), "glowtts_conv_cl(log_prior)")
+    _lib.api().glowtts_conv_cl(ctypes.byref(a), _lib.stream())
     return (out, tx, ty) if return_lengths else out
 
 
@@ -82,8 +80,7 @@ def maximum_path_t(value_t, token_lengths, mel_lengths, max_neg_val=-1e9):
     idx = torch.empty(B, Ty, dtype=torch.int32, device=value_t.device)
     tx = token_lengths if token_lengths.dtype == torch.int32 else token_lengths.to(torch.int32).contiguous()
     ty = mel_lengths if mel_lengths.dtype == torch.int32 else mel_lengths.to(torch.int32).contiguous()
-    _lib.check(_lib.lib().glowtts_mas_dp_f32_t(_lib.ptr(value_t), _lib.ptr(tx), _lib.ptr(ty), _lib.ptr(idx), None, B, Tx, Ty,
-                                            max_neg_val, _lib.stream()), "glowtts_mas_dp_f32_t")
+    _lib.api().glowtts_mas_dp_f32_t(_lib.ptr(value_t), _lib.ptr(tx), _lib.ptr(ty), _lib.ptr(idx), None, B, Tx, Ty, max_neg_val, _lib.stream())
     return idx
 
 
@@ -101,7 +98,7 @@ class ExpandPrior(torch.autograd.Function):
         B, C, Tx = src.shape
         Ty = idx.shape[1]
         out = torch.empty(B, C, Ty, device=src.device)
-        _lib.check(_lib.lib().glowtts_expand_fwd(_lib.ptr(src), _lib.ptr(idx), _lib.ptr(out), B, C, Tx, Ty, _lib.stream()), "glowtts_expand_fwd")
+        _lib.api().glowtts_expand_fwd(_lib.ptr(src), _lib.ptr(idx), _lib.ptr(out), B, C, Tx, Ty, _lib.stream())
         ctx.save_for_backward(idx)
         ctx.Tx, ctx.bwd_stream = Tx, bwd_stream
         return out
@@ -115,7 +112,7 @@ class ExpandPrior(torch.autograd.Function):
 
         def run():
             dsrc = torch.empty(B, C, ctx.Tx, device=dout.device)
-            _lib.check(_lib.lib().glowtts_expand_bwd(_lib.ptr(dout), _lib.ptr(idx), _lib.ptr(dsrc), B, C, ctx.Tx, Ty, _lib.stream()), "glowtts_expand_bwd")
+            _lib.api().glowtts_expand_bwd(_lib.ptr(dout), _lib.ptr(idx), _lib.ptr(dsrc), B, C, ctx.Tx, Ty, _lib.stream())
             return dsrc
         if s is None or s == cur:
             return run(), None, None
@@ -160,9 +157,8 @@ def prior_sample(mean, log_std, dur, mel_lengths, seeds, noise_scales, Tmax, wan
         raise ValueError("prior_sample: mean / log_std [B, C, Tx] f32, dur [B, Tx] f32, mel_lengths [B] i64, noise_scales [B] f32")
     z, idx = torch.empty(B, C, Tmax, device=dev), torch.empty(B, Tmax, dtype=torch.int32, device=dev)
     attn = torch.empty(B, Tx, Tmax, device=dev) if want_attn else None
-    _lib.check(_lib.lib().glowtts_prior_sample(_lib.ptr(mean), _lib.ptr(log_std), _lib.ptr(dur), _lib.ptr(mel_lengths.contiguous()), _lib.ptr(seeds.contiguous()),
-                                               _lib.ptr(noise_scales.contiguous()), _lib.ptr(z), _lib.ptr(idx), _lib.ptr(attn), B, C, Tx, Tmax, _lib.stream()),
-               "glowtts_prior_sample")
+    _lib.api().glowtts_prior_sample(_lib.ptr(mean), _lib.ptr(log_std), _lib.ptr(dur), _lib.ptr(mel_lengths.contiguous()), _lib.ptr(seeds.contiguous()),
+                                    _lib.ptr(noise_scales.contiguous()), _lib.ptr(z), _lib.ptr(idx), _lib.ptr(attn), B, C, Tx, Tmax, _lib.stream())
     return z, idx, attn
 
 
@@ -171,8 +167,7 @@ def duration_targets(idx, token_lengths, Tx):
     """log(sum_t attentions + 1e-7) * token_mask (Modules.py:122) -> [B,1,Tx]."""
     B, Ty = idx.shape
     out = torch.empty(B, Tx, device=idx.device)
-    _lib.check(_lib.lib().glowtts_duration_targets(_lib.ptr(idx), _lib.ptr(token_lengths.contiguous()), _lib.ptr(out), B, Tx, Ty, _lib.stream()),
-               "glowtts_duration_targets")
+    _lib.api().glowtts_duration_targets(_lib.ptr(idx), _lib.ptr(token_lengths.contiguous()), _lib.ptr(out), B, Tx, Ty, _lib.stream())
     return out.unsqueeze(1)
 
 
@@ -184,7 +179,7 @@ def _segment_sums(dout, idx, Tx, stream):
 
     def run():
         dsrc = torch.empty(B, C, Tx, device=dout.device)
-        _lib.check(_lib.lib().glowtts_expand_bwd(_lib.ptr(dout), _lib.ptr(idx), _lib.ptr(dsrc), B, C, Tx, Ty, _lib.stream()), "glowtts_expand_bwd")
+        _lib.api().glowtts_expand_bwd(_lib.ptr(dout), _lib.ptr(idx), _lib.ptr(dsrc), B, C, Tx, Ty, _lib.stream())
         return dsrc
     if stream is None or stream == cur:
         return run()
@@ -211,17 +206,16 @@ class ExpandPair(torch.autograd.Function):
         dev = mean.device
         om, ol, tg = torch.empty(B, C, Ty, device=dev), torch.empty(B, C, Ty, device=dev), torch.empty(B, Tx, device=dev)
         path = None
-        L = _lib.lib()
+        L = _lib.api()
         if Ty % 4 == 0:
             if want_path:
                 path = torch.empty(B, Tx, Ty, device=dev)
-            _lib.check(L.glowtts_expand_pair_targets(_lib.ptr(mean), _lib.ptr(log_std), _lib.ptr(idx), _lib.ptr(token_lengths.contiguous()), _lib.ptr(om),
-                                                     _lib.ptr(ol), _lib.ptr(tg), _lib.ptr(path), B, C, Tx, Ty, _lib.stream()), "glowtts_expand_pair_targets")
+            L.glowtts_expand_pair_targets(_lib.ptr(mean), _lib.ptr(log_std), _lib.ptr(idx), _lib.ptr(token_lengths.contiguous()), _lib.ptr(om),
+                                          _lib.ptr(ol), _lib.ptr(tg), _lib.ptr(path), B, C, Tx, Ty, _lib.stream())
         else:
-            _lib.check(L.glowtts_expand_fwd(_lib.ptr(mean), _lib.ptr(idx), _lib.ptr(om), B, C, Tx, Ty, _lib.stream()), "glowtts_expand_fwd")
-            _lib.check(L.glowtts_expand_fwd(_lib.ptr(log_std), _lib.ptr(idx), _lib.ptr(ol), B, C, Tx, Ty, _lib.stream()), "glowtts_expand_fwd")
-            _lib.check(L.glowtts_duration_targets(_lib.ptr(idx), _lib.ptr(token_lengths.contiguous()), _lib.ptr(tg), B, Tx, Ty, _lib.stream()),
-                       "glowtts_duration_targets")
+            L.glowtts_expand_fwd(_lib.ptr(mean), _lib.ptr(idx), _lib.ptr(om), B, C, Tx, Ty, _lib.stream())
+            L.glowtts_expand_fwd(_lib.ptr(log_std), _lib.ptr(idx), _lib.ptr(ol), B, C, Tx, Ty, _lib.stream())
+            L.glowtts_duration_targets(_lib.ptr(idx), _lib.ptr(token_lengths.contiguous()), _lib.ptr(tg), B, Tx, Ty, _lib.stream())
             if want_path:
                 from .monotonic_align import path_from_idx
                 path = path_from_idx(idx, Tx, torch.float32)
@@ -272,9 +266,8 @@ class MLELoss(torch.autograd.Function):
         dev = z.device
         loss, inv = torch.empty((), device=dev), torch.empty(1, device=dev)
         scratch = torch.empty(1024, device=dev)
-        _lib.check(_lib.lib().glowtts_mle_loss_fwd(_lib.ptr(z), _lib.ptr(mean), _lib.ptr(log_std), _lib.ptr(log_dets), _lib.ptr(lengths.contiguous()),
-                                                loss.data_ptr(), inv.data_ptr(), _lib.ptr(scratch), z.numel(), z.shape[0], n_squeeze, mel_dim,
-                                                _lib.stream()), "glowtts_mle_loss_fwd")
+        _lib.api().glowtts_mle_loss_fwd(_lib.ptr(z), _lib.ptr(mean), _lib.ptr(log_std), _lib.ptr(log_dets), _lib.ptr(lengths.contiguous()),
+                                     loss.data_ptr(), inv.data_ptr(), _lib.ptr(scratch), z.numel(), z.shape[0], n_squeeze, mel_dim, _lib.stream())
         ctx.save_for_backward(z, mean, log_std, inv)
         ctx.B = z.shape[0]
         return loss
@@ -285,8 +278,8 @@ class MLELoss(torch.autograd.Function):
         dz, dm, dl = torch.empty_like(z), torch.empty_like(z), torch.empty_like(z)
         dl_ = dloss.contiguous().reshape(1)
         dlogdet = torch.empty(ctx.B, device=z.device)
-        _lib.check(_lib.lib().glowtts_mle_loss_bwd(_lib.ptr(z), _lib.ptr(mean), _lib.ptr(log_std), _lib.ptr(dl_), _lib.ptr(inv), _lib.ptr(dz),
-                                                _lib.ptr(dm), _lib.ptr(dl), z.numel(), _lib.ptr(dlogdet), ctx.B, _lib.stream()), "glowtts_mle_loss_bwd")
+        _lib.api().glowtts_mle_loss_bwd(_lib.ptr(z), _lib.ptr(mean), _lib.ptr(log_std), _lib.ptr(dl_), _lib.ptr(inv), _lib.ptr(dz),
+                                     _lib.ptr(dm), _lib.ptr(dl), z.numel(), _lib.ptr(dlogdet), ctx.B, _lib.stream())
         return dz, dm, dl, dlogdet, None, None, None
 
 
@@ -309,21 +302,20 @@ class PriorLoss(torch.autograd.Function):
         Tx = mean_tok.shape[2]
         loss, inv = torch.empty((), device=dev), torch.empty(1, device=dev)
         scratch = torch.empty(1024, device=dev)
-        L = _lib.lib()
+        L = _lib.api()
         counter = _lib.counter(dev, "prior_loss", owner) if seed is not None else None
         ctx.seed, ctx.stash = None, None
         if counter is not None:
             dz, dm, dl = torch.empty_like(z), torch.empty_like(mean_tok), torch.empty_like(ls_tok)
             dlogdet = torch.empty(B, device=dev)
-            _lib.check(L.glowtts_prior_loss(_lib.ptr(z), _lib.ptr(mel_mean.contiguous()), _lib.ptr(mel_ls.contiguous()), _lib.ptr(mean_tok), _lib.ptr(ls_tok),
-                                            _lib.ptr(idx), _lib.ptr(log_dets), _lib.ptr(lengths.contiguous()), _lib.ptr(seed), _lib.ptr(scratch), _lib.ptr(counter),
-                                            loss.data_ptr(), inv.data_ptr(), _lib.ptr(dz), _lib.ptr(dm), _lib.ptr(dl), _lib.ptr(dlogdet), B, C, Tx, Ty,
-                                            int(n_squeeze), int(mel_dim), _lib.stream()), "glowtts_prior_loss")
+            L.glowtts_prior_loss(_lib.ptr(z), _lib.ptr(mel_mean.contiguous()), _lib.ptr(mel_ls.contiguous()), _lib.ptr(mean_tok), _lib.ptr(ls_tok),
+                                 _lib.ptr(idx), _lib.ptr(log_dets), _lib.ptr(lengths.contiguous()), _lib.ptr(seed), _lib.ptr(scratch), _lib.ptr(counter),
+                                 loss.data_ptr(), inv.data_ptr(), _lib.ptr(dz), _lib.ptr(dm), _lib.ptr(dl), _lib.ptr(dlogdet), B, C, Tx, Ty,
+                                 int(n_squeeze), int(mel_dim), _lib.stream())
             ctx.seed, ctx.stash = seed, (dz, dm, dl, dlogdet)
         else:
-            _lib.check(L.glowtts_mle_loss_fwd(_lib.ptr(z), _lib.ptr(mel_mean.contiguous()), _lib.ptr(mel_ls.contiguous()), _lib.ptr(log_dets),
-                                              _lib.ptr(lengths.contiguous()), loss.data_ptr(), inv.data_ptr(), _lib.ptr(scratch), z.numel(), B, n_squeeze,
-                                              mel_dim, _lib.stream()), "glowtts_mle_loss_fwd")
+            L.glowtts_mle_loss_fwd(_lib.ptr(z), _lib.ptr(mel_mean.contiguous()), _lib.ptr(mel_ls.contiguous()), _lib.ptr(log_dets),
+                                   _lib.ptr(lengths.contiguous()), loss.data_ptr(), inv.data_ptr(), _lib.ptr(scratch), z.numel(), B, n_squeeze, mel_dim, _lib.stream())
         ctx.save_for_backward(z, mean_tok, ls_tok, idx, inv)
         return loss
 
@@ -339,8 +331,8 @@ class PriorLoss(torch.autograd.Function):
         Tx = mean_tok.shape[2]
         dz, dm, dl = torch.empty_like(z), torch.empty_like(mean_tok), torch.empty_like(ls_tok)
         dlogdet = torch.empty(B, device=z.device)
-        _lib.check(_lib.lib().glowtts_prior_loss_bwd(_lib.ptr(z), _lib.ptr(mean_tok), _lib.ptr(ls_tok), _lib.ptr(idx), _lib.ptr(dloss.contiguous().reshape(1)), _lib.ptr(inv),
-                                                  _lib.ptr(dz), _lib.ptr(dm), _lib.ptr(dl), _lib.ptr(dlogdet), B, C, Tx, Ty, _lib.stream()), "glowtts_prior_loss_bwd")
+        _lib.api().glowtts_prior_loss_bwd(_lib.ptr(z), _lib.ptr(mean_tok), _lib.ptr(ls_tok), _lib.ptr(idx), _lib.ptr(dloss.contiguous().reshape(1)), _lib.ptr(inv),
+                                       _lib.ptr(dz), _lib.ptr(dm), _lib.ptr(dl), _lib.ptr(dlogdet), B, C, Tx, Ty, _lib.stream())
         return (dz, dm, dl, dlogdet) + none
 
 
@@ -420,8 +412,8 @@ class DurationMSE(torch.autograd.Function):
         one = _lib.one(a.device) if seed is not None else None
         unit = seed is not None and one is not None and seed.data_ptr() == one.data_ptr()        # (the forward writes the gradient for the seed 1 only)
         da = torch.empty_like(a) if unit else None
-        _lib.check(_lib.lib().glowtts_mse_loss_fwd(_lib.ptr(a), _lib.ptr(target), loss.data_ptr(), a.numel(), 1.0 / a.numel(), _lib.ptr(tl), B, _lib.ptr(ext),
-                                                _lib.ptr(da), _lib.stream()), "glowtts_mse_loss_fwd")
+        _lib.api().glowtts_mse_loss_fwd(_lib.ptr(a), _lib.ptr(target), loss.data_ptr(), a.numel(), 1.0 / a.numel(), _lib.ptr(tl), B, _lib.ptr(ext),
+                                     _lib.ptr(da), _lib.stream())
         ctx.save_for_backward(a, target, tl, ext)
         ctx.seed, ctx.stash = (seed if unit else None), da
         return loss
@@ -433,8 +425,8 @@ class DurationMSE(torch.autograd.Function):
         if ctx.seed is not None and dloss.data_ptr() == ctx.seed.data_ptr() and dloss.numel() == 1:
             return stash, None, None, None, None
         da = torch.empty_like(a)
-        _lib.check(_lib.lib().glowtts_mse_loss_bwd(_lib.ptr(a), _lib.ptr(target), _lib.ptr(dloss.contiguous().reshape(1)), _lib.ptr(da), a.numel(), 1.0 / a.numel(),
-                                                _lib.ptr(tl), int(a.shape[0]), _lib.ptr(ext), _lib.stream()), "glowtts_mse_loss_bwd")
+        _lib.api().glowtts_mse_loss_bwd(_lib.ptr(a), _lib.ptr(target), _lib.ptr(dloss.contiguous().reshape(1)), _lib.ptr(da), a.numel(), 1.0 / a.numel(),
+                                     _lib.ptr(tl), int(a.shape[0]), _lib.ptr(ext), _lib.stream())
         return da, None, None, None, None
 
 

@@ -13,7 +13,8 @@ import torch
 from . import _lib, ops
 from .abi import WgradArgs  # noqa: F401
 
-_L = _lib.lib                            # the bound library (tools and tests call CF._L())
+_L = _lib.lib                            # the bound library, raw statuses (tests call CF._L())
+_A = _lib.api                            # the same entry points, a failing status raises (this module and tools call CF._A())
 
 
 def wgrad(dy, x, O, ca, taps, precision, want_bias=True, splits=0, xpro=0, io_flags=0):
@@ -28,7 +29,7 @@ def wgrad(dy, x, O, ca, taps, precision, want_bias=True, splits=0, xpro=0, io_fl
     a.precision, a.splits, a.accumulate = precision, splits, 1
     a.xpro, a.io_flags = xpro, io_flags
     a.dw, a.dbias = dw.data_ptr(), (db.data_ptr() if db is not None else None)
-    _lib.check(_L().glowtts_wgrad_cl(ctypes.byref(a), _lib.stream()), "glowtts_wgrad_cl")
+    _A().glowtts_wgrad_cl(ctypes.byref(a), _lib.stream())
     return dw, db
 
 
@@ -70,7 +71,7 @@ class WgradTape:
         """-> (scratch [nfloats], gb [2C]) of the next LayerNorm backward: slices of two buffers that `flush` reduces with one
         glowtts_colsum_batched (every LayerNorm registered through `ln_count` in the forward has the same shape)."""
         if self.ln is None:
-            nf = _L().glowtts_layernorm_scratch_floats(R, C)
+            nf = _A().glowtts_layernorm_scratch_floats(R, C)
             self.ln = {"scratch": torch.empty(self.ln_count, nf, device=device), "gb": torch.empty(self.ln_count, 2 * C, device=device),
                        "used": 0, "nblk": nf // (2 * C), "C": C, "R": R}
         st = self.ln
@@ -82,7 +83,7 @@ class WgradTape:
     def att_slot(self, B, Tp, H, D, win, device):
         """-> (scratch, drel [2][2 win + 1][D]) of the next attention backward: the kernel leaves its per-workgroup partial sums of (d relK | d relV) in
         `scratch`, `flush` reduces every layer's with one launch - the reduction is not on the chain to the next layer's gradient."""
-        L = _L()
+        L = _A()
         if self.att is None:
             nf = L.glowtts_rpr_attention_scratch_floats(B, Tp, H, D, win)
             cols = 2 * (2 * win + 1) * D
@@ -128,20 +129,20 @@ class WgradTape:
         for g in groups.values():
             g.launch_segment(0)
         if part is not None:                                   # gradients = sum of the splits' partial images (one launch, fixed order)
-            _lib.check(_L().glowtts_sum_slices(part.data_ptr(), self.arena.data_ptr(), S, self.used, _lib.stream()), "glowtts_sum_slices")
+            _A().glowtts_sum_slices(part.data_ptr(), self.arena.data_ptr(), S, self.used, _lib.stream())
         self.jobs = []        # (dz / x stay referenced by the launched work's stream ordering: same stream, freed after)
         self.arena, self.used = None, 0
         if self.ln is not None:
             st = self.ln
             assert st["used"] == self.ln_count, "a LayerNorm of the block functions did not run its backward"
-            _lib.check(_L().glowtts_colsum_batched(st["scratch"].data_ptr(), st["gb"].data_ptr(), st["nblk"], 2 * st["C"], st["used"],
-                                                   st["scratch"].shape[1], 2 * st["C"], _lib.stream()), "glowtts_colsum_batched")
+            _A().glowtts_colsum_batched(st["scratch"].data_ptr(), st["gb"].data_ptr(), st["nblk"], 2 * st["C"], st["used"],
+                                        st["scratch"].shape[1], 2 * st["C"], _lib.stream())
             self.ln = None
         if self.att is not None:
             st = self.att
             assert st["used"] == self.att_count, "an attention core of the block functions did not run its backward"
-            _lib.check(_L().glowtts_colsum_batched(st["scratch"].data_ptr(), st["out"].data_ptr(), st["rows"], st["cols"], st["used"],
-                                                   st["scratch"].shape[1], st["cols"], _lib.stream()), "glowtts_colsum_batched")
+            _A().glowtts_colsum_batched(st["scratch"].data_ptr(), st["out"].data_ptr(), st["rows"], st["cols"], st["used"],
+                                        st["scratch"].shape[1], st["cols"], _lib.stream())
             self.att = None
 
 
@@ -223,13 +224,12 @@ class ConvRows(torch.autograd.Function):
         if gated:                                              # d(pre-activation): relu / dropout cut exactly where out == 0
             dz = torch.empty(R, O, device=dy.device, dtype=bf if bfpath else torch.float32)
             io = (1 if dy.dtype == bf else 0) | (2 if out.dtype == bf else 0) | (4 if bfpath else 0)
-            _lib.check(_L().glowtts_gate_bwd_io(dy.data_ptr(), out.data_ptr(), _sp(rowmask) if mask_out else None, dz.data_ptr(), R, O,
-                                                1.0 / (1.0 - drop_p) if drop_p > 0 else 1.0, io, _lib.stream()), "glowtts_gate_bwd_io")
+            _A().glowtts_gate_bwd_io(dy.data_ptr(), out.data_ptr(), _sp(rowmask) if mask_out else None, dz.data_ptr(), R, O,
+                                     1.0 / (1.0 - drop_p) if drop_p > 0 else 1.0, io, _lib.stream())
         elif mask_out:
             if dy.dtype == torch.float32 and O % 4 == 0:           # the row mask alone (glowtts_gate_bwd_io without a gate tensor): one vectorised launch
                 dz = torch.empty(R, O, device=dy.device, dtype=bf if bfpath else torch.float32)
-                _lib.check(_L().glowtts_gate_bwd_io(dy.data_ptr(), None, _sp(rowmask), dz.data_ptr(), R, O, 1.0, 4 if bfpath else 0, _lib.stream()),
-                           "glowtts_gate_bwd_io")
+                _A().glowtts_gate_bwd_io(dy.data_ptr(), None, _sp(rowmask), dz.data_ptr(), R, O, 1.0, 4 if bfpath else 0, _lib.stream())
             else:
                 dz = dy * rowmask.unsqueeze(1)
         else:
@@ -272,10 +272,9 @@ class LayerNormRows(torch.autograd.Function):
         y = torch.empty_like(a)
         stats = torch.empty(R, 2, device=a.device)
         s = torch.empty_like(a) if b is not None else a
-        _lib.check(_L().glowtts_layernorm_fwd_io(a.data_ptr(), _sp(b.contiguous() if b is not None else None), s.data_ptr() if b is not None else None,
-                                                 gamma.data_ptr(), beta.data_ptr(), _sp(rowmask), y.data_ptr(), stats.data_ptr(), R, C, 1e-4,
-                                                 int(relu), float(drop_p), int(seed) & 0xFFFFFFFF, _sp(seed_t), _sp(yb), _lib.stream()),
-                   "glowtts_layernorm_fwd_io")
+        _A().glowtts_layernorm_fwd_io(a.data_ptr(), _sp(b.contiguous() if b is not None else None), s.data_ptr() if b is not None else None,
+                                      gamma.data_ptr(), beta.data_ptr(), _sp(rowmask), y.data_ptr(), stats.data_ptr(), R, C, 1e-4,
+                                      int(relu), float(drop_p), int(seed) & 0xFFFFFFFF, _sp(seed_t), _sp(yb), _lib.stream())
         gated = relu or drop_p > 0
         ctx.save_for_backward(s, stats, gamma, rowmask, y if gated else None)
         ctx.cfg = (gated, float(drop_p), b is not None)
@@ -287,12 +286,12 @@ class LayerNormRows(torch.autograd.Function):
         gated, drop_p, has_b = ctx.cfg
         R, C = s.shape
         dy = dy.contiguous()
-        L = _L()
+        L = _A()
         ds = torch.empty_like(s)
         gb = torch.empty(2 * C, device=s.device)
         scratch = torch.empty(L.glowtts_layernorm_scratch_floats(R, C), device=s.device)
-        _lib.check(L.glowtts_layernorm_bwd_io(dy.data_ptr(), _sp(y), s.data_ptr(), stats.data_ptr(), gamma.data_ptr(), _sp(rowmask), ds.data_ptr(),
-                                              gb.data_ptr(), scratch.data_ptr(), R, C, int(gated), drop_p, None, None, 1.0, _lib.stream()), "glowtts_layernorm_bwd_io")
+        L.glowtts_layernorm_bwd_io(dy.data_ptr(), _sp(y), s.data_ptr(), stats.data_ptr(), gamma.data_ptr(), _sp(rowmask), ds.data_ptr(),
+                                   gb.data_ptr(), scratch.data_ptr(), R, C, int(gated), drop_p, None, None, 1.0, _lib.stream())
         return ds, (ds if has_b else None), gb[:C], gb[C:], None, None, None, None, None, None
 
 
@@ -345,13 +344,12 @@ class FFNBlock(torch.autograd.Function):
         qkv = None
         if next_qkv is not None and C == 192 and next_qkv[0].precision == ops.BF16 and next_qkv[0].npad >= 3 * C and R * 3 * C * 4 < 2 ** 31:
             qkv = torch.empty(R, 3 * C, device=dev)
-            _lib.check(_L().glowtts_layernorm_qkv(h1.data_ptr(), x1.data_ptr(), gamma.data_ptr(), beta.data_ptr(), rowmask.data_ptr(), s_.data_ptr(),
-                                                  stats.data_ptr(), y.data_ptr(), yb.data_ptr(), next_qkv[0].data.data_ptr(), next_qkv[0].npad,
-                                                  next_qkv[1].detach().data_ptr(), qkv.data_ptr(), R, C, 1e-4, _lib.stream()), "glowtts_layernorm_qkv")
+            _A().glowtts_layernorm_qkv(h1.data_ptr(), x1.data_ptr(), gamma.data_ptr(), beta.data_ptr(), rowmask.data_ptr(), s_.data_ptr(),
+                                       stats.data_ptr(), y.data_ptr(), yb.data_ptr(), next_qkv[0].data.data_ptr(), next_qkv[0].npad,
+                                       next_qkv[1].detach().data_ptr(), qkv.data_ptr(), R, C, 1e-4, _lib.stream())
         else:
-            _lib.check(_L().glowtts_layernorm_fwd_io(h1.data_ptr(), x1.data_ptr(), s_.data_ptr(), gamma.data_ptr(), beta.data_ptr(), rowmask.data_ptr(),
-                                                     y.data_ptr(), stats.data_ptr(), R, C, 1e-4, 0, 0.0, 0, None, yb.data_ptr(), _lib.stream()),
-                       "glowtts_layernorm_fwd_io")
+            _A().glowtts_layernorm_fwd_io(h1.data_ptr(), x1.data_ptr(), s_.data_ptr(), gamma.data_ptr(), beta.data_ptr(), rowmask.data_ptr(),
+                                          y.data_ptr(), stats.data_ptr(), R, C, 1e-4, 0, 0.0, 0, None, yb.data_ptr(), _lib.stream())
         tape.ln_count += 1
         ctx.save_for_backward(x1b, h0, h1 if drop_p > 0 else None, s_, stats, gamma, rowmask, w0, w1)
         ctx.misc = (tape, packs0[1], packs1[1], float(drop_p))
@@ -374,14 +372,14 @@ class FFNBlock(torch.autograd.Function):
         O0, k = w0.shape[0], w0.shape[2]
         dev = s_.device
         bf = torch.bfloat16
-        L = _L()
+        L = _A()
         scale = 1.0 / (1.0 - drop_p) if drop_p > 0 else 1.0
         dy = dy.contiguous()
         ds, dz1 = torch.empty_like(s_), torch.empty(R, C, device=dev, dtype=bf)
         scratch, gb = tape.ln_slot(R, C, dev)
         # LayerNorm_1 backward; dz1 = d(Conv_1 pre-activation): through the conv's dropout gate when there is one, else ds * mask = ds
-        _lib.check(L.glowtts_layernorm_bwd_io(dy.data_ptr(), None, s_.data_ptr(), stats.data_ptr(), gamma.data_ptr(), rowmask.data_ptr(), ds.data_ptr(),
-                                              None, scratch.data_ptr(), R, C, 0, 0.0, dz1.data_ptr(), _sp(h1), scale, _lib.stream()), "glowtts_layernorm_bwd_io")
+        L.glowtts_layernorm_bwd_io(dy.data_ptr(), None, s_.data_ptr(), stats.data_ptr(), gamma.data_ptr(), rowmask.data_ptr(), ds.data_ptr(),
+                                   None, scratch.data_ptr(), R, C, 0, 0.0, dz1.data_ptr(), _sp(h1), scale, _lib.stream())
         dz0 = torch.empty(R, O0, device=dev, dtype=bf)
         if FUSE["gate_in_dgrad"]:
             # Conv_1 data gradient with the relu / dropout gate of Conv_0's output in its epilogue (h0 == 0 on cut elements and on masked rows)
@@ -389,7 +387,7 @@ class FFNBlock(torch.autograd.Function):
         else:
             dh = torch.empty(R, O0, device=dev, dtype=bf)
             _conv_launch(dz1, pwt1, C, R, k, 0, O0, None, None, dh)                                 # Conv_1 data gradient
-            _lib.check(L.glowtts_gate_bwd_io(dh.data_ptr(), h0.data_ptr(), rowmask.data_ptr(), dz0.data_ptr(), R, O0, scale, 7, _lib.stream()), "glowtts_gate_bwd_io")
+            L.glowtts_gate_bwd_io(dh.data_ptr(), h0.data_ptr(), rowmask.data_ptr(), dz0.data_ptr(), R, O0, scale, 7, _lib.stream())
         dx1 = torch.empty(R, C, device=dev)
         _conv_launch(dz0, pwt0, O0, R, k, 0, C, None, None, dx1, in0=ds)                            # Conv_0 data gradient + the residual branch (ds)
         dw0, db0 = tape.out(w0.shape, dev), tape.out((O0,), dev)
@@ -411,7 +409,7 @@ class AttentionBlock(torch.autograd.Function):
         R, C = x.shape
         dev = x.device
         bf = torch.bfloat16
-        L = _L()
+        L = _A()
         D = C // H
         dflag = ops.F_DROPOUT if drop_p > 0 else 0
         if qkv_pre is not None and qkv_pre.numel():
@@ -422,24 +420,22 @@ class AttentionBlock(torch.autograd.Function):
         att = torch.empty(R, C, device=dev)
         P = torch.empty(B, H, Tp, Tp, device=dev)
         rk, rv = relk.detach().contiguous(), relv.detach().contiguous()
-        _lib.check(L.glowtts_rpr_attention_fwd_prec(qkv.data_ptr(), rk.data_ptr(), rv.data_ptr(), rowmask.data_ptr(), att.data_ptr(), P.data_ptr(),
-                                                    B, Tp, H, D, win, float(drop_p), int(seeds[0]) & 0xFFFFFFFF, _sp(seed_t), ops.BF16, _lib.stream()),
-                   "glowtts_rpr_attention_fwd_prec")
+        L.glowtts_rpr_attention_fwd_prec(qkv.data_ptr(), rk.data_ptr(), rv.data_ptr(), rowmask.data_ptr(), att.data_ptr(), P.data_ptr(),
+                                         B, Tp, H, D, win, float(drop_p), int(seeds[0]) & 0xFFFFFFFF, _sp(seed_t), ops.BF16, _lib.stream())
         y, yb, s_, stats = torch.empty_like(x), torch.empty(R, C, device=dev, dtype=bf), torch.empty_like(x), torch.empty(R, 2, device=dev)
         pw = packs_p[0]
         from .decoder import TUNE
         if FUSE["proj_ln"] and TUNE["enc_proj_ln"] and C == 192 and pw.precision == ops.BF16 and pw.npad >= C and R * C * 4 < 2 ** 31:
             # projection + dropout + residual + LayerNorm as ONE launch (csrc/gemm_cl.hip proj_ln_kernel): one link less in the encoder's forward chain
             proj = torch.empty(R, C, device=dev) if drop_p > 0 else None
-            _lib.check(L.glowtts_proj_layernorm(att.data_ptr(), C, pw.data.data_ptr(), pw.npad, bp.detach().data_ptr(), x.data_ptr(), gamma.data_ptr(),
-                                                beta.data_ptr(), rowmask.data_ptr(), _sp(proj), s_.data_ptr(),
-                                                stats.data_ptr(), y.data_ptr(), yb.data_ptr(), R, C, 1e-4, float(drop_p), int(seeds[1]) & 0xFFFFFFFF,
-                                                _sp(seed_t), _lib.stream()), "glowtts_proj_layernorm")
+            L.glowtts_proj_layernorm(att.data_ptr(), C, pw.data.data_ptr(), pw.npad, bp.detach().data_ptr(), x.data_ptr(), gamma.data_ptr(),
+                                     beta.data_ptr(), rowmask.data_ptr(), _sp(proj), s_.data_ptr(),
+                                     stats.data_ptr(), y.data_ptr(), yb.data_ptr(), R, C, 1e-4, float(drop_p), int(seeds[1]) & 0xFFFFFFFF, _sp(seed_t), _lib.stream())
         else:
             proj = torch.empty(R, C, device=dev)
             _conv_launch(att, packs_p[0], C, R, 1, ops.F_BIAS | dflag, C, bp.detach(), rowmask, proj, drop_p=drop_p, seed=seeds[1], seed_t=seed_t, a_bf=False)
-            _lib.check(L.glowtts_layernorm_fwd_io(proj.data_ptr(), x.data_ptr(), s_.data_ptr(), gamma.data_ptr(), beta.data_ptr(), rowmask.data_ptr(),
-                                                  y.data_ptr(), stats.data_ptr(), R, C, 1e-4, 0, 0.0, 0, None, yb.data_ptr(), _lib.stream()), "glowtts_layernorm_fwd_io")
+            L.glowtts_layernorm_fwd_io(proj.data_ptr(), x.data_ptr(), s_.data_ptr(), gamma.data_ptr(), beta.data_ptr(), rowmask.data_ptr(),
+                                       y.data_ptr(), stats.data_ptr(), R, C, 1e-4, 0, 0.0, 0, None, yb.data_ptr(), _lib.stream())
         tape.ln_count += 1
         defer_rel = bool(FUSE["defer_rel_sum"] and rel_gated)
         if defer_rel:
@@ -458,13 +454,13 @@ class AttentionBlock(torch.autograd.Function):
         D = C // H
         dev = s_.device
         bf = torch.bfloat16
-        L = _L()
+        L = _A()
         scale = 1.0 / (1.0 - drop_p) if drop_p > 0 else 1.0
         dy = dy.contiguous()
         ds, dzp = torch.empty_like(s_), torch.empty(R, C, device=dev, dtype=bf)
         scratch, gb = tape.ln_slot(R, C, dev)
-        _lib.check(L.glowtts_layernorm_bwd_io(dy.data_ptr(), None, s_.data_ptr(), stats.data_ptr(), gamma.data_ptr(), rowmask.data_ptr(), ds.data_ptr(),
-                                              None, scratch.data_ptr(), R, C, 0, 0.0, dzp.data_ptr(), _sp(proj), scale, _lib.stream()), "glowtts_layernorm_bwd_io")
+        L.glowtts_layernorm_bwd_io(dy.data_ptr(), None, s_.data_ptr(), stats.data_ptr(), gamma.data_ptr(), rowmask.data_ptr(), ds.data_ptr(),
+                                   None, scratch.data_ptr(), R, C, 0, 0.0, dzp.data_ptr(), _sp(proj), scale, _lib.stream())
         datt = torch.empty(R, C, device=dev)
         _conv_launch(dzp, pwt_p, C, R, 1, 0, C, None, None, datt)                                     # projection data gradient
         nw = 2 * win + 1
@@ -475,10 +471,10 @@ class AttentionBlock(torch.autograd.Function):
         else:
             drel = torch.empty(2, nw, D, device=dev)
             ascr = torch.empty(L.glowtts_rpr_attention_scratch_floats(B, Tp, H, D, win) + 2 * nw * D, device=dev)
-        _lib.check(L.glowtts_rpr_attention_bwd_prec(qkv.data_ptr(), rk.data_ptr(), rv.data_ptr(), rowmask.data_ptr(), P.data_ptr(), datt.data_ptr(),
-                                                    dS.data_ptr(), dqkv.data_ptr(), None if defer_rel else drel[0].data_ptr(),
-                                                    None if defer_rel else drel[1].data_ptr(), ascr.data_ptr(), B, Tp, H, D, win,
-                                                    drop_p, aseed, _sp(seed_t), ops.BF16, _lib.stream()), "glowtts_rpr_attention_bwd_prec")
+        L.glowtts_rpr_attention_bwd_prec(qkv.data_ptr(), rk.data_ptr(), rv.data_ptr(), rowmask.data_ptr(), P.data_ptr(), datt.data_ptr(),
+                                         dS.data_ptr(), dqkv.data_ptr(), None if defer_rel else drel[0].data_ptr(),
+                                         None if defer_rel else drel[1].data_ptr(), ascr.data_ptr(), B, Tp, H, D, win,
+                                         drop_p, aseed, _sp(seed_t), ops.BF16, _lib.stream())
         dx = torch.empty(R, C, device=dev)
         _conv_launch(dqkv, pwt_qkv, 3 * C, R, 1, 0, C, None, None, dx, in0=ds, a_bf=False)            # QKV data gradient + the residual branch (ds)
         dwq, dbq = tape.out(wqkv.shape, dev), tape.out((3 * C,), dev)
@@ -497,8 +493,7 @@ class EmbeddingRows(torch.autograd.Function):
         V, C = table.shape
         rows = torch.empty(B * (T + 4), C, device=table.device)
         tokens = tokens.contiguous()
-        _lib.check(_L().glowtts_embedding_fwd(tokens.data_ptr(), table.detach().contiguous().data_ptr(), rowmask.data_ptr(), rows.data_ptr(),
-                                              B, T, C, scale, _lib.stream()), "glowtts_embedding_fwd")
+        _A().glowtts_embedding_fwd(tokens.data_ptr(), table.detach().contiguous().data_ptr(), rowmask.data_ptr(), rows.data_ptr(), B, T, C, scale, _lib.stream())
         ctx.save_for_backward(tokens, rowmask)
         ctx.cfg = (V, C, scale)
         return rows
@@ -510,8 +505,7 @@ class EmbeddingRows(torch.autograd.Function):
         V, C, scale = ctx.cfg
         B, T = tokens.shape
         dt = torch.empty(V, C, device=d.device)
-        _lib.check(_L().glowtts_embedding_bwd(tokens.data_ptr(), d.contiguous().data_ptr(), rowmask.data_ptr(), dt.data_ptr(), V, B, T, C, scale,
-                                              _lib.stream()), "glowtts_embedding_bwd")
+        _A().glowtts_embedding_bwd(tokens.data_ptr(), d.contiguous().data_ptr(), rowmask.data_ptr(), dt.data_ptr(), V, B, T, C, scale, _lib.stream())
         stamp("enc_bwd_end")
         return None, dt, None, None
 
@@ -526,8 +520,7 @@ def rpr_attention_eval(qkv, relk, relv, rowmask, B, Tp, H, win, precision=0):
     D = qkv.shape[1] // (3 * H)
     out = torch.empty(B * Tp, H * D, device=qkv.device)
     rk, rv = relk.detach().contiguous(), relv.detach().contiguous()
-    _lib.check(_L().glowtts_rpr_attention_fwd_eval(qkv.data_ptr(), rk.data_ptr(), rv.data_ptr(), rowmask.data_ptr(), out.data_ptr(),
-                                                   B, Tp, H, D, win, int(precision), _lib.stream()), "glowtts_rpr_attention_fwd_eval")
+    _A().glowtts_rpr_attention_fwd_eval(qkv.data_ptr(), rk.data_ptr(), rv.data_ptr(), rowmask.data_ptr(), out.data_ptr(), B, Tp, H, D, win, int(precision), _lib.stream())
     return out
 
 
@@ -550,9 +543,8 @@ class RPRAttention(torch.autograd.Function):
         out = torch.empty(B * Tp, H * D, device=qkv.device)
         P = torch.empty(B, H, Tp, Tp, device=qkv.device)
         rk, rv = relk.detach().contiguous(), relv.detach().contiguous()
-        _lib.check(_L().glowtts_rpr_attention_fwd_prec(qkv.data_ptr(), rk.data_ptr(), rv.data_ptr(), rowmask.data_ptr(), out.data_ptr(), P.data_ptr(),
-                                                       B, Tp, H, D, win, float(drop_p), int(seed) & 0xFFFFFFFF, _sp(seed_t), int(precision), _lib.stream()),
-                   "glowtts_rpr_attention_fwd_prec")
+        _A().glowtts_rpr_attention_fwd_prec(qkv.data_ptr(), rk.data_ptr(), rv.data_ptr(), rowmask.data_ptr(), out.data_ptr(), P.data_ptr(),
+                                            B, Tp, H, D, win, float(drop_p), int(seed) & 0xFFFFFFFF, _sp(seed_t), int(precision), _lib.stream())
         ctx.save_for_backward(qkv, rk, rv, rowmask, P, seed_t)
         ctx.cfg = (B, Tp, H, D, win, float(drop_p), int(seed) & 0xFFFFFFFF, int(precision))
         return out
@@ -561,7 +553,7 @@ class RPRAttention(torch.autograd.Function):
     def backward(ctx, dout):
         qkv, rk, rv, rowmask, P, seed_t = ctx.saved_tensors
         B, Tp, H, D, win, drop_p, seed, precision = ctx.cfg
-        L = _L()
+        L = _A()
         dev = qkv.device
         nw = 2 * win + 1
         dS = torch.empty(B, H, Tp, Tp, device=dev)
@@ -569,8 +561,7 @@ class RPRAttention(torch.autograd.Function):
         drel = torch.empty(2, nw, D, device=dev)
         drk, drv = drel[0], drel[1]
         scratch = torch.empty(L.glowtts_rpr_attention_scratch_floats(B, Tp, H, D, win) + 2 * nw * D, device=dev)
-        _lib.check(L.glowtts_rpr_attention_bwd_prec(qkv.data_ptr(), rk.data_ptr(), rv.data_ptr(), rowmask.data_ptr(), P.data_ptr(),
-                                                    dout.contiguous().data_ptr(), dS.data_ptr(), dqkv.data_ptr(), drk.data_ptr(), drv.data_ptr(),
-                                                    scratch.data_ptr(), B, Tp, H, D, win, drop_p, seed, _sp(seed_t), precision, _lib.stream()),
-                   "glowtts_rpr_attention_bwd_prec")
+        L.glowtts_rpr_attention_bwd_prec(qkv.data_ptr(), rk.data_ptr(), rv.data_ptr(), rowmask.data_ptr(), P.data_ptr(),
+                                         dout.contiguous().data_ptr(), dS.data_ptr(), dqkv.data_ptr(), drk.data_ptr(), drv.data_ptr(),
+                                         scratch.data_ptr(), B, Tp, H, D, win, drop_p, seed, _sp(seed_t), precision, _lib.stream())
         return dqkv, drk.view(1, nw, D), drv.view(1, nw, D), None, None, None, None, None, None, None, None, None

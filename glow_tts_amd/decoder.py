@@ -18,7 +18,8 @@ from .abi import FlowActs, FlowDims, FlowGrads, FlowParams, Packed, PrepJob, Sum
 
 MAXL, ROW_PAD, WN_SLAB = abi.MAX_WN_LAYERS, abi.ROW_PAD, abi.WN_SLAB_BYTES
 c_i64 = ctypes.c_int64
-_L = _lib.lib                            # the bound library (bench.py, tools and tests call D._L())
+_L = _lib.lib                            # the bound library, raw statuses (bench.py and tests call D._L())
+_A = _lib.api                            # the same entry points, a failing status raises (this module and tools call D._A())
 
 
 class PrepJobs:
@@ -35,8 +36,8 @@ class PrepJobs:
         if self.n.value >= self.CAP:
             raise _lib.GlowTTSHipError("too many weight-preparation jobs")
         nb = c_int(0)
-        _lib.check(_L().glowtts_prep_job_init(ctypes.byref(self.jobs[self.n.value]), v, g, inv, batch, inner, O, I, taps, int(transpose), perm, perm_h,
-                                              packed_ptr, outer_stride, inner_stride, w_stride, g_stride, self.blocks.value, ctypes.byref(nb)), "prep_job_init")
+        _A().glowtts_prep_job_init(ctypes.byref(self.jobs[self.n.value]), v, g, inv, batch, inner, O, I, taps, int(transpose), perm, perm_h,
+                                   packed_ptr, outer_stride, inner_stride, w_stride, g_stride, self.blocks.value, ctypes.byref(nb))
         self.n.value += 1
         self.blocks.value += nb.value
         self.max_cols = max(self.max_cols, I * taps)
@@ -46,10 +47,10 @@ class PrepJobs:
             return
         if TUNE["prep_twin"] and not getattr(self, "_twinned", False):
             # the In_l pairs are read ONCE: the forward image's tiles also write the two transposed half images (csrc/prep_ops.hip; no-op without that pattern)
-            _lib.check(_L().glowtts_prep_jobs_twin_in(ctypes.cast(self.jobs, c_void_p), ctypes.byref(self.n), ctypes.byref(self.blocks)), "glowtts_prep_jobs_twin_in")
+            _A().glowtts_prep_jobs_twin_in(ctypes.cast(self.jobs, c_void_p), ctypes.byref(self.n), ctypes.byref(self.blocks))
             self._twinned = True
         # (the table is a HOST array: it travels in the launch's argument segment - no copy node in a captured step)
-        _lib.check(_L().glowtts_prep_launch(ctypes.cast(self.jobs, c_void_p), self.n.value, self.blocks.value, self.max_cols, _lib.stream()), "glowtts_prep_launch")
+        _A().glowtts_prep_launch(ctypes.cast(self.jobs, c_void_p), self.n.value, self.blocks.value, self.max_cols, _lib.stream())
 
 
 _WSTREAM = {}
@@ -113,7 +114,7 @@ def step_seed(device):
     if not capturing:
         return torch.randint(0, 2 ** 31 - 1, (1,), device=device, dtype=torch.int32)
     out = torch.empty(1, dtype=torch.int32, device=device)
-    _lib.check(_L().glowtts_step_seed(st.data_ptr(), out.data_ptr(), _lib.stream()), "glowtts_step_seed")
+    _A().glowtts_step_seed(st.data_ptr(), out.data_ptr(), _lib.stream())
     return out
 
 
@@ -125,7 +126,7 @@ def stamp(name):
     if i >= STAMPS["buf"].numel():                       # (an armed eager run of many steps: the buffer is full, stop stamping)
         return
     STAMPS["names"].append(name)
-    _lib.check(_L().glowtts_debug_stamp(STAMPS["buf"].data_ptr() + 8 * i, _lib.stream()), "glowtts_debug_stamp")
+    _A().glowtts_debug_stamp(STAMPS["buf"].data_ptr() + 8 * i, _lib.stream())
 
 TAIL_STACKS = ("start_g", "start_v", "start_b", "rs_g", "rs_v", "rs_b", "rsl_g", "rsl_v", "rsl_b", "end_w", "end_b")
 
@@ -280,21 +281,19 @@ class WgradGroup:
         if getattr(self, "part", None) is None:
             return
         segs = (SumSeg * len(self.part_segs))(*[SumSeg(p0, off, n) for p0, n, off in self.part_segs])
-        _lib.check(_L().glowtts_sum_slices_seg(self.part.data_ptr(), self.part_S, self.part.shape[1], segs, len(self.part_segs), _lib.stream()), "glowtts_sum_slices_seg")
+        _A().glowtts_sum_slices_seg(self.part.data_ptr(), self.part_S, self.part.shape[1], segs, len(self.part_segs), _lib.stream())
 
     def launch_segment(self, i):
         start, n, tiles = self.segments[i]
         if n == 0:
             return
         if getattr(self, "part", None) is not None:
-            _lib.check(_L().glowtts_wgrad_grouped_phased(self.table.data_ptr() + start * ctypes.sizeof(WgradJob), n, tiles, self.whole_tiles, self.rows, self.taps,
-                                                         _lib.stream()), "glowtts_wgrad_grouped_phased")
+            _A().glowtts_wgrad_grouped_phased(self.table.data_ptr() + start * ctypes.sizeof(WgradJob), n, tiles, self.whole_tiles, self.rows, self.taps, _lib.stream())
             self.sum_parts()
             return
-        _lib.check(_L().glowtts_wgrad_grouped_io(self.table.data_ptr() + start * ctypes.sizeof(WgradJob), n, tiles, self.rows, self.taps,
-                                                 (self.taps - 1) // 2, self.xpro, self.precision, 1, 0,
-                                                 self.io_flags | (ops.WIO_WIDE if self._wide else 0) | (ops.WIO_DMA if (self._dma and self._wide) else 0), _lib.stream()),
-                   "glowtts_wgrad_grouped_io")
+        _A().glowtts_wgrad_grouped_io(self.table.data_ptr() + start * ctypes.sizeof(WgradJob), n, tiles, self.rows, self.taps,
+                                      (self.taps - 1) // 2, self.xpro, self.precision, 1, 0,
+                                      self.io_flags | (ops.WIO_WIDE if self._wide else 0) | (ops.WIO_DMA if (self._dma and self._wide) else 0), _lib.stream())
 
 
 class PackedBatch:
@@ -303,12 +302,12 @@ class PackedBatch:
     def __init__(self, w, transpose, perm, perm_h, precision, g=None, jobs=None):
         """jobs (a PrepJobs) given: `w` is weight_v (g: weight_g [batch, O, 1, 1], or None for a plain weight) and the image is produced by the
         step's one weight-preparation launch instead of a launch of its own."""
-        L = _L()
+        L = _A()
         w = w.contiguous()
         self.batch, O, I, taps = w.shape
         npad, kch = c_int(0), c_int(0)
         args = (self.batch, O, I, taps, int(transpose), perm, perm_h, precision)
-        _lib.check(L.glowtts_pack_weight_batched(None, *args, None, ctypes.byref(npad), ctypes.byref(kch), None), "pack(size)")
+        L.glowtts_pack_weight_batched(None, *args, None, ctypes.byref(npad), ctypes.byref(kch), None)
         self.npad, self.kchunks = npad.value, kch.value
         self.stride = taps * self.kchunks * self.npad * 64
         self.data = torch.empty(self.batch * self.stride, dtype=torch.uint8, device=w.device)
@@ -318,7 +317,7 @@ class PackedBatch:
                      self.data.data_ptr(), self.stride)
             jobs.keep += [w, g, self.data]
             return
-        _lib.check(L.glowtts_pack_weight_batched(_lib.ptr(w), *args, _lib.ptr(self.data), None, None, _lib.stream()), "pack")
+        L.glowtts_pack_weight_batched(_lib.ptr(w), *args, _lib.ptr(self.data), None, None, _lib.stream())
 
     def at(self, i):
         return Packed(self.data.data_ptr() + i * self.stride, self.npad, self.kchunks)
@@ -418,14 +417,14 @@ class _Prepared:
         GV (training, bf16, fused coupling network): {"w_start" | "w_in" | "w_rs" | "w_rs_last": (weight_g, weight_v)} stacked like W's entries, which
         are then absent from W - every image is produced from the weight-norm pairs by ONE launch (csrc/prep_ops.hip; `self.inv` keeps 1 / ||v||
         per class for the weight-norm backward) instead of 4 weight-norm + ~22 packing launches at the head of every step."""
-        L = _L()
+        L = _A()
         F_, H, C, Lw = cfg.F, cfg.H, cfg.C, cfg.L
         P = cfg.precision
         dev = W["an_logs"].device
         self.keep = W
         stamp("dec_prepared_begin")
         self.winfo = torch.empty(F_, 36, device=dev)
-        _lib.check(L.glowtts_inv1x1_prepare(_lib.ptr(W["inv_w"].contiguous()), _lib.ptr(self.winfo), F_, _lib.stream()), "inv1x1_prepare")
+        L.glowtts_inv1x1_prepare(_lib.ptr(W["inv_w"].contiguous()), _lib.ptr(self.winfo), F_, _lib.stream())
         jobs = PrepJobs() if GV is not None else None
         # (round 5) the images only the BACKWARD reads - the fused data-gradient image, the per-conv transposed images - are a second launch that the caller
         # may issue later, off the decoder's chain (`launch_bwd_images`: modules.GlowTTS.forward queues it on the encoder's stream behind the encoder's forward,
@@ -454,9 +453,9 @@ class _Prepared:
         def images(nflows, img_fwd, nbwd, img_bwd, with_inv):
             """the fused kernels' weight images (forward: of the first nflows flows; transposed: of the first nbwd)"""
             if GV is None:
-                _lib.check(L.glowtts_wavenet_pack_images(_lib.ptr(W["w_start"]), _lib.ptr(W["w_in"]), _lib.ptr(W["w_rs"]) if Lw > 1 else None,
-                                                         _lib.ptr(W["w_rs_last"]), _lib.ptr(W["w_end"]), nflows if img_fwd is not None else nbwd, Lw, C // 2,
-                                                         _lib.ptr(img_fwd), _lib.ptr(img_bwd), _lib.stream()), "wavenet_pack_images")
+                L.glowtts_wavenet_pack_images(_lib.ptr(W["w_start"]), _lib.ptr(W["w_in"]), _lib.ptr(W["w_rs"]) if Lw > 1 else None,
+                                              _lib.ptr(W["w_rs_last"]), _lib.ptr(W["w_end"]), nflows if img_fwd is not None else nbwd, Lw, C // 2,
+                                              _lib.ptr(img_fwd), _lib.ptr(img_bwd), _lib.stream())
                 return
             a = []
             for key in ("w_start", "w_in", "w_rs", "w_rs_last"):
@@ -467,15 +466,15 @@ class _Prepared:
                 else:
                     a += [v.data_ptr(), g.data_ptr(), inv.data_ptr() if inv is not None else None]
             jb = cur[0]
-            _lib.check(L.glowtts_wavenet_prep_jobs(ctypes.cast(jb.jobs, c_void_p), PrepJobs.CAP, ctypes.byref(jb.n), ctypes.byref(jb.blocks), *a,
-                                                   W["w_end"].data_ptr(), nflows, Lw, C // 2, _lib.ptr(img_fwd), nbwd, _lib.ptr(img_bwd)), "wavenet_prep_jobs")
+            L.glowtts_wavenet_prep_jobs(ctypes.cast(jb.jobs, c_void_p), PrepJobs.CAP, ctypes.byref(jb.n), ctypes.byref(jb.blocks), *a,
+                                        W["w_end"].data_ptr(), nflows, Lw, C // 2, _lib.ptr(img_fwd), nbwd, _lib.ptr(img_bwd))
             jb.max_cols = max(jb.max_cols, H * cfg.k)
 
         self.wn_img = None
         if fused_wn_supported(cfg):
             # one image per flow holding every forward weight of its coupling network as 24-KiB slabs (glowtts_wavenet_pack_images)
             nb = c_i64(0)
-            _lib.check(L.glowtts_wavenet_image_bytes(Lw, 0, ctypes.byref(nb)), "wavenet_image_bytes")
+            L.glowtts_wavenet_image_bytes(Lw, 0, ctypes.byref(nb))
             nb = nb.value
             self.wn_img = torch.empty(F_, nb, dtype=torch.uint8, device=dev)
             images(F_, self.wn_img, 0, None, True)
@@ -625,8 +624,7 @@ def squeeze_rows(cfg, mels, lengths, want_mask=True, out=None):
     R = B * (T + 2 * ROW_PAD)
     rows = out if out is not None else torch.empty(R, cfg.C, device=mels.device)
     mask = torch.empty(R, device=mels.device) if want_mask else None
-    _lib.check(_L().glowtts_squeeze_rows(_lib.ptr(mels.contiguous()), _lib.ptr(rows), _lib.ptr(mask), _lib.ptr(lengths),
-                                         B, Cm, Tm, cfg.ns, _lib.stream()), "squeeze_rows")
+    _A().glowtts_squeeze_rows(_lib.ptr(mels.contiguous()), _lib.ptr(rows), _lib.ptr(mask), _lib.ptr(lengths), B, Cm, Tm, cfg.ns, _lib.stream())
     return rows, mask, T
 
 
@@ -634,8 +632,8 @@ def unsqueeze_rows(cfg, rows, lengths, B, Tm, fill=None):
     mel = torch.empty(B, cfg.Cm, Tm, device=rows.device)
     if Tm % cfg.ns:
         mel.zero_()
-    _lib.check(_L().glowtts_unsqueeze_rows(_lib.ptr(rows), _lib.ptr(mel), _lib.ptr(lengths), B, cfg.Cm, Tm, cfg.ns,
-                                           0 if fill is None else 1, 0.0 if fill is None else float(fill), _lib.stream()), "unsqueeze_rows")
+    _A().glowtts_unsqueeze_rows(_lib.ptr(rows), _lib.ptr(mel), _lib.ptr(lengths), B, cfg.Cm, Tm, cfg.ns,
+                                0 if fill is None else 1, 0.0 if fill is None else float(fill), _lib.stream())
     return mel
 
 
@@ -694,7 +692,7 @@ def _cond_rows(cfg, prep, f, prow, pitch_w, pitch_b, Tp):
 
 def _run_forward(cfg, prep, mels, lengths, drop_p=0.0, seed=None, pitch=None):
     """pitch: None or (pitches [B, Tm], pitch_w [F, L, 2H, ns], pitch_b [F, L, 2H]) - GR mode."""
-    L = _L()
+    L = _A()
     B, _, Tm = mels.shape
     R = B * (Tm // cfg.ns + 2 * ROW_PAD)
     buf = _Buffers(cfg, prep, R, mels.device)
@@ -718,8 +716,7 @@ def _run_forward(cfg, prep, mels, lengths, drop_p=0.0, seed=None, pitch=None):
             acts.next_an_logs, acts.next_an_bias, acts.next_winfo = pn.an_logs, pn.an_bias, pn.winfo
             acts.next_xmid, acts.next_xout, acts.next_xa_bf = nxt.xmid, nxt.xout, nxt.xa_bf
         dims = _dims(cfg, B, T, drop_p, seed, f)
-        _lib.check(L.glowtts_flow_forward(ctypes.byref(dims), ctypes.byref(prep.params[f]), ctypes.byref(acts), _lib.stream()),
-                   "glowtts_flow_forward")
+        L.glowtts_flow_forward(ctypes.byref(dims), ctypes.byref(prep.params[f]), ctypes.byref(acts), _lib.stream())
     stamp("dec_fwd_end")
     # (z in the reference's [B, C, T] layout and the log-determinants on the encoder's stream, off the chain to the log-prior, was measured in round 5 and lost:
     #  5.07 against 5.01 ms/step - the extra cross-stream edges cost the replayed graph more than the two passes take)
@@ -727,9 +724,8 @@ def _run_forward(cfg, prep, mels, lengths, drop_p=0.0, seed=None, pitch=None):
     z = unsqueeze_rows(cfg, buf.x[cfg.F], lengths, B, Tm)
     part = torch.empty(cfg.F * B, device=mels.device)
     logdet = torch.empty(B, device=mels.device)
-    _lib.check(L.glowtts_decoder_logdet(_lib.ptr(buf.outs), R * prep.ldo, _lib.ptr(an_logs), _lib.ptr(prep.winfo),
-                                        _lib.ptr(rowmask), _lib.ptr(part), _lib.ptr(logdet), cfg.F, B, T + 2 * ROW_PAD, cfg.C, prep.ldo,
-                                        _lib.stream()), "glowtts_decoder_logdet")
+    L.glowtts_decoder_logdet(_lib.ptr(buf.outs), R * prep.ldo, _lib.ptr(an_logs), _lib.ptr(prep.winfo),
+                             _lib.ptr(rowmask), _lib.ptr(part), _lib.ptr(logdet), cfg.F, B, T + 2 * ROW_PAD, cfg.C, prep.ldo, _lib.stream())
     if pitch is not None:
         prep.set_cond(prep.cond)            # the backward addresses the conditioning gradient per utterance
     return z, logdet, buf, rowmask, T, prow
@@ -772,7 +768,7 @@ def decoder_inverse_rows(cfg, prep, x, rowmask, T, B, pitch=None, scratch=None):
     """Flows F-1 .. 0 inverted (Modules.py:664) on squeezed rows x [B*(T+4), C], with the conditioning already attached to `prep`.  x is used as
     scratch; returns the rows tensor that holds the result (x or one of the scratch buffers).  pitch: None or (pitch rows [R, ns] from
     pitch_rows, pitch_w [F, L, 2H, ns], pitch_b [F, L, 2H]) - GR mode."""
-    L = _L()
+    L = _A()
     sc = scratch if scratch is not None else _RowScratch(cfg, prep, x)
     assert sc.other is not x
     dims = _dims(cfg, B, T)
@@ -782,8 +778,7 @@ def decoder_inverse_rows(cfg, prep, x, rowmask, T, B, pitch=None, scratch=None):
             cr = _cond_rows(cfg, prep, f, pitch[0], pitch[1], pitch[2], T + 2 * ROW_PAD)
             prep.set_cond_rows(f, cr)
         a = sc.acts(nxt, sc.xmid[0], cur, rowmask)
-        _lib.check(L.glowtts_flow_inverse(ctypes.byref(dims), ctypes.byref(prep.params[f]), ctypes.byref(a), _lib.stream()),
-                   "glowtts_flow_inverse")
+        L.glowtts_flow_inverse(ctypes.byref(dims), ctypes.byref(prep.params[f]), ctypes.byref(a), _lib.stream())
         cur, nxt = nxt, cur
     return cur
 
@@ -796,7 +791,7 @@ def decoder_encode_rows(cfg, prep, rows, rowmask, T, B, pitch=None, scratch=None
     nxt); xmid alternates between two buffers when chained, so that a launch, which reads its xmid with a halo across 64-row windows, never
     writes a buffer it reads (it writes nxt's x_b half, the next flow's xmid and cur's x_a half - the next flow's output).  pitch: as in
     decoder_inverse_rows."""
-    L = _L()
+    L = _A()
     sc = scratch if scratch is not None else _RowScratch(cfg, prep, rows)
     assert sc.other is not rows
     if TUNE["chain_actnorm"] and pitch is None and any(p.wn_img for p in prep.params[:-1]):
@@ -815,8 +810,7 @@ def decoder_encode_rows(cfg, prep, rows, rowmask, T, B, pitch=None, scratch=None
             pn = prep.params[f + 1]
             a.next_an_logs, a.next_an_bias, a.next_winfo = pn.an_logs, pn.an_bias, pn.winfo
             a.next_xmid, a.next_xout = sc.xmid[(f + 1) % 2].data_ptr(), cur.data_ptr()
-        _lib.check(L.glowtts_flow_encode(ctypes.byref(dims), ctypes.byref(prep.params[f]), ctypes.byref(a), _lib.stream()),
-                   "glowtts_flow_encode")
+        L.glowtts_flow_encode(ctypes.byref(dims), ctypes.byref(prep.params[f]), ctypes.byref(a), _lib.stream())
         cur, nxt = nxt, cur
     if pitch is not None:
         prep.set_cond(prep.cond)
@@ -869,7 +863,7 @@ def actnorm_data_init(cfg, W, mels, lengths, cond=None, allreduce=None, pitch=No
     """ActNorm data-dependent init (Modules.py:685-687, 698-711): runs the flows once, setting
     W['an_logs'][f] / W['an_bias'][f] from the masked batch statistics of each flow's input.
     `allreduce(stats)` (optional) sums the [2C+1] statistics over data-parallel ranks."""
-    L = _L()
+    L = _A()
     with torch.no_grad():
         B, _, Tm = mels.shape
         x, rowmask, T = squeeze_rows(cfg, mels, lengths)
@@ -885,12 +879,10 @@ def actnorm_data_init(cfg, W, mels, lengths, cond=None, allreduce=None, pitch=No
         actp = torch.empty(cfg.L, R, cfg.H, device=dev, dtype=torch.bfloat16) if cfg.act_bf16 else None
         skip = torch.empty(R, cfg.H, device=dev)
         for f in range(cfg.F):
-            _lib.check(L.glowtts_actnorm_stats(_lib.ptr(bufs[0]), _lib.ptr(rowmask), _lib.ptr(stats), _lib.ptr(scratch), R, cfg.C,
-                                               _lib.stream()), "actnorm_stats")
+            L.glowtts_actnorm_stats(_lib.ptr(bufs[0]), _lib.ptr(rowmask), _lib.ptr(stats), _lib.ptr(scratch), R, cfg.C, _lib.stream())
             if allreduce is not None:
                 allreduce(stats)
-            _lib.check(L.glowtts_actnorm_from_stats(_lib.ptr(stats), W["an_logs"][f].data_ptr(), W["an_bias"][f].data_ptr(), cfg.C,
-                                                    _lib.stream()), "actnorm_from_stats")
+            L.glowtts_actnorm_from_stats(_lib.ptr(stats), W["an_logs"][f].data_ptr(), W["an_bias"][f].data_ptr(), cfg.C, _lib.stream())
             prep = _Prepared(cfg, W, need_bwd=False, cond=cond)       # re-pack is cheap relative to a one-off init
             if pitch is not None:
                 prow = pitch_rows(cfg, pitch[0], rowmask, B, T)
@@ -904,8 +896,7 @@ def actnorm_data_init(cfg, W, mels, lengths, cond=None, allreduce=None, pitch=No
                 if actp is not None:
                     a.acts[l] = actp[l].data_ptr()
             a.skip, a.outs, a.rowmask = skip.data_ptr(), outs.data_ptr(), rowmask.data_ptr()
-            _lib.check(L.glowtts_flow_forward(ctypes.byref(dims), ctypes.byref(prep.params[f]), ctypes.byref(a), _lib.stream()),
-                       "glowtts_flow_forward(init)")
+            L.glowtts_flow_forward(ctypes.byref(dims), ctypes.byref(prep.params[f]), ctypes.byref(a), _lib.stream())
             bufs.reverse()
 
 
@@ -991,7 +982,7 @@ class DecoderFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dz, dlogdet, _dz_rows=None):
-        L = _L()
+        L = _A()
         cfg, prep, buf, rowmask, T = ctx.cfg, ctx.prep, ctx.buf, ctx.rowmask, ctx.T
         W = prep.keep
         B, Cm, Tm = ctx.mel_shape
@@ -1131,7 +1122,7 @@ class DecoderFunction(torch.autograd.Function):
         def sum_tail():
             if tail_seg is not None:                       # the one-tap group's partial images -> the gradient tensors
                 segs = (SumSeg * len(tail_seg))(*[SumSeg(p0, off, n) for p0, n, off in tail_seg])
-                _lib.check(L.glowtts_sum_slices_seg(tail_part.data_ptr(), S_t, tail_part.shape[1], segs, len(tail_seg), _lib.stream()), "glowtts_sum_slices_seg")
+                L.glowtts_sum_slices_seg(tail_part.data_ptr(), S_t, tail_part.shape[1], segs, len(tail_seg), _lib.stream())
         main = torch.cuda.current_stream()
         side = _wgrad_stream(dev)
         stamp("dec_bwd_begin")
@@ -1158,8 +1149,7 @@ class DecoderFunction(torch.autograd.Function):
                     g.pitch_rows, g.pitch_ns = ctx.prow.data_ptr(), npit
             acts = buf.acts(f, Lw, rowmask)
             dims = _dims(cfg, B, T, ctx.drop[0], ctx.drop[1], f)
-            _lib.check(L.glowtts_flow_backward(ctypes.byref(dims), ctypes.byref(prep.params[f]), ctypes.byref(acts), ctypes.byref(g),
-                                               _lib.stream()), "glowtts_flow_backward")
+            L.glowtts_flow_backward(ctypes.byref(dims), ctypes.byref(prep.params[f]), ctypes.byref(acts), ctypes.byref(g), _lib.stream())
             stamp(f"dec_bwd_flow{f}")
         if TAIL["defer"]:
             gk.launch_segment(0)
@@ -1207,7 +1197,7 @@ class DecoderFunction(torch.autograd.Function):
 
             def wn_run(jobs, keep=wn_keep):
                 if jobs:                                        # (4.70 / 4.72 / 4.70 against 4.75 / 4.70 / 4.76 ms/step for one launch per class, three alternating pairs)
-                    _lib.check(L.glowtts_weightnorm_bwd_multi((WnBwdJob * len(jobs))(*jobs), len(jobs), _lib.stream()), "glowtts_weightnorm_bwd_multi")
+                    L.glowtts_weightnorm_bwd_multi((WnBwdJob * len(jobs))(*jobs), len(jobs), _lib.stream())
             if wn_pending:
                 TAIL["pending"].append(lambda jobs=wn_pending: wn_run(jobs))
             if tail_fns is not None:
@@ -1217,12 +1207,10 @@ class DecoderFunction(torch.autograd.Function):
 
         def param_sums():
             stamp("dec_wgrads_done")
-            _lib.check(L.glowtts_colsum_batched(scratch.data_ptr(), d_an.data_ptr(), nblk_all, 2 * C + 16, F_, nscr, 2 * C + 16, _lib.stream()),
-                       "glowtts_colsum_batched")
+            L.glowtts_colsum_batched(scratch.data_ptr(), d_an.data_ptr(), nblk_all, 2 * C + 16, F_, nscr, 2 * C + 16, _lib.stream())
             # + the log-determinant terms of the parameters (Modules.py:694, 747): logdet_b += (sum logs + logdet(W) C/4) * len_b
-            _lib.check(L.glowtts_decoder_param_grads(d_an.data_ptr(), dld.data_ptr(), rowmask.data_ptr(), prep.winfo.data_ptr(), G["an_logs"].data_ptr(),
-                                                     G["an_bias"].data_ptr(), G["inv_w"].data_ptr(), F_, B, T + 2 * ROW_PAD, C, _lib.stream()),
-                       "glowtts_decoder_param_grads")
+            L.glowtts_decoder_param_grads(d_an.data_ptr(), dld.data_ptr(), rowmask.data_ptr(), prep.winfo.data_ptr(), G["an_logs"].data_ptr(),
+                                          G["an_bias"].data_ptr(), G["inv_w"].data_ptr(), F_, B, T + 2 * ROW_PAD, C, _lib.stream())
         if tail_fns is None:
             param_sums()
         else:
@@ -1250,7 +1238,7 @@ class DecoderFunction(torch.autograd.Function):
         if dcond is not None:
             # (one launch; a non-finite gate gradient poisons its accumulator and reads NaN here - ADVICE r5)
             acc, dcond = dcond.contiguous(), torch.empty(dcond.shape, device=dcond.device)
-            _lib.check(_L().glowtts_fx_to_float(acc.data_ptr(), dcond.data_ptr(), acc.numel(), _lib.stream()), "glowtts_fx_to_float")
+            _A().glowtts_fx_to_float(acc.data_ptr(), dcond.data_ptr(), acc.numel(), _lib.stream())
         dpw = dpb = None
         if ctx.prow is not None:
             # Pitch_l conv (Modules.py:846-852, 867-869): bias gradient = the conditioning gradient summed over utterances; weight gradient =
@@ -1363,8 +1351,8 @@ class WeightNorm(torch.autograd.Function):
         v, g = v.contiguous(), g.contiguous()
         rows, cols = v.numel() // (v.shape[-1] * v.shape[-2]), v.shape[-1] * v.shape[-2]
         w, inv = torch.empty_like(v), torch.empty(rows, device=v.device)
-        L = _L()
-        _lib.check(L.glowtts_weightnorm_fwd(v.data_ptr(), g.data_ptr(), w.data_ptr(), inv.data_ptr(), rows, cols, _lib.stream()), "glowtts_weightnorm_fwd")
+        L = _A()
+        L.glowtts_weightnorm_fwd(v.data_ptr(), g.data_ptr(), w.data_ptr(), inv.data_ptr(), rows, cols, _lib.stream())
         ctx.save_for_backward(g, v, inv)
         ctx.dims = (rows, cols)
         return w
@@ -1375,8 +1363,7 @@ class WeightNorm(torch.autograd.Function):
         rows, cols = ctx.dims
         dw = dw.contiguous()
         dv, dg = torch.empty_like(v), torch.empty_like(g)
-        run = lambda: _lib.check(_L().glowtts_weightnorm_bwd(dw.data_ptr(), v.data_ptr(), g.data_ptr(), inv.data_ptr(), dv.data_ptr(), dg.data_ptr(),
-                                                             rows, cols, _lib.stream()), "glowtts_weightnorm_bwd")
+        run = lambda: _A().glowtts_weightnorm_bwd(dw.data_ptr(), v.data_ptr(), g.data_ptr(), inv.data_ptr(), dv.data_ptr(), dg.data_ptr(), rows, cols, _lib.stream())
         if ctx.tail and TAIL["defer"]:
             TAIL["pending"].append(run)                  # dw is filled by the deferred weight-gradient launches queued before this one
         else:
@@ -1392,7 +1379,7 @@ class CondLinear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, *args):
-        L = _L()
+        L = _A()
         kinds = [args[i:i + 4] for i in range(0, len(args), 4)]
         B = kinds[0][3].shape[0]
         N = kinds[0][1].numel() // kinds[0][1].shape[-2]
@@ -1404,8 +1391,7 @@ class CondLinear(torch.autograd.Function):
             D = v.shape[-2]
             assert v.shape[-1] == 1 and v.numel() == N * D and g.numel() == N and b.numel() == N and tuple(vec.shape) == (B, D)
             inv = torch.empty(N, device=dev)
-            _lib.check(L.glowtts_cond_linear_fwd(v.data_ptr(), g.data_ptr(), b.data_ptr(), vec.data_ptr(), out.data_ptr(), inv.data_ptr(), N, D, B, int(i > 0),
-                                                 _lib.stream()), "glowtts_cond_linear_fwd")
+            L.glowtts_cond_linear_fwd(v.data_ptr(), g.data_ptr(), b.data_ptr(), vec.data_ptr(), out.data_ptr(), inv.data_ptr(), N, D, B, int(i > 0), _lib.stream())
             keep += [g, v, vec, inv]
         ctx.save_for_backward(*keep)
         ctx.shapes = [(tuple(k[0].shape), tuple(k[1].shape), tuple(k[2].shape)) for k in kinds]
@@ -1413,7 +1399,7 @@ class CondLinear(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        L = _L()
+        L = _A()
         keep = ctx.saved_tensors
         dout = dout.contiguous()
         B, N = dout.shape
@@ -1425,9 +1411,8 @@ class CondLinear(torch.autograd.Function):
             want_vec = ctx.needs_input_grad[4 * i + 3]
             dvec = torch.empty_like(vec) if want_vec else None
             scratch = torch.empty(L.glowtts_cond_linear_bwd_scratch_floats(N, D, B), device=dout.device)
-            _lib.check(L.glowtts_cond_linear_bwd(dout.data_ptr(), N, v.data_ptr(), g.data_ptr(), inv.data_ptr(), vec.data_ptr(), dv.data_ptr(), dg.data_ptr(),
-                                                 db.data_ptr(), dvec.data_ptr() if want_vec else None, scratch.data_ptr(), N, D, B, _lib.stream()),
-                       "glowtts_cond_linear_bwd")
+            L.glowtts_cond_linear_bwd(dout.data_ptr(), N, v.data_ptr(), g.data_ptr(), inv.data_ptr(), vec.data_ptr(), dv.data_ptr(), dg.data_ptr(),
+                                      db.data_ptr(), dvec.data_ptr() if want_vec else None, scratch.data_ptr(), N, D, B, _lib.stream())
             grads += [dg.view(gs), dv.view(vs), db.view(bs), dvec]
         return tuple(grads)
 
@@ -1504,7 +1489,7 @@ class DecoderStacks:
         #  so that a shape it rejects takes the matmul path below instead of raising in the forward: ADVICE r5)
         n_out = self.cfg.F * self.cfg.L * 2 * self.cfg.H
         if TUNE["cond_hip"] and all(vec.is_cuda and vec.dtype == torch.float32 and vec.dim() == 2 and vec.shape[1] == self.S[kind + "_v"].tensor().shape[-2]
-                                    and _lib.lib().glowtts_cond_linear_supported(n_out, int(vec.shape[1]), int(vec.shape[0])) for kind, vec in kinds):
+                                    and _lib.api().glowtts_cond_linear_supported(n_out, int(vec.shape[1]), int(vec.shape[0])) for kind, vec in kinds):
             args = []
             for kind, vec in kinds:
                 args += [self.S[kind + "_g"].tensor(), self.S[kind + "_v"].tensor(), self.S[kind + "_b"].tensor(), vec]

@@ -43,8 +43,7 @@ class DurProj(torch.autograd.Function):
         C = int(d.shape[1])
         d, w, bias, mask = d.contiguous(), w.contiguous(), bias.contiguous(), mask.contiguous()
         out = torch.empty(B, 1, T, device=d.device)
-        _lib.check(_lib.lib().glowtts_dur_proj_fwd(_lib.ptr(d), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(mask), _lib.ptr(out), B, T, ROW_PAD, C, _lib.stream()),
-                   "glowtts_dur_proj_fwd")
+        _lib.api().glowtts_dur_proj_fwd(_lib.ptr(d), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(mask), _lib.ptr(out), B, T, ROW_PAD, C, _lib.stream())
         ctx.save_for_backward(d, w, mask)
         ctx.owner = owner
         return out
@@ -61,8 +60,8 @@ class DurProj(torch.autograd.Function):
         if counter is None:                                   # (first use inside a capture: a counter of this launch's own, zeroed by a fill)
             counter = torch.zeros(1, dtype=torch.int32, device=dev)
         scratch = torch.empty(B * (C + 1), device=dev)
-        _lib.check(_lib.lib().glowtts_dur_proj_bwd(_lib.ptr(g), _lib.ptr(mask), _lib.ptr(d), _lib.ptr(w), _lib.ptr(dd), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(scratch),
-                                                   _lib.ptr(counter), B, T, ROW_PAD, C, _lib.stream()), "glowtts_dur_proj_bwd")
+        _lib.api().glowtts_dur_proj_bwd(_lib.ptr(g), _lib.ptr(mask), _lib.ptr(d), _lib.ptr(w), _lib.ptr(dd), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(scratch),
+                                        _lib.ptr(counter), B, T, ROW_PAD, C, _lib.stream())
         return dd, dw, db, None, None
 
 
@@ -75,7 +74,7 @@ class PriorSplit(torch.autograd.Function):
         rows = rows.contiguous()
         M = int(rows.shape[1]) // 2
         mean, ls = torch.empty(B, M, T, device=rows.device), torch.empty(B, M, T, device=rows.device)
-        _lib.check(_lib.lib().glowtts_prior_split_fwd(_lib.ptr(rows), _lib.ptr(mean), _lib.ptr(ls), B, T, ROW_PAD, M, _lib.stream()), "glowtts_prior_split_fwd")
+        _lib.api().glowtts_prior_split_fwd(_lib.ptr(rows), _lib.ptr(mean), _lib.ptr(ls), B, T, ROW_PAD, M, _lib.stream())
         ctx.dims = (B, T, M)
         return mean, ls
 
@@ -88,7 +87,7 @@ class PriorSplit(torch.autograd.Function):
         dm = None if dm is None else dm.contiguous()
         dl = None if dl is None else dl.contiguous()
         drows = torch.empty(B * (T + 2 * ROW_PAD), 2 * M, device=ref.device)
-        _lib.check(_lib.lib().glowtts_prior_split_bwd(_lib.ptr(dm), _lib.ptr(dl), _lib.ptr(drows), B, T, ROW_PAD, M, _lib.stream()), "glowtts_prior_split_bwd")
+        _lib.api().glowtts_prior_split_bwd(_lib.ptr(dm), _lib.ptr(dl), _lib.ptr(drows), B, T, ROW_PAD, M, _lib.stream())
         return drows, None, None
 
 
@@ -108,12 +107,12 @@ class _EncoderPacks(ops.PackSet):
 
 def token_masks(token_lengths, T):
     """-> (mask [B, 1, T] float, rowmask [B * (T + 4)]) of a token batch, one launch (glowtts_token_masks)."""
-    L = _lib.lib()
+    L = _lib.api()
     B = token_lengths.shape[0]
     tl = token_lengths.to(torch.int64).contiguous()
     mask = torch.empty(B, 1, T, device=tl.device)
     rowmask = torch.empty(B * (T + 2 * ROW_PAD), device=tl.device)
-    _lib.check(L.glowtts_token_masks(tl.data_ptr(), mask.data_ptr(), rowmask.data_ptr(), B, T, _lib.stream()), "glowtts_token_masks")
+    L.glowtts_token_masks(tl.data_ptr(), mask.data_ptr(), rowmask.data_ptr(), B, T, _lib.stream())
     return mask, rowmask
 
 
@@ -297,7 +296,7 @@ def encoder_forward(P, hp, tokens, mask, speakers=None, prosodies=None, training
     # Projection to one channel: N = 1 is not a GEMM; a masked dot product per frame (multiply + row reduction: rocBLAS' gemv took
     # 82 us for these 3.5k x 256 rows, 5x the two elementwise kernels)
     wq = prefix + ".layer_Dict.Duration_Predictor.layer_Dict.Projection"
-    if d.is_cuda and d.dtype == torch.float32 and Pc[wq + ".weight"].dtype == torch.float32 and _lib.lib().glowtts_dur_proj_supported(int(d.shape[1])):
+    if d.is_cuda and d.dtype == torch.float32 and Pc[wq + ".weight"].dtype == torch.float32 and _lib.api().glowtts_dur_proj_supported(int(d.shape[1])):
         log_dur = DurProj.apply(d, Pc[wq + ".weight"], Pc[wq + ".bias"], mask, cache)
     else:
         log_dur = ((d * Pc[wq + ".weight"][0, :, 0]).sum(-1) + Pc[wq + ".bias"]).view(B, Tp)[:, ROW_PAD:-ROW_PAD].unsqueeze(1) * mask

@@ -11,8 +11,7 @@ def maximum_path_idx(value, t_x, t_y, max_neg_val=-1e9, want_q=False):
     B, Tx, Ty = value.shape
     idx = torch.empty((B, Ty), dtype=torch.int32, device=value.device)
     q = value.clone() if want_q else None
-    _lib.check(_lib.lib().glowtts_mas_dp_f32(_lib.ptr(value), _lib.ptr(t_x), _lib.ptr(t_y), _lib.ptr(idx),
-                                             _lib.ptr(q), B, Tx, Ty, max_neg_val, _lib.stream()), "glowtts_mas_dp_f32")
+    _lib.api().glowtts_mas_dp_f32(_lib.ptr(value), _lib.ptr(t_x), _lib.ptr(t_y), _lib.ptr(idx), _lib.ptr(q), B, Tx, Ty, max_neg_val, _lib.stream())
     return (idx, q) if want_q else idx
 
 
@@ -20,8 +19,7 @@ def path_from_idx(idx, Tx, dtype=torch.float32):
     B, Ty = idx.shape
     kind = {torch.int32: 0, torch.float32: 1}[dtype]
     path = torch.empty((B, Tx, Ty), dtype=dtype, device=idx.device)
-    _lib.check(_lib.lib().glowtts_mas_path_from_idx(_lib.ptr(idx), _lib.ptr(path), B, Tx, Ty, kind, _lib.stream()),
-               "glowtts_mas_path_from_idx")
+    _lib.api().glowtts_mas_path_from_idx(_lib.ptr(idx), _lib.ptr(path), B, Tx, Ty, kind, _lib.stream())
     return path
 
 
@@ -49,6 +47,5 @@ def maximum_path_host(value, mask, max_neg_val=-1e9, num_threads=0):
     t_x = np.ascontiguousarray(mk.sum(1)[:, 0], dtype=np.int32)
     t_y = np.ascontiguousarray(mk.sum(2)[:, 0], dtype=np.int32)
     path = np.zeros(v.shape, dtype=np.int32)
-    _lib.check(_lib.lib().glowtts_mas_f32_host(v.ctypes.data, path.ctypes.data, t_x.ctypes.data, t_y.ctypes.data, v.shape[0], v.shape[1], v.shape[2],
-                                      max_neg_val, int(num_threads)), "glowtts_mas_f32_host")
+    _lib.api().glowtts_mas_f32_host(v.ctypes.data, path.ctypes.data, t_x.ctypes.data, t_y.ctypes.data, v.shape[0], v.shape[1], v.shape[2], max_neg_val, int(num_threads))
     return torch.from_numpy(path).to(dtype) if is_t else path

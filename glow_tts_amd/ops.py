@@ -1,5 +1,5 @@
 """Thin Python wrappers over the C ABI (include/glowtts_hip.h): argument marshalling only.
-Every function launches asynchronously on torch's current HIP stream."""
+Every function launches asynchronously on torch's current HIP stream, through the checked handle `_lib.api()`: a status other than GLOWTTS_OK raises there."""
 import ctypes
 
 import torch
@@ -21,15 +21,13 @@ class PackedWeight:
 
 def pack_weight(w, transpose=False, perm=PERM_NONE, perm_h=0, precision=BF16):
     """w: fp32 device tensor [O, I, taps] (torch Conv1d layout) -> PackedWeight."""
-    L = _lib.lib()
+    L = _lib.api()
     w = w.contiguous()
     O, I, taps = w.shape
     npad, kch = c_int(0), c_int(0)
-    _lib.check(L.glowtts_pack_weight(None, O, I, taps, int(transpose), perm, perm_h, precision, None,
-                                     ctypes.byref(npad), ctypes.byref(kch), None), "glowtts_pack_weight(size)")
+    L.glowtts_pack_weight(None, O, I, taps, int(transpose), perm, perm_h, precision, None, ctypes.byref(npad), ctypes.byref(kch), None)
     buf = torch.empty(taps * kch.value * npad.value * 64, dtype=torch.uint8, device=w.device)
-    _lib.check(L.glowtts_pack_weight(_lib.ptr(w), O, I, taps, int(transpose), perm, perm_h, precision, _lib.ptr(buf),
-                                     None, None, _lib.stream()), "glowtts_pack_weight")
+    L.glowtts_pack_weight(_lib.ptr(w), O, I, taps, int(transpose), perm, perm_h, precision, _lib.ptr(buf), None, None, _lib.stream())
     n = I if transpose else O
     return PackedWeight(buf, npad.value, kch.value, taps, precision, n)
 
@@ -40,7 +38,7 @@ class PackSet:
     (call it once per forward: the optimizer changes them in place).  `matches(items)` tells whether the pointers still hold."""
 
     def __init__(self, items, precision=BF16):
-        L = _lib.lib()
+        L = _lib.api()
         assert items
         dev = items[0][1].device
         n = len(items)
@@ -50,16 +48,15 @@ class PackSet:
         for i, (_, w, tr) in enumerate(items):
             assert w.dim() == 3 and w.is_contiguous() and w.dtype == torch.float32
             O, I, k = w.shape
-            _lib.check(L.glowtts_pack_job_init(ctypes.byref(jobs[i]), None, O, I, k, int(tr), PERM_NONE, 0, precision, None, 0,
-                                               ctypes.byref(blocks), ctypes.byref(nbytes)), "glowtts_pack_job_init(size)")
+            L.glowtts_pack_job_init(ctypes.byref(jobs[i]), None, O, I, k, int(tr), PERM_NONE, 0, precision, None, 0, ctypes.byref(blocks), ctypes.byref(nbytes))
             offs.append(total)
             total += (nbytes.value + 255) // 256 * 256
         self.data = torch.empty(total, dtype=torch.uint8, device=dev)
         self.packed, b0 = {}, 0
         for i, (key, w, tr) in enumerate(items):
             O, I, k = w.shape
-            _lib.check(L.glowtts_pack_job_init(ctypes.byref(jobs[i]), w.data_ptr(), O, I, k, int(tr), PERM_NONE, 0, precision,
-                                               self.data.data_ptr() + offs[i], b0, ctypes.byref(blocks), ctypes.byref(nbytes)), "glowtts_pack_job_init")
+            L.glowtts_pack_job_init(ctypes.byref(jobs[i]), w.data_ptr(), O, I, k, int(tr), PERM_NONE, 0, precision,
+                                    self.data.data_ptr() + offs[i], b0, ctypes.byref(blocks), ctypes.byref(nbytes))
             b0 += blocks.value
             self.packed[(key, bool(tr))] = PackedWeight(self.data[offs[i]:offs[i] + nbytes.value], jobs[i].npad, jobs[i].kchunks, k, precision,
                                                         I if tr else O)
@@ -72,8 +69,7 @@ class PackSet:
         return tuple((k, w.data_ptr(), tuple(w.shape), bool(tr)) for k, w, tr in items)
 
     def run(self):
-        _lib.check(_lib.lib().glowtts_pack_weight_multi(self.table.data_ptr(), self.njobs, self.blocks, self.precision, _lib.stream()),
-                   "glowtts_pack_weight_multi")
+        _lib.api().glowtts_pack_weight_multi(self.table.data_ptr(), self.njobs, self.blocks, self.precision, _lib.stream())
 
     def get(self, key):
         """(forward pack, transposed pack or None)"""
@@ -109,77 +105,75 @@ def conv_cl(a, pw, ca, rows, *, lda=None, a2=None, lda2=0, ca1=0, apro=APRO_NONE
     args.seed_ptr = seed_t.data_ptr() if seed_t is not None else None
     args.io_flags = io_flags
     assert not (io_flags and (a_off or out0_off))
-    _lib.check(_lib.lib().glowtts_conv_cl(ctypes.byref(args), _lib.stream()), "glowtts_conv_cl")
+    _lib.api().glowtts_conv_cl(ctypes.byref(args), _lib.stream())
 
 
 # ---- Griffin-Lim vocoder (csrc/vocoder_ops.hip).  geo = (n_fft, win_length, hop); lengths: int32 device tensors [B] ----
 def mel_to_linear(mels, frame_lengths, basis, mag, max_abs):
     """mels [B, Mel, T] -> mag [B, T, F] (glowtts_mel_to_linear_f32)."""
     B, Mel, T = mels.shape
-    _lib.check(_lib.lib().glowtts_mel_to_linear_f32(_lib.ptr(mels), _lib.ptr(frame_lengths), _lib.ptr(basis), _lib.ptr(mag), B, Mel, T, mag.shape[2],
-                                                    float(max_abs), _lib.stream()), "glowtts_mel_to_linear_f32")
+    _lib.api().glowtts_mel_to_linear_f32(_lib.ptr(mels), _lib.ptr(frame_lengths), _lib.ptr(basis), _lib.ptr(mag), B, Mel, T, mag.shape[2], float(max_abs), _lib.stream())
 
 
 def stft(wav, wav_lengths, window, twiddle, spec, geo):
     """wav [B, L] -> spec [B, T, F, 2] (glowtts_stft_f32)."""
-    _lib.check(_lib.lib().glowtts_stft_f32(_lib.ptr(wav), _lib.ptr(wav_lengths), _lib.ptr(window), _lib.ptr(twiddle), _lib.ptr(spec), wav.shape[0],
-                                           wav.shape[1], spec.shape[1], *geo, _lib.stream()), "glowtts_stft_f32")
+    _lib.api().glowtts_stft_f32(_lib.ptr(wav), _lib.ptr(wav_lengths), _lib.ptr(window), _lib.ptr(twiddle), _lib.ptr(spec), wav.shape[0],
+                                wav.shape[1], spec.shape[1], *geo, _lib.stream())
 
 
 def istft(spec, frame_lengths, window, twiddle, frames, wav, geo):
     """spec [B, T, F, 2] -> wav [B, L >= hop (T - 1)] through frames [B, T, win] (glowtts_istft_f32)."""
-    _lib.check(_lib.lib().glowtts_istft_f32(_lib.ptr(spec), _lib.ptr(frame_lengths), _lib.ptr(window), _lib.ptr(twiddle), _lib.ptr(frames), _lib.ptr(wav),
-                                            spec.shape[0], spec.shape[1], wav.shape[1], *geo, _lib.stream()), "glowtts_istft_f32")
+    _lib.api().glowtts_istft_f32(_lib.ptr(spec), _lib.ptr(frame_lengths), _lib.ptr(window), _lib.ptr(twiddle), _lib.ptr(frames), _lib.ptr(wav),
+                                 spec.shape[0], spec.shape[1], wav.shape[1], *geo, _lib.stream())
 
 
 def overlap_add(frames, frame_lengths, window, wav, geo):
     """frames [B, T, win] -> wav [B, L] (glowtts_overlap_add_f32)."""
-    _lib.check(_lib.lib().glowtts_overlap_add_f32(_lib.ptr(frames), _lib.ptr(frame_lengths), _lib.ptr(window), _lib.ptr(wav), frames.shape[0], frames.shape[1],
-                                                  wav.shape[1], *geo, _lib.stream()), "glowtts_overlap_add_f32")
+    _lib.api().glowtts_overlap_add_f32(_lib.ptr(frames), _lib.ptr(frame_lengths), _lib.ptr(window), _lib.ptr(wav), frames.shape[0], frames.shape[1],
+                                       wav.shape[1], *geo, _lib.stream())
 
 
 def griffin_lim_step(x, x_prev, mag, frame_lengths, window, twiddle, alpha, frames, geo):
     """One fused Griffin-Lim iteration: (x, x_prev) [B, L], mag [B, T, F] -> frames [B, T, win] (glowtts_griffin_lim_step_f32)."""
-    _lib.check(_lib.lib().glowtts_griffin_lim_step_f32(_lib.ptr(x), _lib.ptr(x_prev), _lib.ptr(mag), _lib.ptr(frame_lengths), _lib.ptr(window), _lib.ptr(twiddle),
-                                                       float(alpha), _lib.ptr(frames), mag.shape[0], mag.shape[1], x.shape[1], *geo, _lib.stream()),
-               "glowtts_griffin_lim_step_f32")
+    _lib.api().glowtts_griffin_lim_step_f32(_lib.ptr(x), _lib.ptr(x_prev), _lib.ptr(mag), _lib.ptr(frame_lengths), _lib.ptr(window), _lib.ptr(twiddle),
+                                            float(alpha), _lib.ptr(frames), mag.shape[0], mag.shape[1], x.shape[1], *geo, _lib.stream())
 
 
 # ---- analysis front end (csrc/frontend_ops.hip).  wav [B, L] fp32, wav_lengths int32 [B], both on the device ----
 def mel_analysis(wav, wav_lengths, window, twiddle, fb_index, fb_weight, mel, geo, pre_emphasis, min_db, max_abs):
     """wav [B, L] -> normalised mel [B, T, Mel] (glowtts_mel_analysis_f32); fb_index [Mel, 3] int32 / fb_weight: the sparse filterbank."""
     B, T, Mel = mel.shape
-    _lib.check(_lib.lib().glowtts_mel_analysis_f32(_lib.ptr(wav), _lib.ptr(wav_lengths), _lib.ptr(window), _lib.ptr(twiddle), _lib.ptr(fb_index),
-                                                   _lib.ptr(fb_weight), _lib.ptr(mel), B, wav.shape[1], T, Mel, fb_weight.numel(), *geo, float(pre_emphasis),
-                                                   float(min_db), float(max_abs), _lib.stream()), "glowtts_mel_analysis_f32")
+    _lib.api().glowtts_mel_analysis_f32(_lib.ptr(wav), _lib.ptr(wav_lengths), _lib.ptr(window), _lib.ptr(twiddle), _lib.ptr(fb_index),
+                                        _lib.ptr(fb_weight), _lib.ptr(mel), B, wav.shape[1], T, Mel, fb_weight.numel(), *geo, float(pre_emphasis),
+                                        float(min_db), float(max_abs), _lib.stream())
 
 
 def yin(wav, wav_lengths, pitch, w_len, w_step, tau_min, tau_max, thresh, sample_rate, cmnd=None):
     """wav [B, L] -> pitch [B, T] in Hz, 0 where unvoiced (glowtts_yin_f32); cmnd [B, T, tau_max]: optionally the normalised difference function."""
     B, T = pitch.shape
-    _lib.check(_lib.lib().glowtts_yin_f32(_lib.ptr(wav), _lib.ptr(wav_lengths), _lib.ptr(pitch), _lib.ptr(cmnd), B, wav.shape[1], T, int(w_len), int(w_step),
-                                          int(tau_min), int(tau_max), float(thresh), float(sample_rate), _lib.stream()), "glowtts_yin_f32")
+    _lib.api().glowtts_yin_f32(_lib.ptr(wav), _lib.ptr(wav_lengths), _lib.ptr(pitch), _lib.ptr(cmnd), B, wav.shape[1], T, int(w_len), int(w_step),
+                               int(tau_min), int(tau_max), float(thresh), float(sample_rate), _lib.stream())
 
 
 # ---- neural vocoder (csrc/pwg_ops.hip).  Rows are samples, channels-last; frame_lengths: int32 device tensor [B] ----
 def pwg_condition(mels, frame_lengths, w_in, firs, scales, work, c, ctx):
     """mels [B, A, Lmax] -> c [B, Lmax * hop, A] (glowtts_pwg_condition); scales: a ctypes int array on the host."""
     B, A, Lmax = mels.shape
-    _lib.check(_lib.lib().glowtts_pwg_condition(_lib.ptr(mels), _lib.ptr(frame_lengths), _lib.ptr(w_in), _lib.ptr(firs), scales, len(scales), _lib.ptr(work),
-                                                _lib.ptr(c), B, A, Lmax, int(ctx), _lib.stream()), "glowtts_pwg_condition")
+    _lib.api().glowtts_pwg_condition(_lib.ptr(mels), _lib.ptr(frame_lengths), _lib.ptr(w_in), _lib.ptr(firs), scales, len(scales), _lib.ptr(work),
+                                     _lib.ptr(c), B, A, Lmax, int(ctx), _lib.stream())
 
 
 def pwg_first(noises, seeds, frame_lengths, w, bias, x, Lmax, hop):
     """x [B, Lmax * hop, R] = first_conv(z); z: noises [B, Lmax * hop] or the in-kernel draw from seeds [B, 2] (glowtts_pwg_first)."""
-    _lib.check(_lib.lib().glowtts_pwg_first(_lib.ptr(noises), _lib.ptr(seeds), _lib.ptr(frame_lengths), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(x), x.shape[0],
-                                            int(Lmax), int(hop), x.shape[2], _lib.stream()), "glowtts_pwg_first")
+    _lib.api().glowtts_pwg_first(_lib.ptr(noises), _lib.ptr(seeds), _lib.ptr(frame_lengths), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(x), x.shape[0],
+                                 int(Lmax), int(hop), x.shape[2], _lib.stream())
 
 
 def pwg_layer(x, c, w1, b1, w2, b2, x_out, skips, frame_lengths, Lmax, hop, dilation, accumulate):
     """One WaveNet layer (glowtts_pwg_layer): x, x_out [B, Lmax * hop, R], c [.., A], skips [.., S]."""
-    _lib.check(_lib.lib().glowtts_pwg_layer(_lib.ptr(x), _lib.ptr(c), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(x_out), _lib.ptr(skips),
-                                            _lib.ptr(frame_lengths), x.shape[0], int(Lmax), int(hop), x.shape[2], skips.shape[2], c.shape[2], int(dilation),
-                                            int(bool(accumulate)), _lib.stream()), "glowtts_pwg_layer")
+    _lib.api().glowtts_pwg_layer(_lib.ptr(x), _lib.ptr(c), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(x_out), _lib.ptr(skips),
+                                 _lib.ptr(frame_lengths), x.shape[0], int(Lmax), int(hop), x.shape[2], skips.shape[2], c.shape[2], int(dilation),
+                                 int(bool(accumulate)), _lib.stream())
 
 
 def pwg_layer_bf16(x, c, w1p, b1, w2p, b2, x_out, skips, frame_lengths, Lmax, hop, dilation, accumulate):
@@ -188,12 +182,11 @@ def pwg_layer_bf16(x, c, w1p, b1, w2p, b2, x_out, skips, frame_lengths, Lmax, ho
     if w1p.dtype != torch.bfloat16 or w2p.dtype != torch.bfloat16 or tuple(w1p.shape) != ((3 * R + A + 31) // 32 * 4, 2 * R, 8) or \
             tuple(w2p.shape) != ((R + 31) // 32 * 4, R + S, 8):
         raise _lib.GlowTTSHipError("glowtts_pwg_layer_bf16 needs the packed bf16 weight images of vocoder.pwg_pack_bf16 for these sizes")
-    _lib.check(_lib.lib().glowtts_pwg_layer_bf16(_lib.ptr(x), _lib.ptr(c), _lib.ptr(w1p), _lib.ptr(b1), _lib.ptr(w2p), _lib.ptr(b2), _lib.ptr(x_out), _lib.ptr(skips),
-                                                 _lib.ptr(frame_lengths), x.shape[0], int(Lmax), int(hop), R, S, A, int(dilation), int(bool(accumulate)),
-                                                 _lib.stream()), "glowtts_pwg_layer_bf16")
+    _lib.api().glowtts_pwg_layer_bf16(_lib.ptr(x), _lib.ptr(c), _lib.ptr(w1p), _lib.ptr(b1), _lib.ptr(w2p), _lib.ptr(b2), _lib.ptr(x_out), _lib.ptr(skips),
+                                      _lib.ptr(frame_lengths), x.shape[0], int(Lmax), int(hop), R, S, A, int(dilation), int(bool(accumulate)), _lib.stream())
 
 
 def pwg_head(skips, frame_lengths, w1, b1, w2, b2, wav, Lmax, hop, scale):
     """skips [B, Lmax * hop, S] -> wav [B, Lmax * hop], zero beyond each utterance (glowtts_pwg_head)."""
-    _lib.check(_lib.lib().glowtts_pwg_head(_lib.ptr(skips), _lib.ptr(frame_lengths), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(wav),
-                                           skips.shape[0], int(Lmax), int(hop), skips.shape[2], float(scale), _lib.stream()), "glowtts_pwg_head")
+    _lib.api().glowtts_pwg_head(_lib.ptr(skips), _lib.ptr(frame_lengths), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(wav),
+                                skips.shape[0], int(Lmax), int(hop), skips.shape[2], float(scale), _lib.stream())

@@ -31,7 +31,7 @@ class _JobTable:
         capturing = torch.cuda.is_current_stream_capturing()
         if sig == self.sig and not capturing:
             return
-        chunk = _lib.lib().glowtts_opt_chunk()
+        chunk = _lib.api().glowtts_opt_chunk()
         order = range(len(items)) if canonical else sorted(range(len(items)), key=lambda i: sig[1 + i][0])
         jobs, cur = [], None
         for i in order:
@@ -66,10 +66,9 @@ def clip_grad_norm_(parameters, max_norm, _table_key=None):
     tab.update([(p.grad, p.grad, None, None) for p in params], dev, canonical=True)
     partial = torch.empty(tab.blocks, device=dev)
     out = torch.empty(2, device=dev)
-    L = _lib.lib()
-    _lib.check(L.glowtts_multi_grad_norm(tab.table.data_ptr(), tab.njobs, tab.blocks, float(max_norm), partial.data_ptr(), out.data_ptr(),
-                                         _lib.stream()), "glowtts_multi_grad_norm")
-    _lib.check(L.glowtts_multi_grad_scale(tab.table.data_ptr(), tab.njobs, tab.blocks, out.data_ptr() + 4, _lib.stream()), "glowtts_multi_grad_scale")
+    L = _lib.api()
+    L.glowtts_multi_grad_norm(tab.table.data_ptr(), tab.njobs, tab.blocks, float(max_norm), partial.data_ptr(), out.data_ptr(), _lib.stream())
+    L.glowtts_multi_grad_scale(tab.table.data_ptr(), tab.njobs, tab.blocks, out.data_ptr() + 4, _lib.stream())
     return out[0]
 
 
@@ -147,7 +146,7 @@ class RAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        L = _lib.lib()
+        L = _lib.api()
         for gi, group in enumerate(self.param_groups):
             plist = [p for p in group["params"] if p.grad is not None]
             if not plist:
@@ -168,8 +167,8 @@ class RAdam(torch.optim.Optimizer):
                 tab.update([(p, p.grad, self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"]) for p in ps], dev)
                 # captured: the words arrive by advance_host() before every replay; eager: sent now
                 hp = self._hyper[key] if (torch.cuda.is_current_stream_capturing() and key in self._hyper) else self._write_hyper(key, group, step, dev)
-                _lib.check(L.glowtts_radam_step(tab.table.data_ptr(), tab.njobs, tab.blocks, hp[1].data_ptr(),
-                                                grad_scale.data_ptr() if grad_scale is not None else None, _lib.stream()), "glowtts_radam_step")
+                L.glowtts_radam_step(tab.table.data_ptr(), tab.njobs, tab.blocks, hp[1].data_ptr(),
+                                     grad_scale.data_ptr() if grad_scale is not None else None, _lib.stream())
         return loss
 
 
@@ -183,8 +182,7 @@ def grad_norm_and_coef(parameters, max_norm, _table_key="fused"):
     tab = _CLIP_TABLES.setdefault((_table_key, id(params[0]), len(params)), _JobTable())
     tab.update([(p.grad, p.grad, None, None) for p in params], dev, canonical=True)
     partial, out = torch.empty(tab.blocks, device=dev), torch.empty(2, device=dev)
-    _lib.check(_lib.lib().glowtts_multi_grad_norm(tab.table.data_ptr(), tab.njobs, tab.blocks, float(max_norm), partial.data_ptr(), out.data_ptr(),
-                                            _lib.stream()), "glowtts_multi_grad_norm")
+    _lib.api().glowtts_multi_grad_norm(tab.table.data_ptr(), tab.njobs, tab.blocks, float(max_norm), partial.data_ptr(), out.data_ptr(), _lib.stream())
     return out[0], out[1:2]
 
 

@@ -18,24 +18,23 @@ class _GRUFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w_ih, w_hh, b_ih, b_hh):
-        L = _lib.lib()
+        L = _lib.api()
         B, T, _ = x.shape
         H = w_hh.shape[1]
         gi = torch.addmm(b_ih, x.reshape(B * T, -1), w_ih.t()).contiguous()
         hs, keep = torch.empty(B, T, H, device=x.device), torch.empty(B, T, 4 * H, device=x.device)
         w_hh_c, b_hh_c = w_hh.contiguous(), b_hh.contiguous()
-        _lib.check(L.glowtts_gru_fwd(_lib.ptr(gi), _lib.ptr(w_hh_c), _lib.ptr(b_hh_c), _lib.ptr(hs), _lib.ptr(keep), B, T, H, _lib.stream()), "glowtts_gru_fwd")
+        L.glowtts_gru_fwd(_lib.ptr(gi), _lib.ptr(w_hh_c), _lib.ptr(b_hh_c), _lib.ptr(hs), _lib.ptr(keep), B, T, H, _lib.stream())
         ctx.save_for_backward(x, w_ih, w_hh_c, hs, keep)
         return hs
 
     @staticmethod
     def backward(ctx, dhs):
         x, w_ih, w_hh, hs, keep = ctx.saved_tensors
-        L = _lib.lib()
+        L = _lib.api()
         B, T, H = hs.shape
         dgi, dgh = torch.empty(B, T, 3 * H, device=x.device), torch.empty(B, T, 3 * H, device=x.device)
-        _lib.check(L.glowtts_gru_bwd(_lib.ptr(dhs.contiguous()), _lib.ptr(hs), _lib.ptr(keep), _lib.ptr(w_hh), _lib.ptr(dgi), _lib.ptr(dgh), B, T, H,
-                                     _lib.stream()), "glowtts_gru_bwd")
+        L.glowtts_gru_bwd(_lib.ptr(dhs.contiguous()), _lib.ptr(hs), _lib.ptr(keep), _lib.ptr(w_hh), _lib.ptr(dgi), _lib.ptr(dgh), B, T, H, _lib.stream())
         dgi2, dgh2 = dgi.view(B * T, 3 * H), dgh.view(B * T, 3 * H)
         hprev = torch.cat([hs.new_zeros(B, 1, H), hs[:, :-1]], dim=1).reshape(B * T, H)
         dx = (dgi2 @ w_ih).view_as(x) if ctx.needs_input_grad[0] else None
@@ -47,14 +46,14 @@ class _ConvImages:
     buffer, plus the device job table of the ONE launch that rewrites them from the current weights (static while the parameters stay in place)."""
 
     def __init__(self, weights, precision, need_bwd):
-        L = _lib.lib()
+        L = _lib.api()
         self.key = (tuple(w.data_ptr() for w in weights), int(precision), bool(need_bwd))
         dev = weights[0].device
         sizes = []
         for w in weights:
             Co, Ci = int(w.shape[0]), int(w.shape[1])
             fwd, dg = ctypes.c_int64(0), (ctypes.c_int64 * 4)()
-            _lib.check(L.glowtts_conv3x3s2_image_bytes(Ci, Co, precision, ctypes.byref(fwd), dg), "glowtts_conv3x3s2_image_bytes")
+            L.glowtts_conv3x3s2_image_bytes(Ci, Co, precision, ctypes.byref(fwd), dg)
             sizes.append((int(fwd.value) if Ci > 1 else 0, [int(v) if (need_bwd and Ci > 1) else 0 for v in dg]))
         total = sum(f + sum(d) for f, d in sizes)
         self.buf = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
@@ -76,8 +75,7 @@ class _ConvImages:
                     off += d[cls]
             for cls, img in todo:
                 job, nb = _PackJob(), ctypes.c_int(0)
-                _lib.check(L.glowtts_conv3x3s2_pack_job_init(ctypes.byref(job), w.data_ptr(), Ci, Co, cls, precision, img, block, ctypes.byref(nb)),
-                           "glowtts_conv3x3s2_pack_job_init")
+                L.glowtts_conv3x3s2_pack_job_init(ctypes.byref(job), w.data_ptr(), Ci, Co, cls, precision, img, block, ctypes.byref(nb))
                 block += nb.value
                 jobs.append(job)
             self.fwd.append(fp)
@@ -91,7 +89,7 @@ class _ConvImages:
 
     def pack(self):
         if self.table is not None:
-            _lib.check(_lib.lib().glowtts_conv3x3s2_pack(self.table.data_ptr(), self.njobs, self.blocks, self.precision, _lib.stream()), "glowtts_conv3x3s2_pack")
+            _lib.api().glowtts_conv3x3s2_pack(self.table.data_ptr(), self.njobs, self.blocks, self.precision, _lib.stream())
 
 
 class _ConvStack(torch.autograd.Function):
@@ -102,7 +100,7 @@ class _ConvStack(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mels, images, precision, *weights):
-        L = _lib.lib()
+        L = _lib.api()
         x = mels.contiguous()                                  # [B][H = Mel][W = T] == channels-last with C = 1
         B, H, W = x.shape
         images.pack()
@@ -112,8 +110,7 @@ class _ConvStack(torch.autograd.Function):
             Co, Ci = int(w.shape[0]), int(w.shape[1])
             Ho, Wo = (H + 1) // 2, (W + 1) // 2
             y = torch.empty(B, Ho, Wo, Co, device=x.device)
-            _lib.check(L.glowtts_conv3x3s2_fwd(acts[-1].data_ptr(), w.data_ptr(), images.fwd[l], y.data_ptr(), B, H, W, Ci, Co, 1, precision, s),
-                       "glowtts_conv3x3s2_fwd")
+            L.glowtts_conv3x3s2_fwd(acts[-1].data_ptr(), w.data_ptr(), images.fwd[l], y.data_ptr(), B, H, W, Ci, Co, 1, precision, s)
             shapes.append((H, W, Ci, Co))
             acts.append(y)
             H, W = Ho, Wo
@@ -125,7 +122,7 @@ class _ConvStack(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        L = _lib.lib()
+        L = _lib.api()
         images, precision, shapes, B = ctx.cfg
         n = len(shapes)
         acts, weights = ctx.saved_tensors[:n + 1], ctx.saved_tensors[n + 1:]
@@ -135,8 +132,7 @@ class _ConvStack(torch.autograd.Function):
         # the last layer's ReLU (tiny: [B, 2, 13, 128] at the default sizes): d pre = d out where the output is not zero - one launch
         dout = dout.contiguous()
         dpre = torch.empty_like(dout)
-        _lib.check(L.glowtts_gate_bwd(_lib.ptr(dout), _lib.ptr(acts[n]), None, _lib.ptr(dpre), dout.numel() // dout.shape[-1], int(dout.shape[-1]), 1.0, s),
-                   "glowtts_gate_bwd")
+        L.glowtts_gate_bwd(_lib.ptr(dout), _lib.ptr(acts[n]), None, _lib.ptr(dpre), dout.numel() // dout.shape[-1], int(dout.shape[-1]), 1.0, s)
         jobs = (_ReduceJob * n)()
         keep, grads = [], [None] * n
         for l in range(n - 1, -1, -1):
@@ -144,8 +140,7 @@ class _ConvStack(torch.autograd.Function):
             x = acts[l]
             partial = torch.empty(int(L.glowtts_conv3x3s2_wgrad_scratch_floats(B, H, W, Ci, Co)), device=x.device)
             splits = ctypes.c_int(0)
-            _lib.check(L.glowtts_conv3x3s2_wgrad(x.data_ptr(), dpre.data_ptr(), partial.data_ptr(), B, H, W, Ci, Co, precision, ctypes.byref(splits), s),
-                       "glowtts_conv3x3s2_wgrad")
+            L.glowtts_conv3x3s2_wgrad(x.data_ptr(), dpre.data_ptr(), partial.data_ptr(), B, H, W, Ci, Co, precision, ctypes.byref(splits), s)
             dw = torch.empty_like(weights[l])
             jobs[l].partial, jobs[l].dw, jobs[l].splits, jobs[l].Ci, jobs[l].Co = partial.data_ptr(), dw.data_ptr(), splits.value, Ci, Co
             keep.append(partial)
@@ -153,10 +148,9 @@ class _ConvStack(torch.autograd.Function):
             if l > 0:
                 dx = torch.empty_like(x)
                 imgs = (ctypes.c_void_p * 4)(*images.dgrad[l])
-                _lib.check(L.glowtts_conv3x3s2_dgrad(dpre.data_ptr(), imgs, x.data_ptr(), dx.data_ptr(), B, H, W, Ci, Co, precision, s),
-                           "glowtts_conv3x3s2_dgrad")
+                L.glowtts_conv3x3s2_dgrad(dpre.data_ptr(), imgs, x.data_ptr(), dx.data_ptr(), B, H, W, Ci, Co, precision, s)
                 dpre = dx
-        _lib.check(L.glowtts_conv3x3s2_wgrad_reduce(jobs, n, s), "glowtts_conv3x3s2_wgrad_reduce")
+        L.glowtts_conv3x3s2_wgrad_reduce(jobs, n, s)
         from . import decoder
         decoder.stamp("pros_convs_bwd_end")
         return (None, None, None) + tuple(grads)
@@ -169,7 +163,7 @@ def conv_stack_supported(convs, mels):
         return False
     if not all(c.kernel_size == (3, 3) and c.stride == (2, 2) and c.padding == (1, 1) and c.bias is None and c.weight.dtype == torch.float32 for c in convs):
         return False
-    L = _lib.lib()
+    L = _lib.api()
     B, H, W = (int(v) for v in mels.shape)
     for c in convs:
         if not L.glowtts_conv3x3s2_supported(B, H, W, c.in_channels, c.out_channels):
@@ -201,7 +195,7 @@ class _GSTTail(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, hs, lengths, stride_prod, heads, tokens, Wq, bq, Wk, bk, Wv, bv, Wp, bp):
-        L = _lib.lib()
+        L = _lib.api()
         hs = hs.contiguous()
         B, Tp, G = hs.shape
         I, NT = tokens.shape
@@ -212,16 +206,16 @@ class _GSTTail(torch.autograd.Function):
         lengths = lengths.to(torch.int64).contiguous()
         K, V, out = torch.empty(C, NT, device=dev), torch.empty(C, NT, device=dev), torch.empty(B, C, device=dev)
         keep = torch.empty(int(L.glowtts_gst_keep_floats(B, G, C, heads, NT, I)), device=dev)
-        _lib.check(L.glowtts_gst_fwd(_lib.ptr(hs), _lib.ptr(lengths), int(stride_prod), _lib.ptr(tokens), _lib.ptr(Wq), _lib.ptr(bq), _lib.ptr(Wk), _lib.ptr(bk),
-                                     _lib.ptr(Wv), _lib.ptr(bv), _lib.ptr(Wp), _lib.ptr(bp), _lib.ptr(K), _lib.ptr(V), _lib.ptr(out), _lib.ptr(keep),
-                                     B, Tp, G, C, int(heads), NT, I, _lib.stream()), "glowtts_gst_fwd")
+        L.glowtts_gst_fwd(_lib.ptr(hs), _lib.ptr(lengths), int(stride_prod), _lib.ptr(tokens), _lib.ptr(Wq), _lib.ptr(bq), _lib.ptr(Wk), _lib.ptr(bk),
+                          _lib.ptr(Wv), _lib.ptr(bv), _lib.ptr(Wp), _lib.ptr(bp), _lib.ptr(K), _lib.ptr(V), _lib.ptr(out), _lib.ptr(keep),
+                          B, Tp, G, C, int(heads), NT, I, _lib.stream())
         ctx.save_for_backward(keep, lengths, tokens, Wq, Wk, Wv, Wp, K, V)
         ctx.cfg = (B, Tp, G, C, int(heads), NT, I, int(stride_prod), bq is not None, bk is not None, bv is not None, bp is not None)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        L = _lib.lib()
+        L = _lib.api()
         keep, lengths, tokens, Wq, Wk, Wv, Wp, K, V = ctx.saved_tensors
         B, Tp, G, C, H, NT, I, sp, hbq, hbk, hbv, hbp = ctx.cfg
         dev = dout.device
@@ -230,10 +224,9 @@ class _GSTTail(torch.autograd.Function):
         scratch = torch.empty(B * (2 * C + H * NT) + 2 * C * NT, device=dev)
         dWq, dWk, dWv, dWp, dtok = torch.empty_like(Wq), torch.empty_like(Wk), torch.empty_like(Wv), torch.empty_like(Wp), torch.empty_like(tokens)
         db = [torch.empty(C, device=dev) if has else None for has in (hbq, hbk, hbv, hbp)]
-        _lib.check(L.glowtts_gst_bwd(_lib.ptr(dout), _lib.ptr(keep), _lib.ptr(lengths), sp, _lib.ptr(tokens), _lib.ptr(Wq), _lib.ptr(Wk), _lib.ptr(Wv), _lib.ptr(Wp),
-                                     _lib.ptr(K), _lib.ptr(V), _lib.ptr(dhs), _lib.ptr(scratch), _lib.ptr(dWq), _lib.ptr(db[0]), _lib.ptr(dWk), _lib.ptr(db[1]),
-                                     _lib.ptr(dWv), _lib.ptr(db[2]), _lib.ptr(dWp), _lib.ptr(db[3]), _lib.ptr(dtok), B, Tp, G, C, H, NT, I, _lib.stream()),
-                   "glowtts_gst_bwd")
+        L.glowtts_gst_bwd(_lib.ptr(dout), _lib.ptr(keep), _lib.ptr(lengths), sp, _lib.ptr(tokens), _lib.ptr(Wq), _lib.ptr(Wk), _lib.ptr(Wv), _lib.ptr(Wp),
+                          _lib.ptr(K), _lib.ptr(V), _lib.ptr(dhs), _lib.ptr(scratch), _lib.ptr(dWq), _lib.ptr(db[0]), _lib.ptr(dWk), _lib.ptr(db[1]),
+                          _lib.ptr(dWv), _lib.ptr(db[2]), _lib.ptr(dWp), _lib.ptr(db[3]), _lib.ptr(dtok), B, Tp, G, C, H, NT, I, _lib.stream())
         return dhs, None, None, None, dtok, dWq, db[0], dWk, db[1], dWv, db[2], dWp, db[3]
 
 
@@ -329,7 +322,7 @@ class Prosody_Encoder(torch.nn.Module):
         att = self.layer_Dict["Attention"]
         q_, k_, v_, p_ = (att.layer_Dict[n] for n in ("Query", "Key", "Value", "Projection"))
         if (self.use_hip_gst and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and
-                _lib.lib().glowtts_gst_supported(x.size(0), x.size(1), x.size(2), q_.weight.shape[0], att.heads, self.gst_Tokens.shape[1], self.gst_Tokens.shape[0])):
+                _lib.api().glowtts_gst_supported(x.size(0), x.size(1), x.size(2), q_.weight.shape[0], att.heads, self.gst_Tokens.shape[1], self.gst_Tokens.shape[0])):
             sq = lambda w: w.squeeze(-1)                       # Conv1d(k = 1) weights [O, I, 1]
             return _GSTTail.apply(x, lengths, int(math.prod(self.strides)), att.heads, self.gst_Tokens, sq(q_.weight), q_.bias, sq(k_.weight), k_.bias,
                                   sq(v_.weight), v_.bias, sq(p_.weight), p_.bias)

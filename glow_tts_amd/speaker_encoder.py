@@ -158,21 +158,19 @@ class GE2E(torch.nn.Module):
         sig = tuple((p.data_ptr(), p._version) for layer in params for p in layer)
         if sig == self._packed_sig:
             return
-        s, L = self.sizes, _lib.lib()
+        s, L = self.sizes, _lib.api()
         dev = params[0][0].device
         if self._images is None or self._images.device != dev:
             self._images = torch.empty(L.glowtts_ge2e_image_floats(s["Mel"], s["H"], s["Stacks"]), dtype=torch.float32, device=dev)
             self._biases = torch.empty(s["Stacks"], 4 * s["H"], dtype=torch.float32, device=dev)
         for k, layer in enumerate(params):
-            _lib.check(L.glowtts_ge2e_pack(*[_lib.ptr(p) for p in layer], _lib.ptr(self._images), _lib.ptr(self._biases), k, s["Mel"], s["H"], s["Stacks"],
-                                           _lib.stream()), "glowtts_ge2e_pack")
+            L.glowtts_ge2e_pack(*[_lib.ptr(p) for p in layer], _lib.ptr(self._images), _lib.ptr(self._biases), k, s["Mel"], s["H"], s["Stacks"], _lib.stream())
         if self.trainable:                                                  # the backward's transposed images: re-packed exactly when the forward's are
             if self._images_t is None or self._images_t.device != dev:
                 self._images_t = torch.empty(L.glowtts_ge2e_train_image_floats(s["H"], s["Stacks"]), dtype=torch.float32, device=dev)
             for k, layer in enumerate(params):
                 above = _lib.ptr(params[k + 1][0]) if k + 1 < s["Stacks"] else None
-                _lib.check(L.glowtts_ge2e_train_pack(_lib.ptr(layer[1]), above, _lib.ptr(self._images_t), k, s["H"], s["Stacks"], _lib.stream()),
-                           "glowtts_ge2e_train_pack")
+                L.glowtts_ge2e_train_pack(_lib.ptr(layer[1]), above, _lib.ptr(self._images_t), k, s["H"], s["Stacks"], _lib.stream())
         self._packed_sig = sig
 
     def invalidate_images(self):
@@ -198,7 +196,7 @@ class GE2E(torch.nn.Module):
     @torch.no_grad()
     def forward_all(self, stack, samples=None, hidden=False, raw=False):
         """stack [N = B * samples, Mel, T] fp32 on the device -> (hs [Stacks, N, T, H] or None, e [N, E] or None, d [B, E])"""
-        s, L = self.sizes, _lib.lib()
+        s, L = self.sizes, _lib.api()
         samples = self.samples if samples is None else int(samples)
         if stack.dim() != 3 or stack.shape[1] != s["Mel"] or stack.shape[0] < 1 or stack.shape[2] < 1 or stack.shape[0] % samples:
             raise ValueError("GE2E: expected a slice stack [B * {}, {}, Slice], got {}".format(samples, s["Mel"], list(stack.shape)))
@@ -212,9 +210,8 @@ class GE2E(torch.nn.Module):
         e = torch.empty(N, s["E"], dtype=torch.float32, device=dev) if raw else None
         d = torch.empty(N // samples, s["E"], dtype=torch.float32, device=dev)
         work = torch.empty(s["Stacks"] * N * s["H"] * (1 if hidden else T + 1), dtype=torch.float32, device=dev)
-        _lib.check(L.glowtts_ge2e_forward(_lib.ptr(x), _lib.ptr(self._images), _lib.ptr(self._biases), _lib.ptr(self.linear.weight), _lib.ptr(self.linear.bias),
-                                          _lib.ptr(work), _lib.ptr(hs), _lib.ptr(e), _lib.ptr(d), N, samples, s["Mel"], T, s["H"], s["Stacks"], s["E"], _lib.stream()),
-                   "glowtts_ge2e_forward")
+        L.glowtts_ge2e_forward(_lib.ptr(x), _lib.ptr(self._images), _lib.ptr(self._biases), _lib.ptr(self.linear.weight), _lib.ptr(self.linear.bias),
+                               _lib.ptr(work), _lib.ptr(hs), _lib.ptr(e), _lib.ptr(d), N, samples, s["Mel"], T, s["H"], s["Stacks"], s["E"], _lib.stream())
         return hs, e, d
 
     def forward(self, stack, samples=None):
@@ -223,33 +220,32 @@ class GE2E(torch.nn.Module):
 
 def train_forward(enc, x):
     """-> (keep, e): `glowtts_ge2e_train_forward` of a trainable encoder on x [N, Mel, T] (contiguous)"""
-    s, L = enc.sizes, _lib.lib()
+    s, L = enc.sizes, _lib.api()
     enc._pack()
     N, _, T = x.shape
     keep = torch.empty(L.glowtts_ge2e_train_keep_floats(N, T, s["H"], s["Stacks"]), dtype=torch.float32, device=x.device)
     e = torch.empty(N, s["E"], dtype=torch.float32, device=x.device)
-    _lib.check(L.glowtts_ge2e_train_forward(_lib.ptr(x), _lib.ptr(enc._images), _lib.ptr(enc._biases), _lib.ptr(enc.linear.weight), _lib.ptr(enc.linear.bias),
-                                            _lib.ptr(keep), _lib.ptr(e), N, s["Mel"], T, s["H"], s["Stacks"], s["E"], _lib.stream()), "glowtts_ge2e_train_forward")
+    L.glowtts_ge2e_train_forward(_lib.ptr(x), _lib.ptr(enc._images), _lib.ptr(enc._biases), _lib.ptr(enc.linear.weight), _lib.ptr(enc.linear.bias),
+                                 _lib.ptr(keep), _lib.ptr(e), N, s["Mel"], T, s["H"], s["Stacks"], s["E"], _lib.stream())
     return keep, e
 
 
 def train_backward(enc, x, keep, de, da=None):
     """-> {parameter name: gradient} (and da [Stacks, N, T, 4 H] is filled when given): `glowtts_ge2e_train_backward`, then `glowtts_ge2e_train_wgrad`
     per layer.  The images are those of the forward (`_pack` ran there)."""
-    s, L = enc.sizes, _lib.lib()
+    s, L = enc.sizes, _lib.api()
     N, _, T = x.shape
     dev = x.device
     if da is None:
         da = torch.empty(s["Stacks"], N, T, 4 * s["H"], dtype=torch.float32, device=dev)
     work = torch.empty(L.glowtts_ge2e_train_work_floats(N, T, s["Mel"], s["H"], s["Stacks"]), dtype=torch.float32, device=dev)
     grads = {name: torch.empty(shape, dtype=torch.float32, device=dev) for name, shape in ge2e_shapes(s).items()}
-    _lib.check(L.glowtts_ge2e_train_backward(_lib.ptr(enc._images_t), _lib.ptr(keep), _lib.ptr(enc.linear.weight), _lib.ptr(de), _lib.ptr(da), _lib.ptr(work),
-                                             _lib.ptr(grads["linear.weight"]), _lib.ptr(grads["linear.bias"]), N, T, s["H"], s["Stacks"], s["E"], _lib.stream()),
-               "glowtts_ge2e_train_backward")
+    L.glowtts_ge2e_train_backward(_lib.ptr(enc._images_t), _lib.ptr(keep), _lib.ptr(enc.linear.weight), _lib.ptr(de), _lib.ptr(da), _lib.ptr(work),
+                                  _lib.ptr(grads["linear.weight"]), _lib.ptr(grads["linear.bias"]), N, T, s["H"], s["Stacks"], s["E"], _lib.stream())
     for k in range(s["Stacks"]):
         g = [grads["lstm.{}_l{}".format(n, k)] for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
-        _lib.check(L.glowtts_ge2e_train_wgrad(_lib.ptr(x), _lib.ptr(keep), _lib.ptr(da), _lib.ptr(work), *[_lib.ptr(t) for t in g], k, N, s["Mel"], T, s["H"],
-                                              s["Stacks"], _lib.stream()), "glowtts_ge2e_train_wgrad")
+        L.glowtts_ge2e_train_wgrad(_lib.ptr(x), _lib.ptr(keep), _lib.ptr(da), _lib.ptr(work), *[_lib.ptr(t) for t in g], k, N, s["Mel"], T, s["H"],
+                                   s["Stacks"], _lib.stream())
     return grads
 
 
@@ -273,13 +269,12 @@ class _Embed(torch.autograd.Function):
 
 def ge2e_loss_launch(e, w, S, M):
     """-> (loss [1], de [N, E], dw [1]) of `glowtts_ge2e_train_loss` for e [S M, E] (row j M + i: speaker j's utterance i) and the device scalar w"""
-    L = _lib.lib()
+    L = _lib.api()
     N, E = e.shape
     dev = e.device
     work = torch.empty(L.glowtts_ge2e_train_loss_work_floats(N, S, E), dtype=torch.float32, device=dev)
     loss, dw, de = torch.empty(1, dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.float32, device=dev), torch.empty_like(e)
-    _lib.check(L.glowtts_ge2e_train_loss(_lib.ptr(e), _lib.ptr(w), _lib.ptr(work), _lib.ptr(loss), _lib.ptr(de), _lib.ptr(dw), S, M, E, _lib.stream()),
-               "glowtts_ge2e_train_loss")
+    L.glowtts_ge2e_train_loss(_lib.ptr(e), _lib.ptr(w), _lib.ptr(work), _lib.ptr(loss), _lib.ptr(de), _lib.ptr(dw), S, M, E, _lib.stream())
     return loss, de, dw
 
 

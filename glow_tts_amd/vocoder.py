@@ -387,7 +387,7 @@ def pwg_condition_stages(voc, mels, lengths, c):
 
 def pwg_condition_backward(voc, mels, lengths, stages, dc, work, grads):
     """d c [B, L * hop, A] -> the FIRs' and conv_in's gradients into `grads` (torch's layouts): `pwg_upsample_bwd` per scale, last to first, then `pwg_cond_in_bwd`."""
-    g, lib, P, st = voc.geo, _lib.lib(), _lib.ptr, _lib.stream()
+    g, lib, P, st = voc.geo, _lib.api(), _lib.ptr, _lib.stream()
     B, A, L = mels.shape
     dcur, mult, off = dc, g["hop"], sum(2 * s + 1 for s in g["scales"])
     for k in reversed(range(len(g["scales"]))):
@@ -395,12 +395,10 @@ def pwg_condition_backward(voc, mels, lengths, stages, dc, work, grads):
         mult //= s
         off -= 2 * s + 1
         din = torch.empty(B, L * mult, A, dtype=torch.float32, device=mels.device)
-        _lib.check(lib.glowtts_pwg_train_upsample_bwd(P(dcur), P(stages[k]), P(voc.firs[off:]), P(lengths), P(work), P(din),
-                                                      P(grads[f"upsample_net.upsample.up_layers.{2 * k + 1}.weight"]), B, A, L, mult, s, st),
-                   "glowtts_pwg_train_upsample_bwd")
+        lib.glowtts_pwg_train_upsample_bwd(P(dcur), P(stages[k]), P(voc.firs[off:]), P(lengths), P(work), P(din),
+                                           P(grads[f"upsample_net.upsample.up_layers.{2 * k + 1}.weight"]), B, A, L, mult, s, st)
         dcur = din
-    _lib.check(lib.glowtts_pwg_train_cond_in_bwd(P(mels), P(dcur), P(lengths), P(grads["upsample_net.conv_in.weight"]), B, A, L, g["ctx"], st),
-               "glowtts_pwg_train_cond_in_bwd")
+    lib.glowtts_pwg_train_cond_in_bwd(P(mels), P(dcur), P(lengths), P(grads["upsample_net.conv_in.weight"]), B, A, L, g["ctx"], st)
 
 
 def pwg_train_forward(voc, mels, lengths, seeds, noises):
@@ -422,7 +420,7 @@ def pwg_train_forward(voc, mels, lengths, seeds, noises):
 
 def pwg_train_backward(voc, mels, lengths, seeds, noises, fwd, dwav):
     """-> {name: gradient in torch's layout} for every name of `pwg_expected_shapes`, from what `pwg_train_forward` kept and d wav [B, T]."""
-    g, lib = voc.geo, _lib.lib()
+    g, lib = voc.geo, _lib.api()
     B, A, L = mels.shape
     hop, R, G, S = g["hop"], g["R"], g["G"], g["S"]
     T, dev, P, st = L * hop, mels.device, _lib.ptr, _lib.stream()
@@ -433,25 +431,23 @@ def pwg_train_backward(voc, mels, lengths, seeds, noises, fwd, dwav):
     dwav = dwav.to(torch.float32).contiguous()
     y, h, dh, dskips = f(B, T, S), f(B, T, S), f(B, T, S), f(B, T, S)
     w1, b1, w2, b2 = voc.head
-    _lib.check(lib.glowtts_pwg_train_head_bwd(P(skips), P(lengths), P(w1), P(voc.head_w1t), P(b1), P(w2), P(dwav), P(y), P(h), P(dh), P(dskips), B, L, hop, S,
-                                              math.sqrt(1.0 / g["layers"]), st), "glowtts_pwg_train_head_bwd")
-    _lib.check(lib.glowtts_pwg_train_head_wgrad(P(y), P(h), P(dh), P(dwav), P(lengths), P(work), P(grads["last_conv_layers.1.weight"]),
-                                                P(grads["last_conv_layers.1.bias"]), P(grads["last_conv_layers.3.weight"]), P(grads["last_conv_layers.3.bias"]),
-                                                B, L, hop, S, st), "glowtts_pwg_train_head_wgrad")
+    lib.glowtts_pwg_train_head_bwd(P(skips), P(lengths), P(w1), P(voc.head_w1t), P(b1), P(w2), P(dwav), P(y), P(h), P(dh), P(dskips), B, L, hop, S,
+                                   math.sqrt(1.0 / g["layers"]), st)
+    lib.glowtts_pwg_train_head_wgrad(P(y), P(h), P(dh), P(dwav), P(lengths), P(work), P(grads["last_conv_layers.1.weight"]),
+                                     P(grads["last_conv_layers.1.bias"]), P(grads["last_conv_layers.3.weight"]), P(grads["last_conv_layers.3.bias"]), B, L, hop, S, st)
     del y, h, dh
     gate, dpre, dc = f(B, T, R), f(B, T, G), f(B, T, A)
     dxp, dx = torch.zeros(B, T, R, dtype=torch.float32, device=dev), f(B, T, R)        # nothing reads the last layer's x': its gradient is zero
     for i in reversed(range(g["layers"])):
         (lw1, lb1, _, _), (w2t, w1t, wauxt), d, q = voc.layer_weights[i], voc.layer_weights_t[i], g["dilations"][i], f"conv_layers.{i}."
-        _lib.check(lib.glowtts_pwg_train_layer_bwd(P(keep[i]), P(c), P(lw1), P(lb1), P(w2t), P(w1t), P(wauxt), P(dxp), P(dskips), P(gate), P(dpre), P(dx), P(dc),
-                                                   P(lengths), B, L, hop, R, S, A, d, int(i == g["layers"] - 1), st), "glowtts_pwg_train_layer_bwd")
-        _lib.check(lib.glowtts_pwg_train_layer_wgrad(P(keep[i]), P(c), P(gate), P(dpre), P(dxp), P(dskips), P(lengths), P(work), P(grads[q + "conv.weight"]),
-                                                     P(grads[q + "conv.bias"]), P(grads[q + "conv1x1_aux.weight"]), P(grads[q + "conv1x1_out.weight"]),
-                                                     P(grads[q + "conv1x1_out.bias"]), P(grads[q + "conv1x1_skip.weight"]), P(grads[q + "conv1x1_skip.bias"]),
-                                                     B, L, hop, R, S, A, d, st), "glowtts_pwg_train_layer_wgrad")
+        lib.glowtts_pwg_train_layer_bwd(P(keep[i]), P(c), P(lw1), P(lb1), P(w2t), P(w1t), P(wauxt), P(dxp), P(dskips), P(gate), P(dpre), P(dx), P(dc),
+                                        P(lengths), B, L, hop, R, S, A, d, int(i == g["layers"] - 1), st)
+        lib.glowtts_pwg_train_layer_wgrad(P(keep[i]), P(c), P(gate), P(dpre), P(dxp), P(dskips), P(lengths), P(work), P(grads[q + "conv.weight"]),
+                                          P(grads[q + "conv.bias"]), P(grads[q + "conv1x1_aux.weight"]), P(grads[q + "conv1x1_out.weight"]),
+                                          P(grads[q + "conv1x1_out.bias"]), P(grads[q + "conv1x1_skip.weight"]), P(grads[q + "conv1x1_skip.bias"]),
+                                          B, L, hop, R, S, A, d, st)
         dxp, dx = dx, dxp
-    _lib.check(lib.glowtts_pwg_train_first_bwd(P(noises), P(seeds), P(dxp), P(lengths), P(work), P(grads["first_conv.weight"]), P(grads["first_conv.bias"]),
-                                               B, L, hop, R, st), "glowtts_pwg_train_first_bwd")
+    lib.glowtts_pwg_train_first_bwd(P(noises), P(seeds), P(dxp), P(lengths), P(work), P(grads["first_conv.weight"]), P(grads["first_conv.bias"]), B, L, hop, R, st)
     pwg_condition_backward(voc, mels, lengths, fwd["stages"], dc, work, grads)
     grads["dx0"] = dxp
     return grads
@@ -507,7 +503,7 @@ class ParallelWaveGAN:
                 raise ValueError("Vocoder.Checkpoint_Path is not set: the neural vocoder needs a Parallel WaveGAN generator checkpoint")
             state_dict = torch.load(path, map_location="cpu")
         w = pwg_load(state_dict, geo)
-        supported = _lib.lib().glowtts_pwg_supported_bf16 if self.precision == "bf16" else _lib.lib().glowtts_pwg_supported
+        supported = _lib.api().glowtts_pwg_supported_bf16 if self.precision == "bf16" else _lib.api().glowtts_pwg_supported
         if not supported(geo["R"], geo["G"], geo["S"], geo["A"], max(geo["dilations"])):
             raise ValueError(f"the Vocoder block's sizes {geo} are not supported by the kernels")
         self._layer_op = ops.pwg_layer_bf16 if self.precision == "bf16" else ops.pwg_layer
@@ -690,26 +686,25 @@ def stft_loss_forward(loss_fn, pred, target):
     """The forward launches of every resolution -> (loss [1], terms [n, 3] = (L_sc, L_mag, the backward's coefficient) per resolution, keeps): the entry
     points' own outputs, for `_STFTLoss` and the tests."""
     B, T = pred.shape
-    L, dev, n = _lib.lib(), pred.device, len(loss_fn.resolutions)
+    L, dev, n = _lib.api(), pred.device, len(loss_fn.resolutions)
     loss, terms, keeps = torch.empty(1, dtype=torch.float32, device=dev), torch.empty(n, 3, dtype=torch.float32, device=dev), []
     for i, ((n_fft, hop, win), (window, twiddle)) in enumerate(zip(loss_fn.resolutions, loss_fn.tables)):
         keep = torch.empty(L.glowtts_stft_loss_keep_floats(B, T, n_fft, hop), dtype=torch.float32, device=dev)
         work = loss_fn._work(L.glowtts_stft_loss_work_floats(B, T, win, hop))
-        _lib.check(L.glowtts_stft_loss_forward(_lib.ptr(pred), _lib.ptr(target), _lib.ptr(window), _lib.ptr(twiddle), _lib.ptr(keep), _lib.ptr(work),
-                                               _lib.ptr(terms[i]), _lib.ptr(loss), B, T, n_fft, win, hop, 1.0 / n, int(i > 0), _lib.stream()),
-                   "glowtts_stft_loss_forward")
+        L.glowtts_stft_loss_forward(_lib.ptr(pred), _lib.ptr(target), _lib.ptr(window), _lib.ptr(twiddle), _lib.ptr(keep), _lib.ptr(work),
+                                    _lib.ptr(terms[i]), _lib.ptr(loss), B, T, n_fft, win, hop, 1.0 / n, int(i > 0), _lib.stream())
         keeps.append(keep)
     return loss, terms, keeps
 
 
 def stft_loss_backward(loss_fn, keeps, terms, grad_out, B, T):
     """The backward launches of every resolution -> d pred [B, T] = grad_out * dL/dpred (grad_out: one device float)."""
-    L, dev, n = _lib.lib(), terms.device, len(loss_fn.resolutions)
+    L, dev, n = _lib.api(), terms.device, len(loss_fn.resolutions)
     dpred = torch.empty(B, T, dtype=torch.float32, device=dev)
     for i, ((n_fft, hop, win), (window, twiddle)) in enumerate(zip(loss_fn.resolutions, loss_fn.tables)):
         work = loss_fn._work(L.glowtts_stft_loss_work_floats(B, T, win, hop))
-        _lib.check(L.glowtts_stft_loss_backward(_lib.ptr(keeps[i]), _lib.ptr(terms[i]), _lib.ptr(grad_out), _lib.ptr(window), _lib.ptr(twiddle), _lib.ptr(work),
-                                                _lib.ptr(dpred), B, T, n_fft, win, hop, 1.0 / n, int(i > 0), _lib.stream()), "glowtts_stft_loss_backward")
+        L.glowtts_stft_loss_backward(_lib.ptr(keeps[i]), _lib.ptr(terms[i]), _lib.ptr(grad_out), _lib.ptr(window), _lib.ptr(twiddle), _lib.ptr(work),
+                                     _lib.ptr(dpred), B, T, n_fft, win, hop, 1.0 / n, int(i > 0), _lib.stream())
     return dpred
 
 
@@ -845,23 +840,23 @@ def pwg_disc_load(obj, geo):
 def pwg_disc_forward(disc, wav, alloc=None):
     """The forward launches on wav [B, T] (fp32, contiguous, on the device) -> dict(wav, scores [B, T], keep: the Layers - 1 hidden outputs [B, T, C] - C floats
     per row and layer, all the backward needs: the output of a LeakyReLU carries its mask).  alloc(*shape): the caller's buffers (tests)."""
-    g, lib, P, st = disc.geo, _lib.lib(), _lib.ptr, _lib.stream()
+    g, lib, P, st = disc.geo, _lib.api(), _lib.ptr, _lib.stream()
     B, T = wav.shape
     C, slope = g["C"], g["slope"]
     f = alloc or (lambda *shape: torch.empty(*shape, dtype=torch.float32, device=wav.device))
     keep, scores = [f(B, T, C) for _ in range(g["layers"] - 1)], f(B, T)
-    _lib.check(lib.glowtts_pwg_disc_first(P(wav), P(disc.first[0]), P(disc.first[1]), P(keep[0]), B, T, C, slope, st), "glowtts_pwg_disc_first")
+    lib.glowtts_pwg_disc_first(P(wav), P(disc.first[0]), P(disc.first[1]), P(keep[0]), B, T, C, slope, st)
     for i in range(1, g["layers"] - 1):
         w, b, _ = disc.middle[i - 1]
-        _lib.check(lib.glowtts_pwg_disc_layer(P(keep[i - 1]), P(w), P(b), P(keep[i]), B, T, C, g["dilations"][i], slope, st), "glowtts_pwg_disc_layer")
-    _lib.check(lib.glowtts_pwg_disc_last(P(keep[-1]), P(disc.last[0]), P(disc.last[1]), P(scores), B, T, C, st), "glowtts_pwg_disc_last")
+        lib.glowtts_pwg_disc_layer(P(keep[i - 1]), P(w), P(b), P(keep[i]), B, T, C, g["dilations"][i], slope, st)
+    lib.glowtts_pwg_disc_last(P(keep[-1]), P(disc.last[0]), P(disc.last[1]), P(scores), B, T, C, st)
     return {"wav": wav, "scores": scores, "keep": keep}
 
 
 def pwg_disc_backward(disc, fwd, dscores, freeze=False, alloc=None):
     """d scores [B, T] -> (d wav [B, T], {name: gradient in torch's layout} or None when `freeze`) from what `pwg_disc_forward` kept (or the views of some of
     its batch rows).  freeze: the data chain alone - no dpre is written and no weight-gradient launch is made."""
-    g, lib, P, st = disc.geo, _lib.lib(), _lib.ptr, _lib.stream()
+    g, lib, P, st = disc.geo, _lib.api(), _lib.ptr, _lib.stream()
     wav, keep = fwd["wav"], fwd["keep"]
     B, T = wav.shape
     C, slope, n, dev = g["C"], g["slope"], g["layers"], wav.device
@@ -873,20 +868,19 @@ def pwg_disc_backward(disc, fwd, dscores, freeze=False, alloc=None):
         work, lengths, dpre = f(lib.glowtts_pwg_disc_work_floats(B, T, C)), torch.full((B,), T, dtype=torch.int32, device=dev), f(B, T, C)
 
     def wgrad(i, a, d_out, cin, cout):
-        _lib.check(lib.glowtts_pwg_disc_wgrad(P(a), P(d_out), P(lengths), P(work), P(grads[f"conv_layers.{i}.weight"]), P(grads[f"conv_layers.{i}.bias"]), B, T, cin,
-                                              cout, g["dilations"][i], st), "glowtts_pwg_disc_wgrad")
+        lib.glowtts_pwg_disc_wgrad(P(a), P(d_out), P(lengths), P(work), P(grads[f"conv_layers.{i}.weight"]), P(grads[f"conv_layers.{i}.bias"]), B, T, cin,
+                                   cout, g["dilations"][i], st)
     dout, dx = f(B, T, C), f(B, T, C)
-    _lib.check(lib.glowtts_pwg_disc_last_bwd(P(dscores), P(disc.last[0]), P(dout), B, T, C, st), "glowtts_pwg_disc_last_bwd")
+    lib.glowtts_pwg_disc_last_bwd(P(dscores), P(disc.last[0]), P(dout), B, T, C, st)
     if not freeze:
         wgrad(n - 1, keep[-1], dscores, C, 1)
     for i in reversed(range(1, n - 1)):
-        _lib.check(lib.glowtts_pwg_disc_layer_bwd(P(dout), P(keep[i]), P(disc.middle[i - 1][2]), P(dx), P(dpre), B, T, C, g["dilations"][i], slope, st),
-                   "glowtts_pwg_disc_layer_bwd")
+        lib.glowtts_pwg_disc_layer_bwd(P(dout), P(keep[i]), P(disc.middle[i - 1][2]), P(dx), P(dpre), B, T, C, g["dilations"][i], slope, st)
         if not freeze:
             wgrad(i, keep[i - 1], dpre, C, C)
         dout, dx = dx, dout
     dwav = f(B, T)
-    _lib.check(lib.glowtts_pwg_disc_first_bwd(P(dout), P(keep[0]), P(disc.first[0]), P(dwav), P(dpre), B, T, C, slope, st), "glowtts_pwg_disc_first_bwd")
+    lib.glowtts_pwg_disc_first_bwd(P(dout), P(keep[0]), P(disc.first[0]), P(dwav), P(dpre), B, T, C, slope, st)
     if not freeze:
         wgrad(0, wav, dpre, 1, C)
     return dwav, grads
@@ -922,7 +916,7 @@ class PWGDiscriminator:
         self.geo = geo = pwg_disc_geometry(hp)                      # before anything touches the device
         self.trainable = bool(trainable)
         w = pwg_disc_load(state_dict, geo) if state_dict is not None else pwg_disc_init(geo, seed)
-        if not _lib.lib().glowtts_pwg_disc_supported(geo["C"], geo["layers"], max(geo["dilations"])):
+        if not _lib.api().glowtts_pwg_disc_supported(geo["C"], geo["layers"], max(geo["dilations"])):
             raise ValueError(f"the {DISC_KEY} block's sizes {geo} are not supported by the kernels")
         self.device = torch.device(device)
         self.params = {k: t.to(self.device).requires_grad_(self.trainable) for k, t in w.items()}
@@ -942,7 +936,7 @@ class PWGDiscriminator:
         if wav.dim() != 2 or wav.dtype != torch.float32 or not wav.is_cuda:
             raise _lib.GlowTTSHipError(f"PWGDiscriminator: expected an fp32 device tensor [B, T] (the HIP path has no CPU fallback), got {list(wav.shape)} {wav.dtype}")
         B, T = wav.shape
-        if B < 1 or T < 1 or not _lib.lib().glowtts_pwg_disc_work_floats(B, T, self.geo["C"]):
+        if B < 1 or T < 1 or not _lib.api().glowtts_pwg_disc_work_floats(B, T, self.geo["C"]):
             raise ValueError(f"PWGDiscriminator: a batch of {B} x {T} samples is outside 1 <= B, 1 <= T, B T < 2^31, B ceil(T / 1024) <= 65535")
 
     def score(self, wav, freeze=False):
@@ -967,10 +961,10 @@ class PWGDiscriminator:
 class _AdversarialMSE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scores, split, v0, v1, factor):
-        lib, P, N = _lib.lib(), _lib.ptr, scores.numel()
+        lib, P, N = _lib.api(), _lib.ptr, scores.numel()
         dp, loss = torch.empty_like(scores), torch.empty(3, dtype=torch.float32, device=scores.device)
         work = torch.empty(4 * (-(-N // 4096)), dtype=torch.float32, device=scores.device)
-        _lib.check(lib.glowtts_pwg_disc_mse(P(scores), P(dp), P(work), P(loss), N, split, v0, v1, factor, _lib.stream()), "glowtts_pwg_disc_mse")
+        lib.glowtts_pwg_disc_mse(P(scores), P(dp), P(work), P(loss), N, split, v0, v1, factor, _lib.stream())
         ctx.dp = dp
         terms = loss[1:].clone()
         ctx.mark_non_differentiable(terms)

@@ -370,3 +370,45 @@ def test_loaded_library_is_bound_as_tabulated():
         assert fn.restype is restype and list(fn.argtypes) == argtypes, n
     with pytest.raises(_lib.GlowTTSHipError, match="glowtts_not_there"):
         _lib._symbol(L, "glowtts_not_there")
+
+
+# ---------------------------------------------------------------------------------------------------------------- the checked handle, _lib.api()
+def test_value_returning_set_is_consistent_with_the_table():
+    from glow_tts_amd import abi
+    assert abi.VALUE_RETURNING <= set(abi.SIGNATURES)
+    for n in abi.VALUE_RETURNING:
+        assert abi.SIGNATURES[n][0] is ctypes.c_int, n
+    assert {n for n in abi.SIGNATURES if "_supported" in n} <= abi.VALUE_RETURNING
+    assert {"glowtts_abi_version", "glowtts_opt_chunk"} <= abi.VALUE_RETURNING
+
+
+def test_checked_handle_is_bound_as_tabulated_and_checks_exactly_the_statuses():
+    from glow_tts_amd import _lib, abi
+    L, A = _lib.lib(), _lib.api()
+    assert A is _lib.api() and L is _lib.lib()
+    assert set(vars(A)) == set(abi.SIGNATURES)
+    for n, (restype, argtypes) in abi.SIGNATURES.items():
+        raw, fn = getattr(L, n), getattr(A, n)
+        assert fn is not raw, n
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, n
+        assert (fn.errcheck is not None) == (restype is ctypes.c_int and n not in abi.VALUE_RETURNING), n
+        assert raw.errcheck is None, n
+
+
+def test_checked_handle_raises_on_a_status_and_passes_values_through():
+    from glow_tts_amd import _lib, abi
+    row = (None,) * 9 + (1, 4, 256, 64, 64, 80, 1, 0, None)                  # every pointer NULL: refused before anything is launched (no device is touched)
+    with pytest.raises(_lib.GlowTTSHipError, match=r"glowtts_pwg_layer_bf16 failed with code -1"):
+        _lib.api().glowtts_pwg_layer_bf16(*row)
+    assert _lib.lib().glowtts_pwg_layer_bf16(*row) == abi.E_ARG
+    assert _lib.api().glowtts_pwg_supported(64, 128, 64, 80, 1) == 1
+    assert _lib.api().glowtts_pwg_supported(60, 120, 64, 80, 1) == 0
+
+
+def test_no_call_site_checks_a_status_by_hand():
+    for top in ("glow_tts_amd", "tools"):
+        for root, _, files in os.walk(os.path.join(REPO, top)):
+            for f in files:
+                path = os.path.join(root, f)
+                if f.endswith(".py") and os.path.relpath(path, REPO) != os.path.join("glow_tts_amd", "_lib.py"):
+                    assert "_lib.check(" not in open(path).read(), f"{os.path.relpath(path, REPO)} checks a status by hand: call through _lib.api()"

@@ -36,15 +36,15 @@ def launched(prefix):
     import ctypes
     from glow_tts_amd import _lib
     buf = ctypes.create_string_buffer(1 << 17)
-    _lib.lib().glowtts_launch_log_dump(buf, len(buf))
+    _lib.api().glowtts_launch_log_dump(buf, len(buf))
     rows = [ln.rsplit(" ", 1) for ln in buf.value.decode().splitlines()]
     return [name for name, n in rows if name.startswith(prefix) and int(n) > 0]
 
 
 def attention_rows(args):
     from glow_tts_amd import _lib
-    from glow_tts_amd.conv_fn import _L
-    L = _L()
+    from glow_tts_amd.conv_fn import _A
+    L = _A()
     H, D, win = 2, 96, 4
     rows = []
     for B in (1, 32):
@@ -58,12 +58,11 @@ def attention_rows(args):
             P = torch.empty(B, H, Tp, Tp, device="cuda") if Tp <= 256 else None
             for prec in (0, 1):
                 # both entries called directly on preallocated outputs: the same host cost per call, so a host-bound small shape skews neither
-                fns = {"eval": lambda: _lib.check(L.glowtts_rpr_attention_fwd_eval(qkv.data_ptr(), relk.data_ptr(), relv.data_ptr(), rowmask.data_ptr(),
-                                                                                     oute.data_ptr(), B, Tp, H, D, win, prec, _lib.stream()), "fwd_eval")}
+                fns = {"eval": lambda: L.glowtts_rpr_attention_fwd_eval(qkv.data_ptr(), relk.data_ptr(), relv.data_ptr(), rowmask.data_ptr(),
+                                                                          oute.data_ptr(), B, Tp, H, D, win, prec, _lib.stream())}
                 if P is not None:
-                    fns["train"] = lambda: _lib.check(L.glowtts_rpr_attention_fwd_prec(qkv.data_ptr(), relk.data_ptr(), relv.data_ptr(), rowmask.data_ptr(),
-                                                                                         out.data_ptr(), P.data_ptr(), B, Tp, H, D, win, 0.0, 0, None, prec,
-                                                                                         _lib.stream()), "fwd_prec")
+                    fns["train"] = lambda: L.glowtts_rpr_attention_fwd_prec(qkv.data_ptr(), relk.data_ptr(), relv.data_ptr(), rowmask.data_ptr(),
+                                                                              out.data_ptr(), P.data_ptr(), B, Tp, H, D, win, 0.0, 0, None, prec, _lib.stream())
                 for fn in fns.values():
                     for _ in range(args.warmup):
                         fn()

@@ -3,7 +3,7 @@ import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from glow_tts_amd import conv_fn as CF, ops, _lib
-L = CF._L()
+L = CF._A()
 R, C, drop_p = 3840, 192, 0.1
 att, x = torch.randn(R, C, device="cuda"), torch.randn(R, C, device="cuda")
 w, b = torch.randn(C, C, 1, device="cuda") * 0.1, torch.randn(C, device="cuda") * 0.1
@@ -14,12 +14,12 @@ proj, y, yb, s, st = (torch.empty(R, C, device="cuda"), torch.empty(R, C, device
                       torch.empty(R, C, device="cuda"), torch.empty(R, 2, device="cuda"))
 def two():
     CF._conv_launch(att, pw, C, R, 1, ops.F_BIAS | ops.F_DROPOUT, C, b, rowmask, proj, drop_p=drop_p, seed=7, seed_t=seed_t, a_bf=False)
-    _lib.check(L.glowtts_layernorm_fwd_io(proj.data_ptr(), x.data_ptr(), s.data_ptr(), gamma.data_ptr(), beta.data_ptr(), rowmask.data_ptr(), y.data_ptr(),
-                                          st.data_ptr(), R, C, 1e-4, 0, 0.0, 0, None, yb.data_ptr(), _lib.stream()), "ln")
+    L.glowtts_layernorm_fwd_io(proj.data_ptr(), x.data_ptr(), s.data_ptr(), gamma.data_ptr(), beta.data_ptr(), rowmask.data_ptr(), y.data_ptr(),
+                               st.data_ptr(), R, C, 1e-4, 0, 0.0, 0, None, yb.data_ptr(), _lib.stream())
 def one():
-    _lib.check(L.glowtts_proj_layernorm(att.data_ptr(), C, pw.data.data_ptr(), pw.npad, b.data_ptr(), x.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                        rowmask.data_ptr(), proj.data_ptr(), s.data_ptr(), st.data_ptr(), y.data_ptr(), yb.data_ptr(),
-                                        R, C, 1e-4, drop_p, 7, seed_t.data_ptr(), _lib.stream()), "proj_ln")
+    L.glowtts_proj_layernorm(att.data_ptr(), C, pw.data.data_ptr(), pw.npad, b.data_ptr(), x.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                             rowmask.data_ptr(), proj.data_ptr(), s.data_ptr(), st.data_ptr(), y.data_ptr(), yb.data_ptr(),
+                             R, C, 1e-4, drop_p, 7, seed_t.data_ptr(), _lib.stream())
 def t(f, n=50):
     for _ in range(5): f()
     torch.cuda.synchronize()

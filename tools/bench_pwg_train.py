@@ -95,7 +95,7 @@ def main():
     hip_ms, base_ms = statistics.median(th), statistics.median(tb)
 
     # the layer launches of a step alone, on the buffers of one forward
-    lib, P, st = V._lib.lib(), V._lib.ptr, V._lib.stream()
+    lib, P, st = V._lib.api(), V._lib.ptr, V._lib.stream()
     R, G, S, A, hop, L = geo["R"], geo["G"], geo["S"], geo["A"], geo["hop"], FRAMES
     voc._build_images({k: p.detach() for k, p in voc.params.items()})
     fwd = V.pwg_train_forward(voc, mels, lengths, None, z)

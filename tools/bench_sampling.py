@@ -29,7 +29,7 @@ def launch_log():
     import ctypes
     from glow_tts_amd import _lib
     buf = ctypes.create_string_buffer(1 << 17)
-    _lib.lib().glowtts_launch_log_dump(buf, len(buf))
+    _lib.api().glowtts_launch_log_dump(buf, len(buf))
     rows = [ln.rsplit(" ", 1) for ln in buf.value.decode().splitlines()]
     return {name: int(n) for name, n in rows if int(n) > 0}
 
@@ -117,7 +117,7 @@ def rows_for(precision, B, args):
         se = lambda: model._seeded_sample(mean, log_std, dur, mel_lengths, BUCKET, sc_t, sd_t)
         logs = {}
         for name, fn in (("unseeded", un), ("seeded", se)):
-            _lib.lib().glowtts_launch_log_reset()
+            _lib.api().glowtts_launch_log_reset()
             fn()
             torch.cuda.synchronize()
             logs[name] = launch_log()

@@ -5,7 +5,7 @@ sys.path.insert(0, "/root/repo")
 from glow_tts_amd import decoder as D, ops, _lib
 
 R, M, CA, TAPS, NJ = 12928, 384, 192, 5, 36
-L = D._L()
+L = D._A()
 io = ops.WIO_DY_BF16 | ops.WIO_X_BF16
 dys = [(torch.randn(R, M, device="cuda") * 0.5).to(torch.bfloat16) for _ in range(NJ)]
 xs = [torch.randn(R, CA, device="cuda").to(torch.bfloat16) for _ in range(NJ)]
@@ -26,7 +26,7 @@ def run(g, n=20):
     start, nj, tiles = g.segments[0]
     flags = g.io_flags | ops.WIO_WIDE | (ops.WIO_DMA if g._dma else 0)
     def once():
-        _lib.check(L.glowtts_wgrad_grouped_io(g.table.data_ptr(), nj, tiles, R, TAPS, 2, ops.APRO_NONE, ops.BF16, 1, 0, flags, _lib.stream()), "wgrad")
+        L.glowtts_wgrad_grouped_io(g.table.data_ptr(), nj, tiles, R, TAPS, 2, ops.APRO_NONE, ops.BF16, 1, 0, flags, _lib.stream())
     for _ in range(3):
         once()
     torch.cuda.synchronize()
@@ -66,7 +66,7 @@ def group1(dma):
 def run1(g, n=20):
     start, nj, tiles = g.segments[0]
     flags = g.io_flags | ops.WIO_WIDE | (ops.WIO_DMA if g._dma else 0)
-    once = lambda: _lib.check(L.glowtts_wgrad_grouped_io(g.table.data_ptr(), nj, tiles, R, 1, 0, ops.APRO_NONE, ops.BF16, 1, 0, flags, _lib.stream()), "wgrad")
+    once = lambda: L.glowtts_wgrad_grouped_io(g.table.data_ptr(), nj, tiles, R, 1, 0, ops.APRO_NONE, ops.BF16, 1, 0, flags, _lib.stream())
     for _ in range(3):
         once()
     torch.cuda.synchronize()

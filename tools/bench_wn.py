@@ -20,7 +20,7 @@ W = dict(zip(D.WEIGHT_KEYS, [w.contiguous() for w in D.stack_decoder_weights(P, 
 mels = torch.randn(B, 80, TM, generator=g).cuda()
 ml = torch.full((B,), TM).cuda()
 seed = torch.tensor([7], device="cuda", dtype=torch.int32)
-L = D._L()
+L = D._A()
 res = {}
 for fused in (True, False):
     D.TUNE["fused_wn"] = fused
@@ -34,7 +34,7 @@ for fused in (True, False):
         if os.environ.get("GLOWTTS_WN_ABL") in ("16", "32", "96", "160", "288") and fused:
             acts.skip_bf = tl.data_ptr()
         dims = D._dims(dc, B, T, DROP, seed if DROP > 0 else None, 0)
-        run = lambda: _lib.check(L.glowtts_flow_forward(ctypes.byref(dims), ctypes.byref(prep.params[0]), ctypes.byref(acts), _lib.stream()), "flow_forward")
+        run = lambda: L.glowtts_flow_forward(ctypes.byref(dims), ctypes.byref(prep.params[0]), ctypes.byref(acts), _lib.stream())
         for _ in range(3):
             run()
         torch.cuda.synchronize()
@@ -72,7 +72,7 @@ for fused in (True, False):
         for l in range(dc.L):
             gb.dh[l] = dh0.data_ptr() if l == 0 else dhn[l].data_ptr()
             gb.dins[l] = dins[l].data_ptr()
-        runb = lambda: _lib.check(L.glowtts_flow_backward(ctypes.byref(dims), ctypes.byref(prepb.params[0]), ctypes.byref(acts), ctypes.byref(gb), _lib.stream()), "flow_backward")
+        runb = lambda: L.glowtts_flow_backward(ctypes.byref(dims), ctypes.byref(prepb.params[0]), ctypes.byref(acts), ctypes.byref(gb), _lib.stream())
         for _ in range(3):
             runb()
         torch.cuda.synchronize()

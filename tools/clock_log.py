@@ -13,7 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from glow_tts_amd import _lib
 
-L = _lib.lib()
+L = _lib.api()
 ncu = torch.cuda.get_device_properties(0).multi_processor_count
 out = torch.zeros(ncu, 2, dtype=torch.int64, device="cuda")
 khz = ctypes.c_int(0)
@@ -40,7 +40,7 @@ t_start = time.time()
 rows = []
 for i in range(10):
     t0 = time.time()
-    _lib.check(L.glowtts_mfma_clock_probe(out.data_ptr(), ncu, ITERS, ctypes.byref(khz), _lib.stream()), "probe")
+    L.glowtts_mfma_clock_probe(out.data_ptr(), ncu, ITERS, ctypes.byref(khz), _lib.stream())
     torch.cuda.synchronize()
     t1 = time.time()
     o = out.double()

@@ -3,7 +3,7 @@ import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from glow_tts_amd import _lib
-L = _lib.lib()
+L = _lib.api()
 x = torch.ones(1 << 20, device="cuda")
 for n_elem in (64, 1 << 20):
     s = torch.cuda.Stream()

@@ -19,11 +19,11 @@ for _ in range(iters):
     torch.mul(x, 1.5, out=y)                         # reads 1 GiB, writes 1 GiB
 if os.environ.get("PMC_PROBE"):                      # calibration of the MFMA-busy pass: a loop of back-to-back bf16 MFMAs, one wave per SIMD on every CU
     from glow_tts_amd import _lib
-    L = _lib.lib()
+    L = _lib.api()
     ncu = torch.cuda.get_device_properties(0).multi_processor_count
     out = torch.zeros(ncu, 2, dtype=torch.int64, device="cuda")
     for _ in range(iters):
-        _lib.check(L.glowtts_mfma_clock_probe(out.data_ptr(), ncu, 20000, None, _lib.stream()), "probe")
+        L.glowtts_mfma_clock_probe(out.data_ptr(), ncu, 20000, None, _lib.stream())
 torch.cuda.synchronize()
 print("ran", list(cases), "x", iters)
 if os.environ.get("PMC_WN_BWD"):                    # + one flow's fused data-gradient launch (wn_bwd_kernel) at the same shape: tools/bench_wn.py's set-up

@@ -8,10 +8,10 @@ dev = torch.device("cuda:0")
 model, mle, hp = bench.build_model("bf16", dev)
 batch = bench.synthetic_batch(32, 120, 800, 80, 1234, dev)
 for _ in range(3):
-    bench.train_step(model, mle, batch)
+    bench.train_step(model, mle, batch, (None, None))
 torch.cuda.synchronize()
 with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA], record_shapes=True, with_stack=False) as prof:
-    bench.train_step(model, mle, batch)
+    bench.train_step(model, mle, batch, (None, None))
     torch.cuda.synchronize()
 rows = []
 for e in prof.key_averages(group_by_input_shape=True):

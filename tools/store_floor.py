@@ -4,7 +4,7 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from glow_tts_amd import _lib
-L = _lib.lib()
+L = _lib.api()
 for mb in (1, 4, 12, 48, 192):
     n = mb * (1 << 20) // 4
     for nbuf in (1, 50):
