@@ -26,6 +26,7 @@ C2D_MAX_LAYERS = 8
 SAMPLE_SCAN_CHUNK = 1024
 SAMPLE_TILE = 64
 GE2E_MAX_MEL, GE2E_MAX_H, GE2E_MAX_STACKS, GE2E_MAX_E = 512, 768, 8, 1024
+DTW_MAX_FRAMES, DTW_MAX_K = 4096, 64
 
 # ---- struct mirrors: `c_name` is the C struct whose layout the class restates ------------------------------------------------------------
 I, L, F, U, P = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_uint32, ctypes.c_void_p
@@ -307,6 +308,11 @@ SIGNATURES = {
     "glowtts_pwg_disc_layer_bwd": (I, [P] * 5 + [I] * 4 + [F, P]),
     "glowtts_pwg_disc_first_bwd": (I, [P] * 5 + [I] * 3 + [F, P]),
     "glowtts_pwg_disc_wgrad": (I, [P] * 6 + [I] * 5 + [P]),
+    "glowtts_mel_cepstrum_supported": (I, [I] * 2),
+    "glowtts_mel_cepstrum": (I, [P] * 4 + [I] * 4 + [L] * 3 + [F, P]),
+    "glowtts_dtw_supported": (I, [I] * 3),
+    "glowtts_dtw_work_bytes": (L, [I] * 2),
+    "glowtts_dtw": (I, [P] * 10 + [I] * 4 + [P]),
 }
 
 # ---- the entry points above whose `int` result is a VALUE (a version, a chunk size, a yes / no), not a GLOWTTS_OK / _E_ARG / _E_LAUNCH status: `_lib.api()`
@@ -315,5 +321,5 @@ VALUE_RETURNING = frozenset({
     "glowtts_abi_version", "glowtts_opt_chunk",
     "glowtts_cond_linear_supported", "glowtts_gst_supported", "glowtts_conv3x3s2_supported", "glowtts_dur_proj_supported", "glowtts_vocoder_supported",
     "glowtts_pwg_supported", "glowtts_pwg_supported_bf16", "glowtts_ge2e_supported", "glowtts_pwg_train_supported", "glowtts_stft_loss_supported",
-    "glowtts_pwg_disc_supported",
+    "glowtts_pwg_disc_supported", "glowtts_mel_cepstrum_supported", "glowtts_dtw_supported",
 })

@@ -1081,6 +1081,32 @@ int glowtts_pwg_disc_first_bwd(const float *dout, const float *out, const float 
 int glowtts_pwg_disc_wgrad(const float *a, const float *dpre, const int32_t *lengths, float *work, float *dw, float *db, int B, int T, int Cin, int Cout,
                            int dilation, void *stream);
 
+/* ---- Objective evaluation: mel cepstra and dynamic time warping (csrc/eval_ops.hip; f32; additions, the ABI version stays) ----
+ * glowtts_mel_cepstrum   `eval_mel_cepstrum`: mels in this project's normalisation m = 2A (db + 100) / 100 - A (A = max_abs; values at the clip +- A taken
+ *   as they are), read through the element strides (stride_b, stride_t, stride_m) - [B][T][Mel] or the models' [B][Mel][T] - with lengths [B] int64 (device)
+ *   -> cep [B][T][K] f32.  L = ln(amplitude) = (ln 10 / 20) ((m + A) 100 / (2A) - 100); c_k = sqrt(2 / Mel) sum_m L_m cos(pi k (m + 1/2) / Mel), k = 1 .. K:
+ *   the orthonormal DCT-II without its 0th coefficient, so a constant offset of the mel drops out.  basis [K][Mel] f32 (device) holds
+ *   sqrt(2 / Mel) cos(pi (k + 1) (m + 1/2) / Mel) for row k = 0 .. K - 1; the sum runs over m ascending, one fused multiply-add per term.  Rows t >= lengths[b]
+ *   are zeros.  Supported (glowtts_mel_cepstrum_supported, else GLOWTTS_E_ARG): 1 <= K <= 64, K < Mel <= 512, Mel K <= 4096; 1 <= B <= 65535, B T <= 2^30.
+ * glowtts_dtw            `eval_dtw`: B pairs X_b [x_lengths[b]][K], Y_b [y_lengths[b]][K] of the padded batches x [B][tx_max][K], y [B][ty_max][K] (lengths
+ *   int32, device, each in [1, its max]).  Local cost d(i, j) = sqrt(sum_k (x_ik - y_jk)^2) in f32, k ascending, one fused multiply-add per term, correctly
+ *   rounded square root.  D(0, 0) = d(0, 0); the first row and column accumulate along themselves; else D(i, j) = d(i, j) + min(D(i-1, j-1), D(i-1, j),
+ *   D(i, j-1)), the predecessor being the diagonal if it is <= both others, else (i-1, j) if it is <= (i, j-1), else (i, j-1).  No band or slope constraint.
+ *   Backtrack from (Tx-1, Ty-1).  Outputs per pair: cost [B] = D(Tx-1, Ty-1); steps [B] = N; ix, iy [B][tx_max + ty_max - 1] int32 = the path in forward
+ *   order, -1 beyond N; moves [B][3] int32 = the number of diagonal, (i-1, j) and (i, j-1) steps.  A pair whose length is out of range gets cost NaN,
+ *   steps 0 and no path.  work: B * glowtts_dtw_work_bytes(tx_max, ty_max) bytes (2-bit back-pointers); nothing is allocated.  One workgroup per pair, no
+ *   atomics: a pair's result is bit-identical alone, in any batch, at any padding and from run to run.
+ *   Supported (glowtts_dtw_supported, else GLOWTTS_E_ARG): tx_max, ty_max in [1, GLOWTTS_DTW_MAX_FRAMES], k in [1, GLOWTTS_DTW_MAX_K]; 1 <= B <= 65535. */
+#define GLOWTTS_DTW_MAX_FRAMES 4096
+#define GLOWTTS_DTW_MAX_K 64
+int glowtts_mel_cepstrum_supported(int Mel, int K);
+int glowtts_mel_cepstrum(const float *mel, const int64_t *lengths, const float *basis, float *cep, int B, int T, int Mel, int K, int64_t stride_b,
+                         int64_t stride_t, int64_t stride_m, float max_abs, void *stream);
+int glowtts_dtw_supported(int tx_max, int ty_max, int k);
+int64_t glowtts_dtw_work_bytes(int tx_max, int ty_max);
+int glowtts_dtw(const float *x, const int32_t *x_lengths, const float *y, const int32_t *y_lengths, void *work, float *cost, int32_t *steps, int32_t *ix,
+                int32_t *iy, int32_t *moves, int B, int tx_max, int ty_max, int K, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
