@@ -263,6 +263,7 @@ SIGNATURES = {
     "glowtts_mel_analysis_f32": (I, [P] * 7 + [I] * 8 + [F] * 3 + [P]),
     "glowtts_yin_f32": (I, [P] * 4 + [I] * 7 + [F, F, P]),
     "glowtts_prior_sample": (I, [P] * 9 + [I] * 4 + [P]),
+    "glowtts_prior_sample_aligned": (I, [P] * 10 + [I] * 4 + [P]),
     "glowtts_pwg_supported": (I, [I] * 5),
     "glowtts_pwg_condition": (I, [P] * 5 + [I] + [P] * 2 + [I] * 4 + [P]),
     "glowtts_pwg_first": (I, [P] * 6 + [I] * 4 + [P]),

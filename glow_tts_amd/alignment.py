@@ -163,6 +163,46 @@ def prior_sample(mean, log_std, dur, mel_lengths, seeds, noise_scales, Tmax, wan
 
 
 @torch.no_grad()
+def aligned_sample(mean, log_std, idx, z_rec, seeds, noise_scales, want_z=True):
+    """The teacher-forced counterpart of `prior_sample` (csrc/sample_ops.hip, glowtts_prior_sample_aligned): the index is GIVEN - MAS's, [B, Tmax] i32, -1
+    past an utterance - instead of built from durations.  mean / log_std [B, C, Tx], z_rec [B, C, Tmax] (the recording's latent) or None, seeds / noise_scales
+    as in `prior_sample` -> (z [B, C, Tmax] or None: the seeded sample of the prior along idx, the bits `prior_sample` writes for the same idx;
+    dur [B, Tx] i32: the frames of every token; score [B] or None (z_rec None): the mean log-prior density per element along the alignment - what MAS
+    maximised, not a likelihood).  One launch, a second small one for the score; an utterance's results do not depend on the batch around it or on Tmax."""
+    mean, log_std, idx = mean.contiguous(), log_std.contiguous(), idx.contiguous()
+    B, C, Tx = mean.shape
+    dev = mean.device
+    if idx.dim() != 2 or idx.shape[0] != B or idx.dtype != torch.int32 or tuple(log_std.shape) != (B, C, Tx) or mean.dtype != torch.float32 or \
+            log_std.dtype != torch.float32:
+        raise ValueError("aligned_sample: mean / log_std [B, C, Tx] f32, idx [B, Tmax] i32")
+    Tmax = idx.shape[1]
+    if z_rec is not None:
+        z_rec = z_rec.contiguous()
+        if tuple(z_rec.shape) != (B, C, Tmax) or z_rec.dtype != torch.float32:
+            raise ValueError("aligned_sample: z_rec [B, C, Tmax] f32 (the frame axis of idx)")
+    z = None
+    if want_z:
+        if seeds is None:
+            raise ValueError("aligned_sample: z is sampled from `seeds` [B, 2] (want_z=False asks for the durations and the score alone)")
+        if not torch.is_tensor(seeds) or seeds.dtype != torch.int32 or seeds.device != dev or tuple(seeds.shape) != (B, 2):
+            seeds = seed_words(seeds, B, dev)
+        if not torch.is_tensor(noise_scales) or tuple(noise_scales.shape) != (B,) or noise_scales.dtype != torch.float32:
+            raise ValueError("aligned_sample: noise_scales [B] f32")
+        seeds, noise_scales = seeds.contiguous(), noise_scales.contiguous()
+        z = torch.empty(B, C, Tmax, device=dev)
+    else:
+        seeds = noise_scales = None
+    dur = torch.empty(B, Tx, dtype=torch.int32, device=dev)
+    score = partials = None
+    if z_rec is not None:
+        from . import abi
+        score, partials = torch.empty(B, device=dev), torch.empty(B, (Tmax + abi.SAMPLE_TILE - 1) // abi.SAMPLE_TILE, device=dev)
+    _lib.api().glowtts_prior_sample_aligned(_lib.ptr(mean), _lib.ptr(log_std), _lib.ptr(idx), _lib.ptr(z_rec), _lib.ptr(seeds), _lib.ptr(noise_scales),
+                                            _lib.ptr(z), _lib.ptr(dur), _lib.ptr(score), _lib.ptr(partials), B, C, Tx, Tmax, _lib.stream())
+    return z, dur, score
+
+
+@torch.no_grad()
 def duration_targets(idx, token_lengths, Tx):
     """log(sum_t attentions + 1e-7) * token_mask (Modules.py:122) -> [B,1,Tx]."""
     B, Ty = idx.shape

@@ -270,6 +270,73 @@ class Inferencer:
                                              sample_index=k if samples > 1 else None, vocoder_seeds=vseeds)
         return files
 
+    @torch.no_grad()
+    def Align(self, texts, mels_or_wavs, speakers=None, speaker_references=None, pitches=None, labels=None, seed=None, noise_scale=1.0, reconstruct=False):
+        """Teacher-forced pass (`GlowTTS.teacher_forced`) over recordings and their texts: the monotonic alignment of every recording to its text and,
+        `reconstruct`, the model's own mel for it, frame-aligned with the recording (a ground-truth-aligned mel).  texts: strings (filtered and tokenised
+        as `Inference` does) or ready token id arrays (<S> and <E> included); mels_or_wavs: one per text, the formats of `_reference` (mel array or .npy
+        [T, Mel], wav file, (mel, pitch) pair); pitches: GR mode, one track per recording where the recording itself does not give one.  speakers /
+        speaker_references as in `Inference` (PE / GR: the prosody vector is the recording's own).  Batches of Inference_Batch_Size, sorted by mel length;
+        results in input order: one dict per utterance with label, tokens [Tt] i32, durations [Tt] i32 (frames per token, <S> and <E> included; they sum
+        to `frames`), frames (the mel length cut to whole squeeze groups), score (the mean log-prior density per element along the alignment - what
+        the alignment search maximised, not a likelihood) and mel ([frames, Mel] f32, or None).  seed: the noise of the reconstruction comes from
+        `utterance_seed_words(seed, label, 0)`; without a seed noise_scale must be 0 (the prior's mean) - there is no unseeded draw.  GE2E mode: the random
+        offset of the speaker references' slices comes from `utterance_seed_words(seed, label)` as in `Inference` and, without a seed, from the run seed 0 -
+        never from `np.random` - so every result is a function of the inputs, the labels and the seed."""
+        hp, dev = self.hp, self.device
+        model = self.model_Dict["GlowTTS"]
+        n = len(texts)
+        if len(mels_or_wavs) != n:
+            raise ValueError("`mels_or_wavs` gives one recording per text")
+        labels = [str(x) for x in labels] if labels is not None else [str(i) for i in range(n)]
+        if self.ge2e_mode and (speaker_references is None or len(speaker_references) != n or any(r is None for r in speaker_references)):
+            raise ValueError("Speaker_Embedding.Type 'GE2E': `speaker_references` must give every utterance a wav, a mel or a d-vector")
+        if reconstruct and seed is None and float(noise_scale) != 0.0:
+            raise ValueError("a reconstruction draws its noise from `seed` only: without `seed`, `noise_scale` must be 0 (the prior's mean)")
+        toks = []
+        for t in texts:
+            if isinstance(t, str):
+                f = data.text_filtering(t)
+                if f is None:
+                    raise ValueError("text {!r} holds symbols outside the training alphabet".format(t))
+                t = data.text_to_token(f, self.token_Dict)
+            toks.append(np.asarray(t, np.int64))
+        mp = [self._reference(r) for r in mels_or_wavs]
+        if pitches is not None:
+            mp = [(m, p if q is None else np.asarray(q, np.float32)) for (m, p), q in zip(mp, pitches)]
+        gr = "Pitch_Interpolater" in model.layer_Dict
+        if gr and any(p is None for _, p in mp):
+            raise ValueError("GR mode: every recording needs its pitch track (a wav, a (mel, pitch) pair or `pitches`)")
+        lut = "LUT" in model.layer_Dict
+        if lut and (speakers is None or any(s is None for s in speakers)):
+            raise ValueError("Speaker_Embedding.Type 'LUT': `speakers` must give every utterance its speaker index")
+        bs = hp.Inference_Batch_Size or hp.Train.Batch_Size
+        order = sorted(range(n), key=lambda i: (mp[i][0].shape[0], i))
+        out = [None] * n
+        for s in range(0, n, bs):
+            part = order[s:s + bs]
+            tl = torch.tensor([len(toks[i]) for i in part], dtype=torch.int64)
+            tokens = torch.full((len(part), int(tl.max())), self.token_Dict["<E>"], dtype=torch.int64)
+            for b, i in enumerate(part):
+                tokens[b, :len(toks[i])] = torch.from_numpy(toks[i])
+            mels, ml, pit = self._pad_mels([mp[i] if gr else (mp[i][0], None) for i in part])
+            ge2es = None
+            if self.ge2e_mode:
+                # (no unseeded draw here either: without a seed the slices' offset comes from the label under the run seed 0, never from `np.random`)
+                rngs = [np.random.RandomState(utterance_seed_words(0 if seed is None else seed, labels[i])[0]) for i in part]
+                ge2es = torch.from_numpy(self.D_Vectors([speaker_references[i] for i in part], rngs)).to(dev)
+            spk = torch.tensor([int(speakers[i]) for i in part], dtype=torch.int64, device=dev) if lut else None
+            seeds = None if (seed is None or not reconstruct) else torch.tensor([utterance_seed_words(seed, labels[i], 0) for i in part], dtype=torch.int64)
+            r = model.teacher_forced(tokens.to(dev), tl.to(dev), mels.to(dev), ml.to(dev), speakers=spk, mels_for_ge2e=ge2es,
+                                     pitches=None if pit is None else pit.to(dev), noise_scale=float(noise_scale) if seeds is not None else 0.0, seeds=seeds,
+                                     reconstruct=reconstruct)
+            dur, score, frames = r.durations.cpu().numpy(), r.score.cpu().numpy(), r.mel_lengths.cpu().tolist()
+            rec = r.mels.cpu().numpy() if reconstruct else None
+            for b, i in enumerate(part):
+                out[i] = {"label": labels[i], "tokens": toks[i].astype(np.int32), "durations": dur[b, :len(toks[i])].copy(), "frames": int(frames[b]),
+                          "score": float(score[b]), "mel": np.ascontiguousarray(rec[b, :, :frames[b]].T) if reconstruct else None}
+        return out
+
     def Vocode(self, labels, mels, inference_path="./inference"):
         """Recorded or previously generated mels - .npy paths or arrays [T, Mel] - through the active vocoder, in batches of Inference_Batch_Size:
         one WAV/<label>.wav per mel; returns the written files (also in `last_wav_files`)."""

@@ -4,6 +4,7 @@ parameters from ./Hyper_Parameters.yaml), call signatures, return tuples, attrib
 (Modules.py:16-229, 1020-1029), so checkpoints and yaml files drop in unchanged.  All arithmetic runs in the
 HIP library (glow_tts_amd/csrc) or, for the parts still marked interim in DESIGN.md, in PyTorch-ROCm device ops.
 """
+import collections
 import math
 
 import os
@@ -11,6 +12,9 @@ import torch
 
 from . import alignment, decoder, encoder, ops
 from .hparams import get_hp
+
+
+TeacherForced = collections.namedtuple("TeacherForced", "durations idx score z mels mel_lengths")      # what `GlowTTS.teacher_forced` returns
 
 
 class _Dict(torch.nn.Module):
@@ -494,19 +498,21 @@ class GlowTTS(torch.nn.Module):
 
     def _seeded_sample(self, mean, log_std, dur, mel_lengths, max_mel_length, noise_scale, seeds):
         """Modules.py:175-191 as ONE launch (durations -> hard alignment -> dense attentions, expanded prior, sample) with counter-hash noise."""
-        B = mean.shape[0]
         Tmax = int(max_mel_length) if max_mel_length is not None else int(torch.max(mel_lengths))
+        z, _, attn = alignment.prior_sample(mean, log_std, dur, mel_lengths, seeds, self._noise_scales(noise_scale, mean.shape[0], mean.device), Tmax)
+        return z, attn
+
+    @staticmethod
+    def _noise_scales(noise_scale, B, device):
+        """a float, a 0-d / one-element tensor or a [B] tensor -> the [B] f32 device buffer the sampling kernels read"""
         if torch.is_tensor(noise_scale):
-            scales = noise_scale.to(device=mean.device, dtype=torch.float32).reshape(-1)
+            scales = noise_scale.to(device=device, dtype=torch.float32).reshape(-1)
             if scales.numel() == 1:
                 scales = scales.expand(B)
             elif scales.numel() != B:
                 raise ValueError(f"`noise_scale` must be a scalar or a [B] tensor (B = {B}), got {tuple(noise_scale.shape)}")
-            scales = scales.contiguous()
-        else:
-            scales = torch.full((B,), float(noise_scale), device=mean.device)
-        z, _, attn = alignment.prior_sample(mean, log_std, dur, mel_lengths, seeds, scales, Tmax)
-        return z, attn
+            return scales.contiguous()
+        return torch.full((B,), float(noise_scale), device=device)
 
     def _inverse_flow(self, sample, mel_lengths, spk, pro, prep, pitches, pitch_lengths):
         """Modules.py:193-204 on the sampled z: -> (mels, mel_lengths, attentions)"""
@@ -554,6 +560,38 @@ class GlowTTS(torch.nn.Module):
         spk, pro = self._conditioning(P, speakers, mels_for_ge2e, mels, mel_lengths)
         cond = stacks.conditioning(spk, pro)
         return decoder.decoder_convert(self.dec_cfg, prep, mels.contiguous(), mel_lengths, cond, None, None, pitch, encode_only=True)
+
+    @torch.no_grad()
+    def teacher_forced(self, tokens, token_lengths, mels, mel_lengths, speakers=None, mels_for_ge2e=None, pitches=None, noise_scale=1.0, seeds=None,
+                       reconstruct=True):
+        """A trained model over its own recordings, teacher-forced: the monotonic alignment of every recording to its text and, `reconstruct`, the model's
+        own mel for it, frame-aligned with the recording (a ground-truth-aligned mel).  Eval arithmetic whatever `self.training` is, no kept activation,
+        no dense attention: `encode_mels`' pass for z, the text encoder without dropout, the fp32 log-prior and MAS, one launch from the MAS index to
+        durations, alignment score and the seeded sample of the prior along the index (`alignment.aligned_sample`), the inverse flows under the same
+        conditioning (what `forward` computes from these arguments).  -> TeacherForced(durations [B, Tt] i32 frames per token, idx [B, T'] i32,
+        score [B], z [B, Mel, T'] the recording's latent, mels [B, Mel, T'] or None with -Max_Abs_Mel beyond each utterance, mel_lengths cut to whole
+        squeeze groups); T' as in `encode_mels`.  score is the mean log-prior density per element along the alignment - the quantity MAS maximised,
+        not a likelihood (no log-determinants).  seeds as in `inference`; without seeds noise_scale must be 0 (the prior's mean): there is no unseeded
+        draw.  Runs at dec_cfg.precision."""
+        if seeds is None and bool((noise_scale != 0).any() if torch.is_tensor(noise_scale) else float(noise_scale) != 0.0):
+            raise ValueError("teacher_forced draws its noise from `seeds` only: without `seeds`, `noise_scale` must be 0 (the prior's mean)")
+        hp = self.hp
+        P, stacks, prep, pitch = self._decoder_pass_inputs(mels, mel_lengths, pitches)
+        spk, pro = self._conditioning(P, speakers, mels_for_ge2e, mels, mel_lengths)
+        cond = stacks.conditioning(spk, pro)
+        z, z_lengths = decoder.decoder_convert(self.dec_cfg, prep, mels.contiguous(), mel_lengths, cond, None, None, pitch, encode_only=True)
+        token_mask = self.Mask_Generate(token_lengths, tokens.shape[1])
+        mean, log_std, _ = encoder.encoder_forward(P, hp, tokens, token_mask, spk, pro, False, precision=self.dec_cfg.precision, cache=self._enc_cache)
+        value_t, tx32, ty32 = alignment.log_prior_t(mean, log_std, z, token_lengths, mel_lengths, int(hp.Decoder.Num_Squeeze), return_lengths=True)
+        idx = alignment.maximum_path_t(value_t, tx32, ty32)
+        B = mean.shape[0]
+        if seeds is None:
+            seeds = torch.zeros(B, 2, dtype=torch.int32, device=mean.device)
+        sample, durations, score = alignment.aligned_sample(mean, log_std, idx, z, seeds, self._noise_scales(noise_scale, B, mean.device), want_z=reconstruct)
+        out = None
+        if reconstruct:
+            out = decoder.decoder_inverse(self.dec_cfg, None, sample, z_lengths, cond=cond, fill=-float(hp.Sound.Max_Abs_Mel), prep=prep, pitch=pitch)
+        return TeacherForced(durations, idx, score, z, out, z_lengths)
 
     @torch.no_grad()
     def voice_conversion(self, mels, mel_lengths, speakers=None, mels_for_ge2e=None, pitches=None, target_speakers=None, target_mels_for_ge2e=None,

@@ -873,6 +873,26 @@ int glowtts_yin_f32(const float *wav, const int32_t *wav_lengths, float *pitch, 
 #define GLOWTTS_SAMPLE_TILE 64
 int glowtts_prior_sample(const float *mean, const float *log_std, const float *dur, const int64_t *mel_lengths, const uint32_t *seeds,
                          const float *noise_scales, float *z, int32_t *idx, float *attn, int B, int C, int Tx, int Tmax, void *stream);
+/* The teacher-forced counterpart (an addition, the ABI version stays): the sample of the prior ALONG a given index, the index's run lengths and the
+ * alignment score, logged as `prior_sample_aligned` (+ `prior_score_final` when score is asked for; the durations are a token-indexed block of the
+ * first launch's grid, not a launch of their own).
+ *   idx   [B][Tmax]     the per-frame token index as glowtts_mas_dp_f32_t and glowtts_prior_sample write it: values in [0, Tx), -1 past the utterance.
+ *                       ANY value outside [0, Tx) is treated as -1; nothing is read out of bounds.
+ *   z_rec [B][C][Tmax]  the recording's latent; may be NULL (then score must be NULL)
+ * Outputs, each may be NULL independently (not all three), except that score needs score_partials and z_rec:
+ *   z     [B][C][Tmax]  mean[idx] + exp(log_std[idx]) * gauss(seeds[b][0], seeds[b][1], c, y, C) * noise_scales[b] where idx >= 0, exactly 0 elsewhere: the
+ *                       bits glowtts_prior_sample writes for the same idx (one device function serves both).  seeds / noise_scales: device buffers as
+ *                       above, required with z.
+ *   dur   [B][Tx]       the number of frames y with idx[y] == x; every element is written
+ *   score [B]           the mean over the utterance's valid (c, y) of  -0.5 log(2 pi) - ls - 0.5 (z_rec - m)^2 exp(-2 ls),  m / ls gathered by idx: the
+ *                       log-prior density per element along the alignment (what MAS maximised), NOT a likelihood (no log-determinants); 0 for an
+ *                       utterance without a valid frame.  Per-tile partials go to score_partials [B][ceil(Tmax / GLOWTTS_SAMPLE_TILE)] by one fixed
+ *                       summation tree (the same in both store forms, invalid frames add +0.0); the second launch adds the tiles in ascending order and
+ *                       divides.  No float atomics: an utterance's score has the same bits alone, in any batch, at any Tmax.
+ * GLOWTTS_E_ARG as for glowtts_prior_sample (NULL required pointer, B outside 1..65535, counters out of range). */
+int glowtts_prior_sample_aligned(const float *mean, const float *log_std, const int32_t *idx, const float *z_rec, const uint32_t *seeds,
+                                 const float *noise_scales, float *z, int32_t *dur, float *score, float *score_partials, int B, int C, int Tx, int Tmax,
+                                 void *stream);
 
 /* ---- neural vocoder: Parallel WaveGAN generator (csrc/pwg_ops.hip; inference, f32; additions, the ABI version stays) ----
  * Rows are samples, channels-last: x [B][Lmax hop][R], c [B][Lmax hop][A], skips [B][Lmax hop][S]; frame_lengths [B] i32 (device) are the utterances'
