@@ -27,6 +27,7 @@ SAMPLE_SCAN_CHUNK = 1024
 SAMPLE_TILE = 64
 GE2E_MAX_MEL, GE2E_MAX_H, GE2E_MAX_STACKS, GE2E_MAX_E = 512, 768, 8, 1024
 DTW_MAX_FRAMES, DTW_MAX_K = 4096, 64
+TSNE_MAX_N, TSNE_MAX_D = 8192, 1024
 
 # ---- struct mirrors: `c_name` is the C struct whose layout the class restates ------------------------------------------------------------
 I, L, F, U, P = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_uint32, ctypes.c_void_p
@@ -314,6 +315,12 @@ SIGNATURES = {
     "glowtts_dtw_supported": (I, [I] * 3),
     "glowtts_dtw_work_bytes": (L, [I] * 2),
     "glowtts_dtw": (I, [P] * 10 + [I] * 4 + [P]),
+    "glowtts_tsne_supported": (I, [I] * 2),
+    "glowtts_tsne_work_bytes": (L, [I]),
+    "glowtts_tsne_sqdist": (I, [P] * 2 + [I] * 3 + [P]),
+    "glowtts_tsne_affinities": (I, [P] * 2 + [I] * 2 + [F, I, P]),
+    "glowtts_tsne_forces": (I, [P] * 4 + [I] * 2 + [P]),
+    "glowtts_tsne_iterate": (I, [P] * 5 + [I] * 4 + [F, I, I, P]),
 }
 
 # ---- the entry points above whose `int` result is a VALUE (a version, a chunk size, a yes / no), not a GLOWTTS_OK / _E_ARG / _E_LAUNCH status: `_lib.api()`
@@ -322,5 +329,5 @@ VALUE_RETURNING = frozenset({
     "glowtts_abi_version", "glowtts_opt_chunk",
     "glowtts_cond_linear_supported", "glowtts_gst_supported", "glowtts_conv3x3s2_supported", "glowtts_dur_proj_supported", "glowtts_vocoder_supported",
     "glowtts_pwg_supported", "glowtts_pwg_supported_bf16", "glowtts_ge2e_supported", "glowtts_pwg_train_supported", "glowtts_stft_loss_supported",
-    "glowtts_pwg_disc_supported", "glowtts_mel_cepstrum_supported", "glowtts_dtw_supported",
+    "glowtts_pwg_disc_supported", "glowtts_mel_cepstrum_supported", "glowtts_dtw_supported", "glowtts_tsne_supported",
 })

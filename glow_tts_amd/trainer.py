@@ -352,6 +352,35 @@ class Trainer:
             logging.info("(Steps: {}) Evaluation {}".format(self.steps, {t: float(v) / n for t, v in self.scalar_Dict["Evaluation"].items()}))
         self.scalar_Dict["Evaluation"] = defaultdict(float)
         model.train()
+        if getattr(self.hp.Train, "Prosody_Check", None) is not None and self.hp.Mode.upper() in ("PE", "GR") and \
+                self.steps % int(self.hp.Train.Prosody_Check_Interval) == 0:                                    # Train.py:357-358
+            self.Prosody_Check_Epoch()
+
+    # ------------------------------------------------------------------ Train.py:463-492, Datasets.py:168-214
+    def Prosody_Check_Epoch(self):
+        """The prosody vectors of up to Speakers x Samples_per_Speaker training patterns, mapped by exact t-SNE on the device (`visualizer.write_map`) into
+        <Inference_Path>/Step-<steps>/PROSODY - the reference hands them to TensorBoard's projector.  Only with the optional yaml block `Train.Prosody_Check`
+        (without it: nothing, as before the block existed), on rank 0, in eval mode.  -> the dict of map.json, or None"""
+        from . import projection, visualizer
+        check = visualizer.prosody_check_settings(self.hp)
+        if check is None or self.rank != 0:
+            return None
+        hp = self.hp
+        logging.info("(Steps: {}) Start prosody check.".format(self.steps))
+        settings = projection.projection_settings(hp)
+        root, files = visualizer.pattern_selection(hp, "train", check["Speakers"], check["Samples_per_Speaker"], 0)
+        rows, mels = visualizer.load_patterns(root, files)
+        model = self.model_Dict["GlowTTS"]
+        model.eval()
+        try:
+            vectors = visualizer.prosody_vectors(model, mels, int(hp.Inference_Batch_Size or hp.Train.Batch_Size), hp.Sound.Max_Abs_Mel, self.device)
+        finally:
+            model.train()
+        out_dir = os.path.join(hp.Inference_Path, "Step-{}".format(self.steps), "PROSODY").replace("\\", "/")
+        info = visualizer.write_map(out_dir, vectors, rows, settings, 0, {"what": "prosody", "steps": int(self.steps)})
+        logging.info("(Steps: {}) Prosody check: final KL {:.4f}; nearest-neighbour agreement with the speakers: embeddings {:.3f}, map {:.3f}".format(
+            self.steps, info["kl"][-1], info["nearest_neighbour_agreement"]["embeddings"], info["nearest_neighbour_agreement"]["map"]))
+        return info
 
     # ------------------------------------------------------------------ Train.py:498-553
     def Load_Checkpoint(self):

@@ -1127,6 +1127,39 @@ int64_t glowtts_dtw_work_bytes(int tx_max, int ty_max);
 int glowtts_dtw(const float *x, const int32_t *x_lengths, const float *y, const int32_t *y_lengths, void *work, float *cost, int32_t *steps, int32_t *ix,
                 int32_t *iy, int32_t *moves, int B, int tx_max, int ty_max, int K, void *stream);
 
+/* ---- Embedding maps: exact t-SNE into two dimensions (csrc/tsne_ops.hip; f32; additions, the ABI version stays) ----
+ * The matrix of the fit is N rows of pitch ld = (N + 3) & ~3 floats (rows 16-byte aligned; the pad columns hold 0 once it is P) at the start of the workspace:
+ * squared distances, then conditional affinities, then the joint affinities P, in place.  work: glowtts_tsne_work_bytes(N) bytes = that matrix, then the per-row
+ * partials sums [N][4] f32 and shares [N][4] float64 of the last `tsne_forces` launch; 16-byte aligned; nothing is allocated.
+ * glowtts_tsne_sqdist      `tsne_sqdist`: x [N][D] -> d2 [N][ld], ld >= N: d2[i][j] = sum_k (x_ik - x_jk)^2 by direct differences, k ascending, one fused
+ *   multiply-add per term (never the Gram form: identical rows give exactly 0).  Columns j >= N are not written.
+ * glowtts_tsne_affinities  `tsne_sqdist`, `tsne_affinity` and, with joint != 0, `tsne_symmetrize`: x -> the matrix of the workspace.  Row i works on
+ *   d_j = d2[i][j] - min_{j != i} d2[i][j], j != i, and bisects beta in exactly 64 steps from beta = 1, lo = 0, hi = inf: each step evaluates e_j = exp(-beta d_j),
+ *   s = sum e_j, H = ln s + beta sum d_j e_j / s (the two sums in float64 over the f32 terms, rounded to f32; H in f32); H > ln(perplexity): lo = beta and beta
+ *   doubles while hi is inf, else beta = (beta + hi) / 2; otherwise hi = beta, beta = (beta + lo) / 2.  p_{j|i} = e_j / s of the last beta evaluated, p_{i|i} = 0
+ *   (joint == 0 stops here: the conditional rows, for tests).  P_ij = max((p_{j|i} + p_{i|j}) / (2N), 1e-12) off the diagonal, 0 on it: symmetric bit for bit.
+ * glowtts_tsne_forces      `tsne_forces` (kl != 0: `tsne_forces,kl`), one evaluation: p (the matrix P), y [N][2] -> sums [N][4] f32 = sum_j P_ij w_ij (y_i - y_j)
+ *   (x, y) and sum_j w_ij^2 (y_i - y_j) (x, y), w_ij = 1 / (1 + |y_i - y_j|^2), j != i; shares [N][4] float64 = sum_j w_ij, and with kl != 0
+ *   sum_j P_ij (ln P_ij - ln w_ij) and sum_j P_ij (else 0, 0), and 0.  w and the force terms are f32.  kl == 0: the Z share adds the f32 w in float64
+ *   (within 3 * 2^-24 Z of the exact sum).  kl != 0, the launch whose figures are reported: the Z share and the KL share's terms are float64 arithmetic on
+ *   the exact differences of the f32 y, -ln w_ij taken as ln(1 + |y_i - y_j|^2).  Every sum runs in a fixed order.
+ * glowtts_tsne_iterate     iterations t = t0 .. t1 - 1 on the state y, u, gain [N][2] (f32, in place), two launches each: `tsne_forces` (`tsne_forces,kl` when
+ *   kl_every > 0 and t % kl_every == 0) and `tsne_step` (one workgroup): Z = sum_i shares; a = 12, mu = 0.5 while t < exaggeration_iterations, then a = 1,
+ *   mu = 0.8; g = 4 (a attractive - repulsive / Z); gain += 0.2 where sign(g) != sign(u) (sign(0) = 0), else gain *= 0.8, floor 0.01; u = mu u - lr gain g; y += u;
+ *   y -= mean(y).  A measuring iteration writes KL = sum_ij P_ij (ln P_ij - ln w_ij) + ln Z sum_ij P_ij (float64) of the y it STARTS from into kl[t / kl_every];
+ *   kl_final != 0 adds one `tsne_forces,kl` and one `tsne_step,finish` launch that write the KL of the final y into kl[ceil(t1 / kl_every)] (kl[0] when
+ *   kl_every <= 0) and change no state.  No host synchronisation; no atomics; every reduction order is fixed: the state is bit-identical from run to run.
+ *   Supported (glowtts_tsne_supported, else GLOWTTS_E_ARG): N in [8, GLOWTTS_TSNE_MAX_N], D in [1, GLOWTTS_TSNE_MAX_D], 1 <= perplexity <= (N - 1) / 3. */
+#define GLOWTTS_TSNE_MAX_N 8192
+#define GLOWTTS_TSNE_MAX_D 1024
+int glowtts_tsne_supported(int N, int D);
+int64_t glowtts_tsne_work_bytes(int N);
+int glowtts_tsne_sqdist(const float *x, float *d2, int N, int D, int ld, void *stream);
+int glowtts_tsne_affinities(const float *x, void *work, int N, int D, float perplexity, int joint, void *stream);
+int glowtts_tsne_forces(const float *p, const float *y, float *sums, double *shares, int N, int kl, void *stream);
+int glowtts_tsne_iterate(void *work, float *y, float *u, float *gain, double *kl, int N, int t0, int t1, int exaggeration_iterations, float learning_rate,
+                         int kl_every, int kl_final, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
