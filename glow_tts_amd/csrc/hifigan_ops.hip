@@ -1,0 +1,286 @@
+// Neural vocoder: the HiFi-GAN generator (Kong et al. 2020; transposed convolutions that raise the row rate, each followed by parallel residual stacks whose
+// mean is the stage's output - the multi-receptive-field fusion, MRF) for gfx950, inference, f32.
+// Rows are samples, channels-last: a stage's tensors are [B][Lmax mult][C] with mult rows per mel frame; an utterance of L frames owns rows [0, L mult) of
+// its slab and nothing beyond them is read or (the waveform excepted) written.  Every matrix product runs on the exact-f32 MFMA v_mfma_f32_16x16x4_f32
+// (A operand: lane l holds A[l & 15][l >> 4], B operand B[l >> 4][l & 15], result col = l & 15, row = 4 (l >> 4) + reg) against K-major weight images
+// [taps Cin][Cout] (row = tap * Cin + input channel) streamed from L2 as B operands.
+//
+//   hifigan_conv      ONE launch per convolution: a dilated K-tap convolution over rows.  A workgroup owns 64 consecutive rows of one utterance and RT NT 16
+//                     output columns (the column group is blockIdx.y).  It walks the input channels in chunks of 64:
+//                       1. stages the rows [s0 - pad, s0 + 63 + pad] of the chunk into LDS, LeakyReLU(slope) applied, zero outside the utterance
+//                          (LeakyReLU(0) = 0: prologue and padding commute); the mel of conv_pre is read channels-first as the caller gives it;
+//                       2. per tap and k step of 4: one LDS read per row tile, one weight load per column tile, RT x NT MFMAs.  The products of one
+//                          (chunk, tap) - at most 64 - are one fmaf chain from zero, channel ascending; the chains are added to the sum, which starts at the
+//                          bias, chunk by chunk and tap by tap.  Summing in blocks keeps the rounding error of K = taps Cin up to 5632 products near that
+//                          of sqrt(K) of them (one chain over all of K measured 2e-6 of the largest output at K = 1792, eight times the float32
+//                          convolution of torch on the host); the sums live in registers across the chunks.
+//                     Epilogue: + residual; then out = y, out = out + y (MRF accumulate) or out = (out + y) / nk (the stage's last block).
+//   hifigan_upsample  the transposed convolution in polyphase form, the same tile body: blockIdx.y = (column group, phase).  Output row t = u s + ph sums the taps
+//                     j = j0 + m u (j0 = (ph + p) % u, p = (k - u) / 2) of input row s + (ph + p) / u - m: per phase a dense product over K = Cin taps(ph), the
+//                     phases of one (u, k) may have different tap counts.  LeakyReLU(slope) prologue; a workgroup owns 64 input positions, i.e. 64 output rows u apart.
+//   hifigan_conv,post the single-channel form (conv_post): LeakyReLU, K taps x Cin -> 1 as a fixed-order fmaf chain per row, tanh; zeros beyond the utterance.
+// The wave layout follows the width: RT row tiles x NT column tiles per wave - (4, 2) for Cout % 128 == 0, (4, 1) for % 64, (1, 2) for % 32, else (1, 1) - so
+// every wave of a narrow late stage still owns MFMA work.  Tiles start at the utterance's own row 0 and every sum has one fixed order: a row's value depends on
+// its utterance alone, bit-identical alone, in any batch, at any padding and from run to run.  No atomics, no workgroup waits on another.
+#include <algorithm>
+
+#include "launch_log.h"
+#include "pwg_common.h"
+
+namespace {
+
+constexpr int HG_MAX_CHANNELS = 512, HG_MAX_TAPS = 11, HG_MAX_DILATION = 16, HG_MAX_RATE = 16, HG_MAX_UP_TAPS = 64, HG_MAX_PHASE_TAPS = 8;
+constexpr int HG_CK = 64;                                  // input channels per LDS chunk
+
+__device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
+
+// How a launch walks its taps: the input row of (position s, tap m) is s + o0 + m ts; the weight rows of tap m start at (w0 + m wstep) Cin.
+struct HgTaps {
+    int nt, o0, ts, w0, wstep;
+};
+
+// The tile body of both kernels.  inb: the utterance's slab (channels-last [Tin_max][Cin], or channels-first [Cin][tin_max] with cf); Tin: its own rows;
+// position s writes output row s os + oph of outb ([..][Cout]).  Xs: LDS, (64 + reach) rows of lds_stride_of(min(Cin, 64)) floats.
+template <int RT, int NT>
+__device__ __forceinline__ void hg_tile(const float* __restrict__ inb, const float* __restrict__ w, const float* __restrict__ bias, const float* resb,
+                                        float* outb, float* Xs, int Tin, int tin_max, int s0, int Cin, int Cout, int colgroup, HgTaps tp, float slope, int cf,
+                                        int os, int oph, int accumulate, float divisor)
+{
+    constexpr int WR = WAVES / RT, WC = WAVES / WR;        // the waves as WR row groups x WC column groups
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
+    const int wr = wave % WR, wc = wave / WR;
+    const int col0 = (colgroup * WC + wc) * NT * 16;
+    const int last = tp.o0 + (tp.nt - 1) * tp.ts;
+    const int lo = min(tp.o0, last), span = TM + max(tp.o0, last) - lo;
+    const int xs = lds_stride_of(min(Cin, HG_CK));
+
+    f32x4 acc[RT][NT];
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+        const float bv = bias[col0 + n * 16 + r];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) acc[rt][n] = f32x4{bv, bv, bv, bv};
+    }
+
+    for (int c0 = 0; c0 < Cin; c0 += HG_CK) {
+        const int ck = min(HG_CK, Cin - c0);
+        if (c0) __syncthreads();                           // every wave is done with the previous chunk
+        if (cf) {                                          // channels-first source (the mel): consecutive threads along the rows
+            for (int e = tid; e < span * ck; e += THREADS) {
+                const int c = e / span, row = e - c * span, t = s0 + lo + row;
+                Xs[row * xs + c] = (t >= 0 && t < Tin) ? lrelu(inb[(size_t)(c0 + c) * tin_max + t], slope) : 0.f;
+            }
+        } else {
+            const int kq = ck >> 2;
+            for (int e = tid; e < span * kq; e += THREADS) {
+                const int row = e / kq, k4 = (e - row * kq) * 4, t = s0 + lo + row;
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (t >= 0 && t < Tin) {
+                    v = *reinterpret_cast<const float4*>(inb + (size_t)t * Cin + c0 + k4);
+                    v.x = lrelu(v.x, slope); v.y = lrelu(v.y, slope); v.z = lrelu(v.z, slope); v.w = lrelu(v.w, slope);
+                }
+                *reinterpret_cast<float4*>(Xs + row * xs + k4) = v;
+            }
+        }
+        __syncthreads();
+        for (int m = 0; m < tp.nt; ++m) {
+            const float* xa = Xs + (wr * RT * 16 + r + tp.o0 + m * tp.ts - lo) * xs + q;
+            const float* wp = w + ((size_t)(tp.w0 + m * tp.wstep) * Cin + c0 + q) * Cout + col0 + r;
+            f32x4 part[RT][NT];                            // this (chunk, tap)'s chain
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                for (int n = 0; n < NT; ++n) part[rt][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+            auto step = [&](int k0) {
+                float bw[NT];
+#pragma unroll
+                for (int n = 0; n < NT; ++n) bw[n] = wp[(size_t)k0 * Cout + n * 16];
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) {
+                    const float a = xa[rt * 16 * xs + k0];
+#pragma unroll
+                    for (int n = 0; n < NT; ++n) part[rt][n] = mfma4(a, bw[n], part[rt][n]);
+                }
+            };
+            int k0 = 0;
+            for (; k0 + 16 <= ck; k0 += 16) {              // four k steps at a time: their weight loads are in flight together
+#pragma unroll
+                for (int u = 0; u < 4; ++u) step(k0 + 4 * u);
+            }
+            for (; k0 < ck; k0 += 4) step(k0);
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                for (int n = 0; n < NT; ++n) acc[rt][n] += part[rt][n];
+        }
+    }
+
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int s = s0 + (wr * RT + rt) * 16 + q * 4 + i;
+            if (s >= Tin) continue;                        // padded rows are never written
+#pragma unroll
+            for (int n = 0; n < NT; ++n) {
+                const size_t idx = ((size_t)s * os + oph) * Cout + col0 + n * 16 + r;
+                float y = acc[rt][n][i];
+                if (resb) y += resb[idx];
+                if (accumulate == 1) y = outb[idx] + y;
+                else if (accumulate == 2) y = (outb[idx] + y) / divisor;
+                outb[idx] = y;
+            }
+        }
+}
+
+// grid (ceil(Lmax mult / 64), Cout / (RT NT 16), B); dynamic LDS (64 + (taps - 1) d) rows
+template <int RT, int NT>
+__global__ __launch_bounds__(THREADS) void hifigan_conv_kernel(const float* __restrict__ in, const float* __restrict__ w, const float* __restrict__ bias,
+                                                               const float* res, float* out, const int32_t* __restrict__ lengths, int Lmax, int mult, int Cin,
+                                                               int Cout, int taps, int d, float slope, int accumulate, float divisor, int cf)
+{
+    extern __shared__ __attribute__((aligned(16))) float hg_smem[];
+    const int b = blockIdx.z, s0 = blockIdx.x * TM;
+    const int Tmax = Lmax * mult, T = min(lengths[b], Lmax) * mult;
+    if (s0 >= T) return;                                   // (uniform over the workgroup)
+    const size_t row0 = (size_t)b * Tmax;
+    const HgTaps tp = {taps, -((taps - 1) / 2) * d, d, 0, 1};
+    hg_tile<RT, NT>(in + row0 * Cin, w, bias, res ? res + row0 * Cout : nullptr, out + row0 * Cout, hg_smem, T, Tmax, s0, Cin, Cout, blockIdx.y, tp, slope, cf, 1, 0,
+                    accumulate, divisor);
+}
+
+// grid (ceil(Lmax mult / 64), u Cout / (RT NT 16), B); in [B][Lmax mult][Cin] -> out [B][Lmax mult u][Cout];  w [k Cin][Cout]: row = tap * Cin + input channel
+template <int RT, int NT>
+__global__ __launch_bounds__(THREADS) void hifigan_upsample_kernel(const float* __restrict__ in, const float* __restrict__ w, const float* __restrict__ bias,
+                                                                   float* __restrict__ out, const int32_t* __restrict__ lengths, int Lmax, int mult, int Cin,
+                                                                   int Cout, int k, int u, float slope)
+{
+    extern __shared__ __attribute__((aligned(16))) float hg_smem[];
+    const int b = blockIdx.z, s0 = blockIdx.x * TM;
+    const int Tmax = Lmax * mult, T = min(lengths[b], Lmax) * mult;
+    if (s0 >= T) return;                                   // (uniform over the workgroup)
+    const int ph = blockIdx.y % u, colgroup = blockIdx.y / u;
+    const int shift = ph + (k - u) / 2, j0 = shift % u;
+    const HgTaps tp = {(k - j0 + u - 1) / u, shift / u, -1, j0, u};
+    const size_t row0 = (size_t)b * Tmax;
+    hg_tile<RT, NT>(in + row0 * Cin, w, bias, nullptr, out + row0 * u * Cout, hg_smem, T, Tmax, s0, Cin, Cout, colgroup, tp, slope, 0, u, ph, 0, 1.f);
+}
+
+// ---- conv_post: grid (ceil(Lmax mult / 256), B), a row per thread;  w [taps Cin] (row = tap * Cin + input channel), bias [1] -----------------------------
+__global__ __launch_bounds__(THREADS) void hifigan_post_kernel(const float* __restrict__ in, const float* __restrict__ w, const float* __restrict__ bias,
+                                                               float* __restrict__ wav, const int32_t* __restrict__ lengths, int Lmax, int mult, int Cin, int taps,
+                                                               float slope)
+{
+    const int b = blockIdx.y, t = blockIdx.x * THREADS + threadIdx.x;
+    const int Tmax = Lmax * mult, T = min(lengths[b], Lmax) * mult;
+    if (t >= Tmax) return;
+    const size_t row0 = (size_t)b * Tmax;
+    float v = 0.f;                                         // beyond the utterance: zeros
+    if (t < T) {
+        v = bias[0];
+        for (int j = 0; j < taps; ++j) {
+            const int ts = t + j - (taps - 1) / 2;
+            if (ts < 0 || ts >= T) continue;               // zero padding at the utterance's own ends
+            const float* x = in + (row0 + ts) * Cin;
+            const float* wj = w + j * Cin;
+            for (int c = 0; c < Cin; c += 4) {
+                const float4 xv = *reinterpret_cast<const float4*>(x + c), wv = *reinterpret_cast<const float4*>(wj + c);
+                v = fmaf(wv.x, lrelu(xv.x, slope), v); v = fmaf(wv.y, lrelu(xv.y, slope), v);
+                v = fmaf(wv.z, lrelu(xv.z, slope), v); v = fmaf(wv.w, lrelu(xv.w, slope), v);
+            }
+        }
+        v = tanhf(v);
+    }
+    wav[row0 + t] = v;
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------------------------
+bool hg_channels(int Cin, int Cout)
+{
+    return Cin >= 4 && Cin <= HG_MAX_CHANNELS && Cin % 4 == 0 && Cout >= 16 && Cout <= HG_MAX_CHANNELS && Cout % 16 == 0;
+}
+
+int hg_lds_bytes(int reach, int Cin) { return (TM + reach) * lds_stride_of(std::min(Cin, HG_CK)) * 4; }
+
+// the wave layout of an output width: columns per workgroup = RT NT 16
+void hg_layout(int Cout, int* rt, int* nt)
+{
+    *rt = Cout % 64 == 0 ? 4 : 1;
+    *nt = (Cout % 128 == 0 || (Cout % 64 != 0 && Cout % 32 == 0)) ? 2 : 1;
+}
+
+}  // namespace
+
+extern "C" int glowtts_hifigan_supported(int Cin, int Cout, int taps, int dilation, int rate)
+{
+    if (rate == 0) {                                       // a convolution; Cout == 1: the conv_post form
+        if (taps < 1 || taps > HG_MAX_TAPS || taps % 2 == 0 || dilation < 1 || dilation > HG_MAX_DILATION) return 0;
+        if (Cout == 1) return Cin >= 4 && Cin <= HG_MAX_CHANNELS && Cin % 4 == 0 && dilation == 1;
+        return hg_channels(Cin, Cout) && hg_lds_bytes((taps - 1) * dilation, Cin) <= MAX_LDS;
+    }
+    return dilation == 1 && rate >= 1 && rate <= HG_MAX_RATE && taps >= rate && taps <= HG_MAX_UP_TAPS && (taps - rate) % 2 == 0 &&
+           (taps + rate - 1) / rate <= HG_MAX_PHASE_TAPS && hg_channels(Cin, Cout);
+}
+
+extern "C" int glowtts_hifigan_conv(const float* in, const float* w, const float* bias, const float* residual, float* out, const int32_t* frame_lengths, int B,
+                                    int Lmax, int mult, int Cin, int Cout, int taps, int dilation, float slope, int accumulate, float divisor, int channels_first,
+                                    void* stream)
+{
+    if (!in || !w || !bias || !out || !frame_lengths || in == out || bad_batch(B, Lmax, mult) || Cout == 1 || !glowtts_hifigan_supported(Cin, Cout, taps, dilation, 0) ||
+        accumulate < 0 || accumulate > 2 || (accumulate == 2 && !(divisor > 0.f)))
+        return GLOWTTS_E_ARG;
+    int rt, nt;
+    hg_layout(Cout, &rt, &nt);
+    const int lds = hg_lds_bytes((taps - 1) * dilation, Cin);
+    const dim3 grid((Lmax * mult + TM - 1) / TM, Cout / (rt * nt * 16), B);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+#define HG_CONV(RT_, NT_)                                                                                                                                        \
+    do {                                                                                                                                                         \
+        if (allow_lds<&hifigan_conv_kernel<RT_, NT_>>(lds) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;                                                               \
+        hipLaunchKernelGGL((hifigan_conv_kernel<RT_, NT_>), grid, dim3(THREADS), (size_t)lds, s, in, w, bias, residual, out, frame_lengths, Lmax, mult, Cin, Cout, \
+                           taps, dilation, slope, accumulate, divisor, channels_first);                                                                          \
+    } while (0)
+    if (rt == 4 && nt == 2) HG_CONV(4, 2);
+    else if (rt == 4) HG_CONV(4, 1);
+    else if (nt == 2) HG_CONV(1, 2);
+    else HG_CONV(1, 1);
+#undef HG_CONV
+    GLOWTTS_NOTE_STATIC("hifigan_conv");
+    RET_LAUNCH();
+}
+
+extern "C" int glowtts_hifigan_upsample(const float* in, const float* w, const float* bias, float* out, const int32_t* frame_lengths, int B, int Lmax, int mult,
+                                        int Cin, int Cout, int taps, int rate, float slope, void* stream)
+{
+    if (!in || !w || !bias || !out || !frame_lengths || in == out || rate < 1 || rate > HG_MAX_RATE || bad_batch(B, Lmax, mult) ||
+        (int64_t)mult * rate > (1 << 16) || bad_batch(B, Lmax, mult * rate) || !glowtts_hifigan_supported(Cin, Cout, taps, 1, rate))
+        return GLOWTTS_E_ARG;
+    int rt, nt;
+    hg_layout(Cout, &rt, &nt);
+    const int lds = hg_lds_bytes((taps + rate - 1) / rate - 1, Cin);
+    const dim3 grid((Lmax * mult + TM - 1) / TM, rate * (Cout / (rt * nt * 16)), B);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+#define HG_UP(RT_, NT_)                                                                                                                                          \
+    do {                                                                                                                                                         \
+        if (allow_lds<&hifigan_upsample_kernel<RT_, NT_>>(lds) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;                                                           \
+        hipLaunchKernelGGL((hifigan_upsample_kernel<RT_, NT_>), grid, dim3(THREADS), (size_t)lds, s, in, w, bias, out, frame_lengths, Lmax, mult, Cin, Cout, taps, \
+                           rate, slope);                                                                                                                         \
+    } while (0)
+    if (rt == 4 && nt == 2) HG_UP(4, 2);
+    else if (rt == 4) HG_UP(4, 1);
+    else if (nt == 2) HG_UP(1, 2);
+    else HG_UP(1, 1);
+#undef HG_UP
+    GLOWTTS_NOTE_STATIC("hifigan_upsample");
+    RET_LAUNCH();
+}
+
+extern "C" int glowtts_hifigan_post(const float* in, const float* w, const float* bias, float* wav, const int32_t* frame_lengths, int B, int Lmax, int mult, int Cin,
+                                    int taps, float slope, void* stream)
+{
+    if (!in || !w || !bias || !wav || !frame_lengths || bad_batch(B, Lmax, mult) || !glowtts_hifigan_supported(Cin, 1, taps, 1, 0)) return GLOWTTS_E_ARG;
+    hipLaunchKernelGGL(hifigan_post_kernel, dim3((Lmax * mult + THREADS - 1) / THREADS, B), dim3(THREADS), 0, static_cast<hipStream_t>(stream), in, w, bias, wav,
+                       frame_lengths, Lmax, mult, Cin, taps, slope);
+    GLOWTTS_NOTE_STATIC("hifigan_conv,post");
+    RET_LAUNCH();
+}

@@ -3,7 +3,8 @@ references, inference_path)`), thin: text -> tokens (`Token.yaml`), optional ref
 checkpoint (ActNorm marked initialised, `Inference.py:258-270`), `GlowTTS.inference` (replayed as hipGraphs through `graph_infer.GraphedInference`
 where the mode allows it), one `.npy` mel per utterance (`Inference.py:213-220`; the PNG plots are out of scope) and, with `wav=True`, one
 `WAV/<label>.wav` next to it from the active vocoder: Griffin-Lim (`vocoder.GriffinLim`: a baseline vocoder, not a neural one) or, with the yaml block
-`Vocoder` / `vocoder='pwg'` and a checkpoint, the Parallel WaveGAN generator (`vocoder.ParallelWaveGAN`).  `references` are either
+`Vocoder` / `vocoder='pwg'` and a checkpoint, the Parallel WaveGAN generator (`vocoder.ParallelWaveGAN`), or, with `Type: 'HiFiGAN'` in that block /
+`vocoder='hifigan'`, the HiFi-GAN generator (`vocoder.HiFiGAN`).  `references` are either
 `.npy` files / arrays holding mels [T, Mel] (what `Pattern_Generator.Pattern_Generate` produces) or wav files, which go through
 `glow_tts_amd.audio` (librosa-free restatement of `Audio.py`; resampling is not implemented: the wav must be at hp.Sound.Sample_Rate).
 With `Speaker_Embedding.Type: 'GE2E'` the speaker is given by `speaker_references` (wav files, mels or ready d-vectors), which go through
@@ -32,17 +33,17 @@ class Inferencer:
                  vocoder_precision=None):
         """device_frontend: wav references and wav voice-conversion sources are analysed on the device (`frontend.Analyzer`) instead of the host's
         `audio.pattern_from_wav`; decoding, trimming and normalisation stay `audio.audio_prep` either way.
-        vocoder: 'pwg' (the neural vocoder), 'griffin_lim' (forces the baseline) or None: 'pwg' when the yaml has the `Vocoder` block or
-        `vocoder_checkpoint` (overrides `Vocoder.Checkpoint_Path`) is given, Griffin-Lim otherwise.
-        vocoder_precision: 'f32', 'bf16' or None (the yaml's `Vocoder.Precision`, default 'f32') - the neural vocoder's layer arithmetic
-        (`vocoder.ParallelWaveGAN`); Griffin-Lim ignores it.
+        vocoder: 'pwg' or 'hifigan' (the neural vocoders), 'griffin_lim' (forces the baseline) or None: 'hifigan' when the yaml's `Vocoder` block has
+        `Type: 'HiFiGAN'`, 'pwg' for any other `Vocoder` block or when `vocoder_checkpoint` (overrides `Vocoder.Checkpoint_Path`) is given, Griffin-Lim
+        otherwise (`vocoder.vocoder_kind`; `vocoder.make_vocoder` builds it).
+        vocoder_precision: 'f32', 'bf16' or None (the yaml's `Vocoder.Precision`, default 'f32') - the Parallel WaveGAN's layer arithmetic
+        (`vocoder.ParallelWaveGAN`); the HiFi-GAN generator is f32 only and refuses 'bf16'; Griffin-Lim ignores it.
         speaker_encoder: GE2E mode only - a callable mapping a slice stack [B * Samples, Mel, Slice] to unit d-vectors [B, Embedding_Size].  None: the
         `speaker_encoder.GE2E` of `Speaker_Embedding.GE2E.Checkpoint_Path`, else the one the GlowTTS checkpoint carries under `layer_Dict.GE2E.*` (keys of
         another layout: a warning, and they are dropped), else none - then only ready d-vectors can be given."""
         self.hp = hp if hp is not None else get_hp()
-        if vocoder not in (None, "pwg", "griffin_lim"):
-            raise ValueError("vocoder must be 'pwg', 'griffin_lim' or None, got {!r}".format(vocoder))
-        self.vocoder_kind = vocoder or ("pwg" if vocoder_checkpoint or getattr(self.hp, "Vocoder", None) is not None else "griffin_lim")
+        from .vocoder import vocoder_kind
+        self.vocoder_kind = vocoder_kind(self.hp, vocoder, vocoder_checkpoint)
         self.vocoder_checkpoint = vocoder_checkpoint
         if vocoder_precision not in (None, "f32", "bf16"):
             raise ValueError("vocoder_precision must be 'f32', 'bf16' or None, got {!r}".format(vocoder_precision))
@@ -81,21 +82,14 @@ class Inferencer:
         logging.info("Checkpoint loaded at {} steps.".format(state_Dict.get("Steps")))
 
     def _make_vocoder(self):
-        from . import vocoder
-        if self.vocoder_kind != "pwg":
-            return vocoder.GriffinLim(self.hp, self.device)
-        hp = self.hp
-        if self.vocoder_checkpoint:                                              # the argument overrides the yaml's path
-            import argparse
-            import copy
-            hp = copy.copy(hp)
-            hp.Vocoder = argparse.Namespace(**dict(vocoder.pwg_settings(hp), Checkpoint_Path=self.vocoder_checkpoint))
-        return vocoder.ParallelWaveGAN(hp, self.device, precision=self.vocoder_precision)
+        from .vocoder import make_vocoder
+        return make_vocoder(self.hp, self.device, self.vocoder_kind, self.vocoder_checkpoint, self.vocoder_precision)
 
     def _write_wavs(self, mels, mel_lengths, names, inference_path, seeds=None, vocoder_seeds=None):
         """The active vocoder on the mels as the model produced them ([B, Mel, T], on the device) -> WAV/<name>.wav, 16-bit, Sound.Sample_Rate.
         Neural vocoder: frames * Frame_Shift samples, clipped to [-1, 1], no de-emphasis; vocoder_seeds (integer [B, 2], `vocoder.pwg_seed_words`): its noise is
-        the counter hash of those words, so the wav repeats byte for byte; None: torch's device generator.
+        the counter hash of those words, so the wav repeats byte for byte; None: torch's device generator.  The HiFi-GAN generator has no noise: it ignores
+        the words and its wav repeats byte for byte with or without them.
         Griffin-Lim: de-emphasised.
         seeds (integer [B, 2], seeded sampling): Griffin-Lim's start phase of every utterance is drawn from a host generator seeded with its two seed words,
         over that utterance's own frames (zero beyond) - a function of the seed and the utterance's length only, so the wav is as reproducible as the mel.
@@ -104,8 +98,8 @@ class Inferencer:
         if self._vocoder is None:
             self._vocoder = self._make_vocoder()
         mels = mels[:, :, :int(mel_lengths.max())]                                # a served batch may be padded beyond its longest utterance
-        phase = None
-        if self.vocoder_kind == "pwg":
+        phase, neural = None, self.vocoder_kind != "griffin_lim"
+        if neural:
             wavs = self._vocoder.to_host(*self._vocoder(mels, mel_lengths, seeds=vocoder_seeds))
         elif seeds is not None:
             T, F = mels.shape[2], self._vocoder.n_freq
@@ -114,7 +108,7 @@ class Inferencer:
                 n = min(int(n), T)
                 g = torch.Generator().manual_seed((int(s0) & 0xFFFFFFFF) | ((int(s1) & 0x7FFFFFFF) << 32))
                 phase[b, :n] = (torch.rand(n, F, generator=g) * 2.0 - 1.0) * float(np.pi)
-        if self.vocoder_kind != "pwg":
+        if not neural:
             wavs = self._vocoder.to_host(*self._vocoder(mels, mel_lengths, initial_phase=phase))
         os.makedirs(os.path.join(inference_path, "WAV").replace("\\", "/"), exist_ok=True)
         for name, x in zip(names, wavs):
@@ -470,11 +464,12 @@ def build_parser():
     ap.add_argument("-o", "--out", default="./inference")
     ap.add_argument("--convert", default=None, metavar="LIST.tsv",
                     help="voice conversion instead of text-to-mel: label, source mel (.npy [T, Mel] or wav), source speaker, target speaker[, target reference]")
-    ap.add_argument("--wav", action="store_true", help="also write WAV/<label>.wav per utterance: Griffin-Lim (a baseline vocoder, not a neural one) or, see --vocoder, the Parallel WaveGAN generator")
-    ap.add_argument("--vocoder", choices=["griffin_lim", "pwg"], default=None,
-                    help="the vocoder behind --wav / --vocode: pwg = the neural vocoder (Parallel WaveGAN generator; needs a checkpoint), griffin_lim = the baseline; "
-                         "default: pwg when the yaml has a `Vocoder` block or --vocoder-checkpoint is given, else griffin_lim")
-    ap.add_argument("--vocoder-checkpoint", default=None, metavar="PATH", help="Parallel WaveGAN generator checkpoint (overrides Vocoder.Checkpoint_Path of the yaml)")
+    ap.add_argument("--wav", action="store_true", help="also write WAV/<label>.wav per utterance: Griffin-Lim (a baseline vocoder, not a neural one) or, see --vocoder, the Parallel WaveGAN or the HiFi-GAN generator")
+    ap.add_argument("--vocoder", choices=["griffin_lim", "pwg", "hifigan"], default=None,
+                    help="the vocoder behind --wav / --vocode: pwg / hifigan = the neural vocoders (Parallel WaveGAN / HiFi-GAN generator; they need a checkpoint), "
+                         "griffin_lim = the baseline; default: hifigan when the yaml's `Vocoder` block has Type: 'HiFiGAN', pwg for any other `Vocoder` block or when "
+                         "--vocoder-checkpoint is given, else griffin_lim")
+    ap.add_argument("--vocoder-checkpoint", default=None, metavar="PATH", help="generator checkpoint of the neural vocoder (overrides Vocoder.Checkpoint_Path of the yaml)")
     ap.add_argument("--vocoder-precision", choices=["f32", "bf16"], default=None,
                     help="arithmetic of the neural vocoder's layers (overrides Vocoder.Precision of the yaml; default f32): bf16 rounds the layers' operands, "
                          "weights and gate to bf16 - faster, and with --seed its own reproducible wav, not the f32 one")

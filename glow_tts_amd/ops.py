@@ -190,3 +190,24 @@ def pwg_head(skips, frame_lengths, w1, b1, w2, b2, wav, Lmax, hop, scale):
     """skips [B, Lmax * hop, S] -> wav [B, Lmax * hop], zero beyond each utterance (glowtts_pwg_head)."""
     _lib.api().glowtts_pwg_head(_lib.ptr(skips), _lib.ptr(frame_lengths), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(wav),
                                 skips.shape[0], int(Lmax), int(hop), skips.shape[2], float(scale), _lib.stream())
+
+
+# ---- neural vocoder (csrc/hifigan_ops.hip).  Rows are samples, channels-last; frame_lengths: int32 device tensor [B]; w: K-major images [taps * Cin, Cout] ----
+def hifigan_conv(x, w, bias, out, frame_lengths, Lmax, mult, taps, dilation, slope=1.0, residual=None, accumulate=0, divisor=1.0, channels_first=False):
+    """out [B, Lmax * mult, Cout] from x [B, Lmax * mult, Cin] (channels_first: [B, Cin, Lmax * mult]): one dilated convolution (glowtts_hifigan_conv)."""
+    Cin = x.shape[1] if channels_first else x.shape[2]
+    _lib.api().glowtts_hifigan_conv(_lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(residual), _lib.ptr(out), _lib.ptr(frame_lengths), x.shape[0], int(Lmax),
+                                    int(mult), Cin, out.shape[2], int(taps), int(dilation), float(slope), int(accumulate), float(divisor), int(bool(channels_first)),
+                                    _lib.stream())
+
+
+def hifigan_upsample(x, w, bias, out, frame_lengths, Lmax, mult, taps, rate, slope):
+    """x [B, Lmax * mult, Cin] -> out [B, Lmax * mult * rate, Cout]: the transposed convolution in polyphase form (glowtts_hifigan_upsample)."""
+    _lib.api().glowtts_hifigan_upsample(_lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(out), _lib.ptr(frame_lengths), x.shape[0], int(Lmax), int(mult),
+                                        x.shape[2], out.shape[2], int(taps), int(rate), float(slope), _lib.stream())
+
+
+def hifigan_post(x, w, bias, wav, frame_lengths, Lmax, mult, taps, slope):
+    """x [B, Lmax * mult, Cin] -> wav [B, Lmax * mult] = tanh(conv_post(lrelu(x))), zero beyond each utterance (glowtts_hifigan_post)."""
+    _lib.api().glowtts_hifigan_post(_lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(wav), _lib.ptr(frame_lengths), x.shape[0], int(Lmax), int(mult), x.shape[2],
+                                    int(taps), float(slope), _lib.stream())

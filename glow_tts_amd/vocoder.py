@@ -1,5 +1,6 @@
-"""Waveform output.  Two vocoders: Griffin-Lim (below, the default) and - with the optional yaml block `Vocoder` and a checkpoint - the Parallel WaveGAN
-generator `ParallelWaveGAN` on the kernels of csrc/pwg_ops.hip (second half of this file).
+"""Waveform output.  Three vocoders: Griffin-Lim (below, the default) and - with the optional yaml block `Vocoder` and a checkpoint - the Parallel WaveGAN
+generator `ParallelWaveGAN` on the kernels of csrc/pwg_ops.hip (second half of this file) or, with `Type: 'HiFiGAN'` in that block, the HiFi-GAN generator
+`HiFiGAN` on the kernels of csrc/hifigan_ops.hip (the end of this file, with `make_vocoder`, the one place that chooses).
 
 Griffin-Lim: a vocoder on the HIP kernels of csrc/vocoder_ops.hip.  A BASELINE vocoder (no weights, audibly phasey), not a neural one:
 it inverts exactly the front end `audio.py` restates (pre-emphasis, centred reflect-padded STFT, periodic Hann of Frame_Length zero-padded to n_fft, hop
@@ -274,7 +275,8 @@ def pwg_geometry(hp):
     if precision not in PWG_PRECISIONS:
         raise ValueError(f"Vocoder.Precision = {precision!r} must be 'f32' or 'bf16' (bf16: the layer launches' operands only, inference only)")
     if v["Type"] != "PWG":
-        raise ValueError(f"Vocoder.Type = {v['Type']!r}: the only neural vocoder is 'PWG' (the Parallel WaveGAN generator)")
+        raise ValueError(f"Vocoder.Type = {v['Type']!r}: the Parallel WaveGAN generator needs Vocoder.Type: 'PWG' (a 'HiFiGAN' block describes the HiFi-GAN "
+                         "generator, `HiFiGAN`; `make_vocoder` chooses between them)")
     layers, stacks, R, G, S, ctx = (int(v[k]) for k in ("Layers", "Stacks", "Residual_Channels", "Gate_Channels", "Skip_Channels", "Aux_Context_Window"))
     scales = [int(s) for s in v["Upsample_Scales"]]
     A, hop = int(hp.Sound.Mel_Dim), int(hp.Sound.Frame_Shift)
@@ -991,3 +993,308 @@ def adversarial_mse(scores, value, factor=1.0):
     else:
         split, v0, v1 = N, float(value), 0.0
     return _AdversarialMSE.apply(scores.contiguous(), split, v0, v1, float(factor))
+
+
+# ================================================================================================================================================
+# Neural vocoder: the HiFi-GAN generator (Kong et al. 2020) on the kernels of csrc/hifigan_ops.hip: inference, f32.  The network, the launch plan and the
+# boundary rule are written down in DESIGN.md ("HiFi-GAN generator"); the checkpoint layout restates the most widely used implementation's names from
+# memory and is UNPINNED, like the Parallel WaveGAN's.  The state-dict finder, the weight-norm fold, the checked load and the initialiser are the shared ones.
+# ================================================================================================================================================
+HIFIGAN_DEFAULTS = {"Type": "HiFiGAN", "Checkpoint_Path": None, "Initial_Channels": 512, "Upsample_Rates": [8, 8, 2, 2], "Upsample_Kernel_Sizes": [16, 16, 4, 4],
+                    "Resblock": "1", "Resblock_Kernel_Sizes": [3, 7, 11], "Resblock_Dilations": [[1, 3, 5], [1, 3, 5], [1, 3, 5]], "Precision": "f32"}
+HIFIGAN_MAX_CHANNELS, HIFIGAN_MAX_TAPS, HIFIGAN_MAX_DILATION, HIFIGAN_MAX_RATE, HIFIGAN_MAX_UP_TAPS, HIFIGAN_MAX_PHASE_TAPS = 512, 11, 16, 16, 64, 8
+HIFIGAN_PRE_TAPS = HIFIGAN_POST_TAPS = 7
+HIFIGAN_SLOPE, HIFIGAN_LAST_SLOPE = 0.1, 0.01                       # LeakyReLU: 0.1 everywhere but before conv_post, which has torch's default
+
+
+def hifigan_settings(hp):
+    """The `Vocoder` block of the yaml over HIFIGAN_DEFAULTS (an absent block: the defaults, the V1 sizes)."""
+    v = getattr(hp, "Vocoder", None)
+    return {k: getattr(v, k, d) if v is not None else d for k, d in HIFIGAN_DEFAULTS.items()}
+
+
+def hifigan_geometry(hp):
+    """The generator's sizes as a dict (A, hop, C0, rates, kernels, channels, resblock, rk, rd, nk, precision); raises ValueError naming the offending yaml
+    keys when the kernels do not support them - the idiom of `pwg_geometry`."""
+    v = hifigan_settings(hp)
+    if v["Type"] != "HiFiGAN":
+        raise ValueError(f"Vocoder.Type = {v['Type']!r}: the HiFi-GAN generator needs Vocoder.Type: 'HiFiGAN' (a 'PWG' block describes the Parallel WaveGAN generator)")
+    if v["Precision"] != "f32":
+        raise ValueError(f"Vocoder.Precision = {v['Precision']!r}: the HiFi-GAN generator runs in 'f32' only (bf16 is the Parallel WaveGAN layers' mode)")
+    resblock = str(v["Resblock"])
+    if resblock not in ("1", "2"):
+        raise ValueError(f"Vocoder.Resblock = {v['Resblock']!r} must be '1' (two convolutions per dilation) or '2' (one)")
+    try:
+        C0 = int(v["Initial_Channels"])
+        rates, kernels, rk = ([int(x) for x in v[k]] for k in ("Upsample_Rates", "Upsample_Kernel_Sizes", "Resblock_Kernel_Sizes"))
+        rd = [[int(d) for d in ds] for ds in v["Resblock_Dilations"]]
+    except (TypeError, ValueError):
+        raise ValueError("Vocoder.Initial_Channels must be an integer, Vocoder.Upsample_Rates, Vocoder.Upsample_Kernel_Sizes and Vocoder.Resblock_Kernel_Sizes lists "
+                         "of integers and Vocoder.Resblock_Dilations a list of such lists") from None
+    A, hop = int(hp.Sound.Mel_Dim), int(hp.Sound.Frame_Shift)
+    if A < 4 or A % 4 or A > HIFIGAN_MAX_CHANNELS:
+        raise ValueError(f"Sound.Mel_Dim = {A} must be a multiple of 4 in [4, {HIFIGAN_MAX_CHANNELS}] for the neural vocoder (Vocoder block)")
+    if not rates or len(rates) != len(kernels):
+        raise ValueError(f"Vocoder.Upsample_Rates = {rates} and Vocoder.Upsample_Kernel_Sizes = {kernels} must be non-empty lists of one length")
+    for u, k in zip(rates, kernels):
+        if u < 1 or k < u or (k - u) % 2:
+            raise ValueError(f"Vocoder.Upsample_Kernel_Sizes = {kernels} over Vocoder.Upsample_Rates = {rates}: a kernel k of rate u >= 1 needs k >= u and k - u even "
+                             f"(padding (k - u) / 2 gives exactly u rows per input row), got k = {k}, u = {u}")
+        if u > HIFIGAN_MAX_RATE or k > HIFIGAN_MAX_UP_TAPS or -(-k // u) > HIFIGAN_MAX_PHASE_TAPS:
+            raise ValueError(f"Vocoder.Upsample_Rates = {rates} with Vocoder.Upsample_Kernel_Sizes = {kernels}: rates up to {HIFIGAN_MAX_RATE}, kernels up to "
+                             f"{HIFIGAN_MAX_UP_TAPS} taps and at most {HIFIGAN_MAX_PHASE_TAPS} taps per phase (ceil(k / u)) are supported, got k = {k}, u = {u}")
+    if math.prod(rates) != hop:
+        raise ValueError(f"Vocoder.Upsample_Rates = {rates} multiply to {math.prod(rates)}, Sound.Frame_Shift is {hop}: the vocoder must produce one hop per frame")
+    if C0 < 16 or C0 > HIFIGAN_MAX_CHANNELS or C0 % (16 << len(rates)):
+        raise ValueError(f"Vocoder.Initial_Channels = {C0} halves once per stage of Vocoder.Upsample_Rates = {rates}: every width must stay a multiple of 16, so it "
+                         f"must be a multiple of {16 << len(rates)} in [{16 << len(rates)}, {HIFIGAN_MAX_CHANNELS}]")
+    if not rk or len(rk) != len(rd) or any(not ds for ds in rd):
+        raise ValueError(f"Vocoder.Resblock_Kernel_Sizes = {rk} and Vocoder.Resblock_Dilations = {rd} must be non-empty lists of one length (one non-empty list "
+                         "of dilations per kernel size)")
+    if any(k < 1 or k % 2 == 0 or k > HIFIGAN_MAX_TAPS for k in rk):
+        raise ValueError(f"Vocoder.Resblock_Kernel_Sizes = {rk} must be odd (the padding keeps the row count) and at most {HIFIGAN_MAX_TAPS}")
+    if any(d < 1 or d > HIFIGAN_MAX_DILATION for ds in rd for d in ds):
+        raise ValueError(f"Vocoder.Resblock_Dilations = {rd} must lie in [1, {HIFIGAN_MAX_DILATION}]")
+    return {"A": A, "hop": hop, "C0": C0, "rates": rates, "kernels": kernels, "channels": [C0 >> (i + 1) for i in range(len(rates))], "resblock": resblock,
+            "rk": rk, "rd": rd, "nk": len(rk), "precision": "f32"}
+
+
+def hifigan_expected_shapes(geo):
+    """state-dict key -> shape of the generator with the sizes `geo`"""
+    e = {"conv_pre.weight": (geo["C0"], geo["A"], HIFIGAN_PRE_TAPS), "conv_pre.bias": (geo["C0"],)}
+    cin = geo["C0"]
+    for i, (k, c) in enumerate(zip(geo["kernels"], geo["channels"])):
+        e[f"ups.{i}.weight"], e[f"ups.{i}.bias"] = (cin, c, k), (c,)               # ConvTranspose1d: [in, out, k]
+        for j, (rk, ds) in enumerate(zip(geo["rk"], geo["rd"])):
+            for m in range(len(ds)):
+                for convs in ("convs1", "convs2")[:2 if geo["resblock"] == "1" else 1]:
+                    q = f"resblocks.{i * geo['nk'] + j}.{convs}.{m}."
+                    e[q + "weight"], e[q + "bias"] = (c, c, rk), (c,)
+        cin = c
+    e["conv_post.weight"], e["conv_post.bias"] = (1, cin, HIFIGAN_POST_TAPS), (1,)
+    return e
+
+
+def hifigan_launches(geo):
+    """Launches of one call: conv_pre, per stage the transposed convolution and every resblock convolution, conv_post (78 at the V1 sizes)."""
+    per_dilation = 2 if geo["resblock"] == "1" else 1
+    return 1 + len(geo["rates"]) * (1 + per_dilation * sum(len(ds) for ds in geo["rd"])) + 1
+
+
+def hifigan_find_state_dict(obj):
+    """The generator's state dict inside what torch.load returned: at the top level or under `generator` / `Generator`, possibly inside `model`."""
+    return find_state_dict(obj, ((), ("generator",), ("Generator",), ("model",), ("model", "generator"), ("model", "Generator")),
+                           lambda d: any(str(k).startswith("conv_pre.") for k in d),
+                           "no HiFi-GAN generator state dict found (looked for `conv_pre.*` at the top level, under generator / Generator and inside model)")
+
+
+def hifigan_load(obj, geo):
+    """-> {key: float32 host tensor} with exactly the keys of `hifigan_expected_shapes`: weight-norm pairs are folded once, in float64 (`fold_weight_norm`: its
+    norm over everything but dim 0 is also torch's for the transposed convolutions); a missing, surplus or wrongly shaped tensor raises a ValueError naming
+    the key (`checked_load`)."""
+    return checked_load(hifigan_find_state_dict(obj), hifigan_expected_shapes(geo), "vocoder", "HiFi-GAN generator", "Vocoder")
+
+
+def hifigan_init(geo, seed=0):
+    """A fresh generator's state dict (the names and shapes of `hifigan_expected_shapes`, plain weights): `conv_default_init`."""
+    return conv_default_init(hifigan_expected_shapes(geo), seed)
+
+
+def hifigan_conv_image(weight):
+    """Conv1d weight [Cout, Cin, taps] -> the K-major image [taps * Cin, Cout] of csrc/hifigan_ops.hip (row = tap * Cin + input channel)"""
+    return weight.permute(2, 1, 0).reshape(-1, weight.shape[0]).contiguous()
+
+
+def hifigan_up_image(weight):
+    """ConvTranspose1d weight [Cin, Cout, taps] -> the K-major image [taps * Cin, Cout] (row = tap * Cin + input channel)"""
+    return weight.permute(2, 0, 1).reshape(-1, weight.shape[1]).contiguous()
+
+
+class HiFiGAN:
+    """HiFiGAN(hp, device, state_dict=None)(mels [B, Mel, T], mel_lengths) -> (wav [B, T * hop] fp32 on the device, wav_lengths [B] int64).
+    state_dict None: `Vocoder.Checkpoint_Path` is loaded.  The generator has no noise input: `seeds` / `noises` are accepted (the call signature of
+    `ParallelWaveGAN`) and ignored, a waveform repeats bit for bit.  An utterance's waveform is bit-identical alone, in any batch, at any padding and from
+    run to run.  precision: 'f32' or None; 'bf16' raises (f32 only).  `.last_rows` holds the rows entering conv_post of the last call ([B, T * hop,
+    channels[-1]], a view of the work buffers: the next call overwrites it; `return_rows=True` returns a copy as a third result).
+    `.conv`, `.upsample` and `.stage` run single operators (tests)."""
+
+    def __init__(self, hp, device="cuda:0", state_dict=None, precision=None):
+        if precision not in (None, "f32"):
+            raise ValueError(f"precision = {precision!r}: the HiFi-GAN generator runs in 'f32' only (Vocoder.Precision: 'bf16' is the Parallel WaveGAN layers' mode)")
+        self.geo = geo = hifigan_geometry(hp)                       # before anything touches the device or the disk
+        self.precision = "f32"
+        if state_dict is None:
+            path = hifigan_settings(hp)["Checkpoint_Path"]
+            if not path:
+                raise ValueError("Vocoder.Checkpoint_Path is not set: the neural vocoder needs a HiFi-GAN generator checkpoint")
+            state_dict = torch.load(path, map_location="cpu")
+        w = hifigan_load(state_dict, geo)
+        supported = _lib.api().glowtts_hifigan_supported
+        cin, ok = geo["C0"], supported(geo["A"], geo["C0"], HIFIGAN_PRE_TAPS, 1, 0)
+        for u, k, c in zip(geo["rates"], geo["kernels"], geo["channels"]):
+            ok = ok and supported(cin, c, k, 1, u) and all(supported(c, c, rk, d, 0) for rk, ds in zip(geo["rk"], geo["rd"]) for d in ds + [1])
+            cin = c
+        if not (ok and supported(cin, 1, HIFIGAN_POST_TAPS, 1, 0)):
+            raise ValueError(f"the Vocoder block's sizes {geo} are not supported by the kernels")
+        self.device = torch.device(device)
+        self.sample_rate, self.n_mel, self.hop = int(hp.Sound.Sample_Rate), geo["A"], geo["hop"]
+        self._capacity, self._buffers, self.last_rows = 0, None, None
+        self._build_images(w)
+
+    def _build_images(self, w):
+        """The K-major weight images (the MFMA B operand reads 16 consecutive output channels of one input row), built once."""
+        geo = self.geo
+        dev = lambda t: t.contiguous().to(self.device)
+        pair = lambda q, image: (dev(image(w[q + ".weight"])), dev(w[q + ".bias"]))
+        self.pre = pair("conv_pre", hifigan_conv_image)
+        self.ups = [pair(f"ups.{i}", hifigan_up_image) for i in range(len(geo["rates"]))]
+        self.blocks = []                                            # per resblock: per dilation (d, convs1 pair, convs2 pair or None)
+        for n in range(len(geo["rates"]) * geo["nk"]):
+            ds = geo["rd"][n % geo["nk"]]
+            self.blocks.append([(d, pair(f"resblocks.{n}.convs1.{m}", hifigan_conv_image),
+                                 pair(f"resblocks.{n}.convs2.{m}", hifigan_conv_image) if geo["resblock"] == "1" else None) for m, d in enumerate(ds)])
+        self.post = (dev(w["conv_post.weight"].permute(2, 1, 0).reshape(-1)), dev(w["conv_post.bias"]))
+
+    def _work(self, B, L):
+        """Work buffers of a call (two stage outputs that alternate, the transposed convolution's output and two resblock buffers): views of ONE set sized for
+        the largest B x L (rounded up to T_BUCKET frames) seen so far, like `GriffinLim._work`.  The kernels honour the lengths and write every row they later
+        read."""
+        g = self.geo
+        frames = B * (-(-L // T_BUCKET) * T_BUCKET)
+        if frames > self._capacity:
+            self._buffers = self.last_rows = None
+            per_frame, mult = g["C0"], 1
+            for u, c in zip(g["rates"], g["channels"]):
+                mult *= u
+                per_frame = max(per_frame, mult * c)
+            self._buffers = [torch.empty(frames * per_frame, dtype=torch.float32, device=self.device) for _ in range(5)]
+            self._capacity = frames
+        return self._buffers
+
+    def _lengths(self, lengths, B, L):
+        n = torch.as_tensor(lengths).to(device=self.device, dtype=torch.int32).reshape(B).contiguous()
+        return n.clamp(min=0, max=L)
+
+    def _rows(self, x):
+        if not x.is_cuda:
+            raise _lib.GlowTTSHipError("expected a device tensor (the HIP path has no CPU fallback)")
+        return x.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def conv(self, x, frame_lengths, key=None, weight=None, bias=None, dilation=1, slope=1.0, residual=None, out=None, accumulate=0, divisor=1.0):
+        """One `hifigan_conv` launch on rows x [B, T, Cin] whose utterances own `frame_lengths` rows each -> out [B, T, Cout] (given, or a new tensor).  The
+        weights are the generator's own under the state-dict prefix `key` ('conv_pre', 'resblocks.0.convs1.1', ...) or a Conv1d `weight` [Cout, Cin, taps] and
+        `bias`.  accumulate: 0 out = y, 1 out = out + y, 2 out = (out + y) / divisor; residual: added first (may be `out`)."""
+        x = self._rows(x)
+        B, T, _ = x.shape
+        if key is not None:
+            n, m = (int(s) for s in key.split(".")[1::2]) if key.startswith("resblocks.") else (0, 0)
+            image, bias = self.pre if key == "conv_pre" else self.blocks[n][m][1 if ".convs1." in key else 2]
+        else:
+            image, bias = hifigan_conv_image(weight.to(device=self.device, dtype=torch.float32)), bias.to(device=self.device, dtype=torch.float32).contiguous()
+        taps = image.shape[0] // x.shape[2]
+        out = out if out is not None else torch.empty(B, T, image.shape[1], dtype=torch.float32, device=self.device)
+        ops.hifigan_conv(x, image, bias, out, self._lengths(frame_lengths, B, T), T, 1, taps, dilation, slope, residual, accumulate, divisor)
+        return out
+
+    def upsample(self, i, x, frame_lengths, out=None, weight=None, bias=None, rate=None):
+        """One `hifigan_upsample` launch: rows x [B, T, Cin] -> out [B, T * rate, Cout] with stage i's own weights (LeakyReLU(0.1) prologue) or, i None, a
+        ConvTranspose1d `weight` [Cin, Cout, taps], `bias` and `rate`."""
+        x = self._rows(x)
+        B, T, _ = x.shape
+        if i is not None:
+            (image, bias), rate = self.ups[i], self.geo["rates"][i]
+        else:
+            image, bias = hifigan_up_image(weight.to(device=self.device, dtype=torch.float32)), bias.to(device=self.device, dtype=torch.float32).contiguous()
+        out = out if out is not None else torch.empty(B, T * rate, image.shape[1], dtype=torch.float32, device=self.device)
+        ops.hifigan_upsample(x, image, bias, out, self._lengths(frame_lengths, B, T), T, 1, image.shape[0] // x.shape[2], rate, HIFIGAN_SLOPE)
+        return out
+
+    def _stage(self, i, x, lengths, Lmax, mult, U, X, T, acc):
+        """Stage i on rows x (mult rows per frame) -> acc: the transposed convolution into U, then the nk resblocks on U through X and T; the last convolution
+        of every block adds into `acc` in its epilogue - the first block writes, the last divides by nk - so the MRF mean costs no launch."""
+        g = self.geo
+        u, nk = g["rates"][i], g["nk"]
+        ops.hifigan_upsample(x, *self.ups[i], U, lengths, Lmax, mult, g["kernels"][i], u, HIFIGAN_SLOPE)
+        mult *= u
+        for j in range(nk):
+            rk, steps, cur = g["rk"][j], self.blocks[i * nk + j], U
+            mode = 0 if j == 0 else (2 if j == nk - 1 else 1)
+            for m, (d, c1, c2) in enumerate(steps):
+                last = m == len(steps) - 1
+                if c2 is not None:                                  # type '1': t = conv1(lrelu(x)), x = conv2(lrelu(t)) + x
+                    ops.hifigan_conv(cur, *c1, T, lengths, Lmax, mult, rk, d, HIFIGAN_SLOPE)
+                    ops.hifigan_conv(T, *c2, acc if last else X, lengths, Lmax, mult, rk, 1, HIFIGAN_SLOPE, residual=cur, accumulate=mode if last else 0, divisor=nk)
+                    cur = X
+                else:                                               # type '2': x = conv1(lrelu(x)) + x
+                    dst = acc if last else (T if cur is X else X)
+                    ops.hifigan_conv(cur, *c1, dst, lengths, Lmax, mult, rk, d, HIFIGAN_SLOPE, residual=cur, accumulate=mode if last else 0, divisor=nk)
+                    cur = dst
+
+    def stage(self, i, x, frame_lengths):
+        """Stage i alone (the transposed convolution and its MRF) on rows x [B, T, c_{i-1}] -> [B, T * rate_i, c_i] (tests)."""
+        x = self._rows(x)
+        B, T, _ = x.shape
+        u, c = self.geo["rates"][i], self.geo["channels"][i]
+        U, X, Tb, acc = (torch.empty(B, T * u, c, dtype=torch.float32, device=self.device) for _ in range(4))
+        self._stage(i, x, self._lengths(frame_lengths, B, T), T, 1, U, X, Tb, acc)
+        return acc
+
+    @torch.no_grad()
+    def __call__(self, mels, mel_lengths, seeds=None, noises=None, return_rows=False):
+        if not mels.is_cuda:
+            raise _lib.GlowTTSHipError("expected a device tensor (the HIP path has no CPU fallback)")
+        mels = mels.to(device=self.device, dtype=torch.float32).contiguous()
+        B, Mel, L = mels.shape
+        if Mel != self.n_mel:
+            raise ValueError(f"mels have {Mel} channels, Sound.Mel_Dim = {self.n_mel}")
+        g = self.geo
+        lengths = self._lengths(mel_lengths, B, L)
+        p0, p1, U, X, T = self._work(B, L)
+        view = lambda buf, rows, c: buf[:B * rows * c].view(B, rows, c)
+        x, mult = view(p0, L, g["C0"]), 1
+        ops.hifigan_conv(mels, *self.pre, x, lengths, L, 1, HIFIGAN_PRE_TAPS, 1, channels_first=True)     # the mel as the caller holds it: [B, Mel, L]
+        for i, (u, c) in enumerate(zip(g["rates"], g["channels"])):
+            rows = L * mult * u
+            acc = view(p1 if i % 2 == 0 else p0, rows, c)
+            self._stage(i, x, lengths, L, mult, view(U, rows, c), view(X, rows, c), view(T, rows, c), acc)
+            x, mult = acc, mult * u
+        wav = torch.empty(B, L * g["hop"], dtype=torch.float32, device=self.device)
+        ops.hifigan_post(x, *self.post, wav, lengths, L, g["hop"], HIFIGAN_POST_TAPS, HIFIGAN_LAST_SLOPE)
+        self.last_rows = x
+        wav_lengths = lengths.to(torch.int64) * g["hop"]
+        return (wav, wav_lengths, x.clone()) if return_rows else (wav, wav_lengths)
+
+    def to_host(self, wav, wav_lengths):
+        """Device waveforms -> list of float32 numpy arrays clipped to [-1, 1] (what `audio.write_wav` takes).  No de-emphasis: the vocoder was trained on
+        final audio."""
+        wav, n = wav.cpu().numpy(), wav_lengths.cpu().tolist()
+        return [np.clip(w[:m], -1.0, 1.0).astype(np.float32) for w, m in zip(wav, n)]
+
+
+VOCODER_KINDS = ("griffin_lim", "pwg", "hifigan")
+
+
+def vocoder_kind(hp, kind=None, checkpoint=None):
+    """Which vocoder a run uses: `kind` when given; else 'hifigan' for a `Vocoder` block whose Type is 'HiFiGAN', 'pwg' for any other `Vocoder` block or a
+    checkpoint argument alone, 'griffin_lim' without either."""
+    if kind not in (None,) + VOCODER_KINDS:
+        raise ValueError("vocoder must be 'pwg', 'hifigan', 'griffin_lim' or None, got {!r}".format(kind))
+    block = getattr(hp, "Vocoder", None)
+    if kind is None and getattr(block, "Type", None) == "HiFiGAN":
+        return "hifigan"
+    return kind or ("pwg" if checkpoint or block is not None else "griffin_lim")
+
+
+def make_vocoder(hp, device, kind=None, checkpoint=None, precision=None):
+    """The one place that chooses a vocoder: `kind` as `vocoder_kind` resolves it; `checkpoint` overrides `Vocoder.Checkpoint_Path` of the yaml; `precision`
+    is the neural vocoders' (Griffin-Lim ignores it; HiFi-GAN takes 'f32' only)."""
+    import argparse
+    import copy
+    kind = vocoder_kind(hp, kind, checkpoint)
+    if kind == "griffin_lim":
+        return GriffinLim(hp, device)
+    settings = pwg_settings if kind == "pwg" else hifigan_settings
+    if checkpoint:                                                  # the argument overrides the yaml's path
+        hp = copy.copy(hp)
+        hp.Vocoder = argparse.Namespace(**dict(settings(hp), Checkpoint_Path=checkpoint))
+    return (ParallelWaveGAN if kind == "pwg" else HiFiGAN)(hp, device, precision=precision)

@@ -932,6 +932,32 @@ int glowtts_pwg_layer_bf16(const float *x, const float *c, const uint16_t *w1p, 
                            float *skips, const int32_t *frame_lengths, int B, int Lmax, int hop, int R, int S, int A, int dilation, int accumulate,
                            void *stream);
 
+/* ---- neural vocoder: HiFi-GAN generator (csrc/hifigan_ops.hip; inference, f32; additions, the ABI version stays) ----
+ * Rows are samples, channels-last: a tensor of a stage with `mult` rows per mel frame is [B][Lmax mult][C]; frame_lengths [B] i32 (device) are the
+ * utterances' frame counts L <= Lmax, an utterance owns rows [0, L mult) of its slab and only those are read or written (the waveform is zero beyond them):
+ * a tap outside them reads zero, padded rows are never written.  Every value depends on its own utterance and a fixed summation order only (no atomics, no
+ * workgroup waits on another).  All matrix products: v_mfma_f32_16x16x4_f32, against K-major weight images w [taps Cin][Cout], row = tap * Cin + input
+ * channel (a Conv1d weight [Cout][Cin][taps] permuted (2, 1, 0); a ConvTranspose1d weight [Cin][Cout][taps] permuted (2, 0, 1)); bias [Cout].
+ * slope is the LeakyReLU applied to the input rows as they are gathered (x > 0 ? x : x slope; 1.0f: none).
+ * Supported (glowtts_hifigan_supported(Cin, Cout, taps, dilation, rate), else GLOWTTS_E_ARG before any launch): Cin a multiple of 4 and Cout a multiple of 16,
+ * both <= 512; rate == 0, a convolution: taps odd <= 11, dilation in [1, 16] (Cout == 1: the conv_post form, dilation 1); rate >= 1, a transposed
+ * convolution: rate <= 16, rate <= taps <= 64, taps - rate even, at most 8 taps per phase, dilation 1.  1 <= B <= 65535, output rows Lmax mult (rate) <= 2^30.
+ * glowtts_hifigan_conv: y = conv(lrelu(in)) + bias, zero padding (taps - 1) / 2 * dilation, then + residual (NULL: none; may be `out`), then
+ *   out = y (accumulate 0), out = out + y (1: the MRF sum) or out = (out + y) / divisor (2: the last block of a stage).  in != out.  channels_first != 0:
+ *   `in` is [B][Cin][Lmax mult] (the mel as the caller holds it).  One launch, logged as `hifigan_conv`.
+ * glowtts_hifigan_upsample: the transposed convolution of stride `rate` and padding (taps - rate) / 2 in polyphase form: in [B][Lmax mult][Cin] ->
+ *   out [B][Lmax mult rate][Cout], exactly `rate` rows per input row; output row t sums the taps j with (t + p - j) % rate == 0 of input row
+ *   (t + p - j) / rate.  One launch, logged as `hifigan_upsample`.
+ * glowtts_hifigan_post: wav [B][Lmax mult] = tanh(conv(lrelu(in)) + bias[0]) with w [taps Cin], a fixed-order sum per row.  Logged as `hifigan_conv,post`. */
+int glowtts_hifigan_supported(int Cin, int Cout, int taps, int dilation, int rate);
+int glowtts_hifigan_conv(const float *in, const float *w, const float *bias, const float *residual, float *out, const int32_t *frame_lengths, int B,
+                         int Lmax, int mult, int Cin, int Cout, int taps, int dilation, float slope, int accumulate, float divisor, int channels_first,
+                         void *stream);
+int glowtts_hifigan_upsample(const float *in, const float *w, const float *bias, float *out, const int32_t *frame_lengths, int B, int Lmax, int mult,
+                             int Cin, int Cout, int taps, int rate, float slope, void *stream);
+int glowtts_hifigan_post(const float *in, const float *w, const float *bias, float *wav, const int32_t *frame_lengths, int B, int Lmax, int mult, int Cin,
+                         int taps, float slope, void *stream);
+
 /* ---- GE2E speaker encoder: stacked LSTM -> linear -> d-vector (csrc/ge2e_ops.hip; inference, f32; additions, the ABI version stays) ----
  * torch.nn.LSTM's definition (gates i, f, g, o; bias b_ih + b_hh; h0 = c0 = 0), then e = W h_{T-1}^{top} + b per slice, w = e / max(|e|, 1e-12),
  * d = normalize(mean over an utterance's Samples consecutive slices of w).  Every product runs on v_mfma_f32_16x16x4_f32; a sequence's values depend on
