@@ -1,0 +1,350 @@
+// Training the HiFi-GAN generator: the backward of csrc/hifigan_ops.hip for gfx950, f32.  Layouts, lengths and ownership are the forward's: rows are samples,
+// channels-last, an utterance owns rows [0, T_b) of its slab, nothing is read beyond them and nothing is written there.  Every matrix product runs on
+// v_mfma_f32_16x16x4_f32, every sum has one fixed order that depends on the sizes alone, no float atomics, no workgroup waits on another: every gradient is
+// bit-identical from run to run.
+//
+//   hifigan_conv_bwd      the data gradient of one dilated convolution, ONE launch: the convolution of dy with the tap-reversed, channel-transposed image
+//                         wt [taps Cout][Cin] (row = (taps - 1 - tap) Cout + output channel) on the forward's tile body (`hg_tile<.., BWD>`: LDS staging, zero
+//                         outside [0, T_b), chunked summation, sums from zero).  Epilogue: y = sum * lrelu'(x) * scale (x: the kept input of the forward's
+//                         LeakyReLU; 1 where x > 0, the slope elsewhere, at x == 0 as well) + residual * res_scale (the skip branch's gradient, may be `out`),
+//                         then out = y or out = out + y (the nk blocks of a stage add their input gradients into dU in block order).  The 1 / nk of the MRF mean
+//                         is `scale` / `res_scale` of the launches that read d acc.
+//   hifigan_upsample_bwd  the data gradient of the transposed convolution, ONE launch on the same kernel: dy [T u][Cout] IS [T][u Cout] in memory, so
+//                         dx[s] = sum over row offsets e in [lo, hi] of Wt_e^T dyview[s + e] is an ordinary few-tap convolution over rows with u Cout input
+//                         channels, against an image [(hi - lo + 1) u Cout][Cin] that holds zeros where a (phase, offset) pair has no tap.
+//   hifigan_post_bwd      d pre = d wav (1 - wav^2) (kept for the weight gradient); d rows = lrelu'(rows) * sum over the taps of w d pre, a fixed-order fmaf chain.
+//   hifigan_wgrad         dW[tap][ci][co] = sum over the utterances' rows of lrelu(x)[t + offset(tap)][ci] dy[t][co] and the bias gradient (column sums of dy, added in double).
+//                         A workgroup owns 32 x 32 (ci, co) of EVERY tap over one split of the rows: it stages 64 rows of lrelu(x) (with the taps' reach) and
+//                         of dy in LDS once and takes every tap from that one tile - the tap only shifts the row index - so both MFMA operands are reads of 16
+//                         consecutive channels of one row (row stride 48 floats: the four rows of a k step fall on distinct banks).  A wave owns one 16 x 16
+//                         tile per tap (taps x 4 accumulators).  The partition is fixed: per utterance, chunks of 1024 rows; a split is `group` consecutive
+//                         (utterance, chunk) units, walked in ascending order (group = 1024 / rows of a slab when that is below 1024, else 1).  The transposed
+//                         convolution uses the same kernel on the [T][u Cout] view: tap = row offset, column = (phase, output channel).
+//   hifigan_wgrad_sum     adds the splits in ascending order, scales, writes torch's layout (Conv1d [Cout][Cin][taps], ConvTranspose1d [Cin][Cout][k]; the view's
+//                         (offset, phase) pairs without a tap are dropped, the bias adds the phases in ascending order).
+#include "hifigan_common.h"
+
+namespace {
+
+constexpr int HW_ROWS = 1024;                              // rows of one chunk of the weight-gradient partition
+constexpr int HW_C = 32, HW_LD = 48;                       // channels of x and of dy per workgroup; LDS row stride (48 % 32 == 16: rows k .. k + 3 hit distinct banks)
+constexpr int HW_MAX_TAPS = 11;
+constexpr int HB_MAX_VIEW = 4096;                          // u Cout of the transposed convolution's view
+
+// The row offsets e = m - o0(ph) of the transposed convolution (k taps, rate u) in the [T][u Cout] view: [lo, hi]
+void hg_up_reach(int k, int u, int* lo, int* hi)
+{
+    *lo = 1 << 20; *hi = -(1 << 20);
+    for (int ph = 0; ph < u; ++ph) {
+        const int shift = ph + (k - u) / 2, j0 = shift % u, o0 = shift / u, nt = (k - j0 + u - 1) / u;
+        *lo = std::min(*lo, -o0);
+        *hi = std::max(*hi, nt - 1 - o0);
+    }
+}
+
+// grid (ceil(Lmax mult / 64), Cdx / (RT NT 16), B); dy [B][Lmax mult][Cdy] -> out [B][Lmax mult][Cdx];  dynamic LDS (64 + (taps - 1) |ts|) rows
+template <int RT, int NT>
+__global__ __launch_bounds__(THREADS) void hifigan_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ wt, const float* __restrict__ x,
+                                                              const float* res, float* out, const int32_t* __restrict__ lengths, int Lmax, int mult, int Cdy,
+                                                              int Cdx, int taps, int o0, int ts, float mslope, float scale, float res_scale, int accumulate)
+{
+    extern __shared__ __attribute__((aligned(16))) float hg_smem[];
+    const int b = blockIdx.z, s0 = blockIdx.x * TM;
+    const int Tmax = Lmax * mult, T = min(lengths[b], Lmax) * mult;
+    if (s0 >= T) return;                                   // (uniform over the workgroup)
+    const size_t row0 = (size_t)b * Tmax;
+    const HgTaps tp = {taps, o0, ts, 0, 1};
+    hg_tile<RT, NT, true>(dy + row0 * Cdy, wt, nullptr, res ? res + row0 * Cdx : nullptr, out + row0 * Cdx, hg_smem, T, Tmax, s0, Cdy, Cdx, blockIdx.y, tp, 1.f, 0,
+                          1, 0, accumulate, scale, x + row0 * Cdx, mslope, res_scale);
+}
+
+// grid (ceil(Lmax mult Cin / 4 / 256), B): a thread owns four channels of one row
+__global__ __launch_bounds__(THREADS) void hifigan_post_bwd_kernel(const float* __restrict__ dwav, const float* __restrict__ wav, const float* __restrict__ x,
+                                                                   const float* __restrict__ w, float* __restrict__ dpre, float* __restrict__ dx,
+                                                                   const int32_t* __restrict__ lengths, int Lmax, int mult, int Cin, int taps, float slope)
+{
+    const int b = blockIdx.y, cq = Cin >> 2;
+    const int64_t e = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    const int Tmax = Lmax * mult, T = min(lengths[b], Lmax) * mult;
+    const int s = (int)(e / cq), c = (int)(e - (int64_t)s * cq) * 4;
+    if (s >= T) return;                                    // rows beyond the utterance are never written
+    const size_t row0 = (size_t)b * Tmax;
+    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int j = 0; j < taps; ++j) {                       // row s fed output t = s - (j - (taps - 1) / 2) through tap j
+        const int t = s - j + (taps - 1) / 2;
+        if (t < 0 || t >= T) continue;
+        const float y = wav[row0 + t], d = dwav[row0 + t] * (1.f - y * y);
+        const float4 wv = *reinterpret_cast<const float4*>(w + j * Cin + c);
+        g.x = fmaf(wv.x, d, g.x); g.y = fmaf(wv.y, d, g.y); g.z = fmaf(wv.z, d, g.z); g.w = fmaf(wv.w, d, g.w);
+    }
+    const float4 xv = *reinterpret_cast<const float4*>(x + (row0 + s) * Cin + c);
+    g.x *= xv.x > 0.f ? 1.f : slope; g.y *= xv.y > 0.f ? 1.f : slope; g.z *= xv.z > 0.f ? 1.f : slope; g.w *= xv.w > 0.f ? 1.f : slope;
+    *reinterpret_cast<float4*>(dx + (row0 + s) * Cin + c) = g;
+    if (c == 0) {
+        const float y = wav[row0 + s];
+        dpre[row0 + s] = dwav[row0 + s] * (1.f - y * y);
+    }
+}
+
+struct HwArgs {
+    const float* a;            // x: [B][Tmax][Ca], or channels-first [B][Ca][Tmax]
+    const float* dy;           // [B][Tmax][Cd]
+    const int32_t* lengths;
+    float* partial;            // [splits][taps CiP CoP + CoP], CiP = 32 gridDim.x, CoP = 32 gridDim.y
+    int B, Lmax, mult, Ca, Cd, taps, o0, ts, cf, nchunk, group;
+    float slope;
+};
+
+// grid (ceil(Ca / 32), ceil(Cd / 32), splits); dynamic LDS (64 + reach + 64) rows of 48 floats
+template <int MAXT>
+__global__ __launch_bounds__(THREADS) void hifigan_wgrad_kernel(const HwArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float hw_smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
+    const int wr = wave & 1, wc = wave >> 1;               // the wave's tile: 16 channels of x, 16 of dy
+    const int ci0 = blockIdx.x * HW_C, co0 = blockIdx.y * HW_C;
+    const int last = a.o0 + (a.taps - 1) * a.ts, lo = min(a.o0, last), span = TM + max(a.o0, last) - lo;
+    float* Xs = hw_smem;
+    float* Ds = hw_smem + span * HW_LD;
+    const int Tmax = a.Lmax * a.mult;
+    const bool with_bias = blockIdx.x == 0 && wr == 0;     // (uniform over the wave)
+
+    f32x4 acc[MAXT];
+    double sb = 0.0;                                       // the bias gradient: column r of dy over the rows k = q (mod 4), in double
+#pragma unroll
+    for (int j = 0; j < MAXT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int units = a.B * a.nchunk, u_end = min(((int)blockIdx.z + 1) * a.group, units);
+    for (int unit = blockIdx.z * a.group; unit < u_end; ++unit) {
+        const int b = unit / a.nchunk, chunk = unit - b * a.nchunk;
+        const int T = min(a.lengths[b], a.Lmax) * a.mult, t_end = min((chunk + 1) * HW_ROWS, T);
+        const float* ab = a.a + (size_t)b * Tmax * a.Ca;
+        const float* db = a.dy + (size_t)b * Tmax * a.Cd;
+        for (int t0 = chunk * HW_ROWS; t0 < t_end; t0 += TM) {
+            __syncthreads();                               // every wave is done with the previous tile
+            if (a.cf) {                                    // channels-first source (the mel): consecutive threads along the rows
+                for (int e = tid; e < span * HW_C; e += THREADS) {
+                    const int c = e / span, row = e - c * span, t = t0 + lo + row;
+                    Xs[row * HW_LD + c] = (t >= 0 && t < T && ci0 + c < a.Ca) ? lrelu(ab[(size_t)(ci0 + c) * Tmax + t], a.slope) : 0.f;
+                }
+            } else {
+                for (int e = tid; e < span * (HW_C / 4); e += THREADS) {
+                    const int row = e / (HW_C / 4), k4 = (e - row * (HW_C / 4)) * 4, t = t0 + lo + row;
+                    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (t >= 0 && t < T && ci0 + k4 < a.Ca) {
+                        v = *reinterpret_cast<const float4*>(ab + (size_t)t * a.Ca + ci0 + k4);
+                        v.x = lrelu(v.x, a.slope); v.y = lrelu(v.y, a.slope); v.z = lrelu(v.z, a.slope); v.w = lrelu(v.w, a.slope);
+                    }
+                    *reinterpret_cast<float4*>(Xs + row * HW_LD + k4) = v;
+                }
+            }
+            if (a.Cd & 3) {                                // conv_post: one column
+                for (int e = tid; e < TM * HW_C; e += THREADS) {
+                    const int row = e / HW_C, c = e - row * HW_C, t = t0 + row;
+                    Ds[row * HW_LD + c] = (t < t_end && co0 + c < a.Cd) ? db[(size_t)t * a.Cd + co0 + c] : 0.f;
+                }
+            } else {
+                for (int e = tid; e < TM * (HW_C / 4); e += THREADS) {
+                    const int row = e / (HW_C / 4), k4 = (e - row * (HW_C / 4)) * 4, t = t0 + row;
+                    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (t < t_end && co0 + k4 < a.Cd) v = *reinterpret_cast<const float4*>(db + (size_t)t * a.Cd + co0 + k4);
+                    *reinterpret_cast<float4*>(Ds + row * HW_LD + k4) = v;
+                }
+            }
+            __syncthreads();
+            const int k_end = min(TM, (t_end - t0 + 3) & ~3);      // rows of dy beyond the chunk are zero
+            const float* xa = Xs + (q + a.o0 - lo) * HW_LD + wr * 16 + r;
+            const float* da = Ds + q * HW_LD + wc * 16 + r;
+            // this tile's chains start at zero: summing in blocks keeps the rounding error of thousands of rows near that of sqrt of them
+            f32x4 part[MAXT];
+#pragma unroll
+            for (int j = 0; j < MAXT; ++j) part[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int k0 = 0; k0 < k_end; k0 += 4) {
+                const float bv = da[k0 * HW_LD];
+#pragma unroll
+                for (int j = 0; j < MAXT; ++j)
+                    if (j < a.taps) part[j] = mfma4(xa[(k0 + j * a.ts) * HW_LD], bv, part[j]);
+                if (with_bias) sb += (double)bv;
+            }
+#pragma unroll
+            for (int j = 0; j < MAXT; ++j) acc[j] += part[j];
+        }
+    }
+
+    const int CiP = gridDim.x * HW_C, CoP = gridDim.y * HW_C;
+    float* out = a.partial + (size_t)blockIdx.z * ((size_t)a.taps * CiP * CoP + CoP);
+#pragma unroll
+    for (int j = 0; j < MAXT; ++j)
+        if (j < a.taps) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) out[((size_t)j * CiP + ci0 + wr * 16 + q * 4 + i) * CoP + co0 + wc * 16 + r] = acc[j][i];
+        }
+    if (with_bias) {                                       // (q0 + q1) + (q2 + q3): a column sum is a handful of numbers that nearly cancel, and a float32 chain
+        sb += __shfl_xor(sb, 16);                          // over 1200 rows missed the bar on conv_post's single bias
+        sb += __shfl_xor(sb, 32);
+        if (q == 0) out[(size_t)a.taps * CiP * CoP + co0 + wc * 16 + r] = (float)sb;
+    }
+}
+
+// One thread per element of a split's partial, in its order (coalesced reads); rate 0: dw [Cd][Ca][taps]; rate u: the view's column is (phase, output
+// channel), its tap the row offset o0 + j: dw [Ca][Cout][k] with Cout = Cd / u.
+__global__ __launch_bounds__(THREADS) void hifigan_wgrad_sum_kernel(const float* __restrict__ partial, float* __restrict__ dw, float* __restrict__ dbias, int splits,
+                                                                    int taps, int Ca, int Cd, int CiP, int CoP, int o0, int rate, int k, float scale)
+{
+    const int64_t body = (int64_t)taps * CiP * CoP, P = body + CoP, e = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    if (e >= P) return;
+    if (e >= body) {                                       // the bias: the phases of an output channel in ascending order
+        const int co = (int)(e - body), u = rate ? rate : 1, Cout = Cd / u;
+        if (co >= Cout || !dbias) return;
+        double s = 0.0;
+        for (int ph = 0; ph < u; ++ph)
+            for (int z = 0; z < splits; ++z) s += (double)partial[(size_t)z * P + e + ph * Cout];
+        dbias[co] = (float)s * scale;
+        return;
+    }
+    const int n = (int)(e % CoP), ci = (int)((e / CoP) % CiP), j = (int)(e / ((int64_t)CoP * CiP));
+    if (n >= Cd || ci >= Ca) return;
+    size_t dst;
+    if (rate == 0) {
+        dst = ((size_t)n * Ca + ci) * taps + j;
+    } else {
+        const int Cout = Cd / rate, ph = n / Cout, co = n - ph * Cout;
+        const int shift = ph + (k - rate) / 2, j0 = shift % rate, m = shift / rate - (o0 + j);
+        if (m < 0 || j0 + m * rate >= k) return;           // this (phase, offset) pair has no tap
+        dst = ((size_t)ci * Cout + co) * k + j0 + m * rate;
+    }
+    float s = 0.f;
+    for (int z = 0; z < splits; ++z) s += partial[(size_t)z * P + e];
+    dw[dst] = s * scale;
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------------------------
+// the weight gradient's walk of a convolution (rate 0) or of a transposed convolution's view: taps, first offset, step, columns of dy
+bool hw_walk(int Cd, int taps, int dilation, int rate, int* wt, int* o0, int* ts, int* cd)
+{
+    if (rate == 0) {
+        *wt = taps; *o0 = -((taps - 1) / 2) * dilation; *ts = dilation; *cd = Cd;
+    } else {
+        int lo, hi;
+        hg_up_reach(taps, rate, &lo, &hi);
+        *wt = hi - lo + 1; *o0 = -hi; *ts = 1; *cd = rate * Cd;
+    }
+    return *wt >= 1 && *wt <= HW_MAX_TAPS;
+}
+
+int hw_group(int Tmax) { return Tmax < HW_ROWS ? HW_ROWS / Tmax : 1; }
+int hw_nchunk(int Tmax) { return (Tmax + HW_ROWS - 1) / HW_ROWS; }
+int hw_splits(int B, int Tmax)
+{
+    const int64_t units = (int64_t)B * hw_nchunk(Tmax), g = hw_group(Tmax);
+    return (int)((units + g - 1) / g);
+}
+
+template <int RT, int NT>
+int hb_launch(dim3 grid, int lds, hipStream_t s, const float* dy, const float* wt, const float* x, const float* res, float* out, const int32_t* lengths, int Lmax,
+              int mult, int Cdy, int Cdx, int taps, int o0, int ts, float mslope, float scale, float res_scale, int accumulate)
+{
+    if (allow_lds<&hifigan_bwd_kernel<RT, NT>>(lds) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;
+    hipLaunchKernelGGL((hifigan_bwd_kernel<RT, NT>), grid, dim3(THREADS), (size_t)lds, s, dy, wt, x, res, out, lengths, Lmax, mult, Cdy, Cdx, taps, o0, ts, mslope, scale,
+                       res_scale, accumulate);
+    return GLOWTTS_OK;
+}
+
+int hb_dispatch(const float* dy, const float* wt, const float* x, const float* res, float* out, const int32_t* lengths, int B, int Lmax, int mult, int Cdy, int Cdx,
+                int taps, int o0, int ts, float mslope, float scale, float res_scale, int accumulate, void* stream)
+{
+    int rt, nt;
+    hg_layout(Cdx, &rt, &nt);
+    const int lds = hg_lds_bytes((taps - 1) * ts, Cdy);
+    const dim3 grid((Lmax * mult + TM - 1) / TM, Cdx / (rt * nt * 16), B);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+#define HB_ARGS grid, lds, s, dy, wt, x, res, out, lengths, Lmax, mult, Cdy, Cdx, taps, o0, ts, mslope, scale, res_scale, accumulate
+    if (rt == 4 && nt == 2) return hb_launch<4, 2>(HB_ARGS);
+    if (rt == 4) return hb_launch<4, 1>(HB_ARGS);
+    if (nt == 2) return hb_launch<1, 2>(HB_ARGS);
+    return hb_launch<1, 1>(HB_ARGS);
+#undef HB_ARGS
+}
+
+}  // namespace
+
+extern "C" int glowtts_hifigan_train_supported(int Cin, int Cout, int taps, int dilation, int rate)
+{
+    if (!glowtts_hifigan_supported(Cin, Cout, taps, dilation, rate)) return 0;
+    int wt, o0, ts, cd;
+    if (!hw_walk(Cout, taps, dilation, rate, &wt, &o0, &ts, &cd)) return 0;
+    if (rate == 0) return Cout == 1 || hg_lds_bytes((taps - 1) * dilation, Cout) <= MAX_LDS;      // (the data gradient also needs Cin % 16 == 0: conv_pre has none)
+    return Cin % 16 == 0 && cd <= HB_MAX_VIEW && hg_lds_bytes(wt - 1, cd) <= MAX_LDS;
+}
+
+extern "C" int64_t glowtts_hifigan_wgrad_work_floats(int B, int Lmax, int mult, int Cin, int Cout, int taps, int rate)
+{
+    int wt, o0, ts, cd;
+    if (bad_batch(B, Lmax, mult) || Cin < 1 || Cout < 1 || rate < 0 || rate > HG_MAX_RATE || taps < 1 || !hw_walk(Cout, taps, 1, rate, &wt, &o0, &ts, &cd)) return 0;
+    const int64_t CiP = (Cin + HW_C - 1) / HW_C * HW_C, CoP = (cd + HW_C - 1) / HW_C * HW_C;
+    return (int64_t)hw_splits(B, Lmax * mult) * (wt * CiP * CoP + CoP);
+}
+
+extern "C" int glowtts_hifigan_conv_bwd(const float* dy, const float* wt, const float* x, const float* residual, float* out, const int32_t* frame_lengths, int B,
+                                        int Lmax, int mult, int Cin, int Cout, int taps, int dilation, float mask_slope, float scale, float res_scale,
+                                        int accumulate, void* stream)
+{
+    if (!dy || !wt || !x || !out || !frame_lengths || dy == out || bad_batch(B, Lmax, mult) || Cout == 1 || Cin % 16 ||
+        !glowtts_hifigan_train_supported(Cin, Cout, taps, dilation, 0) || accumulate < 0 || accumulate > 1)
+        return GLOWTTS_E_ARG;
+    if (hb_dispatch(dy, wt, x, residual, out, frame_lengths, B, Lmax, mult, Cout, Cin, taps, -((taps - 1) / 2) * dilation, dilation, mask_slope, scale, res_scale,
+                    accumulate, stream) != GLOWTTS_OK)
+        return GLOWTTS_E_LAUNCH;
+    GLOWTTS_NOTE_STATIC("hifigan_conv_bwd");
+    RET_LAUNCH();
+}
+
+extern "C" int glowtts_hifigan_upsample_bwd(const float* dy, const float* wt, const float* x, float* out, const int32_t* frame_lengths, int B, int Lmax, int mult,
+                                            int Cin, int Cout, int taps, int rate, float mask_slope, void* stream)
+{
+    if (!dy || !wt || !x || !out || !frame_lengths || dy == out || rate < 1 || rate > HG_MAX_RATE || bad_batch(B, Lmax, mult) || (int64_t)mult * rate > (1 << 16) ||
+        bad_batch(B, Lmax, mult * rate) || !glowtts_hifigan_train_supported(Cin, Cout, taps, 1, rate))
+        return GLOWTTS_E_ARG;
+    int lo, hi;
+    hg_up_reach(taps, rate, &lo, &hi);
+    if (hb_dispatch(dy, wt, x, nullptr, out, frame_lengths, B, Lmax, mult, rate * Cout, Cin, hi - lo + 1, lo, 1, mask_slope, 1.f, 1.f, 0, stream) != GLOWTTS_OK)
+        return GLOWTTS_E_LAUNCH;
+    GLOWTTS_NOTE_STATIC("hifigan_upsample_bwd");
+    RET_LAUNCH();
+}
+
+extern "C" int glowtts_hifigan_post_bwd(const float* dwav, const float* wav, const float* x, const float* w, float* dpre, float* dx, const int32_t* frame_lengths,
+                                        int B, int Lmax, int mult, int Cin, int taps, float slope, void* stream)
+{
+    if (!dwav || !wav || !x || !w || !dpre || !dx || !frame_lengths || bad_batch(B, Lmax, mult) || !glowtts_hifigan_supported(Cin, 1, taps, 1, 0)) return GLOWTTS_E_ARG;
+    const int64_t threads = (int64_t)Lmax * mult * (Cin / 4);
+    hipLaunchKernelGGL(hifigan_post_bwd_kernel, dim3((unsigned)((threads + THREADS - 1) / THREADS), B), dim3(THREADS), 0, static_cast<hipStream_t>(stream), dwav, wav, x,
+                       w, dpre, dx, frame_lengths, Lmax, mult, Cin, taps, slope);
+    GLOWTTS_NOTE_STATIC("hifigan_post_bwd");
+    RET_LAUNCH();
+}
+
+extern "C" int glowtts_hifigan_wgrad(const float* x, const float* dy, const int32_t* frame_lengths, float* work, float* dw, float* dbias, int B, int Lmax, int mult,
+                                     int Cin, int Cout, int taps, int dilation, int rate, float slope, float scale, int channels_first, void* stream)
+{
+    int wt, o0, ts, cd;
+    if (!x || !dy || !frame_lengths || !work || !dw || !dbias || bad_batch(B, Lmax, mult) || !glowtts_hifigan_train_supported(Cin, Cout, taps, dilation, rate) ||
+        (channels_first && rate) || !hw_walk(Cout, taps, dilation, rate, &wt, &o0, &ts, &cd))
+        return GLOWTTS_E_ARG;
+    const int Tmax = Lmax * mult, splits = hw_splits(B, Tmax);
+    if (splits > 65535) return GLOWTTS_E_ARG;
+    const dim3 grid((Cin + HW_C - 1) / HW_C, (cd + HW_C - 1) / HW_C, splits);
+    const int CiP = grid.x * HW_C, CoP = grid.y * HW_C;
+    const int lds = (TM + (wt - 1) * ts + TM) * HW_LD * 4;         // at most (64 + 160 + 64) rows: 55296 bytes, within the default
+    const HwArgs a = {x, dy, frame_lengths, work, B, Lmax, mult, Cin, cd, wt, o0, ts, channels_first, hw_nchunk(Tmax), hw_group(Tmax), slope};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (wt <= 3) hipLaunchKernelGGL(hifigan_wgrad_kernel<3>, grid, dim3(THREADS), (size_t)lds, s, a);
+    else if (wt <= 7) hipLaunchKernelGGL(hifigan_wgrad_kernel<7>, grid, dim3(THREADS), (size_t)lds, s, a);
+    else hipLaunchKernelGGL(hifigan_wgrad_kernel<HW_MAX_TAPS>, grid, dim3(THREADS), (size_t)lds, s, a);
+    GLOWTTS_NOTE_STATIC("hifigan_wgrad");
+    const int64_t P = (int64_t)wt * CiP * CoP + CoP;
+    hipLaunchKernelGGL(hifigan_wgrad_sum_kernel, dim3((unsigned)((P + THREADS - 1) / THREADS)), dim3(THREADS), 0, s, work, dw, dbias, splits, wt, Cin, cd, CiP, CoP, o0,
+                       rate, taps, scale);
+    GLOWTTS_NOTE_STATIC("hifigan_wgrad_sum");
+    RET_LAUNCH();
+}

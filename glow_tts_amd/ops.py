@@ -211,3 +211,36 @@ def hifigan_post(x, w, bias, wav, frame_lengths, Lmax, mult, taps, slope):
     """x [B, Lmax * mult, Cin] -> wav [B, Lmax * mult] = tanh(conv_post(lrelu(x))), zero beyond each utterance (glowtts_hifigan_post)."""
     _lib.api().glowtts_hifigan_post(_lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(wav), _lib.ptr(frame_lengths), x.shape[0], int(Lmax), int(mult), x.shape[2],
                                     int(taps), float(slope), _lib.stream())
+
+
+# ---- training the HiFi-GAN generator (csrc/hifigan_train_ops.hip).  x: the forward's input before its LeakyReLU; wt: the transposed images of vocoder.py ----
+def hifigan_conv_bwd(dy, wt, x, out, frame_lengths, Lmax, mult, taps, dilation, mask_slope, residual=None, scale=1.0, res_scale=1.0, accumulate=False):
+    """dy [B, Lmax * mult, Cout] -> out [B, Lmax * mult, Cin]: the data gradient of `hifigan_conv` with the mask / residual / accumulate epilogue
+    (glowtts_hifigan_conv_bwd)."""
+    _lib.api().glowtts_hifigan_conv_bwd(_lib.ptr(dy), _lib.ptr(wt), _lib.ptr(x), _lib.ptr(residual), _lib.ptr(out), _lib.ptr(frame_lengths), dy.shape[0], int(Lmax),
+                                        int(mult), out.shape[2], dy.shape[2], int(taps), int(dilation), float(mask_slope), float(scale), float(res_scale),
+                                        int(bool(accumulate)), _lib.stream())
+
+
+def hifigan_upsample_bwd(dy, wt, x, out, frame_lengths, Lmax, mult, taps, rate, mask_slope):
+    """dy [B, Lmax * mult * rate, Cout] -> out [B, Lmax * mult, Cin]: the data gradient of `hifigan_upsample` (glowtts_hifigan_upsample_bwd)."""
+    _lib.api().glowtts_hifigan_upsample_bwd(_lib.ptr(dy), _lib.ptr(wt), _lib.ptr(x), _lib.ptr(out), _lib.ptr(frame_lengths), dy.shape[0], int(Lmax), int(mult),
+                                            out.shape[2], dy.shape[2], int(taps), int(rate), float(mask_slope), _lib.stream())
+
+
+def hifigan_post_bwd(dwav, wav, x, w, dpre, dx, frame_lengths, Lmax, mult, taps, slope):
+    """d wav [B, Lmax * mult] -> dpre [B, Lmax * mult] and dx [B, Lmax * mult, Cin], the gradient of the rows entering conv_post (glowtts_hifigan_post_bwd)."""
+    _lib.api().glowtts_hifigan_post_bwd(_lib.ptr(dwav), _lib.ptr(wav), _lib.ptr(x), _lib.ptr(w), _lib.ptr(dpre), _lib.ptr(dx), _lib.ptr(frame_lengths), x.shape[0],
+                                        int(Lmax), int(mult), x.shape[2], int(taps), float(slope), _lib.stream())
+
+
+def hifigan_wgrad_work_floats(B, Lmax, mult, Cin, Cout, taps, rate=0):
+    return int(_lib.api().glowtts_hifigan_wgrad_work_floats(int(B), int(Lmax), int(mult), int(Cin), int(Cout), int(taps), int(rate)))
+
+
+def hifigan_wgrad(x, dy, frame_lengths, work, dw, dbias, Lmax, mult, taps, dilation=1, rate=0, slope=1.0, scale=1.0, channels_first=False):
+    """dw (torch's layout: Conv1d [Cout, Cin, taps]; rate >= 1: ConvTranspose1d [Cin, Cout, taps]) and dbias [Cout] of one convolution from its input x before
+    the LeakyReLU and dy; dy [B, Lmax * mult (* rate)] for conv_post (glowtts_hifigan_wgrad)."""
+    Cin = x.shape[1] if channels_first else x.shape[2]
+    _lib.api().glowtts_hifigan_wgrad(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(frame_lengths), _lib.ptr(work), _lib.ptr(dw), _lib.ptr(dbias), x.shape[0], int(Lmax), int(mult),
+                                     Cin, dbias.shape[0], int(taps), int(dilation), int(rate), float(slope), float(scale), int(bool(channels_first)), _lib.stream())

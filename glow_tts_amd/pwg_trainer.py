@@ -29,8 +29,8 @@ BUNDLES = (("", "model", "pwg", pwg_load, ("generator", "Optimizer", "Steps")),
            ("disc_", "discriminator", "pwg_disc", pwg_disc_load, ("discriminator", "Discriminator_Optimizer", "Discriminator_Steps")))
 
 
-def train_settings(hp):
-    """The optional yaml block `Vocoder.Train` over DEFAULTS (`hparams.overlay_settings`), checked: a ValueError names every bad key.  The optional
+def train_settings(hp, defaults=DEFAULTS):
+    """The optional yaml block `Vocoder.Train` over `defaults` (`hparams.overlay_settings`), checked: a ValueError names every bad key.  The optional
     sub-block `Discriminator` (`vocoder.pwg_disc_settings`) appears in the result only when the yaml has it."""
     def rules(s, need):
         for k in ("Batch_Size", "Segment_Frames", "Max_Step", "Checkpoint_Save_Interval", "Evaluation_Interval"):
@@ -38,7 +38,7 @@ def train_settings(hp):
         for k in ("Learning_Rate", "Epsilon", "Gradient_Norm"):
             need(k, lambda v: float(v) > 0, "positive")
         need("Learning_Rate_Decay", lambda v: int(v["Step"]) >= 1 and 0 < float(v["Gamma"]) <= 1, "Step >= 1, 0 < Gamma <= 1")
-    s = overlay_settings(getattr(getattr(hp, "Vocoder", None), "Train", None), DEFAULTS, TRAIN_KEY, "vocoder", rules, also=("Discriminator",))
+    s = overlay_settings(getattr(getattr(hp, "Vocoder", None), "Train", None), defaults, TRAIN_KEY, "vocoder", rules, also=("Discriminator",))
     s["STFT_Resolutions"] = stft_loss_geometry(s["STFT_Resolutions"], int(s["Segment_Frames"]) * int(hp.Sound.Frame_Shift))
     if "Discriminator" in s:
         s["Discriminator"] = pwg_disc_settings(hp)
@@ -96,14 +96,16 @@ class Sampler(aux_trainer.PatternSampler):
 
 
 class PWG_Trainer(aux_trainer.Trainer):
+    """A subclass for another generator (`hifigan_trainer.HiFiGAN_Trainer`) replaces PREFIX, BUNDLES and the four hooks below `__init__`."""
     PREFIX = "PWG"
+    BUNDLES = BUNDLES
 
     def __init__(self, steps=0, hp=None, device="cuda:0", seed=0):
         hp = hp if hp is not None else get_hp()
-        self.geo = pwg_geometry(hp)
-        s = train_settings(hp)
+        self.geo = self.geometry(hp)
+        s = self.settings(hp)
         super().__init__(hp, s, steps, device, seed, Sampler, (s["Batch_Size"], s["Segment_Frames"], self.geo["hop"]))
-        self.model = ParallelWaveGAN(self.hp, self.device, trainable=True, seed=self.seed, precision="f32")     # (Vocoder.Precision is a serving setting)
+        self.model = self.make_model()
         self.criterion = MultiResolutionSTFTLoss(s["STFT_Resolutions"], self.device)
         self.params = list(self.model.params.values())
         self.optimizer = optim.RAdam(self.params, lr=float(s["Learning_Rate"]), eps=float(s["Epsilon"]))
@@ -115,6 +117,15 @@ class PWG_Trainer(aux_trainer.Trainer):
             self.disc_optimizer = optim.RAdam(self.disc_params, lr=float(self.disc_set["Learning_Rate"]), eps=float(self.disc_set["Epsilon"]))
         if self.steps > 0:
             self.Load_Checkpoint()
+
+    geometry, settings = staticmethod(pwg_geometry), staticmethod(train_settings)
+
+    def make_model(self):
+        return ParallelWaveGAN(self.hp, self.device, trainable=True, seed=self.seed, precision="f32")            # (Vocoder.Precision is a serving setting)
+
+    def generate(self, mel, lengths, step):
+        """The generator's waveform of batch `step` with its backward"""
+        return self.model.generate(mel, lengths, seeds=self.seeds(step, mel.shape[0]))[0]
 
     def learning_rate(self, step):
         return step_decay(self.set, step)
@@ -134,7 +145,7 @@ class PWG_Trainer(aux_trainer.Trainer):
         forward over [target; wav]; L_G's backward reaches the generator alone, L_D's the discriminator alone."""
         mel, target = mel.to(self.device, non_blocking=True), target.to(self.device, non_blocking=True)
         B, _, L = mel.shape
-        wav, _ = self.model.generate(mel, [L] * B, seeds=self.seeds(step, B))
+        wav = self.generate(mel, [L] * B, step)
         stft = self.criterion(wav, target)
         if not adversarial:
             return stft
@@ -168,7 +179,7 @@ class PWG_Trainer(aux_trainer.Trainer):
         if self.adversarial(self.steps):
             return self.Adversarial_Step(mel, target)
         loss = self.forward(mel, target, self.steps)
-        norm, = self.update(BUNDLES[:1], [loss])
+        norm, = self.update(self.BUNDLES[:1], [loss])
         self.last = {"Loss": loss.detach(), "Terms": self.criterion.terms, "Gradient_Norm": norm}
         return loss.detach()
 
@@ -176,7 +187,7 @@ class PWG_Trainer(aux_trainer.Trainer):
         """A step of stage two: both updates are computed from the state before the step (the discriminator's forward and both backwards precede both updates).
         The backward of `loss` reaches the generator alone (the fake rows' data chain, no weight gradients), that of `d_loss` the discriminator alone."""
         loss, d_loss, adv_terms, stft = self.forward(mel, target, self.steps, adversarial=True)
-        norm, d_norm = self.update(BUNDLES, [loss, d_loss])
+        norm, d_norm = self.update(self.BUNDLES, [loss, d_loss])
         self.last = {"Loss": loss.detach(), "Terms": self.criterion.terms, "Gradient_Norm": norm, "STFT_Loss": stft.detach(), "Discriminator_Loss": d_loss.detach(),
                      "L_adv": adv_terms[0], "Real_Term": adv_terms[1], "Fake_Term": adv_terms[2], "Discriminator_Gradient_Norm": d_norm}
         return loss.detach()
@@ -200,7 +211,7 @@ class PWG_Trainer(aux_trainer.Trainer):
         return ev if self.discriminator is None else ev + (torch.stack(adv).mean(0),)
 
     def bundles(self):
-        return BUNDLES if self.discriminator is not None else BUNDLES[:1]
+        return self.BUNDLES if self.discriminator is not None else self.BUNDLES[:1]
 
     def state_dict(self):
         state = {}

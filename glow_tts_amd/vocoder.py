@@ -1110,19 +1110,228 @@ def hifigan_up_image(weight):
     return weight.permute(2, 0, 1).reshape(-1, weight.shape[1]).contiguous()
 
 
+# ---- training (csrc/hifigan_train_ops.hip; DESIGN.md "Training the HiFi-GAN generator") ----
+HIFIGAN_TRAIN_MAX_OFFSETS, HIFIGAN_TRAIN_MAX_VIEW = 11, 4096
+
+
+def hifigan_conv_image_t(weight):
+    """Conv1d weight [Cout, Cin, taps] -> the data gradient's image [taps * Cout, Cin]: tap-reversed and channel-transposed, row = (taps - 1 - tap) * Cout +
+    output channel.  The convolution of dy (same padding, same dilation) with it is dx."""
+    return weight.flip(2).permute(2, 0, 1).reshape(-1, weight.shape[1]).contiguous()
+
+
+def hifigan_up_reach(u, k):
+    """(lo, hi): the range of the row offsets e = m - o0(ph) that the transposed convolution (rate u, k taps, padding (k - u) / 2) reaches in dy read as
+    [T, u * Cout]: output row u s + ph sums the taps j0 + m u of input row s + o0 - m (j0 = (ph + p) % u, o0 = (ph + p) // u), so dx[s] reads view row s + e."""
+    p, lo, hi = (k - u) // 2, None, None
+    for ph in range(u):
+        j0, o0 = (ph + p) % u, (ph + p) // u
+        nt = (k - j0 + u - 1) // u
+        lo, hi = -o0 if lo is None else min(lo, -o0), nt - 1 - o0 if hi is None else max(hi, nt - 1 - o0)
+    return lo, hi
+
+
+def hifigan_up_taps(u, k):
+    """[hi - lo + 1, u] int64: the tap j0 + (e + o0) u of (row offset e, phase ph), k where the pair has none"""
+    p = (k - u) // 2
+    lo, hi = hifigan_up_reach(u, k)
+    idx = torch.full((hi - lo + 1, u), k, dtype=torch.int64)
+    for ph in range(u):
+        j0, o0 = (ph + p) % u, (ph + p) // u
+        for m in range((k - j0 + u - 1) // u):
+            idx[m - o0 - lo, ph] = j0 + m * u
+    return idx
+
+
+def hifigan_up_image_t(weight, u, taps=None):
+    """ConvTranspose1d weight [Cin, Cout, k] of rate u -> the data gradient's image [(hi - lo + 1) * u * Cout, Cin] over dy read as [T, u * Cout]:
+    row = (e - lo) * u * Cout + ph * Cout + output channel holds the tap of (e, ph), zero where there is none (`hifigan_up_taps`, given as `taps` when cached).
+    A convolution over the view's rows with offsets lo .. hi against it is dx."""
+    k = weight.shape[2]
+    idx = (hifigan_up_taps(u, k) if taps is None else taps).to(weight.device)
+    padded = torch.cat([weight, weight.new_zeros(weight.shape[0], weight.shape[1], 1)], dim=2)
+    return padded[:, :, idx].permute(2, 3, 1, 0).reshape(-1, weight.shape[0]).contiguous()
+
+
+def hifigan_convs(geo):
+    """Every convolution of the generator in forward order: (state-dict prefix, Cin, Cout, taps, dilation, rate, rows per frame of its input)"""
+    out = [("conv_pre", geo["A"], geo["C0"], HIFIGAN_PRE_TAPS, 1, 0, 1)]
+    cin, mult = geo["C0"], 1
+    for i, (u, k, c) in enumerate(zip(geo["rates"], geo["kernels"], geo["channels"])):
+        out.append((f"ups.{i}", cin, c, k, 1, u, mult))
+        mult *= u
+        for j, (rk, ds) in enumerate(zip(geo["rk"], geo["rd"])):
+            for m, d in enumerate(ds):
+                out.append((f"resblocks.{i * geo['nk'] + j}.convs1.{m}", c, c, rk, d, 0, mult))
+                if geo["resblock"] == "1":
+                    out.append((f"resblocks.{i * geo['nk'] + j}.convs2.{m}", c, c, rk, 1, 0, mult))
+        cin = c
+    out.append(("conv_post", cin, 1, HIFIGAN_POST_TAPS, 1, 0, mult))
+    return out
+
+
+def hifigan_train_geometry(geo):
+    """Raises ValueError naming the yaml keys for sizes that infer but cannot train (the backward's limits, `glowtts_hifigan_train_supported`): a transposed
+    convolution's data gradient runs over dy read as [T, u * Cout] - at most HIFIGAN_TRAIN_MAX_VIEW columns and HIFIGAN_TRAIN_MAX_OFFSETS row offsets - and
+    writes Cin columns in tiles of 16.  Construction with trainable=True only."""
+    cin = geo["C0"]
+    for u, k, c in zip(geo["rates"], geo["kernels"], geo["channels"]):
+        lo, hi = hifigan_up_reach(u, k)
+        if u * c > HIFIGAN_TRAIN_MAX_VIEW or hi - lo + 1 > HIFIGAN_TRAIN_MAX_OFFSETS or cin % 16:
+            raise ValueError(f"Vocoder.Upsample_Rates = {geo['rates']} with Vocoder.Upsample_Kernel_Sizes = {geo['kernels']} and Vocoder.Initial_Channels = {geo['C0']}: "
+                             f"training needs rate * channels <= {HIFIGAN_TRAIN_MAX_VIEW} and at most {HIFIGAN_TRAIN_MAX_OFFSETS} row offsets per stage, got u = {u}, "
+                             f"k = {k} at {c} channels (inference supports these sizes, trainable=True does not)")
+        cin = c
+    supported = _lib.api().glowtts_hifigan_train_supported
+    for name, ci, co, taps, d, rate, _ in hifigan_convs(geo):
+        if not supported(ci, co, taps, d, rate):
+            raise ValueError(f"the Vocoder block's sizes do not train: {name} ({ci} -> {co} channels, {taps} taps, dilation {d}, rate {rate}) is beyond the backward "
+                             "kernels (Vocoder.Initial_Channels, Vocoder.Upsample_Rates, Vocoder.Upsample_Kernel_Sizes, Vocoder.Resblock_Kernel_Sizes, "
+                             "Vocoder.Resblock_Dilations)")
+
+
+def hifigan_train_launches(geo):
+    """Launches of one training forward + backward by their names in the launch log: the forward is the inference launches (`hifigan_launches`); the backward is
+    conv_post's, then per convolution one data gradient (conv_pre has none: the mel gets no gradient) and the weight gradient's two launches."""
+    convs = hifigan_launches(geo) - 2 - len(geo["rates"])           # the resblock convolutions
+    n = hifigan_launches(geo)
+    return {"hifigan_conv": 1 + convs, "hifigan_upsample": len(geo["rates"]), "hifigan_conv,post": 1, "hifigan_post_bwd": 1, "hifigan_conv_bwd": convs,
+            "hifigan_upsample_bwd": len(geo["rates"]), "hifigan_wgrad": n, "hifigan_wgrad_sum": n}
+
+
+def hifigan_train_keep_floats(geo):
+    """Floats per mel frame that a training forward keeps for the backward: conv_pre's output, per stage the transposed convolution's output, every
+    resblock convolution's input but the first of a block (which is that output) and the stage's mean, and the waveform."""
+    per_block = [(2 if geo["resblock"] == "1" else 1) * len(ds) - 1 for ds in geo["rd"]]
+    n, mult = geo["C0"], 1
+    for u, c in zip(geo["rates"], geo["channels"]):
+        mult *= u
+        n += mult * c * (2 + sum(per_block))
+    return n + geo["hop"]
+
+
+def hifigan_train_forward(voc, mels, lengths):
+    """The inference launches with every convolution writing a slab of its own -> dict(wav, x0, stages): stages[i] = dict(U, blocks, acc) with blocks[j][m] =
+    (x_m, t_m): the input of step m of resblock j (x_0 is U) and, type '1', the input of its second convolution.  Only these pre-activation tensors are kept;
+    LeakyReLU and its mask are recomputed from them.  The arithmetic is `HiFiGAN.__call__`'s launch for launch: the waveform is bit-identical."""
+    g = voc.geo
+    B, _, L = mels.shape
+    f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=mels.device)
+    x, mult, nk, stages = f(B, L, g["C0"]), 1, g["nk"], []
+    ops.hifigan_conv(mels, *voc.pre, x, lengths, L, 1, HIFIGAN_PRE_TAPS, 1, channels_first=True)
+    fwd = {"x0": x, "stages": stages}
+    for i, (u, c) in enumerate(zip(g["rates"], g["channels"])):
+        U, acc = f(B, L * mult * u, c), f(B, L * mult * u, c)
+        ops.hifigan_upsample(x, *voc.ups[i], U, lengths, L, mult, g["kernels"][i], u, HIFIGAN_SLOPE)
+        mult *= u
+        blocks = []
+        for j in range(nk):
+            rk, steps, cur, kept = g["rk"][j], voc.blocks[i * nk + j], U, []
+            mode = 0 if j == 0 else (2 if j == nk - 1 else 1)
+            for m, (d, c1, c2) in enumerate(steps):
+                last = m == len(steps) - 1
+                dst = acc if last else torch.empty_like(U)
+                if c2 is not None:
+                    t = torch.empty_like(U)
+                    ops.hifigan_conv(cur, *c1, t, lengths, L, mult, rk, d, HIFIGAN_SLOPE)
+                    ops.hifigan_conv(t, *c2, dst, lengths, L, mult, rk, 1, HIFIGAN_SLOPE, residual=cur, accumulate=mode if last else 0, divisor=nk)
+                else:
+                    t = None
+                    ops.hifigan_conv(cur, *c1, dst, lengths, L, mult, rk, d, HIFIGAN_SLOPE, residual=cur, accumulate=mode if last else 0, divisor=nk)
+                kept.append((cur, t))
+                cur = dst
+            blocks.append(kept)
+        stages.append({"U": U, "blocks": blocks, "acc": acc})
+        x = acc
+    fwd["wav"] = f(B, L * g["hop"])
+    ops.hifigan_post(x, *voc.post, fwd["wav"], lengths, L, g["hop"], HIFIGAN_POST_TAPS, HIFIGAN_LAST_SLOPE)
+    return fwd
+
+
+def hifigan_train_backward(voc, mels, lengths, fwd, dwav):
+    """-> {name: gradient in torch's layout} for every name of `hifigan_expected_shapes`, from what `hifigan_train_forward` kept and d wav [B, L * hop].
+    Per convolution, last to first: the weight gradient from its kept input and its output's gradient, and the data gradient (`hifigan_conv_bwd`: mask of the
+    kept input, + the skip branch's gradient; a block's first step adds into dU, so dU is the sum of the nk blocks' input gradients in block order).  The
+    1 / nk of the MRF mean scales the launches that read d acc."""
+    g = voc.geo
+    B, _, L = mels.shape
+    nk, type1 = g["nk"], g["resblock"] == "1"
+    f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=mels.device)
+    grads = {k: f(*shape) for k, shape in hifigan_expected_shapes(g).items()}
+    work = f(max(ops.hifigan_wgrad_work_floats(B, L, mult, ci, co, taps, rate) for _, ci, co, taps, _, rate, mult in hifigan_convs(g)))
+    wg = lambda key, x, dy, mult, taps, **kw: ops.hifigan_wgrad(x, dy, lengths, work, grads[key + ".weight"], grads[key + ".bias"], L, mult, taps, **kw)
+    dwav = dwav.to(torch.float32).contiguous()
+    mult, x = g["hop"], fwd["stages"][-1]["acc"]
+    dpre, dA = f(B, L * mult), torch.empty_like(x)
+    ops.hifigan_post_bwd(dwav, fwd["wav"], x, voc.post[0], dpre, dA, lengths, L, mult, HIFIGAN_POST_TAPS, HIFIGAN_LAST_SLOPE)
+    wg("conv_post", x, dpre, mult, HIFIGAN_POST_TAPS, slope=HIFIGAN_LAST_SLOPE)
+    for i in reversed(range(len(g["rates"]))):
+        u, k, st = g["rates"][i], g["kernels"][i], fwd["stages"][i]
+        x_in = fwd["x0"] if i == 0 else fwd["stages"][i - 1]["acc"]
+        dU, G1, G2 = (torch.empty_like(dA) for _ in range(3))
+        for j in range(nk):
+            rk, n = g["rk"][j], i * nk + j
+            dout, sc = dA, 1.0 / nk                                 # d acc / nk is every block's output gradient
+            for m in reversed(range(len(voc.blocks[n]))):
+                d, (x_m, t_m), (w1t, w2t), q = voc.blocks[n][m][0], st["blocks"][j][m], voc.blocks_t[n][m], f"resblocks.{n}."
+                first = m == 0
+                if type1:                                           # x' = conv2(lrelu(t)) + x, t = conv1(lrelu(x))
+                    dst = dU if first else G2
+                    ops.hifigan_conv_bwd(dout, w2t, t_m, G1, lengths, L, mult, rk, 1, HIFIGAN_SLOPE, scale=sc)
+                    wg(q + f"convs2.{m}", t_m, dout, mult, rk, slope=HIFIGAN_SLOPE, scale=sc)
+                    ops.hifigan_conv_bwd(G1, w1t, x_m, dst, lengths, L, mult, rk, d, HIFIGAN_SLOPE, residual=dout, res_scale=sc, accumulate=first and j > 0)
+                    wg(q + f"convs1.{m}", x_m, G1, mult, rk, dilation=d, slope=HIFIGAN_SLOPE)
+                else:                                               # x' = conv1(lrelu(x)) + x
+                    dst = dU if first else (G1 if dout is G2 else G2)
+                    ops.hifigan_conv_bwd(dout, w1t, x_m, dst, lengths, L, mult, rk, d, HIFIGAN_SLOPE, residual=dout, scale=sc, res_scale=sc,
+                                         accumulate=first and j > 0)
+                    wg(q + f"convs1.{m}", x_m, dout, mult, rk, dilation=d, slope=HIFIGAN_SLOPE, scale=sc)
+                dout, sc = dst, 1.0
+        mult //= u
+        wg(f"ups.{i}", x_in, dU, mult, k, rate=u, slope=HIFIGAN_SLOPE)
+        dA = torch.empty_like(x_in)
+        ops.hifigan_upsample_bwd(dU, voc.ups_t[i], x_in, dA, lengths, L, mult, k, u, HIFIGAN_SLOPE)
+    wg("conv_pre", mels, dA, 1, HIFIGAN_PRE_TAPS, channels_first=True)
+    return grads
+
+
+class _HiFiGenerate(torch.autograd.Function):
+    """wav = HiFiGAN.generate(...): forward and backward are HIP launches (csrc/hifigan_ops.hip, csrc/hifigan_train_ops.hip); the mel gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, voc, mels, lengths, *params):
+        voc._build_images({k: t.detach() for k, t in zip(voc.params, params)})
+        fwd = hifigan_train_forward(voc, mels, lengths)
+        ctx.voc, ctx.args, ctx.fwd = voc, (mels, lengths), fwd
+        return fwd["wav"]
+
+    @staticmethod
+    def backward(ctx, dwav):
+        grads = hifigan_train_backward(ctx.voc, *ctx.args, ctx.fwd, dwav)
+        ctx.fwd = None
+        return (None,) * 3 + tuple(grads[k] for k in ctx.voc.params)
+
+
 class HiFiGAN:
     """HiFiGAN(hp, device, state_dict=None)(mels [B, Mel, T], mel_lengths) -> (wav [B, T * hop] fp32 on the device, wav_lengths [B] int64).
     state_dict None: `Vocoder.Checkpoint_Path` is loaded.  The generator has no noise input: `seeds` / `noises` are accepted (the call signature of
     `ParallelWaveGAN`) and ignored, a waveform repeats bit for bit.  An utterance's waveform is bit-identical alone, in any batch, at any padding and from
     run to run.  precision: 'f32' or None; 'bf16' raises (f32 only).  `.last_rows` holds the rows entering conv_post of the last call ([B, T * hop,
     channels[-1]], a view of the work buffers: the next call overwrites it; `return_rows=True` returns a copy as a third result).
-    `.conv`, `.upsample` and `.stage` run single operators (tests)."""
+    `.conv`, `.upsample` and `.stage` run single operators (tests).
+    trainable=True (DESIGN.md "Training the HiFi-GAN generator"): `params` holds float32 device leaves in `hifigan_expected_shapes`' names - plain weights,
+    from `state_dict` or, without one, `hifigan_init(geo, seed)` - and `generate` returns the same waveform with a backward (csrc/hifigan_train_ops.hip)."""
 
-    def __init__(self, hp, device="cuda:0", state_dict=None, precision=None):
+    def __init__(self, hp, device="cuda:0", state_dict=None, precision=None, trainable=False, seed=0):
         if precision not in (None, "f32"):
             raise ValueError(f"precision = {precision!r}: the HiFi-GAN generator runs in 'f32' only (Vocoder.Precision: 'bf16' is the Parallel WaveGAN layers' mode)")
         self.geo = geo = hifigan_geometry(hp)                       # before anything touches the device or the disk
         self.precision = "f32"
+        self.trainable = bool(trainable)
+        if self.trainable:
+            hifigan_train_geometry(geo)
+            if state_dict is None:
+                state_dict = hifigan_init(geo, seed)
         if state_dict is None:
             path = hifigan_settings(hp)["Checkpoint_Path"]
             if not path:
@@ -1139,10 +1348,15 @@ class HiFiGAN:
         self.device = torch.device(device)
         self.sample_rate, self.n_mel, self.hop = int(hp.Sound.Sample_Rate), geo["A"], geo["hop"]
         self._capacity, self._buffers, self.last_rows = 0, None, None
+        if self.trainable:                                          # float32 device leaves in hifigan_expected_shapes' names; the images follow them
+            self.params = {k: t.to(self.device).requires_grad_(True) for k, t in w.items()}
+            w = {k: t.detach() for k, t in self.params.items()}
+            self._up_taps = [hifigan_up_taps(u, k).to(self.device) for u, k in zip(geo["rates"], geo["kernels"])]
         self._build_images(w)
 
     def _build_images(self, w):
-        """The K-major weight images (the MFMA B operand reads 16 consecutive output channels of one input row), built once."""
+        """The K-major weight images (the MFMA B operand reads 16 consecutive output channels of one input row) from the tensors `w` (host or device): built
+        once for a frozen generator; a trainable one rebuilds them on the device at every `generate`, with the transposed images of the backward."""
         geo = self.geo
         dev = lambda t: t.contiguous().to(self.device)
         pair = lambda q, image: (dev(image(w[q + ".weight"])), dev(w[q + ".bias"]))
@@ -1154,6 +1368,11 @@ class HiFiGAN:
             self.blocks.append([(d, pair(f"resblocks.{n}.convs1.{m}", hifigan_conv_image),
                                  pair(f"resblocks.{n}.convs2.{m}", hifigan_conv_image) if geo["resblock"] == "1" else None) for m, d in enumerate(ds)])
         self.post = (dev(w["conv_post.weight"].permute(2, 1, 0).reshape(-1)), dev(w["conv_post.bias"]))
+        if self.trainable:
+            image_t = lambda q: dev(hifigan_conv_image_t(w[q + ".weight"]))
+            self.ups_t = [dev(hifigan_up_image_t(w[f"ups.{i}.weight"], u, self._up_taps[i])) for i, u in enumerate(geo["rates"])]
+            self.blocks_t = [[(image_t(f"resblocks.{n}.convs1.{m}"), image_t(f"resblocks.{n}.convs2.{m}") if geo["resblock"] == "1" else None)
+                              for m in range(len(geo["rd"][n % geo["nk"]]))] for n in range(len(self.blocks))]
 
     def _work(self, B, L):
         """Work buffers of a call (two stage outputs that alternate, the transposed convolution's output and two resblock buffers): views of ONE set sized for
@@ -1248,6 +1467,8 @@ class HiFiGAN:
         if Mel != self.n_mel:
             raise ValueError(f"mels have {Mel} channels, Sound.Mel_Dim = {self.n_mel}")
         g = self.geo
+        if self.trainable:                                          # the images follow the parameters (an optimizer step writes the leaves in place)
+            self._build_images({k: t.detach() for k, t in self.params.items()})
         lengths = self._lengths(mel_lengths, B, L)
         p0, p1, U, X, T = self._work(B, L)
         view = lambda buf, rows, c: buf[:B * rows * c].view(B, rows, c)
@@ -1263,6 +1484,21 @@ class HiFiGAN:
         self.last_rows = x
         wav_lengths = lengths.to(torch.int64) * g["hop"]
         return (wav, wav_lengths, x.clone()) if return_rows else (wav, wav_lengths)
+
+    def generate(self, mels, mel_lengths):
+        """The training forward: `__call__`'s launches with every convolution's output in a slab of its own (so the waveform is bit-identical) ->
+        (wav [B, T * hop], wav_lengths) with a backward that fills `.grad` of every tensor of `self.params`.  Only for `trainable=True`."""
+        if not self.trainable:
+            raise _lib.GlowTTSHipError("HiFiGAN.generate needs a generator constructed with trainable=True (this one holds frozen weight images only)")
+        if not mels.is_cuda:
+            raise _lib.GlowTTSHipError("expected a device tensor (the HIP path has no CPU fallback)")
+        mels = mels.to(device=self.device, dtype=torch.float32).contiguous()
+        B, Mel, L = mels.shape
+        if Mel != self.n_mel:
+            raise ValueError(f"mels have {Mel} channels, Sound.Mel_Dim = {self.n_mel}")
+        lengths = self._lengths(mel_lengths, B, L)
+        wav = _HiFiGenerate.apply(self, mels, lengths, *self.params.values())
+        return wav, lengths.to(torch.int64) * self.geo["hop"]
 
     def to_host(self, wav, wav_lengths):
         """Device waveforms -> list of float32 numpy arrays clipped to [-1, 1] (what `audio.write_wav` takes).  No de-emphasis: the vocoder was trained on

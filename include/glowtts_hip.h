@@ -958,6 +958,38 @@ int glowtts_hifigan_upsample(const float *in, const float *w, const float *bias,
 int glowtts_hifigan_post(const float *in, const float *w, const float *bias, float *wav, const int32_t *frame_lengths, int B, int Lmax, int mult, int Cin,
                          int taps, float slope, void *stream);
 
+/* ---- training the HiFi-GAN generator (csrc/hifigan_train_ops.hip; f32; additions, the ABI version stays) ----
+ * Layouts, lengths and ownership as above: nothing is read beyond an utterance's rows [0, L mult) and nothing is written there.  Every product runs on
+ * v_mfma_f32_16x16x4_f32, every sum has a fixed order that depends on the sizes alone (no float atomics): every gradient is bit-identical from run to run.
+ * Cin, Cout, taps, dilation, rate always name the FORWARD convolution.  Supported: glowtts_hifigan_train_supported(Cin, Cout, taps, dilation, rate) -
+ * glowtts_hifigan_supported, and for rate >= 1 Cin a multiple of 16, rate Cout <= 4096 and at most 11 row offsets; else GLOWTTS_E_ARG before any launch.
+ * glowtts_hifigan_conv_bwd: the data gradient of glowtts_hifigan_conv, one launch logged as `hifigan_conv_bwd`: dy [B][Lmax mult][Cout] against the
+ *   tap-reversed, channel-transposed image wt [taps Cout][Cin] (row = (taps - 1 - tap) Cout + output channel), then
+ *   y = sum * (x > 0 ? 1 : mask_slope) * scale + residual * res_scale with x [B][Lmax mult][Cin] the forward's input before its LeakyReLU and residual
+ *   (NULL: none; may be `out`) laid out as out [B][Lmax mult][Cin]; out = y (accumulate 0) or out = out + y (1).  Cin a multiple of 16; dy != out.
+ * glowtts_hifigan_upsample_bwd: the data gradient of glowtts_hifigan_upsample, one launch logged as `hifigan_upsample_bwd`: dy [B][Lmax mult rate][Cout] read
+ *   as [B][Lmax mult][rate Cout], an (hi - lo + 1)-tap convolution over rows against wt [(hi - lo + 1) rate Cout][Cin]: row (e - lo) rate Cout + ph Cout + co
+ *   holds W[ci][co][j0 + (e + o0) rate] (j0 = (ph + p) % rate, o0 = (ph + p) / rate, p = (taps - rate) / 2) where that tap exists, else zero; [lo, hi] is the
+ *   range of e = m - o0 over the phases' taps m.  out [B][Lmax mult][Cin] = sum * (x > 0 ? 1 : mask_slope).
+ * glowtts_hifigan_post_bwd: dpre [B][Lmax mult] = dwav (1 - wav^2) and dx [B][Lmax mult][Cin] = (x > 0 ? 1 : slope) * sum over the taps of w dpre (w [taps Cin]
+ *   as glowtts_hifigan_post takes it), a fixed-order sum per element.  Logged as `hifigan_post_bwd`.
+ * glowtts_hifigan_wgrad: dw and dbias of one convolution (rate 0: x [B][Lmax mult][Cin], channels_first [B][Cin][Lmax mult]; dy [B][Lmax mult][Cout];
+ *   dw [Cout][Cin][taps]; Cout == 1: the conv_post form) or transposed convolution (rate >= 1: dy [B][Lmax mult rate][Cout]; dw [Cin][Cout][taps]) in torch's
+ *   layouts, both times `scale`: the sum over the utterances' rows of lrelu(x, slope) dy.  Partition: per utterance chunks of 1024 rows, consecutive
+ *   (utterance, chunk) units grouped by 1024 / (Lmax mult) when that exceeds 1, partial sums added in ascending order.  work: at least
+ *   glowtts_hifigan_wgrad_work_floats(...) floats.  Two launches, logged as `hifigan_wgrad` and `hifigan_wgrad_sum`. */
+int glowtts_hifigan_train_supported(int Cin, int Cout, int taps, int dilation, int rate);
+int64_t glowtts_hifigan_wgrad_work_floats(int B, int Lmax, int mult, int Cin, int Cout, int taps, int rate);
+int glowtts_hifigan_conv_bwd(const float *dy, const float *wt, const float *x, const float *residual, float *out, const int32_t *frame_lengths, int B,
+                             int Lmax, int mult, int Cin, int Cout, int taps, int dilation, float mask_slope, float scale, float res_scale, int accumulate,
+                             void *stream);
+int glowtts_hifigan_upsample_bwd(const float *dy, const float *wt, const float *x, float *out, const int32_t *frame_lengths, int B, int Lmax, int mult,
+                                 int Cin, int Cout, int taps, int rate, float mask_slope, void *stream);
+int glowtts_hifigan_post_bwd(const float *dwav, const float *wav, const float *x, const float *w, float *dpre, float *dx, const int32_t *frame_lengths,
+                             int B, int Lmax, int mult, int Cin, int taps, float slope, void *stream);
+int glowtts_hifigan_wgrad(const float *x, const float *dy, const int32_t *frame_lengths, float *work, float *dw, float *dbias, int B, int Lmax, int mult,
+                          int Cin, int Cout, int taps, int dilation, int rate, float slope, float scale, int channels_first, void *stream);
+
 /* ---- GE2E speaker encoder: stacked LSTM -> linear -> d-vector (csrc/ge2e_ops.hip; inference, f32; additions, the ABI version stays) ----
  * torch.nn.LSTM's definition (gates i, f, g, o; bias b_ih + b_hh; h0 = c0 = 0), then e = W h_{T-1}^{top} + b per slice, w = e / max(|e|, 1e-12),
  * d = normalize(mean over an utterance's Samples consecutive slices of w).  Every product runs on v_mfma_f32_16x16x4_f32; a sequence's values depend on
