@@ -143,9 +143,12 @@ __global__ __launch_bounds__(WN_NT) void wn_fwd_kernel(const wn_fwd_args p)
     {
         const int C2 = p.C2, per_row = C2 >> 2;
         unsigned char* const ST = AT;
-        float4 xv[2]; int xi[2];
+        // WN_XR rows of at most 96 / 4 = 24 four-channel pieces: three rounds of the workgroup (two cover C2 <= 88 only)
+        constexpr int XA_ROUNDS = (WN_XR * 24 + WN_NT - 1) / WN_NT;
+        static_assert(XA_ROUNDS * WN_NT >= WN_XR * (96 / 4), "the x_a staging loop covers every state row at the largest C2");
+        float4 xv[XA_ROUNDS]; int xi[XA_ROUNDS];
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
+        for (int k = 0; k < XA_ROUNDS; ++k) {
             const int idx = tid + k * WN_NT;
             xi[k] = idx < WN_XR * per_row ? idx : -1;
             const int i = idx / per_row, c4 = idx - i * per_row;
@@ -176,7 +179,7 @@ __global__ __launch_bounds__(WN_NT) void wn_fwd_kernel(const wn_fwd_args p)
         for (int k = 0; k < (int)((blockIdx.x >> 3) & 7) * p.stagger; ++k) __builtin_amdgcn_s_sleep(8);
 #endif
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
+        for (int k = 0; k < XA_ROUNDS; ++k) {
             if (xi[k] < 0) continue;
             const int i = xi[k] / per_row, c4 = xi[k] - i * per_row;
             const int ch = c4 * 4, kc = ch >> 5, cc = ch & 31;

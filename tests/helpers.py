@@ -51,16 +51,18 @@ def tiny_hp_dict(mode):
     return hp
 
 
-def full_width_state(n_flows, g, spk_dim=0):
+def full_width_state(n_flows, g, spk_dim=0, mel_dim=80, n_layers=4):
     """Seeded decoder weights at the default Hyper_Parameters sizes (C=160, H=192, 4 layers, k=5); spk_dim > 0 adds the SE-mode
-    Speaker_l conditioning convs (Modules.py:832-838)."""
+    Speaker_l conditioning convs (Modules.py:832-838).  mel_dim / n_layers: another Sound.Mel_Dim / WaveNet.Num_Layers (the defaults draw
+    exactly the numbers they always drew)."""
     from oracle import glowtts_ref as O
-    cfg = O.Cfg(n_flows=n_flows, mode="SE" if spk_dim else "Vanilla", spk_dim=spk_dim or 256)
+    cfg = O.Cfg(n_flows=n_flows, mode="SE" if spk_dim else "Vanilla", spk_dim=spk_dim or 256, mel_dim=mel_dim, wn_layers=n_layers)
+    C = mel_dim * cfg.n_squeeze
     sd = {}
     for f in range(cfg.n_flows):
         q = f"layer_Dict.Decoder.layer_Dict.Flows.{f}.layers"
-        sd[q + ".0.logs"] = torch.randn(1, 160, 1, generator=g) * 0.1
-        sd[q + ".0.bias"] = torch.randn(1, 160, 1, generator=g) * 0.1
+        sd[q + ".0.logs"] = torch.randn(1, C, 1, generator=g) * 0.1
+        sd[q + ".0.bias"] = torch.randn(1, C, 1, generator=g) * 0.1
         w4 = torch.linalg.qr(torch.randn(4, 4, generator=g))[0] + 0.05 * torch.randn(4, 4, generator=g)
         if torch.det(w4) < 0:                       # the reference keeps det > 0 (Modules.py:722-723)
             w4[:, 0] = -w4[:, 0]
@@ -69,14 +71,14 @@ def full_width_state(n_flows, g, spk_dim=0):
             sd[f"{q}.2.layer_Dict.{name}.weight_v"] = torch.randn(o, i, k, generator=g) / (i * k) ** 0.5
             sd[f"{q}.2.layer_Dict.{name}.weight_g"] = torch.rand(o, 1, 1, generator=g) + 0.5
             sd[f"{q}.2.layer_Dict.{name}.bias"] = torch.randn(o, generator=g) * 0.05
-        wn("Start", 192, 80, 1)
-        for l in range(4):
+        wn("Start", 192, C // 2, 1)
+        for l in range(n_layers):
             wn(f"WaveNet.layer_Dict.In_{l}", 384, 192, 5)
-            wn(f"WaveNet.layer_Dict.Res_Skip_{l}", 384 if l < 3 else 192, 192, 1)
+            wn(f"WaveNet.layer_Dict.Res_Skip_{l}", 384 if l < n_layers - 1 else 192, 192, 1)
             if spk_dim:
                 wn(f"WaveNet.layer_Dict.Speaker_{l}", 384, spk_dim, 1)
-        sd[f"{q}.2.layer_Dict.End.weight"] = torch.randn(160, 192, 1, generator=g) * 0.02
-        sd[f"{q}.2.layer_Dict.End.bias"] = torch.randn(160, generator=g) * 0.02
+        sd[f"{q}.2.layer_Dict.End.weight"] = torch.randn(C, 192, 1, generator=g) * 0.02
+        sd[f"{q}.2.layer_Dict.End.bias"] = torch.randn(C, generator=g) * 0.02
     return cfg, sd
 
 

@@ -3,63 +3,15 @@ launch, Modules.py:785-806 / 858-887) against the per-conv launches it replaces,
 k = 5).  Both paths round the same tensors to bf16 (WaveNet state, gates, tanh * sigmoid) and differ only in fp32 accumulation order, so a
 kept bf16 tensor may differ by an occasional one-ulp flip and what follows from it; a halo / tile-seam bug would show as O(1) errors on the
 rows next to a multiple of the 52-row tile.  The oracle comparisons of the fused path itself are tests/test_gpu_decoder_fullwidth.py and
-tests/test_gpu_fullsize.py (which run it by default)."""
+tests/test_gpu_fullsize.py (which run it by default); the other layer counts and widths of the kernels' shape contract, and the comparison with an
+independent restatement of the rounding contract, are tests/test_gpu_wavenet_fused_contract.py (helpers shared through tests/wavenet_fused_gpu.py)."""
 import pytest
 import torch
 
 from helpers import full_width_state, launch_counts, launch_reset
+from wavenet_fused_gpu import close_rows as _close, forward as _forward, grads as _grads, outs_columns as _outs_columns, seam_rows, setup as _setup
 
 pytestmark = pytest.mark.gpu
-
-
-def _setup(n_flows, lengths, tm, spk_dim=0, seed=0):
-    from glow_tts_amd import decoder as D
-    g = torch.Generator().manual_seed(seed)
-    cfg, sd = full_width_state(n_flows, g, spk_dim=spk_dim)
-    dc = D.DecoderConfig(cfg.mel_dim, cfg.n_flows, cfg.n_squeeze, cfg.n_split, cfg.wn_channels, cfg.wn_layers, cfg.wn_kernel, 1)
-    P = {k: v.cuda() for k, v in sd.items()}
-    B = len(lengths)
-    mels = (torch.randn(B, 80, tm, generator=g) * 1.5).clamp(-4, 4).cuda()
-    ml = torch.tensor(lengths).cuda()
-    spk = None
-    if spk_dim:
-        spk = torch.randn(B, spk_dim, generator=g)
-        spk = (spk / spk.norm(dim=1, keepdim=True)).cuda()
-    W = dict(zip(D.WEIGHT_KEYS, [w.contiguous() for w in D.stack_decoder_weights(P, dc)]))
-    cond = D.conditioning(P, dc, speakers=spk) if spk is not None else None
-    return D, dc, W, mels, ml, cond
-
-
-def _forward(D, dc, W, mels, ml, cond, fused, drop_p=0.0, seed=None):
-    D.TUNE["fused_wn"] = fused
-    try:
-        with torch.no_grad():
-            prep = D._Prepared(dc, W, need_bwd=False, cond=cond)
-            launch_reset()
-            z, logdet, buf, rowmask, T, _ = D._run_forward(dc, prep, mels, ml, drop_p, seed)
-            torch.cuda.synchronize()
-            return z, logdet, buf, rowmask, launch_counts()
-    finally:
-        D.TUNE["fused_wn"] = True
-
-
-def _outs_columns(c2=80):
-    """Columns of the kept (m, logs) buffer: packed column p * 64 + h * 32 + j holds half h (0 = m, 1 = logs) of channel p * 32 + j < c2."""
-    m = [p * 64 + j for p in range(3) for j in range(32) if p * 32 + j < c2]
-    return torch.tensor(m, device="cuda"), torch.tensor([c + 32 for c in m], device="cuda")
-
-
-def _close(a, b, what, rowmask=None, atol=0.0, frac=0.0, big=None):
-    """|a - b| <= atol everywhere except on at most `frac` of the elements (bf16 one-ulp flips), where it stays <= big."""
-    a, b = a.float(), b.float()
-    if rowmask is not None:
-        m = rowmask.view(-1, *([1] * (a.dim() - 1)))
-        a, b = a * m, b * m
-    d = (a - b).abs()
-    bad = (d > atol).float().mean().item()
-    assert bad <= frac, (what, "fraction above atol", bad, "max", d.max().item())
-    if big is not None:
-        assert d.max().item() <= big, (what, d.max().item())
 
 
 @pytest.mark.parametrize("lengths,tm", [([640, 522, 240, 2], 640), ([800] * 3, 800), ([104], 104), ([2], 2), ([422, 36, 36, 36, 36, 800], 800)])
@@ -102,9 +54,7 @@ def test_fused_forward_matches_per_conv_launches(lengths, tm):
     # tile seams: the error next to the 52-row tile boundaries is of the same size as elsewhere
     R = bf.x.shape[1]
     err = ((bf.x[1] - bu.x[1]).abs().max(dim=1).values * rm)
-    seam = torch.zeros(R, dtype=torch.bool, device="cuda")
-    for k in range(0, R, 52):
-        seam[max(k - 2, 0):k + 2] = True
+    seam = seam_rows(R, 52, 2)
     if seam.any() and (~seam).any() and err[~seam].max() > 0:
         assert err[seam].max() <= 4 * err[~seam].max() + 1e-3, (err[seam].max().item(), err[~seam].max().item())
 
@@ -195,26 +145,6 @@ def test_exact_wait_counts_equal_conservative_waits():
                 assert torch.equal(getattr(got[2], name), getattr(ref[2], name)), name
             cm, cl = _outs_columns()
             assert torch.equal(got[2].outs[:, :, cm], ref[2].outs[:, :, cm]) and torch.equal(got[2].outs[:, :, cl], ref[2].outs[:, :, cl])
-
-
-def _grads(D, dc, P, mels, ml, wz, wl, fused_bwd, drop_p=0.0, cond=None):
-    default = D.TUNE["fused_wn_bwd"]
-    D.TUNE["fused_wn_bwd"] = fused_bwd
-    try:
-        Pg = {k: v.clone().requires_grad_(True) for k, v in P.items()}
-        x = mels.clone().requires_grad_(True)
-        W = D.stack_decoder_weights(Pg, dc)
-        c = cond.clone().requires_grad_(True) if cond is not None else None
-        launch_reset()
-        z, logdet, _ = D.DecoderFunction.apply(dc, x, ml, c, drop_p, None, None, None, *W)
-        ((z * wz).sum() + (logdet * wl).sum()).backward()
-        torch.cuda.synchronize()
-        g = {k: p.grad for k, p in Pg.items() if p.grad is not None}
-        if c is not None:
-            g["<conditioning>"] = c.grad
-        return g, x.grad, launch_counts()
-    finally:
-        D.TUNE["fused_wn_bwd"] = default
 
 
 @pytest.mark.parametrize("lengths,tm,drop", [([640, 522, 240, 2], 640, 0.0), ([800] * 3, 800, 0.3), ([104], 104, 0.0), ([422, 36, 36, 800], 800, 0.05)])
