@@ -873,37 +873,83 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_cl_kernel(const glowtts_con
 //   * ONE fat workgroup per CU: WMR waves (4..16, chosen by the host so that all tiles fit the chip in one round), each wave
 //     a 32-row x 64-column strip, so a weight tile is staged once per CU instead of once per 128 rows;
 //   * staging is global_load_lds_dwordx4 (no VGPR round trip, no ds_write): 1 KiB per wave-instruction into a linear LDS
-//     image; the XOR swizzle the fragment reads expect is applied to the per-lane SOURCE address (same involution);
-//   * three LDS stages, one barrier per K chunk: chunks ss+1 and ss+2 stream in while the 2*TAPS*NI MFMAs of chunk ss run
-//     (counted vmcnt waits, raw s_barrier: __syncthreads() would drain the DMA queue).
+//     image; the slot swizzle the fragment reads expect (swz16) is applied to the per-lane SOURCE address (same involution);
+//   * two or three LDS stages, one barrier per K chunk: later chunks stream in while the 4*TAPS*NI 4-pass MFMAs
+//     (v_mfma_f32_16x16x32_bf16) of chunk ss run (counted vmcnt waits, raw s_barrier: __syncthreads() would drain the DMA queue);
+//   * between the barrier of a stage and its last MFMA the code is straight-line: fragment reads are inline asm one sub-step
+//     ahead with counted lgkmcnt waits, the refill DMAs are address arithmetic only (no branch, no select).
 // Rows outside [0, rows) are clamped, not zeroed: they only feed outputs of rows outside the tensor (dropped by the epilogue's
 // bounds check) and of the first / last utterance's outermost pad rows, which every consumer masks.
 // ------------------------------------------------------------------------------------------------
 extern __shared__ __attribute__((aligned(1024))) unsigned char dma_smem[];
 constexpr int DMA1_CPS = 2;             // 1x1 convs: K chunks per pipeline stage
 
-// KS (round 2): the K loop is bound by LDS fragment reads - a 32-row x 64-column strip per wave reads 1 A + 2 B fragments (3 KiB) for
-// two MFMAs per 16-wide k-step, 1.5 KiB per MFMA against the 1 KiB per MFMA the LDS can feed at full matrix rate.  With KS the waves
-// work in PAIRS: wave (g, kh) multiplies a 64-row x 64-column tile over only ONE half (kh) of every 32-wide K chunk: 2 A + 2 B fragments for
-// four MFMAs = 1 KiB per MFMA, same MFMA count per wave, same LDS image, same staging.  After the loop the partners swap halves of their
-// partial sums through LDS (each keeps the 32-row fragment kh of the pair's 64 rows), which leaves every wave with exactly the
-// accumulators of the plain kernel: the epilogue is unchanged.
-template <int EPI, int TAPS, int NI = 2, bool KS = false>
-__global__ __launch_bounds__(1024) void conv_dma_kernel(const glowtts_conv_args pin, const int nst /* LDS stages: 2 or 3 */,
-                                                        const int nload /* loader waves (0: every wave stages its share) */)
+// Fragment geometry of the K loop (v_mfma_f32_16x16x32_bf16, 4 passes: the SIMD keeps issuing LDS-DMA and LDS reads between them, which it
+// does not between back-to-back 8-pass 32x32x16 MFMAs - tools/wn_lab.hip).  A wave's 32-row x (NI*32)-column strip is 2 x 2*NI fragments
+// of f32x4.  Row fragment mt reads, as A-operand row a = lane & 15, the strip row 16 mt + dma_arow(a): bits 2 and 3 of a swapped.  That
+// costs nothing (the same 16 rows per ds_read_b128 lane group, so swz16 stays conflict-free at every tap shift) and makes the lanes' values
+// those of the 32x32 accumulator layout up to one exchange between the lanes l and l ^ 16: element i of fragments (mt, 2 ni) and
+// (mt, 2 ni + 1) turns into registers 8 mt + i and 8 mt + 4 + i of the 32x32 fragment ni with one v_permlane16_swap.  The shared
+// epilogue therefore runs unchanged, without a round trip through LDS.
+__host__ __device__ constexpr int dma_arow(int a) { return (a & 3) | (((a >> 3) & 1) << 2) | (((a >> 2) & 1) << 3); }
+__host__ __device__ constexpr int dma_acc_row(int mt, int lane, int i) { return 16 * mt + dma_arow(4 * (lane >> 4) + i); }
+__host__ __device__ constexpr int dma_acc_col(int ct, int lane) { return 16 * ct + (lane & 15); }
+// 64 lanes x 4 elements x 2 x 2*NI fragments cover the strip exactly once, and the lane exchange lands every value on the (row, column) the
+// 32x32 epilogue expects for that lane and register
+template <int NI> constexpr bool dma_geometry_ok()
+{
+    int seen[32][NI * 32] = {};
+    for (int mt = 0; mt < 2; ++mt)
+        for (int ct = 0; ct < 2 * NI; ++ct)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int i = 0; i < 4; ++i) {
+                    const int r = dma_acc_row(mt, lane, i), c = dma_acc_col(ct, lane);
+                    if (r < 0 || r >= 32 || c < 0 || c >= NI * 32) return false;
+                    ++seen[r][c];
+                }
+    for (int r = 0; r < 32; ++r)
+        for (int c = 0; c < NI * 32; ++c)
+            if (seen[r][c] != 1) return false;
+    for (int ni = 0; ni < NI; ++ni)
+        for (int mt = 0; mt < 2; ++mt)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int i = 0; i < 4; ++i) {
+                    const bool up = (lane >> 4) & 1;                       // v_permlane16_swap x, y: lanes 16-31 / 48-63 of x <-> lanes 0-15 / 32-47 of y
+                    const int xs_ct = up ? 2 * ni + 1 : 2 * ni, xs_lane = up ? lane - 16 : lane;      // where x' of this lane comes from
+                    const int ys_ct = up ? 2 * ni + 1 : 2 * ni, ys_lane = up ? lane : lane + 16;      // where y' of this lane comes from
+                    if (dma_acc_row(mt, xs_lane, i) != acc_row(8 * mt + i, lane >> 5) || dma_acc_col(xs_ct, xs_lane) != ni * 32 + (lane & 31)) return false;
+                    if (dma_acc_row(mt, ys_lane, i) != acc_row(8 * mt + 4 + i, lane >> 5) || dma_acc_col(ys_ct, ys_lane) != ni * 32 + (lane & 31)) return false;
+                }
+    return true;
+}
+static_assert(dma_geometry_ok<1>() && dma_geometry_ok<2>() && dma_geometry_ok<3>(), "conv_dma_kernel: fragment geometry");
+
+// LDS-DMA instructions per wave and stage: the units (16 rows or columns x 64 B) of a stage are dealt round robin to the W waves; a wave whose
+// last turn falls behind the last unit stages that last unit again (the same bytes to the same place), so every wave issues the same, compile-time
+// number - the refill sits between the MFMAs without a branch and the vmcnt waits are immediates.
+__host__ __device__ constexpr int dma_units(int taps, int ni, int w) { return (taps == 1 ? DMA1_CPS * (2 * w) + DMA1_CPS * ni * 2 : ((32 * w + taps - 1 + 15) >> 4) + taps * ni * 2); }
+__host__ __device__ constexpr int dma_npw(int taps, int ni, int w) { return (dma_units(taps, ni, w) + w - 1) / w; }
+__host__ __device__ constexpr int dma_wmax(int taps) { return taps == 1 ? 10 : 16; }          // three LDS stages must fit 160 KiB; at most 16 waves
+constexpr int DMA_WMIN = 4;
+
+// PITCH: the epilogue variant that also accumulates the GR-mode Pitch_l weight gradient (see conv_epilogue).  Only `false` is instantiated: the host
+// declines such calls for this kernel, and tests/test_abi.py finds the benchmarked instantiations by that argument in their names.
+template <int EPI, int TAPS, int NI = 2, bool PITCH = false>
+__global__ __launch_bounds__(1024) void conv_dma_kernel(const glowtts_conv_args pin, const int nst /* LDS stages: 2 or 3 */)
 {
     typedef __bf16 CT;
-    constexpr int BN = NI * 32, KC = 32;                      // NI = 2: 64-column strips; NI = 3: 96 (when that balances the SIMDs better)
+    constexpr int BN = NI * 32, KC = 32;                      // NI = 2: 64-column strips; NI = 3: 96; NI = 1: 32 (few columns, many workgroups)
     constexpr int WTB = BN * 64, WUT = BN / 16;               // bytes / DMA units of one weight tile
     // A stage holds SUB sub-steps.  Multi-tap: one K chunk = one A tile (with its TAPS - 1 halo rows) shared by the TAPS weight
     // tiles.  1x1 (TAPS == 1): DMA1_CPS consecutive K chunks, each with its own A tile and weight tile.
     constexpr bool T1 = (TAPS == 1);
     constexpr int SUB = T1 ? DMA1_CPS : TAPS;
     constexpr int NAT = T1 ? DMA1_CPS : 1;
+    constexpr int NCT = 2 * NI;                               // 16-column fragments of the strip
     glowtts_conv_args p = pin;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);           // scalar: unit indices, LDS bases and branches below are wave-uniform
-    const int WMR = (blockDim.x >> 6) - nload, BM = WMR * 32; // compute waves (the last `nload` waves only issue DMAs)
+    const int WMR = blockDim.x >> 6, BM = WMR * 32;
     const int AU = (BM + TAPS - 1 + 15) >> 4;                 // 16-row (1 KiB) DMA units of one A tile
     constexpr int WU = SUB * WUT;                             // 16-column units of the SUB weight tiles
     const int A_BYTES = NAT * AU * 1024, STAGE = A_BYTES + WU * 1024;
@@ -922,10 +968,10 @@ __global__ __launch_bounds__(1024) void conv_dma_kernel(const glowtts_conv_args 
     const int rot = (T1 && p.a2) ? 0 : (int)((m_tile * 5 + n_tile * 3) % NSS);
     auto ssmap = [&](int ss) __attribute__((always_inline)) { int v = ss + rot; return v >= NSS ? v - NSS : v; };
     constexpr int pad = (TAPS - 1) / 2;
-    const int l31 = lane & 31, lhi = lane >> 5;
 
-    // lane -> (row or column inside a 16-unit, logical 16-byte slot): LDS position `lane` of a unit holds slot q of row lane >> 2
-    const int lrow = lane >> 2, qa = (lane & 3) ^ ((lane >> 4) & 3);
+    // lane -> (row or column inside a 16-unit, logical 16-byte slot): LDS position `lane` of a unit holds slot qa of row lane >> 2 (swz16 is
+    // an involution of the slot index, and bit 2 of a row is bit 4 of the lane because units start on multiples of 16 rows)
+    const int lrow = lane >> 2, qa = (lane & 3) ^ (((lane >> 4) & 1) << 1);
     const int nau = NAT * AU, nun = nau + WU;
     const unsigned char* const abase = reinterpret_cast<const unsigned char*>(p.a);
     const unsigned char* const a2base = reinterpret_cast<const unsigned char*>(p.a2);
@@ -934,179 +980,144 @@ __global__ __launch_bounds__(1024) void conv_dma_kernel(const glowtts_conv_args 
     constexpr uint32_t akstep = KC * 2 * (T1 ? DMA1_CPS : 1);
     // stage-0 source offset of DMA unit u (32-bit byte offset from p.a (p.a2) / p.w, host-checked < 2^31)
     auto unit_off = [&](int u) __attribute__((always_inline)) -> uint32_t {
-        if (u < nau) {
-            const int ja = T1 ? u / AU : 0, ur = u - ja * AU;
-            int g = m0 - pad + ur * 16 + lrow;
-            g = g < 0 ? 0 : (g >= p.rows ? p.rows - 1 : g);
-            return (uint32_t)g * (uint32_t)(p.lda * 2) + (uint32_t)(qa * 16 + ja * (KC * 2));
-        }
+        const int ja = T1 ? u / AU : 0, ur = u - ja * AU;
+        int g = m0 - pad + ur * 16 + lrow;
+        g = g < 0 ? 0 : (g >= p.rows ? p.rows - 1 : g);
+        const uint32_t oa = (uint32_t)g * (uint32_t)(p.lda * 2) + (uint32_t)(qa * 16 + ja * (KC * 2));
         const int w = u - nau, t = w / WUT, cg = w - t * WUT; // t: tap (multi-tap) or chunk inside the stage (1x1)
-        return (uint32_t)((T1 ? t : t * KCH) * p.npad + n0 + cg * 16 + lrow) * 64u + (uint32_t)(qa * 16);
+        const uint32_t ow = (uint32_t)((T1 ? t : t * KCH) * p.npad + n0 + cg * 16 + lrow) * 64u + (uint32_t)(qa * 16);
+        uint32_t o = ow;
+        if (u < nau) o = oa;
+        return o;
     };
-    auto dma = [&](int u, uint32_t off, int buf, int st) __attribute__((always_inline)) {
-        const unsigned char* src;
-        if (u >= nau)       src = wbase + (off + (uint32_t)st * wkstep);
-        else if (st < NSS1) src = abase + (off + (uint32_t)st * akstep);
-        else                src = a2base + (off + (uint32_t)(st - NSS1) * akstep);
-        __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
-                                         (void __attribute__((address_space(3)))*)(dma_smem + buf * STAGE + u * 1024), 16, 0, 0);
-    };
-    if (wave >= WMR) {
-        // ---- loader wave (wave specialisation): an LDS-DMA instruction costs its issuing wave 100-200 clk in a phase that also reads
-        // LDS and feeds the matrix pipe; two waves that do nothing else stage every tile (two LDS stages: stage ss+1 streams in while
-        // the compute waves multiply stage ss).  They take part in every barrier and leave before the epilogue.
-        const int lw = wave - WMR;
-        for (int u = lw; u < nun; u += nload) dma(u, unit_off(u), 0, ssmap(0));
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        for (int ss = 0; ss + 1 < NSS; ++ss) {
-            const int st = ssmap(ss + 1), buf = (ss + 1) & 1;
-            for (int u = lw; u < nun; u += nload) dma(u, unit_off(u), buf, st);
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        }
-        return;
+    f32x4 acc[2][NCT];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[mt][ct][r] = 0.f;
+
+    // DMA units of this wave: u = min(wave + i * WMR, last unit).  Their stage-0 source offsets are computed once; a stage is a uniform
+    // byte step (SUB-or-1 x 64 B along an A row, SUB-or-1 [npad][64 B] slabs of the packed weights).
+    constexpr int NPW_MIN = dma_npw(TAPS, NI, dma_wmax(TAPS)), NPW_MAX = dma_npw(TAPS, NI, DMA_WMIN);
+    const int npw = (nun + WMR - 1) / WMR;
+    // Per DMA slot i of this wave, all wave-uniform: the unit, its source (activation rows or packed weights) and the byte step of a stage.
+    // Resolved once here, so that an LDS-DMA instruction between the MFMAs is address arithmetic only: no select, no branch.
+    uint32_t uoff[NPW_MAX], ustep[NPW_MAX], ulds[NPW_MAX];
+    const unsigned char* ubase[NPW_MAX];
+    const unsigned char* ubase2[NPW_MAX];                     // dual-source 1x1: the base that stages >= NSS1 add their offset to
+#pragma unroll
+    for (int i = 0; i < NPW_MAX; ++i) {
+        const int ui = wave + i * WMR, u = ui < nun ? ui : nun - 1;
+        const bool isw = u >= nau;
+        uoff[i] = unit_off(u);
+        ulds[i] = (uint32_t)(u * 1024);
+        ustep[i] = isw ? wkstep + 0u : akstep + 0u;
+        ubase[i] = isw ? wbase + 0 : abase + 0;
+        ubase2[i] = isw ? wbase + 0 : a2base - (size_t)NSS1 * akstep;
     }
-
-    constexpr int MIK = KS ? 2 : 1;
-    f32x16 acc[MIK][NI];
-#pragma unroll
-    for (int mi = 0; mi < MIK; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
-    const int kgrp = wave >> 1, kh = wave & 1;                // KS: pair index and K half of this wave
-
-    // DMA units of this wave when every wave stages its share: u = wave + i * WMR.  Their stage-0 source offsets are computed once; a
-    // stage is a uniform byte step (SUB-or-1 x 64 B along an A row, SUB-or-1 [npad][64 B] slabs of the packed weights).
-    constexpr int MAXU = NI == 2 ? 8 : 10;                    // >= ceil(units / WMR) for every WMR >= 4
-    uint32_t uoff[MAXU];
-#pragma unroll
-    for (int i = 0; i < MAXU; ++i) uoff[i] = unit_off(wave + i * WMR);       // wave-uniform unit index (wave comes from readfirstlane)
-    const int nmine = nload ? 0 : (nun - wave + WMR - 1) / WMR;              // DMA instructions this wave issues per stage
-    auto issue_unit = [&](auto I_, int buf, int st) __attribute__((always_inline)) {
+    // one LDS-DMA instruction: slot i of pipeline stage st into LDS stage buf
+    auto dma = [&](auto I_, int buf, int st) __attribute__((always_inline)) {
         constexpr int i = decltype(I_)::value;
-        if constexpr (i < MAXU) {
-            const int u = wave + i * WMR;
-            if (u < nun) dma(u, uoff[i], buf, st);
-        }
-    };
-    // MFMAs of stage `buf`; when `nbuf >= 0` the DMAs of a later stage are issued between the sub-steps, so that their issue cost
-    // hides under the matrix pipe instead of serialising after the barrier.
-    // Fragment reads run one sub-step ahead of the MFMAs in a second register set (a wave's next MFMA otherwise waits a full LDS
-    // round trip: measured 3000 instead of 1920 clk per chunk at 3 waves per SIMD).
-    Chunk16 fa[2][2], fb[2][2][NI];                           // [set][k half][fragment]
-    auto compute = [&](int buf, int nbuf, int nst) __attribute__((always_inline)) {
-        const unsigned char* Ab = dma_smem + buf * STAGE;
-        const unsigned char* Wb = Ab + A_BYTES;
-        auto load_frags = [&](auto T_) __attribute__((always_inline)) {
-            constexpr int t = decltype(T_)::value, set = t & 1;
-            const unsigned char* At = T1 ? Ab + t * (AU * 1024) : Ab;
-            if constexpr (KS) {                               // fa[set][mi]: the pair's two row fragments, fb[set][0][ni]; K half kh only
-                const int q = 2 * kh + lhi;
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi) fa[set][mi] = *reinterpret_cast<const Chunk16*>(At + swz(kgrp * 64 + mi * 32 + l31 + (T1 ? 0 : t), q));
-#pragma unroll
-                for (int ni = 0; ni < NI; ++ni) fb[set][0][ni] = *reinterpret_cast<const Chunk16*>(Wb + t * WTB + swz(ni * 32 + l31, q));
-            } else {
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    const int q = 2 * s2 + lhi;
-                    fa[set][s2] = *reinterpret_cast<const Chunk16*>(At + swz(wave * 32 + l31 + (T1 ? 0 : t), q));
-#pragma unroll
-                    for (int ni = 0; ni < NI; ++ni) fb[set][s2][ni] = *reinterpret_cast<const Chunk16*>(Wb + t * WTB + swz(ni * 32 + l31, q));
-                }
-            }
-        };
-        load_frags(IC<0>{});
-        StaticFor<SUB>::run([&](auto T_) __attribute__((always_inline)) {
-            constexpr int t = decltype(T_)::value, set = t & 1;
-            if constexpr (t + 1 < SUB) load_frags(IC<t + 1>{});
-            if constexpr (KS) {
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                    for (int ni = 0; ni < NI; ++ni)
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(&fa[set][mi]),
-                                                                             *reinterpret_cast<const bf16x8*>(&fb[set][0][ni]), acc[mi][ni], 0, 0, 0);
-            } else {
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                    for (int ni = 0; ni < NI; ++ni)
-                        acc[0][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(&fa[set][s2]),
-                                                                            *reinterpret_cast<const bf16x8*>(&fb[set][s2][ni]), acc[0][ni], 0, 0, 0);
-            }
-            if (nbuf >= 0) {
-                constexpr int PER = (MAXU + SUB - 1) / SUB;
-                StaticFor<PER>::run([&](auto J_) __attribute__((always_inline)) { issue_unit(IC<t * PER + decltype(J_)::value>{}, nbuf, nst); });
-            }
-        });
+        const unsigned char* b = ubase[i];
+        if constexpr (T1) b = st < NSS1 ? ubase[i] + 0 : ubase2[i] + 0;
+        const unsigned char* src = b + (uoff[i] + (uint32_t)st * ustep[i]);
+        __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
+                                         (void __attribute__((address_space(3)))*)(dma_smem + buf * STAGE + ulds[i]), 16, 0, 0);
     };
 
-    // Three LDS stages, stages ss+1 and ss+2 in flight while stage ss is multiplied.  s_waitcnt takes an immediate, the number of
-    // DMAs a wave has outstanding per stage (nmine) is uniform but only known at run time: dispatch once per wait.
-    auto wait_keep = [&](int keep) __attribute__((always_inline)) {        // wait until at most `keep` of this wave's DMAs are outstanding, then barrier
-        switch (keep) {
-            case 0:  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
-            case 1:  asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
-            case 2:  asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
-            case 3:  asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
-            case 4:  asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
-            case 5:  asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
-            case 6:  asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
-            case 7:  asm volatile("s_waitcnt vmcnt(7) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
-            default: asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
+    // LDS byte offsets of this lane's fragment reads inside a stage: A row fragment 0 at every tap shift (fragment 1: + 1024 B, the same
+    // swizzle phase), weight fragment 0 of tile 0 (fragment ct of tile t: + t * WTB + ct * 1024)
+    const int l15 = lane & 15, fq = lane >> 4;
+    const uint32_t aoff0 = (uint32_t)((wave * 32 + dma_arow(l15)) * 64 + fq * 16);   // unswizzled; the tap shift moves the swizzle phase (bit 2 of the row)
+    const uint32_t boff = (uint32_t)(A_BYTES + swz16(l15, fq));
+    const uint32_t lds0 = lds_addr(dma_smem);
+
+    // Fragment reads run one sub-step ahead of the MFMAs in a second register set.  They are inline asm with a hand-counted lgkmcnt tied to
+    // the fragment registers: left to the compiler, the reads sink to just before their MFMAs and every sub-step waits out an LDS round trip.
+    Chunk16 fa[2][2], fb[2][NCT];                             // [set][fragment]
+    const int ahead = nst - 1;
+    auto main_loop = [&](auto NPW_) __attribute__((always_inline)) {
+        constexpr int NPW = decltype(NPW_)::value;
+        auto issue_stage = [&](int buf, int st) __attribute__((always_inline)) {
+            StaticFor<NPW>::run([&](auto I_) __attribute__((always_inline)) { dma(I_, buf, st); });
+        };
+        // MFMAs of LDS stage `buf`; with MORE the DMAs of a later stage are issued between the sub-steps, so that their issue cost hides
+        // under the matrix pipe instead of serialising after the barrier
+        auto compute = [&](auto MORE_, int buf, int nbuf, int nstg) __attribute__((always_inline)) {
+            constexpr bool MORE = decltype(MORE_)::value != 0;
+            const uint32_t sb = lds0 + (uint32_t)(buf * STAGE);
+            const uint32_t baddr = sb + boff;
+            auto load_frags = [&](auto T_) __attribute__((always_inline)) {
+                constexpr int t = decltype(T_)::value, set = t & 1;
+                // swz16 on the byte address: bit 5 (slot bit 1) ^= bit 8 (row bit 2).  Stages and A tiles are multiples of 1 KiB: folded in before
+                const uint32_t av = sb + aoff0 + (uint32_t)(T1 ? t * (AU * 1024) : t * 64), aaddr = av ^ ((av >> 3) & 32u);
+                fa[set][0] = lds16_asm<0>(aaddr);
+                fa[set][1] = lds16_asm<1024>(aaddr);
+                StaticFor<NCT>::run([&](auto C_) __attribute__((always_inline)) { constexpr int ct = decltype(C_)::value; fb[set][ct] = lds16_asm<t * WTB + ct * 1024>(baddr); });
+            };
+            load_frags(IC<0>{});
+            StaticFor<SUB>::run([&](auto T_) __attribute__((always_inline)) {
+                constexpr int t = decltype(T_)::value, set = t & 1;
+                if constexpr (t + 1 < SUB) load_frags(IC<t + 1>{});
+                lgkm_wait<(t + 1 < SUB) ? 2 + NCT : 0>(fa[set], fb[set]);       // the reads of sub-step t + 1 stay in flight
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                    for (int ct = 0; ct < NCT; ++ct) acc[mt][ct] = mfma16_bf16(fa[set][mt], fb[set][ct], acc[mt][ct]);
+                if constexpr (MORE)
+                    StaticFor<NPW>::run([&](auto I_) __attribute__((always_inline)) {
+                        constexpr int i = decltype(I_)::value;
+                        if constexpr (i * SUB / NPW == t) dma(I_, nbuf, nstg);
+                    });
+                __builtin_amdgcn_sched_barrier(0);
+            });
+        };
+        // nst LDS stages: stage ss+1 .. ss+nst-1 are in flight while stage ss is multiplied (nst = 3: two ahead; nst = 2: one ahead, two
+        // thirds of the LDS, so that a second workgroup - of another kernel on another stream - can be co-resident on the CU)
+        issue_stage(0, ssmap(0));
+        if (ahead > 1 && NSS > 1) issue_stage(1, ssmap(1));
+        int cur = 0, ss = 0;                                  // LDS stage of pipeline stage ss (ss % nst)
+        // this wave's DMAs of stage ss have landed (those of later stages may still fly: exactly NPW of them); after the barrier so have
+        // everyone's, and every wave is done reading the LDS stage of ss-1, which is refilled with stage ss+ahead during the MFMAs below.
+        // Two loops, each with ONE body (stages that refill, then the last `ahead` that do not): with both bodies in one loop the
+        // accumulators are copied between register sets instead of updated in place.
+        for (; ss + ahead < NSS; ++ss) {
+            if (ahead > 1) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(NPW) : "memory");
+            else           asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            const int nxt = cur == 0 ? nst - 1 : cur - 1;     // (ss + ahead) % nst
+            compute(IC<1>{}, cur, nxt, ssmap(ss + ahead));
+            cur = cur == nst - 1 ? 0 : cur + 1;
+        }
+        for (; ss < NSS; ++ss) {
+            if (ahead > 1 && ss + 1 < NSS) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(NPW) : "memory");
+            else                           asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            compute(IC<0>{}, cur, 0, 0);
+            cur = cur == nst - 1 ? 0 : cur + 1;
         }
     };
-    // nst LDS stages: stage ss+1 .. ss+nst-1 are in flight while stage ss is multiplied (nst = 3: two ahead; nst = 2: one ahead, two
-    // thirds of the LDS, so that a second workgroup - of another kernel on another stream - can be co-resident on the CU)
-    const int ahead = nst - 1;                                // (loader waves: the host passes nst = 2)
-    if (!nload) StaticFor<MAXU>::run([&](auto I_) __attribute__((always_inline)) { issue_unit(I_, 0, ssmap(0)); });
-    if (!nload && ahead > 1 && NSS > 1) StaticFor<MAXU>::run([&](auto I_) __attribute__((always_inline)) { issue_unit(I_, 1, ssmap(1)); });
-    int cur = 0;                                              // LDS stage of pipeline stage ss (ss % nst)
-    for (int ss = 0; ss < NSS; ++ss) {
-        // this wave's DMAs of stage ss have landed (those of later stages may still fly); after the barrier so have everyone's,
-        // and every wave is done reading the LDS stage of ss-1, which is refilled with stage ss+ahead during the MFMAs below
-        wait_keep((ahead > 1 && ss + 1 < NSS) ? nmine : 0);
-        const bool more = !nload && ss + ahead < NSS;
-        const int nxt = cur == 0 ? nst - 1 : cur - 1;         // (ss + ahead) % nst
-        compute(cur, more ? nxt : -1, more ? ssmap(ss + ahead) : 0);
-        cur = cur == nst - 1 ? 0 : cur + 1;
-    }
+    // one peeled copy of the loop per DMA count (wave-uniform, fixed for the launch)
+    StaticFor<NPW_MAX - NPW_MIN + 1>::run([&](auto V_) __attribute__((always_inline)) {
+        constexpr int NPW = NPW_MIN + decltype(V_)::value;
+        if (npw == NPW) main_loop(IC<NPW>{});
+    });
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr (KS) {
-        // partners swap halves of their partial sums: wave (g, kh) hands over row fragment 1 - kh and keeps fragment kh, i.e. rows
-        // [32 * wave, 32 * wave + 32) of the tile - the plain kernel's assignment.  The stage buffers are free now (every DMA has landed,
-        // the barrier below orders the last fragment reads before the overwrite).
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        float* xmine = reinterpret_cast<float*>(dma_smem) + wave * (NI * 16 * 64) + lane;
-        const float* xpart = reinterpret_cast<const float*>(dma_smem) + (wave ^ 1) * (NI * 16 * 64) + lane;
-        if (kh) {
+
+    // 16x16 fragments -> the 32x32 accumulator layout of the shared epilogue (see dma_geometry_ok)
+    f32x16 accf[1][NI];
 #pragma unroll
-            for (int ni = 0; ni < NI; ++ni)
+    for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) xmine[(ni * 16 + r) * 64] = acc[0][ni][r];
-        } else {
+        for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-            for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) xmine[(ni * 16 + r) * 64] = acc[1][ni][r];
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (kh) {
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[0][ni][r] = acc[1][ni][r] + xpart[(ni * 16 + r) * 64];
-        } else {
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[0][ni][r] += xpart[(ni * 16 + r) * 64];
-        }
-    }
-    f32x16 (&accf)[1][NI] = reinterpret_cast<f32x16 (&)[1][NI]>(acc);         // row fragment of this wave: acc[0][*]
-    conv_epilogue<CT, 1, NI, EPI, false>(p, accf, m0, n0, BM, wave, 0, lane, tid, nullptr);
+            for (int i = 0; i < 4; ++i) {
+                const auto xy = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[mt][2 * ni][i]), __float_as_uint(acc[mt][2 * ni + 1][i]), false, false);
+                accf[0][ni][8 * mt + i] = __uint_as_float(xy[0]);
+                accf[0][ni][8 * mt + 4 + i] = __uint_as_float(xy[1]);
+            }
+    conv_epilogue<CT, 1, NI, EPI, PITCH>(p, accf, m0, n0, BM, wave, 0, lane, tid, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1666,25 +1677,15 @@ inline bool dma_prefers_32(const glowtts_conv_args& a)
 template <int EPI, int TAPS, int NI = 2>
 int launch_dma(const glowtts_conv_args& a, hipStream_t s)
 {
-    // wave pairs over the two K halves (see conv_dma_kernel): measured on MI355X at B = 32 (tools/ab_conv.sh), a third less LDS fragment
-    // traffic bought nothing - In_l forward 18.3 vs 17.0 us, data gradient 19.9 vs 19.6, 1x1 convs 13.0 vs 12.6: the K loop is not bound
-    // by LDS read bandwidth but by its barrier / DMA-issue / latency structure.  Instantiated in tools builds only.
-#ifdef GLOWTTS_TOOLS
-    const int ksplit = GLOWTTS_TUNABLE("GLOWTTS_DMA_KSPLIT", 0);
-#else
-    constexpr int ksplit = 0;
-#endif
     // waves per workgroup: all tiles resident at once (one workgroup per CU) if possible, else the fewest rounds
     const int force = GLOWTTS_TUNABLE("GLOWTTS_DMA_WAVES", 0);
-    // GLOWTTS_DMA_LOADERS = 1 | 2: that many extra waves per workgroup do all the LDS-DMA staging (wave specialisation)
-    const int nload_ = GLOWTTS_TUNABLE("GLOWTTS_DMA_LOADERS", 0), nload = (nload_ >= 0 && nload_ <= 4) ? nload_ : 0;
     // GLOWTTS_DMA_CUS: CUs the chain kernels plan for (default: all).  Leaving a few CUs to the concurrently running encoder stream
     // can pay: these kernels are latency-bound, a fatter workgroup on fewer CUs costs them little.
     const int cu_budget = GLOWTTS_TUNABLE("GLOWTTS_DMA_CUS", 0);
     const int gy = a.npad / (NI * 32), ncu = (cu_budget >= 32 && cu_budget <= num_cus()) ? cu_budget : num_cus(), frags = (a.rows + 31) / 32;
     int best = 4; long best_cost = -1;
-    const int WMAX = (TAPS == 1 ? 10 : 16) - nload;       // three LDS stages must fit 160 KiB; at most 16 waves
-    for (int w = 4; w <= WMAX; ++w) {
+    constexpr int WMAX = dma_wmax(TAPS);
+    for (int w = DMA_WMIN; w <= WMAX; ++w) {
         const long tiles = (long)((frags + w - 1) / w) * gy;
         const long cost = ((tiles + ncu - 1) / ncu) * (w + 4);      // rounds x (strip work + fixed prologue / epilogue share)
         if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = w; }
@@ -1695,14 +1696,14 @@ int launch_dma(const glowtts_conv_args& a, hipStream_t s)
     // ms/step.  Only while every workgroup is resident at once; otherwise the round-count model above decides.  The same idea for the
     // k-tap convs (7 waves, two per CU) was box-dependent: -0.07 ms on one, +0.05 on the other; not adopted.
     const int coop = GLOWTTS_TUNABLE("GLOWTTS_DMA_COOP", 1);
-    if (coop && !nload && TAPS == 1) {
+    if (coop && TAPS == 1) {
         const long tiles = (long)((frags + 3) / 4) * gy;
         if (tiles > ncu && tiles <= 3L * ncu) best = 4;
     }
     // k-tap convs with few columns (the WaveNet In data gradient: 192 columns = 3 strips): the round model picks 5 waves x 243 workgroups,
     // i.e. 1.25 waves per SIMD; 7 waves x 174 workgroups hide more of the load latency and leave 80 CUs to the encoder stream's backward:
     // 6.21 -> 6.15 and 6.27 -> 6.21 ms/step on two boxes (8 waves: -0.04, 10: +0.05).  Only while that still fills half the chip.
-    if (coop && !nload && TAPS > 1 && gy <= 3 && best < 7) {
+    if (coop && TAPS > 1 && gy <= 3 && best < 7) {
         const long tiles = (long)((frags + 6) / 7) * gy;
         if (tiles <= ncu && 2 * tiles >= ncu) best = 7;
     }
@@ -1715,8 +1716,6 @@ int launch_dma(const glowtts_conv_args& a, hipStream_t s)
     if (TAPS == 1 && gy <= 3 && force_t1n >= 4 && force_t1n <= WMAX) best = force_t1n;
     const int force_t5n = GLOWTTS_TUNABLE("GLOWTTS_DMA_WAVES_T5_NARROW", 0);      // k-tap convs with <= 192 columns
     if (TAPS > 1 && gy <= 3 && force_t5n >= 4 && force_t5n <= WMAX) best = force_t5n;
-    const bool ks = ksplit && !nload && NI == 2;
-    if (ks && (best & 1)) best += (best < WMAX) ? 1 : -1;                 // wave pairs
     const int BM = best * 32;
     const int nat = TAPS == 1 ? DMA1_CPS : 1, sub = TAPS == 1 ? DMA1_CPS : TAPS;
     // LDS stages: 2 by default.  Alone, the kernel is as fast with 2 as with 3 (17.7 us either way); in the training step the smaller
@@ -1724,24 +1723,18 @@ int launch_dma(const glowtts_conv_args& a, hipStream_t s)
     const int nst0 = GLOWTTS_TUNABLE("GLOWTTS_DMA_STAGES", 2) == 3 ? 3 : 2;
     const int nst_narrow = GLOWTTS_TUNABLE("GLOWTTS_DMA_STAGES_NARROW", 0);
     const int nst = (TAPS > 1 && gy <= 3 && (nst_narrow == 2 || nst_narrow == 3)) ? nst_narrow : nst0;
-    int lds = (nload ? 2 : nst) * ((nat * ((BM + TAPS - 1 + 15) >> 4) + sub * (NI * 2)) * 1024);     // three stages: <= 159 KiB (16 waves x 5 taps, 10 waves 1x1)
-    if (ks) lds = std::max(lds, best * NI * 16 * 64 * 4);                 // the partial-sum exchange reuses the stage buffers
+    const int lds = nst * ((nat * ((BM + TAPS - 1 + 15) >> 4) + sub * (NI * 2)) * 1024);     // three stages: <= 159 KiB (16 waves x 5 taps, 10 waves 1x1)
+    const int npw = dma_npw(TAPS, NI, best);                              // the kernel holds one copy of its loop per DMA count of this range
+    if (npw < dma_npw(TAPS, NI, WMAX) || npw > dma_npw(TAPS, NI, DMA_WMIN)) return GLOWTTS_E_ARG;
     static bool attr_done = false;
     if (!attr_done) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dma_kernel<EPI, TAPS, NI, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
             return GLOWTTS_E_LAUNCH;
-#ifdef GLOWTTS_TOOLS
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dma_kernel<EPI, TAPS, NI, NI == 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return GLOWTTS_E_LAUNCH;
-#endif
         attr_done = true;
     }
     dim3 grid(((a.rows + BM - 1) / BM) * gy);
     GLOWTTS_NOTE_STATIC("conv_dma<%s,%d>", epi_name(EPI), TAPS);
-#ifdef GLOWTTS_TOOLS
-    if (ks) { hipLaunchKernelGGL((conv_dma_kernel<EPI, TAPS, NI, NI == 2>), grid, dim3(best * 64), lds, s, a, nst, 0); RET_LAUNCH(); }
-#endif
-    hipLaunchKernelGGL((conv_dma_kernel<EPI, TAPS, NI, false>), grid, dim3((best + nload) * 64), lds, s, a, nload ? 2 : nst, nload);
+    hipLaunchKernelGGL((conv_dma_kernel<EPI, TAPS, NI, false>), grid, dim3(best * 64), lds, s, a, nst);
     RET_LAUNCH();
 }
 
