@@ -320,6 +320,16 @@ SIGNATURES = {
     "glowtts_pwg_disc_layer_bwd": (I, [P] * 5 + [I] * 4 + [F, P]),
     "glowtts_pwg_disc_first_bwd": (I, [P] * 5 + [I] * 3 + [F, P]),
     "glowtts_pwg_disc_wgrad": (I, [P] * 6 + [I] * 5 + [P]),
+    "glowtts_hifigan_disc_supported": (I, [I] * 3),
+    "glowtts_hifigan_disc_work_floats": (L, [I] * 5),
+    "glowtts_hifigan_disc_first": (I, [P] * 4 + [I] * 5 + [P]),
+    "glowtts_hifigan_disc_conv": (I, [P] * 4 + [I] * 6 + [F, P]),
+    "glowtts_hifigan_disc_post": (I, [P] * 4 + [I] * 4 + [F, P]),
+    "glowtts_hifigan_disc_fm": (I, [P] * 5 + [L, F, I, P]),
+    "glowtts_hifigan_disc_post_bwd": (I, [P] * 7 + [I] * 4 + [F, P]),
+    "glowtts_hifigan_disc_conv_bwd": (I, [P] * 6 + [I] * 6 + [F, P]),
+    "glowtts_hifigan_disc_first_bwd": (I, [P] * 3 + [I] * 6 + [P]),
+    "glowtts_hifigan_disc_wgrad": (I, [P] * 5 + [I] * 8 + [F, P]),
     "glowtts_mel_cepstrum_supported": (I, [I] * 2),
     "glowtts_mel_cepstrum": (I, [P] * 4 + [I] * 4 + [L] * 3 + [F, P]),
     "glowtts_dtw_supported": (I, [I] * 3),
@@ -339,5 +349,5 @@ VALUE_RETURNING = frozenset({
     "glowtts_abi_version", "glowtts_opt_chunk",
     "glowtts_cond_linear_supported", "glowtts_gst_supported", "glowtts_conv3x3s2_supported", "glowtts_dur_proj_supported", "glowtts_vocoder_supported",
     "glowtts_pwg_supported", "glowtts_pwg_supported_bf16", "glowtts_hifigan_supported", "glowtts_hifigan_train_supported", "glowtts_ge2e_supported", "glowtts_pwg_train_supported", "glowtts_stft_loss_supported",
-    "glowtts_pwg_disc_supported", "glowtts_mel_cepstrum_supported", "glowtts_dtw_supported", "glowtts_tsne_supported",
+    "glowtts_pwg_disc_supported", "glowtts_hifigan_disc_supported", "glowtts_mel_cepstrum_supported", "glowtts_dtw_supported", "glowtts_tsne_supported",
 })

@@ -29,16 +29,17 @@ BUNDLES = (("", "model", "pwg", pwg_load, ("generator", "Optimizer", "Steps")),
            ("disc_", "discriminator", "pwg_disc", pwg_disc_load, ("discriminator", "Discriminator_Optimizer", "Discriminator_Steps")))
 
 
-def train_settings(hp, defaults=DEFAULTS):
+def train_settings(hp, defaults=DEFAULTS, also=("Discriminator",)):
     """The optional yaml block `Vocoder.Train` over `defaults` (`hparams.overlay_settings`), checked: a ValueError names every bad key.  The optional
-    sub-block `Discriminator` (`vocoder.pwg_disc_settings`) appears in the result only when the yaml has it."""
+    sub-block `Discriminator` (`vocoder.pwg_disc_settings`) appears in the result only when the yaml has it.  also: the sub-blocks the caller allows and
+    reads (another trainer's stage two has another key)."""
     def rules(s, need):
         for k in ("Batch_Size", "Segment_Frames", "Max_Step", "Checkpoint_Save_Interval", "Evaluation_Interval"):
             need(k, lambda v: int(v) >= 1, "at least 1")
         for k in ("Learning_Rate", "Epsilon", "Gradient_Norm"):
             need(k, lambda v: float(v) > 0, "positive")
         need("Learning_Rate_Decay", lambda v: int(v["Step"]) >= 1 and 0 < float(v["Gamma"]) <= 1, "Step >= 1, 0 < Gamma <= 1")
-    s = overlay_settings(getattr(getattr(hp, "Vocoder", None), "Train", None), defaults, TRAIN_KEY, "vocoder", rules, also=("Discriminator",))
+    s = overlay_settings(getattr(getattr(hp, "Vocoder", None), "Train", None), defaults, TRAIN_KEY, "vocoder", rules, also=also)
     s["STFT_Resolutions"] = stft_loss_geometry(s["STFT_Resolutions"], int(s["Segment_Frames"]) * int(hp.Sound.Frame_Shift))
     if "Discriminator" in s:
         s["Discriminator"] = pwg_disc_settings(hp)
@@ -96,9 +97,10 @@ class Sampler(aux_trainer.PatternSampler):
 
 
 class PWG_Trainer(aux_trainer.Trainer):
-    """A subclass for another generator (`hifigan_trainer.HiFiGAN_Trainer`) replaces PREFIX, BUNDLES and the four hooks below `__init__`."""
+    """A subclass for another generator (`hifigan_trainer.HiFiGAN_Trainer`) replaces PREFIX, BUNDLES, DISC_BLOCK and the hooks below `__init__`."""
     PREFIX = "PWG"
     BUNDLES = BUNDLES
+    DISC_BLOCK = "Discriminator"                           # the key of `settings` (and of Vocoder.Train) that holds stage two's block
 
     def __init__(self, steps=0, hp=None, device="cuda:0", seed=0):
         hp = hp if hp is not None else get_hp()
@@ -110,9 +112,9 @@ class PWG_Trainer(aux_trainer.Trainer):
         self.params = list(self.model.params.values())
         self.optimizer = optim.RAdam(self.params, lr=float(s["Learning_Rate"]), eps=float(s["Epsilon"]))
         # stage two (optional block Vocoder.Train.Discriminator): initialised from the seed at construction, untouched before Start_Step
-        self.disc_set, self.discriminator, self.disc_steps = s.get("Discriminator"), None, 0
+        self.disc_set, self.discriminator, self.disc_steps = s.get(self.DISC_BLOCK), None, 0
         if self.disc_set is not None:
-            self.discriminator = PWGDiscriminator(self.hp, self.device, trainable=True, seed=self.seed)
+            self.discriminator = self.make_discriminator()
             self.disc_params = list(self.discriminator.params.values())
             self.disc_optimizer = optim.RAdam(self.disc_params, lr=float(self.disc_set["Learning_Rate"]), eps=float(self.disc_set["Epsilon"]))
         if self.steps > 0:
@@ -122,6 +124,20 @@ class PWG_Trainer(aux_trainer.Trainer):
 
     def make_model(self):
         return ParallelWaveGAN(self.hp, self.device, trainable=True, seed=self.seed, precision="f32")            # (Vocoder.Precision is a serving setting)
+
+    def make_discriminator(self):
+        return PWGDiscriminator(self.hp, self.device, trainable=True, seed=self.seed)
+
+    def adversarial_losses(self, target, wav, stft):
+        """-> (L_G, L_D, the unscaled (L_adv, real term, fake term) [3], L_stft) from one discriminator forward over [target; wav]"""
+        both, p_fake = self.discriminator.score_pair(target, wav)
+        adv, adv_terms = adversarial_mse(p_fake, 1.0, float(self.disc_set["Lambda_Adversarial"]))
+        d_loss, d_terms = adversarial_mse(both, (1.0, 0.0))
+        return stft + adv, d_loss, torch.cat([adv_terms[:1], d_terms]), stft
+
+    def without_discriminator(self, state):
+        """The bundles to load from a checkpoint `state` that holds no discriminator although this run has one (here: none, an error)"""
+        raise ValueError("{} holds no discriminator: it was written without the block {}.{}".format(self.checkpoint_file(self.steps), TRAIN_KEY, self.DISC_BLOCK))
 
     def generate(self, mel, lengths, step):
         """The generator's waveform of batch `step` with its backward"""
@@ -149,10 +165,7 @@ class PWG_Trainer(aux_trainer.Trainer):
         stft = self.criterion(wav, target)
         if not adversarial:
             return stft
-        both, p_fake = self.discriminator.score_pair(target, wav)
-        adv, adv_terms = adversarial_mse(p_fake, 1.0, float(self.disc_set["Lambda_Adversarial"]))
-        d_loss, d_terms = adversarial_mse(both, (1.0, 0.0))
-        return stft + adv, d_loss, torch.cat([adv_terms[:1], d_terms]), stft
+        return self.adversarial_losses(target, wav, stft)
 
     def update(self, bundles, losses):
         """The backwards of `losses`, then the update of every bundle of `bundles` -> its gradient norms.  Phase by phase over the bundles, so that both
@@ -221,9 +234,10 @@ class PWG_Trainer(aux_trainer.Trainer):
         return state
 
     def load_state_dict(self, state):
+        bundles = self.bundles()
         if self.discriminator is not None and "discriminator" not in state:
-            raise ValueError("{} holds no discriminator: it was written without the block {}.Discriminator".format(self.checkpoint_file(self.steps), TRAIN_KEY))
-        for prefix, model, _, load, (_, optimizer, steps) in self.bundles():
+            bundles = self.without_discriminator(state)
+        for prefix, model, _, load, (_, optimizer, steps) in bundles:
             model = getattr(self, model)
             with torch.no_grad():
                 for k, v in load(state, model.geo).items():

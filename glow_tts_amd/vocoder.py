@@ -1507,6 +1507,294 @@ class HiFiGAN:
         return [np.clip(w[:m], -1.0, 1.0).astype(np.float32) for w, m in zip(wav, n)]
 
 
+# ================================================================================================================================================
+# The HiFi-GAN multi-period discriminator on the kernels of csrc/hifigan_disc_ops.hip: forward, backward, feature matching, f32.  The network is written
+# down in DESIGN.md ("Training the HiFi-GAN discriminator"); it and the checkpoint layout restate the most widely used implementation from memory and are
+# UNPINNED, like the other vocoder contracts.  Kernel sizes 5 / 3 and stride 3 are constants of the architecture, not yaml keys.
+# ================================================================================================================================================
+MPD_KEY = "Vocoder.Train.Adversarial"
+MPD_DEFAULTS = {"Start_Step": 0, "Lambda_Adversarial": 1.0, "Lambda_Feature_Matching": 2.0, "Learning_Rate": 2.0e-4, "Epsilon": 1.0e-6, "Gradient_Norm": 10.0,
+                "Learning_Rate_Decay": {"Step": 200000, "Gamma": 0.5}, "Periods": [2, 3, 5, 7, 11], "Channels": [32, 128, 512, 1024, 1024], "Negative_Slope": 0.1}
+MPD_TAPS, MPD_POST_TAPS, MPD_STRIDE, MPD_MAX_PERIOD, MPD_MAX_PERIODS, MPD_MAX_CHANNELS, MPD_MAX_WIDTHS = 5, 3, 3, 16, 8, 1024, 6
+
+
+def hifigan_disc_settings(hp):
+    """The optional yaml block `Vocoder.Train.Adversarial` over MPD_DEFAULTS (absent block: None), checked: a ValueError names every unknown or bad key."""
+    block = getattr(getattr(getattr(hp, "Vocoder", None), "Train", None), "Adversarial", None)
+    if block is None:
+        return None
+    whole = lambda v: int(v) == v
+
+    def rules(s, need):
+        need("Start_Step", lambda v: whole(v) and int(v) >= 0, "an integer, at least 0")
+        for k in ("Lambda_Adversarial", "Lambda_Feature_Matching"):
+            need(k, lambda v: float(v) >= 0, "not negative")
+        for k in ("Learning_Rate", "Epsilon", "Gradient_Norm"):
+            need(k, lambda v: float(v) > 0, "positive")
+        need("Learning_Rate_Decay", lambda v: int(v["Step"]) >= 1 and 0 < float(v["Gamma"]) <= 1, "Step >= 1, 0 < Gamma <= 1")
+        need("Periods", lambda v: 1 <= len(v) <= MPD_MAX_PERIODS and all(whole(p) and 2 <= int(p) <= MPD_MAX_PERIOD for p in v) and len(set(int(p) for p in v)) == len(v),
+             "1 to {} distinct integers in [2, {}]".format(MPD_MAX_PERIODS, MPD_MAX_PERIOD))
+        need("Channels", lambda v: 2 <= len(v) <= MPD_MAX_WIDTHS and all(whole(c) and 16 <= int(c) <= MPD_MAX_CHANNELS and int(c) % 16 == 0 for c in v),
+             "2 to {} widths, each a multiple of 16 in [16, {}]".format(MPD_MAX_WIDTHS, MPD_MAX_CHANNELS))
+        need("Negative_Slope", lambda v: 0 <= float(v) < 1, "in [0, 1)")
+    s = overlay_settings(block, MPD_DEFAULTS, MPD_KEY, "vocoder", rules)
+    s["Periods"], s["Channels"] = [int(p) for p in s["Periods"]], [int(c) for c in s["Channels"]]
+    return s
+
+
+def hifigan_disc_geometry(hp):
+    """The discriminator's sizes as a dict (periods, channels, strides, slope) from the block `Vocoder.Train.Adversarial` (absent: the defaults); raises
+    ValueError naming the offending yaml keys (`hifigan_disc_settings`)."""
+    s = hifigan_disc_settings(hp) or MPD_DEFAULTS
+    channels = list(s["Channels"])
+    return {"periods": list(s["Periods"]), "channels": channels, "strides": [MPD_STRIDE] * (len(channels) - 1) + [1], "slope": float(s["Negative_Slope"])}
+
+
+def hifigan_disc_rows(geo, T, p):
+    """Rows h of the folded waveform and of every layer's output for period p: [H0 = ceil(T / p), H1, ..., H_last] (conv_post keeps H_last).  T below
+    2 max(Periods) - the reflect pad would reach beyond the waveform - raises a ValueError naming the key."""
+    if T < 2 * max(geo["periods"]):
+        raise ValueError(f"{MPD_KEY}.Periods = {geo['periods']}: a waveform of {T} samples is shorter than 2 max(Periods) = {2 * max(geo['periods'])}, the reflect "
+                         "pad would reach beyond it")
+    H = [-(-T // p)]
+    for s in geo["strides"]:
+        H.append((H[-1] - 1) // s + 1)
+    return H
+
+
+def hifigan_disc_expected_shapes(geo):
+    """state-dict key -> shape of the discriminator with the sizes `geo` (Conv2d weights with a kernel (k, 1))"""
+    e = {}
+    for i in range(len(geo["periods"])):
+        cin = 1
+        for j, c in enumerate(geo["channels"]):
+            e[f"discriminators.{i}.convs.{j}.weight"], e[f"discriminators.{i}.convs.{j}.bias"] = (c, cin, MPD_TAPS, 1), (c,)
+            cin = c
+        e[f"discriminators.{i}.conv_post.weight"], e[f"discriminators.{i}.conv_post.bias"] = (1, cin, MPD_POST_TAPS, 1), (1,)
+    return e
+
+
+def hifigan_disc_init(geo, seed=0):
+    """A fresh discriminator's state dict: torch's default rule per tensor (`conv_default_init`: uniform in +- 1 / sqrt(fan_in), fan_in = Cin * taps)."""
+    return conv_default_init(hifigan_disc_expected_shapes(geo), seed)
+
+
+def hifigan_disc_find_state_dict(obj):
+    """The multi-period discriminator's state dict inside what torch.load returned: at the top level, under `discriminator` / `Discriminator` / `mpd`, or
+    inside `model`.  Neither a Parallel WaveGAN discriminator (`conv_layers.*`) nor a generator (`conv_pre.*`) is taken for it."""
+    names = ("discriminator", "Discriminator", "mpd")
+    return find_state_dict(obj, ((),) + tuple((n,) for n in names) + (("model",),) + tuple(("model", n) for n in names),
+                           lambda d: any(str(k).startswith("discriminators.0.convs.0.weight") for k in d),
+                           "no HiFi-GAN multi-period discriminator state dict found (looked for `discriminators.0.convs.0.weight*` at the top level, under "
+                           "discriminator / Discriminator / mpd and inside model)")
+
+
+def hifigan_disc_load(obj, geo):
+    """-> {key: float32 host tensor} with exactly the keys of `hifigan_disc_expected_shapes` (`checked_load`: weight-norm pairs are folded once)."""
+    return checked_load(hifigan_disc_find_state_dict(obj), hifigan_disc_expected_shapes(geo), "discriminator", "multi-period discriminator", MPD_KEY)
+
+
+def hifigan_disc_forward(disc, wav, alloc=None):
+    """The forward launches on wav [B, T] (fp32, contiguous, on the device) -> dict(wav, periods: per period dict(p, H, keep, scores)).  keep[j] [B, H[j + 1] p,
+    C_j] is layer j's PRE-activation output with the flat row h p + c, scores [B, H[-1] p] conv_post's.  alloc(*shape): the caller's buffers (tests)."""
+    g, lib, P, st = disc.geo, _lib.api(), _lib.ptr, _lib.stream()
+    B, T = wav.shape
+    ch, strides, slope = g["channels"], g["strides"], g["slope"]
+    f = alloc or (lambda *shape: torch.empty(*shape, dtype=torch.float32, device=wav.device))
+    out = []
+    for p, im in zip(g["periods"], disc.images):
+        H = hifigan_disc_rows(g, T, p)
+        keep = [f(B, H[j + 1] * p, c) for j, c in enumerate(ch)]
+        scores = f(B, H[-1] * p)
+        lib.glowtts_hifigan_disc_first(P(wav), P(im["first"][0]), P(im["first"][1]), P(keep[0]), B, T, p, strides[0], ch[0], st)
+        for j in range(1, len(ch)):
+            w, b, _ = im["convs"][j - 1]
+            lib.glowtts_hifigan_disc_conv(P(keep[j - 1]), P(w), P(b), P(keep[j]), B, H[j], p, strides[j], ch[j - 1], ch[j], slope, st)
+        lib.glowtts_hifigan_disc_post(P(keep[-1]), P(im["post"][0]), P(im["post"][1]), P(scores), B, H[-1], p, ch[-1], slope, st)
+        out.append({"p": p, "H": H, "keep": keep, "scores": scores})
+    return {"wav": wav, "periods": out, "images": disc.images}     # the images this forward ran with: its backward must not see a later rebuild
+
+
+def hifigan_disc_feature_maps(disc, period_fwd):
+    """The feature maps of one period of `hifigan_disc_forward` in torch's layout: the activated outputs [B, C_j, H, p], then conv_post's [B, 1, H, p]."""
+    p, slope = period_fwd["p"], disc.geo["slope"]
+    maps = [torch.nn.functional.leaky_relu(k, slope).reshape(k.shape[0], -1, p, k.shape[2]).permute(0, 3, 1, 2) for k in period_fwd["keep"]]
+    return maps + [period_fwd["scores"].reshape(period_fwd["scores"].shape[0], 1, -1, p)]
+
+
+def hifigan_disc_work(disc, B, T, device, alloc=None):
+    """The work buffer of the backward and of the feature-matching loss on a batch of B x T: the largest layer's `glowtts_hifigan_disc_work_floats`."""
+    g, lib = disc.geo, _lib.api()
+    floats = 0
+    for p in g["periods"]:
+        H, cin = hifigan_disc_rows(g, T, p), 1
+        for j, c in enumerate(g["channels"]):
+            floats, cin = max(floats, lib.glowtts_hifigan_disc_work_floats(B, H[j + 1] * p, cin, c, MPD_TAPS)), c
+        floats = max(floats, lib.glowtts_hifigan_disc_work_floats(B, H[-1] * p, cin, 1, MPD_POST_TAPS))
+    f = alloc or (lambda *shape: torch.empty(*shape, dtype=torch.float32, device=device))
+    return f(floats)
+
+
+def hifigan_disc_feature_matching(disc, fwd, alloc=None):
+    """The feature-matching terms of a forward over [real; fake] (2 B rows) -> (terms, l_fm, inj).  terms [periods, widths + 1]: mean |lrelu(real) -
+    lrelu(fake)| per map, raw for conv_post; l_fm [1]: their sum, added up by the kernels themselves in launch order (period, then map); inj: per period the
+    gradients of the sum of its terms with respect to the fake rows' kept pre-activations (widths tensors) and scores (the last), each laid out as the fake
+    half of what the forward kept."""
+    g, lib, P, st = disc.geo, _lib.api(), _lib.ptr, _lib.stream()
+    B2, T = fwd["wav"].shape
+    B, dev = B2 // 2, fwd["wav"].device
+    f = alloc or (lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev))
+    work, terms, total, inj = hifigan_disc_work(disc, B, T, dev, alloc), f(len(g["periods"]), len(g["channels"]) + 1), f(1), []
+    for i, per in enumerate(fwd["periods"]):
+        maps = [(k, g["slope"]) for k in per["keep"]] + [(per["scores"], 1.0)]
+        inj.append([f(B, *k.shape[1:]) for k, _ in maps])
+        for j, (k, slope) in enumerate(maps):
+            lib.glowtts_hifigan_disc_fm(P(k), P(inj[i][j]), P(work), P(terms[i, j:]), P(total), k.numel() // 2, slope, 1 if i or j else 0, st)
+    return terms, total, inj
+
+
+def hifigan_disc_backward(disc, fwd, dscores, freeze=False, inj=None, inj_scale=None, need_dwav=True, alloc=None):
+    """d scores (one [B, H_last p] per period) -> (d wav [B, T] summed over the periods in period order, or None unless `need_dwav`; {name: gradient in
+    torch's layout} or None when `freeze`) from what `hifigan_disc_forward` kept (or the views of some of its batch rows).  inj (`hifigan_disc_feature_matching`)
+    times the device scalar inj_scale is added to every d pre and to d scores on the way down.  freeze: the data chain alone, no weight-gradient launch."""
+    g, lib, P, st = disc.geo, _lib.api(), _lib.ptr, _lib.stream()
+    wav = fwd["wav"]
+    B, T = wav.shape
+    ch, strides, slope, dev, n = g["channels"], g["strides"], g["slope"], wav.device, len(g["channels"])
+    f = alloc or (lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev))
+    grads = work = None
+    if not freeze:
+        grads, work = {k: f(*shape) for k, shape in hifigan_disc_expected_shapes(g).items()}, hifigan_disc_work(disc, B, T, dev, alloc)
+    scale = P(inj_scale) if inj is not None else None
+    dwav = f(B, T) if need_dwav else None
+    for i, (per, im, ds) in enumerate(zip(fwd["periods"], fwd["images"], dscores)):
+        p, H, keep = per["p"], per["H"], per["keep"]
+        ds, ij = ds.to(torch.float32).contiguous(), inj[i] if inj is not None else [None] * (n + 1)
+
+        def wgrad(name, x, dy, h, stride, cin, cout, taps, samples, sl):
+            lib.glowtts_hifigan_disc_wgrad(P(x), P(dy), P(work), P(grads[f"discriminators.{i}.{name}.weight"]), P(grads[f"discriminators.{i}.{name}.bias"]), B, h, p,
+                                           stride, cin, cout, taps, samples, sl, st)
+        d = f(B, H[-1] * p, ch[-1])
+        lib.glowtts_hifigan_disc_post_bwd(P(ds), P(ij[n]) if ij[n] is not None else None, P(keep[-1]), P(im["post"][0]), P(ij[n - 1]) if ij[n - 1] is not None else None,
+                                          scale, P(d), B, H[-1], p, ch[-1], slope, st)
+        if not freeze:
+            wgrad("conv_post", keep[-1], ds, H[-1], 1, ch[-1], 1, MPD_POST_TAPS, 0, slope)
+        for j in reversed(range(1, n)):
+            if not freeze:
+                wgrad(f"convs.{j}", keep[j - 1], d, H[j], strides[j], ch[j - 1], ch[j], MPD_TAPS, 0, slope)
+            dx = f(B, H[j] * p, ch[j - 1])
+            lib.glowtts_hifigan_disc_conv_bwd(P(d), P(im["convs"][j - 1][2]), P(keep[j - 1]), P(ij[j - 1]) if ij[j - 1] is not None else None, scale, P(dx), B, H[j], p,
+                                              strides[j], ch[j - 1], ch[j], slope, st)
+            d = dx
+        if not freeze:
+            wgrad("convs.0", wav, d, H[0], strides[0], 1, ch[0], MPD_TAPS, T, 1.0)
+        if need_dwav:
+            lib.glowtts_hifigan_disc_first_bwd(P(d), P(im["first"][0]), P(dwav), B, T, p, strides[0], ch[0], 1 if i else 0, st)
+    return dwav, grads
+
+
+class _PeriodScore(torch.autograd.Function):
+    """scores = HiFiGANPeriodDiscriminator.score(wav): forward and backward are the HIP launches of csrc/hifigan_disc_ops.hip.  `shared`: a forward that was
+    already run on this waveform with these parameters (`score_pair`) - no forward launch is made then.  freeze: no parameter gradients."""
+
+    @staticmethod
+    def forward(ctx, disc, wav, freeze, shared, *params):
+        if shared is None:
+            disc._build_images({k: t.detach() for k, t in zip(disc.params, params)})
+            shared = hifigan_disc_forward(disc, wav.detach())
+        ctx.disc, ctx.fwd, ctx.freeze, ctx.n = disc, shared, bool(freeze), len(params)
+        return tuple(per["scores"].clone() for per in shared["periods"])
+
+    @staticmethod
+    def backward(ctx, *dscores):
+        dwav, grads = hifigan_disc_backward(ctx.disc, ctx.fwd, dscores, ctx.freeze, need_dwav=ctx.needs_input_grad[1])
+        ctx.fwd = None
+        return (None, dwav, None, None) + (tuple(grads[k] for k in ctx.disc.params) if not ctx.freeze else (None,) * ctx.n)
+
+
+class _FakeTerms(torch.autograd.Function):
+    """(p_fake per period ..., l_fm) of `score_pair` as ONE node: its backward runs the frozen data chain once per period with the feature-matching gradient
+    (times d l_fm, read on the device) injected into every d pre, however many of the outputs the loss used."""
+
+    @staticmethod
+    def forward(ctx, disc, fake, half, l_fm, inj):
+        ctx.disc, ctx.fwd, ctx.inj = disc, half, inj
+        return tuple(per["scores"].clone() for per in half["periods"]) + (l_fm.reshape(()).clone(),)
+
+    @staticmethod
+    def backward(ctx, *g):
+        scale = g[-1].to(torch.float32).reshape(1).contiguous()
+        dwav, _ = hifigan_disc_backward(ctx.disc, ctx.fwd, g[:-1], True, inj=ctx.inj, inj_scale=scale)
+        ctx.fwd = ctx.inj = None
+        return None, dwav, None, None, None
+
+
+class HiFiGANPeriodDiscriminator:
+    """HiFiGANPeriodDiscriminator(hp, device, state_dict=None, trainable=True, seed=0): the multi-period discriminator.  The sizes come from the yaml block
+    `Vocoder.Train.Adversarial` (absent: the defaults).  `params` holds float32 device leaves in `hifigan_disc_expected_shapes`' names - from `state_dict`
+    (`hifigan_disc_load`) or, without one, `hifigan_disc_init(geo, seed)`; the weight images are rebuilt from them at every call (an optimizer step writes
+    the leaves in place).  A row's scores, feature maps and d wav are bit-identical alone, in any batch and from run to run."""
+
+    def __init__(self, hp, device="cuda:0", state_dict=None, trainable=True, seed=0):
+        self.geo = geo = hifigan_disc_geometry(hp)                  # before anything touches the device
+        self.trainable = bool(trainable)
+        w = hifigan_disc_load(state_dict, geo) if state_dict is not None else hifigan_disc_init(geo, seed)
+        lib, widths = _lib.api(), [1] + geo["channels"] + [1]
+        if not all(lib.glowtts_hifigan_disc_supported(p, a, b) for p in geo["periods"] for a, b in zip(widths, widths[1:])):
+            raise ValueError(f"the {MPD_KEY} block's sizes {geo} are not supported by the kernels")
+        self.device = torch.device(device)
+        self.params = {k: t.to(self.device).requires_grad_(self.trainable) for k, t in w.items()}
+        self._build_images({k: t.detach() for k, t in self.params.items()})
+
+    def _build_images(self, w):
+        """Per period the weight images in the kernels' layouts: first [5][C0] and post [3][C] (row = tap); a middle layer's forward image [5 Cin][Cout]
+        (row = tap Cin + input channel) and its backward image [5 Cout][Cin] (row = tap Cout + output channel)."""
+        dev, n = (lambda t: t.contiguous().to(self.device)), len(self.geo["channels"])
+        self.images = []
+        for i in range(len(self.geo["periods"])):
+            q = f"discriminators.{i}."
+            conv = lambda j: w[f"{q}convs.{j}.weight"][..., 0]
+            self.images.append({"first": (dev(conv(0)[:, 0, :].t()), dev(w[f"{q}convs.0.bias"])),
+                                "convs": [(dev(conv(j).permute(2, 1, 0).reshape(-1, conv(j).shape[0])), dev(w[f"{q}convs.{j}.bias"]),
+                                           dev(conv(j).permute(2, 0, 1).reshape(-1, conv(j).shape[1]))) for j in range(1, n)],
+                                "post": (dev(w[f"{q}conv_post.weight"][0, :, :, 0].t()), dev(w[f"{q}conv_post.bias"]))})
+
+    def _check(self, wav):
+        if wav.dim() != 2 or wav.dtype != torch.float32 or not wav.is_cuda:
+            raise _lib.GlowTTSHipError("HiFiGANPeriodDiscriminator: expected an fp32 device tensor [B, T] (the HIP path has no CPU fallback), got "
+                                       f"{list(wav.shape)} {wav.dtype}")
+        B, T = wav.shape
+        for p in self.geo["periods"]:
+            hifigan_disc_rows(self.geo, T, p)
+        if B < 1 or B > 65535 or B * (T + MPD_MAX_PERIOD) > 2 ** 30:
+            raise ValueError(f"HiFiGANPeriodDiscriminator: a batch of {B} x {T} samples is outside 1 <= B <= 65535, B (T + {MPD_MAX_PERIOD}) <= 2^30")
+
+    def score(self, wav, freeze=False):
+        """wav [B, T] -> a list of scores [B, H_last p], one per period, with a backward: d wav summed over the periods in period order and, unless `freeze`,
+        the parameter gradients."""
+        self._check(wav)
+        return list(_PeriodScore.apply(self, wav.contiguous(), freeze, None, *self.params.values()))
+
+    def score_pair(self, real, fake):
+        """ONE forward over [real; fake] (2 B rows) per period -> (both: scores [2 B, N_p] per period whose backward yields the parameter gradients alone;
+        p_fake: scores [B, N_p] of the fake rows per period, and l_fm: the 0-d sum over periods and maps of mean |lrelu(real map) - lrelu(fake map)| - the
+        backward of these two is ONE frozen data chain per period over the fake rows, reaching the fake waveform alone, with no weight-gradient launch;
+        fm_terms [periods, widths + 1]: the terms).  The real rows' feature maps are constants."""
+        self._check(fake)
+        if tuple(real.shape) != tuple(fake.shape):
+            raise ValueError(f"HiFiGANPeriodDiscriminator.score_pair: real {list(real.shape)} and fake {list(fake.shape)} differ in shape")
+        B = fake.shape[0]
+        both = torch.cat([real.detach().to(device=self.device, dtype=torch.float32), fake.detach()]).contiguous()
+        self._check(both)
+        self._build_images({k: t.detach() for k, t in self.params.items()})
+        fwd = hifigan_disc_forward(self, both)
+        terms, l_fm, inj = hifigan_disc_feature_matching(self, fwd)
+        half = {"wav": both[B:], "images": fwd["images"], "periods": [{"p": per["p"], "H": per["H"], "keep": [k[B:] for k in per["keep"]], "scores": per["scores"][B:]}
+                                             for per in fwd["periods"]]}
+        out = _FakeTerms.apply(self, fake.contiguous(), half, l_fm, inj)
+        return list(_PeriodScore.apply(self, both, False, fwd, *self.params.values())), list(out[:-1]), out[-1], terms.detach()
+
+
 VOCODER_KINDS = ("griffin_lim", "pwg", "hifigan")
 
 

@@ -1159,6 +1159,52 @@ int glowtts_pwg_disc_first_bwd(const float *dout, const float *out, const float 
 int glowtts_pwg_disc_wgrad(const float *a, const float *dpre, const int32_t *lengths, float *work, float *dw, float *db, int B, int T, int Cin, int Cout,
                            int dilation, void *stream);
 
+/* ---- The HiFi-GAN multi-period discriminator and the feature-matching loss (csrc/hifigan_disc_ops.hip; f32; additions, the ABI version stays) ----
+ * One sub-network per period p: wav [B][T] is reflect-padded on the right to H0 p samples, H0 = ceil(T / p) (sample T + j is sample T - 2 - j), and folded to
+ * rows (h, c) = (n / p, n % p); convolutions run over h alone: `widths` layers of 5 taps, zero padding 2 and stride 3 (the last: 1), then conv_post with 3
+ * taps, width -> 1.  H' = (H - 1) / stride + 1.  Activations are channels-last [B][H p][C] with the flat row n = h p + c and hold PRE-activations: the
+ * LeakyReLU is the consumer's prologue and the backward recomputes its mask (1 where pre > 0, the slope elsewhere).  Every batch row is of the full length;
+ * a row's result does not depend on the batch around it and nothing beyond the B H p rows is read or written.  Matrix products: v_mfma_f32_16x16x4_f32.
+ * No float atomics, fixed partitions and orders: bit-identical from run to run.  None of these functions allocates.
+ * Supported (glowtts_hifigan_disc_supported, else GLOWTTS_E_ARG): period in [2, 16]; widths multiples of 16 in [16, 1024] (Cin = 1: the first layer,
+ * Cout = 1: conv_post); stride 1 or 3; T >= 2 period; 1 <= B <= 65535, B H p <= 2^30.
+ *   work   glowtts_hifigan_disc_work_floats(B, rows_out, Cin, Cout, taps) floats, 8-byte aligned: the weight gradient's splits of a layer with rows_out flat
+ *          output rows per batch row (one split per batch row and 1024 rows), and at least the block sums of glowtts_hifigan_disc_fm on that layer's output.
+ * glowtts_hifigan_disc_first      `hifigan_disc_first`: wav -> out [B][H1 p][C]; w [5][C] (row = tap), bias [C].
+ * glowtts_hifigan_disc_conv       `hifigan_disc_conv`: x [B][H p][Cin] -> out [B][H' p][Cout] = bias + conv(lrelu(x, slope)); w [5 Cin][Cout]: row = tap Cin +
+ *                                 input channel.
+ * glowtts_hifigan_disc_post       `hifigan_disc_post`: x [B][H p][C] -> scores [B][H p] = bias + conv(lrelu(x, slope)); w [3][C] (row = tap), bias [1].
+ * glowtts_hifigan_disc_fm         `hifigan_disc_fm` + `hifigan_disc_fm_sum`: f holds 2 count floats, a feature map of the real rows then of the fake rows;
+ *                                 term [1] = mean |lrelu(fake) - lrelu(real)| (slope 1: raw), float64 block sums of 4096 elements added in ascending order;
+ *                                 inj [count] = sign(lrelu(fake) - lrelu(real)) lrelu'(fake) / count, sign(0) = 0.  count < 2^30.  total [1] (or NULL):
+ *                                 receives the term (accumulate 0) or total + term (accumulate 1): L_fm as the sum of the terms in launch order.
+ * glowtts_hifigan_disc_post_bwd   `hifigan_disc_post_bwd`: d = dscores + dscores2 *inj_scale ([B][H p]; dscores2 may be NULL) -> dx [B][H p][C] = lrelu'(x) times
+ *                                 the transposed conv_post of d, + inj *inj_scale (inj [B][H p][C] or NULL).  inj_scale: ONE float on the device.
+ * glowtts_hifigan_disc_conv_bwd   `hifigan_disc_conv_bwd`: dy [B][H' p][Cout] (d pre of the layer's output), x [B][H p][Cin] (the kept pre-activation of its
+ *                                 input) -> dx [B][H p][Cin] = lrelu'(x) times the transposed convolution of dy, + inj *inj_scale; wt [5 Cout][Cin]: row = tap
+ *                                 Cout + output channel.
+ * glowtts_hifigan_disc_first_bwd  `hifigan_disc_first_bwd`: dpre [B][H1 p][C] of the first layer -> dwav [B][T]: d(padded wav) gathered at t and, where that
+ *                                 lies in [T, H0 p), at 2 T - 2 - t; accumulate 1: added to what dwav holds (the periods, in period order).
+ * glowtts_hifigan_disc_wgrad      `hifigan_disc_wgrad` + `hifigan_disc_wgrad_sum` (the kernels of glowtts_hifigan_wgrad under the discriminator's row map)
+ *                                 for ONE layer with H input rows: x its input (lrelu(x, slope) is formed on the way in), dy [B][H' p][Cout] -> dw
+ *                                 [Cout][Cin][taps], dbias [Cout] in torch's layouts; overwritten.  taps 5, or 3 with stride 1 (conv_post).  Cin == 1: x is
+ *                                 the waveform [B][wav_samples] itself (slope 1), H = ceil(wav_samples / period); else wav_samples = 0. */
+int glowtts_hifigan_disc_supported(int period, int Cin, int Cout);
+int64_t glowtts_hifigan_disc_work_floats(int B, int rows_out, int Cin, int Cout, int taps);
+int glowtts_hifigan_disc_first(const float *wav, const float *w, const float *bias, float *out, int B, int T, int period, int stride, int C, void *stream);
+int glowtts_hifigan_disc_conv(const float *x, const float *w, const float *bias, float *out, int B, int H, int period, int stride, int Cin, int Cout, float slope,
+                              void *stream);
+int glowtts_hifigan_disc_post(const float *x, const float *w, const float *bias, float *scores, int B, int H, int period, int C, float slope, void *stream);
+int glowtts_hifigan_disc_fm(const float *f, float *inj, float *work, float *term, float *total, int64_t count, float slope, int accumulate, void *stream);
+int glowtts_hifigan_disc_post_bwd(const float *dscores, const float *dscores2, const float *x, const float *w, const float *inj, const float *inj_scale, float *dx,
+                                  int B, int H, int period, int C, float slope, void *stream);
+int glowtts_hifigan_disc_conv_bwd(const float *dy, const float *wt, const float *x, const float *inj, const float *inj_scale, float *dx, int B, int H, int period,
+                                  int stride, int Cin, int Cout, float slope, void *stream);
+int glowtts_hifigan_disc_first_bwd(const float *dpre, const float *w, float *dwav, int B, int T, int period, int stride, int C, int accumulate,
+                                   void *stream);
+int glowtts_hifigan_disc_wgrad(const float *x, const float *dy, float *work, float *dw, float *dbias, int B, int H, int period, int stride, int Cin, int Cout,
+                               int taps, int wav_samples, float slope, void *stream);
+
 /* ---- Objective evaluation: mel cepstra and dynamic time warping (csrc/eval_ops.hip; f32; additions, the ABI version stays) ----
  * glowtts_mel_cepstrum   `eval_mel_cepstrum`: mels in this project's normalisation m = 2A (db + 100) / 100 - A (A = max_abs; values at the clip +- A taken
  *   as they are), read through the element strides (stride_b, stride_t, stride_m) - [B][T][Mel] or the models' [B][Mel][T] - with lengths [B] int64 (device)
