@@ -9,24 +9,27 @@
 //
 //   hifigan_disc_first      1 -> C0, 5 taps, stride s: one thread per (row, 4 channels); bias, then taps ascending on the VALU.  The reflect pad and the fold
 //                           are index arithmetic of the read; no padded copy of the waveform exists.
-//   hifigan_disc_conv       Cin -> Cout, 5 taps, stride s (3, or 1 for the last width): per tile of 64 flat output rows and RT NT 16 output columns (the
-//                           generator's wave layouts, `hg_layout`).  In K chunks of 64 channels the tile stages lrelu(x) of the 64 rows of EVERY tap
-//                           ([5][64] rows: tap m of row (h', c) is input row (s h' + m - 2) p + c, zero outside [0, H); at stride 3 the five taps of 64 rows
-//                           are hardly more than the span they cover, and one staging serves both strides), then runs tap by tap against the K-major image
-//                           [5 Cin][Cout].  The summation order is the generator's: per (chunk, tap) a chain from zero, k ascending, added to the
-//                           bias-initialised accumulator.  Any Cout that is a multiple of 16 (1024: 16 chunks, 8 column groups).
+//   hifigan_disc_conv       Cin -> Cout, 5 taps, stride s (3, or 1 for the last width): the generator's tile body `hg_tile` (hifigan_common.h) with its FOLDED
+//                           row source, per tile of 64 flat output rows and RT NT 16 output columns (the generator's wave layouts, `hg_by_layout`).  In K
+//                           chunks of 64 channels the tile stages lrelu(x) of the 64 rows of EVERY tap ([5][64] rows through `hd_source_row`: tap m of row
+//                           (h', c) is input row (s h' + m - 2) p + c, zero outside [0, H); at stride 3 the five taps of 64 rows are hardly more than the
+//                           span they cover, and one staging serves both strides), then runs tap by tap against the K-major image [5 Cin][Cout].  K loop,
+//                           summation order and epilogue are the generator's text, not a copy of it: per (chunk, tap) a chain from zero, k ascending, added
+//                           to the bias-initialised accumulator.  Any Cout that is a multiple of 16 (1024: 16 chunks, 8 column groups).
 //   hifigan_disc_post       C -> 1, 3 taps, stride 1: one wave per row; a lane owns the channels 4 lane + 256 i (taps, then i ascending), `wave_sum`, + bias.
 //   hifigan_disc_fm         mean |lrelu(f_real) - lrelu(f_fake)| of one feature map kept as [2 B][N][C] (real rows first): float64 block sums of 4096
 //                           elements in a fixed tree order, and the gradient the frozen backward injects, sign(diff) lrelu'(f_fake) / count, laid out as the
 //                           fake rows of the map.  `hifigan_disc_fm_sum`: the blocks in ascending order -> the mean, written and (optionally) added to a running
 //                           total: L_fm is the sum of the terms in launch order, no other reduction.
 //   hifigan_disc_post_bwd   d pre of the last width from d scores: per (row, 4 channels), taps ascending, times lrelu'(kept pre-activation), + injected.
-//   hifigan_disc_conv_bwd   the data gradient of hifigan_disc_conv on the SAME tile body with the inverse row map: input row (h, c) receives tap m from output
-//                           row ((h + 2 - m) / s) p + c when s divides h + 2 - m; the other taps stage zero rows.  Against the channel-transposed image
-//                           [5 Cout][Cin] (row = tap Cout + output channel).  Epilogue: y = sum * lrelu'(kept pre-activation) + injected * *inj_scale.
+//   hifigan_disc_conv_bwd   the data gradient of hifigan_disc_conv: `hg_tile<.., BWD, FOLD>`, the same body under the inverse row map: input row (h, c)
+//                           receives tap m from output row ((h + 2 - m) / s) p + c when s divides h + 2 - m; the other taps stage zero rows.  Against the
+//                           channel-transposed image [5 Cout][Cin] (row = tap Cout + output channel).  Epilogue: the generator's BWD epilogue with scale 1,
+//                           y = sum * lrelu'(kept pre-activation) + injected * *inj_scale.
 //   hifigan_disc_first_bwd  d wav: per sample t the transposed first layer at the padded positions t and (where it lies in [T, Tp)) 2 T - 2 - t, a gather;
 //                           written, or added to what d wav holds (the periods add up in period order).
-//   hifigan_disc_wgrad      the generator's weight-gradient kernel (hifigan_wgrad.h) with the discriminator's row map; + `hifigan_disc_wgrad_sum`.
+//   hifigan_disc_wgrad      the generator's weight-gradient kernel and launch sequence (hifigan_wgrad.h: `hw_launch`) with the same row map; +
+//                           `hifigan_disc_wgrad_sum`.
 #include "hifigan_common.h"
 #include "hifigan_wgrad.h"
 
@@ -35,113 +38,23 @@ namespace {
 constexpr int HD_TAPS = 5, HD_POST_TAPS = 3, HD_MAX_PERIOD = 16, HD_MAX_CHANNELS = 1024;
 constexpr int HD_FM_ELEMS = 4096;                          // elements of one block of the feature-matching sum
 
-// The flat source row that tap m gives the flat row n, or -1 (a zero row).  Forward: n is an output row, the source the input row (s h + m - 2) p + c.
-// INV (data gradient): n is an input row, the source the output row ((h + 2 - m) / s) p + c where s divides h + 2 - m.  Hsrc: rows h of the source.
-template <bool INV>
-__device__ __forceinline__ int hd_source_row(int n, int m, int p, int s, int Hsrc)
-{
-    const int h = n / p, c = n - h * p;
-    int hs;
-    if constexpr (INV) {
-        const int t = h + 2 - m;
-        if (t < 0 || t % s) return -1;
-        hs = t / s;
-    } else {
-        hs = s * h + m - 2;
-    }
-    return hs >= 0 && hs < Hsrc ? hs * p + c : -1;
-}
-
-// grid (ceil(Ndst / 64), Cdst / (RT NT 16), B); src [B][Hsrc p][Csrc] -> out [B][Ndst][Cdst]; dynamic LDS [5][64] rows of lds_stride_of(min(Csrc, 64)) floats.
-// Forward: src = the pre-activation of the layer below (slope_in: its LeakyReLU), w [5 Csrc][Cdst], out = bias + sum.  BWD: src = d pre of the layer's
-// output (slope_in 1), w the transposed image, out = sum * lrelu'(mask) + inj * *inj_scale (mask, inj laid out as out; inj may be NULL).
+// grid (ceil(Ndst / 64), Cdst / (RT NT 16), B); src [B][Hsrc p][Csrc] -> out [B][Ndst][Cdst]; dynamic LDS [taps][64] rows of lds_stride_of(min(Csrc, 64)) floats.
+// `hg_tile` in its folded mode.  Forward: src = the pre-activation of the layer below (slope_in: its LeakyReLU), w [taps Csrc][Cdst], out = bias + sum.  BWD:
+// src = d pre of the layer's output (slope_in 1), w the transposed image, out = sum * lrelu'(mask) + inj * *inj_scale (mask, inj laid out as out; inj may be
+// NULL): the generator's BWD epilogue with divisor 1 and nothing accumulated.
 template <int RT, int NT, bool BWD>
 __global__ __launch_bounds__(THREADS) void hifigan_disc_conv_kernel(const float* __restrict__ src, const float* __restrict__ w, const float* __restrict__ bias,
                                                                     const float* __restrict__ mask, const float* __restrict__ inj,
-                                                                    const float* __restrict__ inj_scale, float* __restrict__ out, int Hsrc, int Ndst, int p, int s,
-                                                                    int Csrc, int Cdst, float slope_in, float mslope)
+                                                                    const float* __restrict__ inj_scale, float* __restrict__ out, int Hsrc, int Ndst, int taps, int p,
+                                                                    int s, int Csrc, int Cdst, float slope_in, float mslope)
 {
     extern __shared__ __attribute__((aligned(16))) float hd_smem[];
-    constexpr int WR = WAVES / RT, WC = WAVES / WR;        // the waves as WR row groups x WC column groups
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
-    const int wr = wave % WR, wc = wave / WR;
-    const int b = blockIdx.z, n0 = blockIdx.x * TM;
-    const int col0 = (blockIdx.y * WC + wc) * NT * 16;
-    const int xs = lds_stride_of(min(Csrc, HG_CK));
-    const float* sb = src + (size_t)b * Hsrc * p * Csrc;
-    float* Xs = hd_smem;
-
-    f32x4 acc[RT][NT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n) {
-        float bv = 0.f;
-        if constexpr (!BWD) bv = bias[col0 + n * 16 + r];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) acc[rt][n] = f32x4{bv, bv, bv, bv};
-    }
-
-    for (int c0 = 0; c0 < Csrc; c0 += HG_CK) {
-        const int ck = min(HG_CK, Csrc - c0), kq = ck >> 2;
-        if (c0) __syncthreads();                           // every wave is done with the previous chunk
-        for (int e = tid; e < HD_TAPS * TM * kq; e += THREADS) {
-            const int sr = e / kq, k4 = (e - sr * kq) * 4, m = sr / TM, n = n0 + sr - m * TM;
-            const int from = n < Ndst ? hd_source_row<BWD>(n, m, p, s, Hsrc) : -1;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (from >= 0) {
-                v = *reinterpret_cast<const float4*>(sb + (size_t)from * Csrc + c0 + k4);
-                v.x = lrelu(v.x, slope_in); v.y = lrelu(v.y, slope_in); v.z = lrelu(v.z, slope_in); v.w = lrelu(v.w, slope_in);
-            }
-            *reinterpret_cast<float4*>(Xs + sr * xs + k4) = v;
-        }
-        __syncthreads();
-        for (int m = 0; m < HD_TAPS; ++m) {
-            const float* xa = Xs + (m * TM + wr * RT * 16 + r) * xs + q;
-            const float* wp = w + ((size_t)m * Csrc + c0 + q) * Cdst + col0 + r;
-            f32x4 part[RT][NT];                            // this (chunk, tap)'s chain
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-                for (int n = 0; n < NT; ++n) part[rt][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-            for (int k0 = 0; k0 < ck; k0 += 4) {
-                float bw[NT];
-#pragma unroll
-                for (int n = 0; n < NT; ++n) bw[n] = wp[(size_t)k0 * Cdst + n * 16];
-#pragma unroll
-                for (int rt = 0; rt < RT; ++rt) {
-                    const float a = xa[rt * 16 * xs + k0];
-#pragma unroll
-                    for (int n = 0; n < NT; ++n) part[rt][n] = mfma4(a, bw[n], part[rt][n]);
-                }
-            }
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-                for (int n = 0; n < NT; ++n) acc[rt][n] += part[rt][n];
-        }
-    }
-
-    const float isc = (BWD && inj) ? inj_scale[0] : 0.f;
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int n = n0 + (wr * RT + rt) * 16 + q * 4 + i;
-            if (n >= Ndst) continue;                       // rows beyond the batch row's own are never written
-#pragma unroll
-            for (int nn = 0; nn < NT; ++nn) {
-                const size_t idx = ((size_t)b * Ndst + n) * Cdst + col0 + nn * 16 + r;
-                float y = acc[rt][nn][i];
-                if constexpr (BWD) {
-                    y *= mask[idx] > 0.f ? 1.f : mslope;
-                    if (inj) y += inj[idx] * isc;
-                }
-                out[idx] = y;
-            }
-        }
+    const size_t out0 = (size_t)blockIdx.z * Ndst * Cdst;
+    const HgTaps tp = {taps, 0, 0, 0, 1, p, s};
+    hg_tile<RT, NT, BWD, true>(src + (size_t)blockIdx.z * Hsrc * p * Csrc, w, bias, (BWD && inj) ? inj + out0 : nullptr, out + out0, hd_smem, Hsrc, Ndst, 0,
+                               blockIdx.x * TM, Csrc, Cdst, blockIdx.y, tp, slope_in, 0, 1, 0, 0, 1.f, BWD ? mask + out0 : nullptr, mslope,
+                               (BWD && inj) ? inj_scale[0] : 0.f);
 }
-
-// the padded waveform's sample n < Tp of a row of T samples
-__device__ __forceinline__ float hd_padded(const float* __restrict__ x, int n, int T) { return x[n < T ? n : 2 * T - 2 - n]; }
 
 // ---- first layer: grid (ceil(N1 C / 4 / 256), B).  w [5][C]: row = tap ----
 __global__ __launch_bounds__(THREADS) void hifigan_disc_first_kernel(const float* __restrict__ wav, const float* __restrict__ w, const float* __restrict__ bias,
@@ -156,8 +69,8 @@ __global__ __launch_bounds__(THREADS) void hifigan_disc_first_kernel(const float
     float4 acc = *reinterpret_cast<const float4*>(bias + c);
 #pragma unroll
     for (int m = 0; m < HD_TAPS; ++m) {
-        const int from = hd_source_row<false>((int)n, m, p, s, H0);
-        if (from < 0) continue;
+        int from;
+        if (!hd_source_row<false>((int)n, m, (HD_TAPS - 1) / 2, p, s, H0, &from)) continue;
         const float xv = hd_padded(x, from, T);
         const float4 wv = *reinterpret_cast<const float4*>(w + m * C + c);
         acc.x = fmaf(wv.x, xv, acc.x); acc.y = fmaf(wv.y, xv, acc.y); acc.z = fmaf(wv.z, xv, acc.z); acc.w = fmaf(wv.w, xv, acc.w);
@@ -256,8 +169,8 @@ __device__ __forceinline__ float hd_dpad(const float* __restrict__ dpre, const f
 {
     float sum = 0.f;
     for (int m = 0; m < HD_TAPS; ++m) {
-        const int from = hd_source_row<true>(n, m, p, s, H1);
-        if (from < 0) continue;
+        int from;
+        if (!hd_source_row<true>(n, m, (HD_TAPS - 1) / 2, p, s, H1, &from)) continue;
         const float* g = dpre + (size_t)from * C;
         float t = 0.f;
         for (int c = 0; c < C; c += 4) {
@@ -289,34 +202,20 @@ bool hd_stride(int s) { return s == 1 || s == 3; }
 int hd_rows_out(int H, int s) { return (H - 1) / s + 1; }
 // every batch row of the full length: B H p <= 2^30 rows (a grid of one thread per row and four channels stays below 2^31 workgroups at 1024 channels)
 bool hd_bad_rows(int B, int H, int p) { return B < 1 || B > 65535 || H < 1 || !hd_period(p) || (int64_t)B * H * p > ((int64_t)1 << 30); }
-int hd_lds_bytes(int Csrc) { return HD_TAPS * TM * lds_stride_of(std::min(Csrc, HG_CK)) * 4; }
+int hd_lds_bytes(int Csrc) { return hg_lds_bytes((HD_TAPS - 1) * TM, Csrc); }         // [5][64] rows
 unsigned hd_quads(int64_t rows, int C) { return (unsigned)((rows * (C / 4) + THREADS - 1) / THREADS); }
 
-template <int RT, int NT, bool BWD>
-int hd_launch(dim3 grid, int lds, hipStream_t st, const float* src, const float* w, const float* bias, const float* mask, const float* inj, const float* inj_scale,
-              float* out, int Hsrc, int Ndst, int p, int s, int Csrc, int Cdst, float slope_in, float mslope)
-{
-    if (allow_lds<&hifigan_disc_conv_kernel<RT, NT, BWD>>(lds) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;
-    hipLaunchKernelGGL((hifigan_disc_conv_kernel<RT, NT, BWD>), grid, dim3(THREADS), (size_t)lds, st, src, w, bias, mask, inj, inj_scale, out, Hsrc, Ndst, p, s, Csrc,
-                       Cdst, slope_in, mslope);
-    return GLOWTTS_OK;
-}
-
+// hifigan_disc_conv in either direction
 template <bool BWD>
-int hd_dispatch(const float* src, const float* w, const float* bias, const float* mask, const float* inj, const float* inj_scale, float* out, int B, int Hsrc, int Ndst,
-                int p, int s, int Csrc, int Cdst, float slope_in, float mslope, void* stream)
+int hd_conv(const float* src, const float* w, const float* bias, const float* mask, const float* inj, const float* inj_scale, float* out, int B, int Hsrc, int Ndst,
+            int p, int s, int Csrc, int Cdst, float slope_in, float mslope, void* stream)
 {
-    int rt, nt;
-    hg_layout(Cdst, &rt, &nt);
-    const int lds = hd_lds_bytes(Csrc);
-    const dim3 grid((Ndst + TM - 1) / TM, Cdst / (rt * nt * 16), B);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-#define HD_ARGS grid, lds, st, src, w, bias, mask, inj, inj_scale, out, Hsrc, Ndst, p, s, Csrc, Cdst, slope_in, mslope
-    if (rt == 4 && nt == 2) return hd_launch<4, 2, BWD>(HD_ARGS);
-    if (rt == 4) return hd_launch<4, 1, BWD>(HD_ARGS);
-    if (nt == 2) return hd_launch<1, 2, BWD>(HD_ARGS);
-    return hd_launch<1, 1, BWD>(HD_ARGS);
-#undef HD_ARGS
+    return hg_by_layout(Cdst, [&](auto rt, auto nt) {
+        constexpr int RT = decltype(rt)::value, NT = decltype(nt)::value;
+        return hg_launch<&hifigan_disc_conv_kernel<RT, NT, BWD>>(dim3((Ndst + TM - 1) / TM, Cdst / (RT * NT * 16), B), hd_lds_bytes(Csrc),
+                                                                 static_cast<hipStream_t>(stream), src, w, bias, mask, inj, inj_scale, out, Hsrc, Ndst, HD_TAPS, p, s,
+                                                                 Csrc, Cdst, slope_in, mslope);
+    });
 }
 
 }  // namespace
@@ -329,9 +228,8 @@ extern "C" int glowtts_hifigan_disc_supported(int period, int Cin, int Cout)
 extern "C" int64_t glowtts_hifigan_disc_work_floats(int B, int rows_out, int Cin, int Cout, int taps)
 {
     if (B < 1 || B > 65535 || rows_out < 1 || Cin < 1 || Cin > HD_MAX_CHANNELS || Cout < 1 || Cout > HD_MAX_CHANNELS || (taps != HD_TAPS && taps != HD_POST_TAPS)) return 0;
-    const int64_t CiP = (Cin + HW_C - 1) / HW_C * HW_C, CoP = (Cout + HW_C - 1) / HW_C * HW_C;
     const int64_t fm = 2 * (((int64_t)B * rows_out * Cout + HD_FM_ELEMS - 1) / HD_FM_ELEMS);       // float64 block sums of a feature map of B rows
-    return std::max((int64_t)hw_splits(B, rows_out) * (taps * CiP * CoP + CoP), fm);
+    return std::max(hw_sizes(B, rows_out, Cin, Cout, taps).floats, fm);
 }
 
 extern "C" int glowtts_hifigan_disc_first(const float* wav, const float* w, const float* bias, float* out, int B, int T, int period, int stride, int C, void* stream)
@@ -349,7 +247,7 @@ extern "C" int glowtts_hifigan_disc_conv(const float* x, const float* w, const f
                                          float slope, void* stream)
 {
     if (!x || !w || !bias || !out || x == out || hd_bad_rows(B, H, period) || !hd_stride(stride) || !hd_width(Cin) || !hd_width(Cout)) return GLOWTTS_E_ARG;
-    if (hd_dispatch<false>(x, w, bias, nullptr, nullptr, nullptr, out, B, H, hd_rows_out(H, stride) * period, period, stride, Cin, Cout, slope, 1.f, stream) != GLOWTTS_OK)
+    if (hd_conv<false>(x, w, bias, nullptr, nullptr, nullptr, out, B, H, hd_rows_out(H, stride) * period, period, stride, Cin, Cout, slope, 1.f, stream) != GLOWTTS_OK)
         return GLOWTTS_E_LAUNCH;
     GLOWTTS_NOTE_STATIC("hifigan_disc_conv");
     RET_LAUNCH();
@@ -392,7 +290,7 @@ extern "C" int glowtts_hifigan_disc_conv_bwd(const float* dy, const float* wt, c
 {
     if (!dy || !wt || !x || !dx || dx == dy || dx == x || (inj && !inj_scale) || hd_bad_rows(B, H, period) || !hd_stride(stride) || !hd_width(Cin) || !hd_width(Cout))
         return GLOWTTS_E_ARG;
-    if (hd_dispatch<true>(dy, wt, nullptr, x, inj, inj_scale, dx, B, hd_rows_out(H, stride), H * period, period, stride, Cout, Cin, 1.f, slope, stream) != GLOWTTS_OK)
+    if (hd_conv<true>(dy, wt, nullptr, x, inj, inj_scale, dx, B, hd_rows_out(H, stride), H * period, period, stride, Cout, Cin, 1.f, slope, stream) != GLOWTTS_OK)
         return GLOWTTS_E_LAUNCH;
     GLOWTTS_NOTE_STATIC("hifigan_disc_conv_bwd");
     RET_LAUNCH();
@@ -417,24 +315,6 @@ extern "C" int glowtts_hifigan_disc_wgrad(const float* x, const float* dy, float
         (taps != HD_TAPS && taps != HD_POST_TAPS) || (taps == HD_POST_TAPS && stride != 1) || wav_samples < 0 || (wav_samples > 0 && Cin != 1) ||
         (wav_samples == 0 && Cin == 1) || (wav_samples > 0 && (wav_samples < 2 * period || (wav_samples + period - 1) / period != H)))
         return GLOWTTS_E_ARG;
-    const int Nout = hd_rows_out(H, stride) * period, splits = hw_splits(B, Nout);
-    if (splits > 65535) return GLOWTTS_E_ARG;
-    const dim3 grid((Cin + HW_C - 1) / HW_C, (Cout + HW_C - 1) / HW_C, splits);
-    const int CiP = grid.x * HW_C, CoP = grid.y * HW_C;
-    const int lds = (taps * TM + TM) * HW_LD * 4;                  // at most 6 x 64 rows: 73728 bytes
-    const HwArgs a = {x, dy, nullptr, work, B, Nout, 1, Cin, Cout, taps, 0, 0, 0, hw_nchunk(Nout), hw_group(Nout), slope, period, stride, H, wav_samples};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (taps == HD_POST_TAPS) {
-        if (allow_lds<&hifigan_wgrad_kernel<3, true>>(lds) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;
-        hipLaunchKernelGGL((hifigan_wgrad_kernel<3, true>), grid, dim3(THREADS), (size_t)lds, st, a);
-    } else {
-        if (allow_lds<&hifigan_wgrad_kernel<HD_TAPS, true>>(lds) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;
-        hipLaunchKernelGGL((hifigan_wgrad_kernel<HD_TAPS, true>), grid, dim3(THREADS), (size_t)lds, st, a);
-    }
-    GLOWTTS_NOTE_STATIC("hifigan_disc_wgrad");
-    const int64_t P = (int64_t)taps * CiP * CoP + CoP;
-    hipLaunchKernelGGL(hifigan_wgrad_sum_kernel, dim3((unsigned)((P + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, work, dw, dbias, splits, taps, Cin, Cout, CiP, CoP, 0,
-                       0, taps, 1.f);
-    GLOWTTS_NOTE_STATIC("hifigan_disc_wgrad_sum");
-    RET_LAUNCH();
+    const HwArgs a = {x, dy, nullptr, work, B, hd_rows_out(H, stride) * period, 1, Cin, Cout, taps, 0, 0, 0, 0, 0, slope, period, stride, H, wav_samples};
+    return hw_launch<true>(a, dw, dbias, 0, taps, 1.f, static_cast<hipStream_t>(stream));
 }

@@ -22,7 +22,9 @@
 // The wave layout follows the width: RT row tiles x NT column tiles per wave - (4, 2) for Cout % 128 == 0, (4, 1) for % 64, (1, 2) for % 32, else (1, 1) - so
 // every wave of a narrow late stage still owns MFMA work.  Tiles start at the utterance's own row 0 and every sum has one fixed order: a row's value depends on
 // its utterance alone, bit-identical alone, in any batch, at any padding and from run to run.  No atomics, no workgroup waits on another.
-// The tile body `hg_tile`, the limits and the host-side layout helpers live in hifigan_common.h: the backward (hifigan_train_ops.hip) runs the same body.
+// The tile body `hg_tile`, the limits and the layout dispatcher `hg_by_layout` live in hifigan_common.h.  It is ONE body with two row sources: these kernels
+// and the backward (hifigan_train_ops.hip) stage the contiguous span of rows described above; the multi-period discriminator (hifigan_disc_ops.hip) stages
+// the rows of every tap through its period-folded row map and runs the same k loop, chains and epilogues.
 #include "hifigan_common.h"
 
 namespace {
@@ -39,7 +41,7 @@ __global__ __launch_bounds__(THREADS) void hifigan_conv_kernel(const float* __re
     if (s0 >= T) return;                                   // (uniform over the workgroup)
     const size_t row0 = (size_t)b * Tmax;
     const HgTaps tp = {taps, -((taps - 1) / 2) * d, d, 0, 1};
-    hg_tile<RT, NT>(in + row0 * Cin, w, bias, res ? res + row0 * Cout : nullptr, out + row0 * Cout, hg_smem, T, Tmax, s0, Cin, Cout, blockIdx.y, tp, slope, cf, 1, 0,
+    hg_tile<RT, NT>(in + row0 * Cin, w, bias, res ? res + row0 * Cout : nullptr, out + row0 * Cout, hg_smem, T, T, Tmax, s0, Cin, Cout, blockIdx.y, tp, slope, cf, 1, 0,
                     accumulate, divisor);
 }
 
@@ -57,7 +59,7 @@ __global__ __launch_bounds__(THREADS) void hifigan_upsample_kernel(const float* 
     const int shift = ph + (k - u) / 2, j0 = shift % u;
     const HgTaps tp = {(k - j0 + u - 1) / u, shift / u, -1, j0, u};
     const size_t row0 = (size_t)b * Tmax;
-    hg_tile<RT, NT>(in + row0 * Cin, w, bias, nullptr, out + row0 * u * Cout, hg_smem, T, Tmax, s0, Cin, Cout, colgroup, tp, slope, 0, u, ph, 0, 1.f);
+    hg_tile<RT, NT>(in + row0 * Cin, w, bias, nullptr, out + row0 * u * Cout, hg_smem, T, T, Tmax, s0, Cin, Cout, colgroup, tp, slope, 0, u, ph, 0, 1.f);
 }
 
 // ---- conv_post: grid (ceil(Lmax mult / 256), B), a row per thread;  w [taps Cin] (row = tap * Cin + input channel), bias [1] -----------------------------
@@ -108,22 +110,13 @@ extern "C" int glowtts_hifigan_conv(const float* in, const float* w, const float
     if (!in || !w || !bias || !out || !frame_lengths || in == out || bad_batch(B, Lmax, mult) || Cout == 1 || !glowtts_hifigan_supported(Cin, Cout, taps, dilation, 0) ||
         accumulate < 0 || accumulate > 2 || (accumulate == 2 && !(divisor > 0.f)))
         return GLOWTTS_E_ARG;
-    int rt, nt;
-    hg_layout(Cout, &rt, &nt);
-    const int lds = hg_lds_bytes((taps - 1) * dilation, Cin);
-    const dim3 grid((Lmax * mult + TM - 1) / TM, Cout / (rt * nt * 16), B);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-#define HG_CONV(RT_, NT_)                                                                                                                                        \
-    do {                                                                                                                                                         \
-        if (allow_lds<&hifigan_conv_kernel<RT_, NT_>>(lds) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;                                                               \
-        hipLaunchKernelGGL((hifigan_conv_kernel<RT_, NT_>), grid, dim3(THREADS), (size_t)lds, s, in, w, bias, residual, out, frame_lengths, Lmax, mult, Cin, Cout, \
-                           taps, dilation, slope, accumulate, divisor, channels_first);                                                                          \
-    } while (0)
-    if (rt == 4 && nt == 2) HG_CONV(4, 2);
-    else if (rt == 4) HG_CONV(4, 1);
-    else if (nt == 2) HG_CONV(1, 2);
-    else HG_CONV(1, 1);
-#undef HG_CONV
+    const int status = hg_by_layout(Cout, [&](auto rt, auto nt) {
+        constexpr int RT = decltype(rt)::value, NT = decltype(nt)::value;
+        return hg_launch<&hifigan_conv_kernel<RT, NT>>(dim3((Lmax * mult + TM - 1) / TM, Cout / (RT * NT * 16), B), hg_lds_bytes((taps - 1) * dilation, Cin),
+                                                       static_cast<hipStream_t>(stream), in, w, bias, residual, out, frame_lengths, Lmax, mult, Cin, Cout, taps,
+                                                       dilation, slope, accumulate, divisor, channels_first);
+    });
+    if (status != GLOWTTS_OK) return status;
     GLOWTTS_NOTE_STATIC("hifigan_conv");
     RET_LAUNCH();
 }
@@ -134,22 +127,13 @@ extern "C" int glowtts_hifigan_upsample(const float* in, const float* w, const f
     if (!in || !w || !bias || !out || !frame_lengths || in == out || rate < 1 || rate > HG_MAX_RATE || bad_batch(B, Lmax, mult) ||
         (int64_t)mult * rate > (1 << 16) || bad_batch(B, Lmax, mult * rate) || !glowtts_hifigan_supported(Cin, Cout, taps, 1, rate))
         return GLOWTTS_E_ARG;
-    int rt, nt;
-    hg_layout(Cout, &rt, &nt);
-    const int lds = hg_lds_bytes((taps + rate - 1) / rate - 1, Cin);
-    const dim3 grid((Lmax * mult + TM - 1) / TM, rate * (Cout / (rt * nt * 16)), B);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-#define HG_UP(RT_, NT_)                                                                                                                                          \
-    do {                                                                                                                                                         \
-        if (allow_lds<&hifigan_upsample_kernel<RT_, NT_>>(lds) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;                                                           \
-        hipLaunchKernelGGL((hifigan_upsample_kernel<RT_, NT_>), grid, dim3(THREADS), (size_t)lds, s, in, w, bias, out, frame_lengths, Lmax, mult, Cin, Cout, taps, \
-                           rate, slope);                                                                                                                         \
-    } while (0)
-    if (rt == 4 && nt == 2) HG_UP(4, 2);
-    else if (rt == 4) HG_UP(4, 1);
-    else if (nt == 2) HG_UP(1, 2);
-    else HG_UP(1, 1);
-#undef HG_UP
+    const int status = hg_by_layout(Cout, [&](auto rt, auto nt) {
+        constexpr int RT = decltype(rt)::value, NT = decltype(nt)::value;
+        return hg_launch<&hifigan_upsample_kernel<RT, NT>>(dim3((Lmax * mult + TM - 1) / TM, rate * (Cout / (RT * NT * 16)), B),
+                                                           hg_lds_bytes((taps + rate - 1) / rate - 1, Cin), static_cast<hipStream_t>(stream), in, w, bias, out,
+                                                           frame_lengths, Lmax, mult, Cin, Cout, taps, rate, slope);
+    });
+    if (status != GLOWTTS_OK) return status;
     GLOWTTS_NOTE_STATIC("hifigan_upsample");
     RET_LAUNCH();
 }

@@ -8,7 +8,8 @@
 //                         outside [0, T_b), chunked summation, sums from zero).  Epilogue: y = sum * lrelu'(x) * scale (x: the kept input of the forward's
 //                         LeakyReLU; 1 where x > 0, the slope elsewhere, at x == 0 as well) + residual * res_scale (the skip branch's gradient, may be `out`),
 //                         then out = y or out = out + y (the nk blocks of a stage add their input gradients into dU in block order).  The 1 / nk of the MRF mean
-//                         is `scale` / `res_scale` of the launches that read d acc.
+//                         is `scale` / `res_scale` of the launches that read d acc.  The discriminator's data gradient (hifigan_disc_ops.hip) is this body
+//                         and this epilogue too, with its rows staged through the period-folded row map in place of the contiguous span.
 //   hifigan_upsample_bwd  the data gradient of the transposed convolution, ONE launch on the same kernel: dy [T u][Cout] IS [T][u Cout] in memory, so
 //                         dx[s] = sum over row offsets e in [lo, hi] of Wt_e^T dyview[s + e] is an ordinary few-tap convolution over rows with u Cout input
 //                         channels, against an image [(hi - lo + 1) u Cout][Cin] that holds zeros where a (phase, offset) pair has no tap.
@@ -52,7 +53,7 @@ __global__ __launch_bounds__(THREADS) void hifigan_bwd_kernel(const float* __res
     if (s0 >= T) return;                                   // (uniform over the workgroup)
     const size_t row0 = (size_t)b * Tmax;
     const HgTaps tp = {taps, o0, ts, 0, 1};
-    hg_tile<RT, NT, true>(dy + row0 * Cdy, wt, nullptr, res ? res + row0 * Cdx : nullptr, out + row0 * Cdx, hg_smem, T, Tmax, s0, Cdy, Cdx, blockIdx.y, tp, 1.f, 0,
+    hg_tile<RT, NT, true>(dy + row0 * Cdy, wt, nullptr, res ? res + row0 * Cdx : nullptr, out + row0 * Cdx, hg_smem, T, T, Tmax, s0, Cdy, Cdx, blockIdx.y, tp, 1.f, 0,
                           1, 0, accumulate, scale, x + row0 * Cdx, mslope, res_scale);
 }
 
@@ -98,30 +99,16 @@ bool hw_walk(int Cd, int taps, int dilation, int rate, int* wt, int* o0, int* ts
     return *wt >= 1 && *wt <= HW_MAX_TAPS;
 }
 
-template <int RT, int NT>
-int hb_launch(dim3 grid, int lds, hipStream_t s, const float* dy, const float* wt, const float* x, const float* res, float* out, const int32_t* lengths, int Lmax,
-              int mult, int Cdy, int Cdx, int taps, int o0, int ts, float mslope, float scale, float res_scale, int accumulate)
+// both data gradients: `taps` row offsets from o0 in steps of ts over Cdy channels of dy
+int hb_data_gradient(const float* dy, const float* wt, const float* x, const float* res, float* out, const int32_t* lengths, int B, int Lmax, int mult, int Cdy,
+                     int Cdx, int taps, int o0, int ts, float mslope, float scale, float res_scale, int accumulate, void* stream)
 {
-    if (allow_lds<&hifigan_bwd_kernel<RT, NT>>(lds) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;
-    hipLaunchKernelGGL((hifigan_bwd_kernel<RT, NT>), grid, dim3(THREADS), (size_t)lds, s, dy, wt, x, res, out, lengths, Lmax, mult, Cdy, Cdx, taps, o0, ts, mslope, scale,
-                       res_scale, accumulate);
-    return GLOWTTS_OK;
-}
-
-int hb_dispatch(const float* dy, const float* wt, const float* x, const float* res, float* out, const int32_t* lengths, int B, int Lmax, int mult, int Cdy, int Cdx,
-                int taps, int o0, int ts, float mslope, float scale, float res_scale, int accumulate, void* stream)
-{
-    int rt, nt;
-    hg_layout(Cdx, &rt, &nt);
-    const int lds = hg_lds_bytes((taps - 1) * ts, Cdy);
-    const dim3 grid((Lmax * mult + TM - 1) / TM, Cdx / (rt * nt * 16), B);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-#define HB_ARGS grid, lds, s, dy, wt, x, res, out, lengths, Lmax, mult, Cdy, Cdx, taps, o0, ts, mslope, scale, res_scale, accumulate
-    if (rt == 4 && nt == 2) return hb_launch<4, 2>(HB_ARGS);
-    if (rt == 4) return hb_launch<4, 1>(HB_ARGS);
-    if (nt == 2) return hb_launch<1, 2>(HB_ARGS);
-    return hb_launch<1, 1>(HB_ARGS);
-#undef HB_ARGS
+    return hg_by_layout(Cdx, [&](auto rt, auto nt) {
+        constexpr int RT = decltype(rt)::value, NT = decltype(nt)::value;
+        return hg_launch<&hifigan_bwd_kernel<RT, NT>>(dim3((Lmax * mult + TM - 1) / TM, Cdx / (RT * NT * 16), B), hg_lds_bytes((taps - 1) * ts, Cdy),
+                                                      static_cast<hipStream_t>(stream), dy, wt, x, res, out, lengths, Lmax, mult, Cdy, Cdx, taps, o0, ts, mslope,
+                                                      scale, res_scale, accumulate);
+    });
 }
 
 }  // namespace
@@ -139,8 +126,7 @@ extern "C" int64_t glowtts_hifigan_wgrad_work_floats(int B, int Lmax, int mult, 
 {
     int wt, o0, ts, cd;
     if (bad_batch(B, Lmax, mult) || Cin < 1 || Cout < 1 || rate < 0 || rate > HG_MAX_RATE || taps < 1 || !hw_walk(Cout, taps, 1, rate, &wt, &o0, &ts, &cd)) return 0;
-    const int64_t CiP = (Cin + HW_C - 1) / HW_C * HW_C, CoP = (cd + HW_C - 1) / HW_C * HW_C;
-    return (int64_t)hw_splits(B, Lmax * mult) * (wt * CiP * CoP + CoP);
+    return hw_sizes(B, Lmax * mult, Cin, cd, wt).floats;
 }
 
 extern "C" int glowtts_hifigan_conv_bwd(const float* dy, const float* wt, const float* x, const float* residual, float* out, const int32_t* frame_lengths, int B,
@@ -150,8 +136,8 @@ extern "C" int glowtts_hifigan_conv_bwd(const float* dy, const float* wt, const 
     if (!dy || !wt || !x || !out || !frame_lengths || dy == out || bad_batch(B, Lmax, mult) || Cout == 1 || Cin % 16 ||
         !glowtts_hifigan_train_supported(Cin, Cout, taps, dilation, 0) || accumulate < 0 || accumulate > 1)
         return GLOWTTS_E_ARG;
-    if (hb_dispatch(dy, wt, x, residual, out, frame_lengths, B, Lmax, mult, Cout, Cin, taps, -((taps - 1) / 2) * dilation, dilation, mask_slope, scale, res_scale,
-                    accumulate, stream) != GLOWTTS_OK)
+    if (hb_data_gradient(dy, wt, x, residual, out, frame_lengths, B, Lmax, mult, Cout, Cin, taps, -((taps - 1) / 2) * dilation, dilation, mask_slope, scale, res_scale,
+                         accumulate, stream) != GLOWTTS_OK)
         return GLOWTTS_E_LAUNCH;
     GLOWTTS_NOTE_STATIC("hifigan_conv_bwd");
     RET_LAUNCH();
@@ -165,7 +151,7 @@ extern "C" int glowtts_hifigan_upsample_bwd(const float* dy, const float* wt, co
         return GLOWTTS_E_ARG;
     int lo, hi;
     hg_up_reach(taps, rate, &lo, &hi);
-    if (hb_dispatch(dy, wt, x, nullptr, out, frame_lengths, B, Lmax, mult, rate * Cout, Cin, hi - lo + 1, lo, 1, mask_slope, 1.f, 1.f, 0, stream) != GLOWTTS_OK)
+    if (hb_data_gradient(dy, wt, x, nullptr, out, frame_lengths, B, Lmax, mult, rate * Cout, Cin, hi - lo + 1, lo, 1, mask_slope, 1.f, 1.f, 0, stream) != GLOWTTS_OK)
         return GLOWTTS_E_LAUNCH;
     GLOWTTS_NOTE_STATIC("hifigan_upsample_bwd");
     RET_LAUNCH();
@@ -189,20 +175,6 @@ extern "C" int glowtts_hifigan_wgrad(const float* x, const float* dy, const int3
     if (!x || !dy || !frame_lengths || !work || !dw || !dbias || bad_batch(B, Lmax, mult) || !glowtts_hifigan_train_supported(Cin, Cout, taps, dilation, rate) ||
         (channels_first && rate) || !hw_walk(Cout, taps, dilation, rate, &wt, &o0, &ts, &cd))
         return GLOWTTS_E_ARG;
-    const int Tmax = Lmax * mult, splits = hw_splits(B, Tmax);
-    if (splits > 65535) return GLOWTTS_E_ARG;
-    const dim3 grid((Cin + HW_C - 1) / HW_C, (cd + HW_C - 1) / HW_C, splits);
-    const int CiP = grid.x * HW_C, CoP = grid.y * HW_C;
-    const int lds = (TM + (wt - 1) * ts + TM) * HW_LD * 4;         // at most (64 + 160 + 64) rows: 55296 bytes, within the default
-    const HwArgs a = {x, dy, frame_lengths, work, B, Lmax, mult, Cin, cd, wt, o0, ts, channels_first, hw_nchunk(Tmax), hw_group(Tmax), slope};
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (wt <= 3) hipLaunchKernelGGL(hifigan_wgrad_kernel<3>, grid, dim3(THREADS), (size_t)lds, s, a);
-    else if (wt <= 7) hipLaunchKernelGGL(hifigan_wgrad_kernel<7>, grid, dim3(THREADS), (size_t)lds, s, a);
-    else hipLaunchKernelGGL(hifigan_wgrad_kernel<HW_MAX_TAPS>, grid, dim3(THREADS), (size_t)lds, s, a);
-    GLOWTTS_NOTE_STATIC("hifigan_wgrad");
-    const int64_t P = (int64_t)wt * CiP * CoP + CoP;
-    hipLaunchKernelGGL(hifigan_wgrad_sum_kernel, dim3((unsigned)((P + THREADS - 1) / THREADS)), dim3(THREADS), 0, s, work, dw, dbias, splits, wt, Cin, cd, CiP, CoP, o0,
-                       rate, taps, scale);
-    GLOWTTS_NOTE_STATIC("hifigan_wgrad_sum");
-    RET_LAUNCH();
+    const HwArgs a = {x, dy, frame_lengths, work, B, Lmax, mult, Cin, cd, wt, o0, ts, channels_first, 0, 0, slope};
+    return hw_launch<false>(a, dw, dbias, rate, taps, scale, static_cast<hipStream_t>(stream));
 }

@@ -2,10 +2,11 @@
 // (hifigan_disc_ops.hip): one body, two ways to reach the rows of x that a tap reads.
 //   MAP = false  the generator: tap j of output row t reads input row t + o0 + j ts - the tile stages one contiguous span of rows and the tap shifts the index.
 //   MAP = true   the discriminator: rows are (h, c) of a waveform folded by the period p (flat row h p + c), the convolution runs over h with stride s, so
-//                tap j of output row (h', c) reads input row (s h' + j - (taps - 1) / 2) p + c, zero outside [0, Hin).  The tile stages the 64 rows of every tap
-//                ([taps][64] rows) - at stride 3 five taps of 64 rows are hardly more than the span they cover.  A source of ONE channel may be the waveform
-//                itself (Twav > 0): flat row n is sample n, reflected at the right end (n >= Twav reads 2 Twav - 2 - n), so no padded copy exists.
-// hifigan_train_ops.hip's head describes the partition, the tile and the summation order; they are the same in both modes.
+//                tap j of output row (h', c) reads the input row that `hd_source_row` (hifigan_common.h: the map of the tile body's folded mode) gives it,
+//                zero outside [0, Hin).  The tile stages the 64 rows of every tap ([taps][64] rows) - at stride 3 five taps of 64 rows are hardly more than
+//                the span they cover.  A source of ONE channel may be the waveform itself (Twav > 0) through the reflect index `hd_padded`: no padded copy.
+// hifigan_train_ops.hip's head describes the partition, the tile and the summation order; they are the same in both modes.  So is the launch: `hw_sizes`
+// is the one place that knows the partials' sizes and `hw_launch` the one launch sequence (kernel by tap bucket, then the sum) of both C entries.
 #pragma once
 #include "hifigan_common.h"
 
@@ -56,16 +57,13 @@ __global__ __launch_bounds__(THREADS) void hifigan_wgrad_kernel(const HwArgs a)
                 for (int e = tid; e < span * (HW_C / 4); e += THREADS) {
                     const int sr = e / (HW_C / 4), k4 = (e - sr * (HW_C / 4)) * 4, j = sr / TM, n = t0 + sr - j * TM;
                     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (n < t_end && ci0 + k4 < a.Ca) {
-                        const int h = n / a.p, c = n - h * a.p, hs = a.s * h + j - (a.taps - 1) / 2;
-                        if (hs >= 0 && hs < a.Hin) {
-                            const int src = hs * a.p + c;
-                            if (a.Twav) {
-                                v.x = ab[src < a.Twav ? src : 2 * a.Twav - 2 - src];
-                            } else {
-                                v = *reinterpret_cast<const float4*>(ab + (size_t)src * a.Ca + ci0 + k4);
-                                v.x = lrelu(v.x, a.slope); v.y = lrelu(v.y, a.slope); v.z = lrelu(v.z, a.slope); v.w = lrelu(v.w, a.slope);
-                            }
+                    int src;
+                    if (n < t_end && ci0 + k4 < a.Ca && hd_source_row<false>(n, j, (a.taps - 1) / 2, a.p, a.s, a.Hin, &src)) {
+                        if (a.Twav) {
+                            v.x = hd_padded(ab, src, a.Twav);
+                        } else {
+                            v = *reinterpret_cast<const float4*>(ab + (size_t)src * a.Ca + ci0 + k4);
+                            v.x = lrelu(v.x, a.slope); v.y = lrelu(v.y, a.slope); v.z = lrelu(v.z, a.slope); v.w = lrelu(v.w, a.slope);
                         }
                     }
                     *reinterpret_cast<float4*>(Xs + sr * HW_LD + k4) = v;
@@ -174,6 +172,48 @@ int hw_splits(int B, int Tmax)
 {
     const int64_t units = (int64_t)B * hw_nchunk(Tmax), g = hw_group(Tmax);
     return (int)((units + g - 1) / g);
+}
+
+// the grid of a weight gradient over B slabs of Tmax rows, Ca x Cd channels, and the floats of its partials: [splits][taps CiP CoP + CoP]
+struct HwSizes {
+    int splits, CiP, CoP;
+    int64_t per_split, floats;
+};
+HwSizes hw_sizes(int B, int Tmax, int Ca, int Cd, int taps)
+{
+    HwSizes z;
+    z.splits = hw_splits(B, Tmax);
+    z.CiP = (Ca + HW_C - 1) / HW_C * HW_C;
+    z.CoP = (Cd + HW_C - 1) / HW_C * HW_C;
+    z.per_split = (int64_t)taps * z.CiP * z.CoP + z.CoP;
+    z.floats = z.splits * z.per_split;
+    return z;
+}
+
+// The launch pair of a weight gradient.  a: everything but nchunk and group, which follow from the rows; dw, dbias, rate, k, scale: the sum kernel's
+// layout arguments (rate 0, k = taps: a convolution).  The kernel's accumulators come in buckets of taps: 3 / 7 / 11 for the generator's kernel sizes (and its
+// views' few offsets), 3 / 5 under MAP, whose callers have no other.  Notes `hifigan_wgrad` + `hifigan_wgrad_sum`, MAP: `hifigan_disc_wgrad` + `.._sum`.
+template <bool MAP>
+int hw_launch(HwArgs a, float* dw, float* dbias, int rate, int k, float scale, hipStream_t st)
+{
+    const int Tmax = a.Lmax * a.mult;
+    const HwSizes z = hw_sizes(a.B, Tmax, a.Ca, a.Cd, a.taps);
+    if (z.splits > 65535 || a.taps > (MAP ? 5 : HW_MAX_TAPS)) return GLOWTTS_E_ARG;
+    a.nchunk = hw_nchunk(Tmax);
+    a.group = hw_group(Tmax);
+    const dim3 grid(z.CiP / HW_C, z.CoP / HW_C, z.splits);
+    const int lds = ((MAP ? a.taps * TM : TM + (a.taps - 1) * a.ts) + TM) * HW_LD * 4;     // MAP with 5 taps: 6 x 64 rows, 73728 bytes, above the default limit
+    int status;
+    if (a.taps <= 3) status = hg_launch<&hifigan_wgrad_kernel<3, MAP>>(grid, lds, st, a);
+    else if constexpr (MAP) status = hg_launch<&hifigan_wgrad_kernel<5, true>>(grid, lds, st, a);
+    else if (a.taps <= 7) status = hg_launch<&hifigan_wgrad_kernel<7>>(grid, lds, st, a);
+    else status = hg_launch<&hifigan_wgrad_kernel<HW_MAX_TAPS>>(grid, lds, st, a);
+    if (status != GLOWTTS_OK) return status;
+    GLOWTTS_NOTE_STATIC("%s", MAP ? "hifigan_disc_wgrad" : "hifigan_wgrad");
+    hipLaunchKernelGGL(hifigan_wgrad_sum_kernel, dim3((unsigned)((z.per_split + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, a.partial, dw, dbias, z.splits, a.taps,
+                       a.Ca, a.Cd, z.CiP, z.CoP, a.o0, rate, k, scale);
+    GLOWTTS_NOTE_STATIC("%s", MAP ? "hifigan_disc_wgrad_sum" : "hifigan_wgrad_sum");
+    RET_LAUNCH();
 }
 
 }  // namespace

@@ -33,6 +33,7 @@ CASES = {
     "rows65": ([5], NARROW, 2, 541),               # 13 * 5 = 65 (pad 4)
     "splits": ([3], NARROW, 1, 3300),              # the first layer writes 367 * 3 = 1101 rows: two chunks of the weight-gradient partition
     "default_p11": ([11], DEFAULT, 1, 600),        # 16 K chunks, 8 column groups, a 1024-wide conv_post
+    "c64_80": ([3], [64, 64, 80], 2, 200),         # the (4, 1) layout in both directions; 80 source channels: a K walk of 64 + 16
 }
 _cache = {}
 
