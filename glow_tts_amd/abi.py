@@ -310,6 +310,11 @@ SIGNATURES = {
     "glowtts_stft_loss_work_floats": (L, [I] * 4),
     "glowtts_stft_loss_forward": (I, [P] * 8 + [I] * 5 + [F, I, P]),
     "glowtts_stft_loss_backward": (I, [P] * 7 + [I] * 5 + [F, I, P]),
+    "glowtts_mel_loss_supported": (I, [I] * 5),
+    "glowtts_mel_loss_keep_floats": (L, [I] * 4),
+    "glowtts_mel_loss_work_floats": (L, [I] * 4),
+    "glowtts_mel_loss_forward": (I, [P] * 10 + [I] * 7 + [F, F, I, P]),
+    "glowtts_mel_loss_backward": (I, [P] * 10 + [I] * 7 + [F, I, P]),
     "glowtts_pwg_disc_supported": (I, [I] * 3),
     "glowtts_pwg_disc_work_floats": (L, [I] * 3),
     "glowtts_pwg_disc_first": (I, [P] * 4 + [I] * 3 + [F, P]),
@@ -349,5 +354,6 @@ VALUE_RETURNING = frozenset({
     "glowtts_abi_version", "glowtts_opt_chunk",
     "glowtts_cond_linear_supported", "glowtts_gst_supported", "glowtts_conv3x3s2_supported", "glowtts_dur_proj_supported", "glowtts_vocoder_supported",
     "glowtts_pwg_supported", "glowtts_pwg_supported_bf16", "glowtts_hifigan_supported", "glowtts_hifigan_train_supported", "glowtts_ge2e_supported", "glowtts_pwg_train_supported", "glowtts_stft_loss_supported",
+    "glowtts_mel_loss_supported",
     "glowtts_pwg_disc_supported", "glowtts_hifigan_disc_supported", "glowtts_mel_cepstrum_supported", "glowtts_dtw_supported", "glowtts_tsne_supported",
 })

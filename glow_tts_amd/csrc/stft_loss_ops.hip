@@ -20,12 +20,14 @@
 //                     taken at the sample's own position and at the at most two padded positions that reflect onto it (left edge first).
 // No atomics, no workgroup waits on another: every value is bit-identical from run to run.  LDS per workgroup at n_fft = 2048, win 1200: 8 KiB twiddles +
 // 8.3 KiB spectrum + 4.7 KiB window + 6 KiB reduction tree = 27 KiB.
-// The LDS layout, the frame packer, the split and its inverse and the frame unpack are vocoder_fft.h's, shared with vocoder_ops.hip and frontend_ops.hip; this
-// file keeps the magnitudes with their float64 sums, the gradient per bin and the fold.
+// The LDS layout, the frame packer, the split and its inverse and the frame unpack are vocoder_fft.h's, shared with vocoder_ops.hip and frontend_ops.hip; the
+// reduction tree and the fold (the overlap-add kernel, logged here as stft_loss_bwd_fold) are stft_frames.h's, shared with mel_loss_ops.hip; this file keeps the
+// magnitudes with their float64 sums and the gradient per bin.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/glowtts_hip.h"
 #include "launch_log.h"
+#include "stft_frames.h"
 #include "vocoder_fft.h"
 
 namespace {
@@ -47,19 +49,6 @@ struct sl_args {
     float weight;
     int B, T, NF, logN, win, hop;
 };
-
-// fixed tree over the workgroup's 256 values of each of the three sums; the result is in red[i][0]
-__device__ __forceinline__ void sl_tree(double (*red)[VOC_NT], int tid)
-{
-    __syncthreads();
-    for (int h = VOC_NT >> 1; h > 0; h >>= 1) {
-        if (tid < h) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) red[i][tid] += red[i][tid + h];
-        }
-        __syncthreads();
-    }
-}
 
 __global__ __launch_bounds__(VOC_NT) void stft_loss_fwd_kernel(const sl_args a)
 {
@@ -111,7 +100,7 @@ __global__ __launch_bounds__(VOC_NT) void stft_loss_fwd_kernel(const sl_args a)
         red[0][tid] = s_sc;
         red[1][tid] = s_y;
         red[2][tid] = s_mag;
-        sl_tree(red, tid);
+        voc_tree<3>(red, tid);
         if (tid < 3) a.partial[(int64_t)f * 3 + tid] = red[tid][0];
         __syncthreads();
     }
@@ -129,7 +118,7 @@ __global__ __launch_bounds__(VOC_NT) void stft_loss_reduce_kernel(const double* 
     }
 #pragma unroll
     for (int i = 0; i < 3; ++i) red[i][tid] = s[i];
-    sl_tree(red, tid);
+    voc_tree<3>(red, tid);
     if (tid == 0) {
         const double nd = sqrt(red[0][0]), ny = sqrt(red[1][0]);
         const float sc = (float)(nd / ny), mg = (float)(red[2][0] / ((double)frames * (double)F));
@@ -180,37 +169,9 @@ __global__ __launch_bounds__(VOC_NT) void stft_loss_bwd_frames_kernel(const sl_a
     }
 }
 
-// d pred[b][s] = dpad(M + s) + [1 <= s <= M] dpad(M - s) + [T - 1 - M <= s <= T - 2] dpad(M + 2 (T - 1) - s), dpad(p) = the frames' contributions at padded
-// position p summed in ascending frame order (window position j = p - lpad - t hop in [0, win))
-__global__ __launch_bounds__(256) void stft_loss_bwd_fold_kernel(const float* __restrict__ dframes, float* __restrict__ dpred, int T, int NF, int n_fft, int win, int hop,
-                                                                 int accumulate)
-{
-    const int b = blockIdx.y, s = blockIdx.x * 256 + threadIdx.x;
-    if (s >= T) return;
-    const int M = n_fft >> 1, lpad = (n_fft - win) >> 1;
-    const float* fb = dframes + (int64_t)b * NF * win;
-    auto dpad = [&](int p) {
-        const int pp = p - lpad;
-        float acc = 0.f;
-        if (pp < 0) return acc;
-        int t_hi = pp / hop;
-        const int t_lo = pp >= win ? (pp - win) / hop + 1 : 0;
-        if (t_hi > NF - 1) t_hi = NF - 1;
-        for (int t = t_lo; t <= t_hi; ++t) acc += fb[(int64_t)t * win + (pp - t * hop)];
-        return acc;
-    };
-    float r = dpad(M + s);
-    if (s >= 1 && s <= M) r += dpad(M - s);
-    if (s >= T - 1 - M && s <= T - 2) r += dpad(M + 2 * (T - 1) - s);
-    float* out = dpred + (int64_t)b * T + s;
-    *out = accumulate ? *out + r : r;
-}
-
-int sl_grid(int frames) { return frames < 1280 ? frames : 1280; }              // 5 resident workgroups (by LDS at n_fft = 2048) on each of 256 CUs; more frames: strided
 bool sl_bad_dims(int B, int T, int n_fft, int win, int hop)
 {
-    return B < 1 || B > 65535 || !glowtts_stft_loss_supported(n_fft, win, hop, T) || (int64_t)B * T >= (int64_t)1 << 31 ||
-           (int64_t)B * (1 + T / hop) > (int64_t)1 << 24;
+    return !glowtts_stft_loss_supported(n_fft, win, hop, T) || voc_frames_bad_batch(B, T, hop);
 }
 
 }  // namespace
@@ -245,7 +206,7 @@ extern "C" int glowtts_stft_loss_forward(const float* pred, const float* target,
     a.spec = keep; a.mag_x = keep + frames * F * 2; a.mag_y = keep + frames * F * 3; a.partial = reinterpret_cast<double*>(work);
     a.weight = weight; a.B = B; a.T = T; a.NF = NF; a.logN = voc_log2(n_fft); a.win = win_length; a.hop = hop;
     GLOWTTS_NOTE_STATIC("stft_loss_fwd");
-    hipLaunchKernelGGL(stft_loss_fwd_kernel, dim3(sl_grid((int)frames)), dim3(VOC_NT), voc_lds_bytes(n_fft, win_length, 0), static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(stft_loss_fwd_kernel, dim3(voc_frames_grid((int)frames)), dim3(VOC_NT), voc_lds_bytes(n_fft, win_length, 0), static_cast<hipStream_t>(stream), a);
     if (hipGetLastError() != hipSuccess) return GLOWTTS_E_LAUNCH;
     GLOWTTS_NOTE_STATIC("stft_loss_reduce");
     hipLaunchKernelGGL(stft_loss_reduce_kernel, dim3(1), dim3(VOC_NT), 0, static_cast<hipStream_t>(stream), a.partial, terms, loss, (int)frames, F, weight, accumulate);
@@ -266,10 +227,10 @@ extern "C" int glowtts_stft_loss_backward(const float* keep, const float* terms,
     a.terms = terms; a.grad_out = grad_out; a.dframes = work + frames * 6;
     a.weight = weight; a.B = B; a.T = T; a.NF = NF; a.logN = voc_log2(n_fft); a.win = win_length; a.hop = hop;
     GLOWTTS_NOTE_STATIC("stft_loss_bwd_frames");
-    hipLaunchKernelGGL(stft_loss_bwd_frames_kernel, dim3(sl_grid((int)frames)), dim3(VOC_NT), voc_lds_bytes(n_fft, win_length, 0), static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(stft_loss_bwd_frames_kernel, dim3(voc_frames_grid((int)frames)), dim3(VOC_NT), voc_lds_bytes(n_fft, win_length, 0), static_cast<hipStream_t>(stream), a);
     if (hipGetLastError() != hipSuccess) return GLOWTTS_E_LAUNCH;
     GLOWTTS_NOTE_STATIC("stft_loss_bwd_fold");
-    hipLaunchKernelGGL(stft_loss_bwd_fold_kernel, dim3((T + 255) / 256, B), dim3(256), 0, static_cast<hipStream_t>(stream), a.dframes, dpred, T, NF, n_fft, win_length, hop,
+    hipLaunchKernelGGL(voc_frames_fold_kernel, dim3((T + 255) / 256, B), dim3(256), 0, static_cast<hipStream_t>(stream), a.dframes, dpred, T, NF, n_fft, win_length, hop,
                        accumulate);
     RET_LAUNCH();
 }

@@ -1,5 +1,5 @@
-// The LDS FFT and the framing around it, shared by the Griffin-Lim vocoder (vocoder_ops.hip), the analysis front end (frontend_ops.hip) and the STFT loss
-// (stft_loss_ops.hip): complex helpers, numpy's reflect index, the one-slot-per-32-elements pad of the spectrum buffer, the in-place radix-4 FFT of n_fft / 2
+// The LDS FFT and the framing around it, shared by the Griffin-Lim vocoder (vocoder_ops.hip), the analysis front end (frontend_ops.hip), the STFT loss
+// (stft_loss_ops.hip) and the mel loss (mel_loss_ops.hip): complex helpers, numpy's reflect index, the one-slot-per-32-elements pad of the spectrum buffer, the in-place radix-4 FFT of n_fft / 2
 // complex points that a real frame of n_fft samples packs into, and - each written once - the LDS layout with its table staging, the frame packer (gather,
 // window, pack bit-reversed), the real-input split of a bin pair and its inverse, the unpack of a frame's samples under the window, and the host's size and
 // range checks.  256-thread workgroups.  Bank-conflict accounting of the pad: see the header of vocoder_ops.hip.

@@ -11,8 +11,9 @@ Stage two (DESIGN.md "Training the HiFi-GAN discriminator"), with the optional s
 L_G = L_stft + Lambda_Adversarial sum_p mean((D_p(G) - 1)^2) + Lambda_Feature_Matching L_fm, L_D = sum_p [mean((D_p(y) - 1)^2) + mean(D_p(G.detach())^2)] -
 both updates from the state before the step, the discriminator with a clipping, a RAdam and a step decay over its own update count; the checkpoint also
 carries `discriminator`, `Discriminator_Optimizer`, `Discriminator_Steps`.  A stage-one checkpoint (no `discriminator`) whose `Steps <= Start_Step` resumes
-with the seeded-init discriminator.  Without the sub-block nothing differs from stage one alone.  The multi-scale discriminator and the mel-L1 loss are out
-of scope; a `Vocoder.Train.Discriminator` block - the Parallel WaveGAN discriminator's - is refused."""
+with the seeded-init discriminator.  Without the sub-block nothing differs from stage one alone.  The optional sub-block
+`Vocoder.Train.Mel_Loss` (DESIGN.md "Mel loss") adds Lambda L_mel to L_stft in both stages, through `PWG_Trainer.forward`.  The multi-scale discriminator
+is out of scope; a `Vocoder.Train.Discriminator` block - the Parallel WaveGAN discriminator's - is refused."""
 import logging
 
 import torch
@@ -31,7 +32,7 @@ ADV_KEY = "Adversarial"
 def train_settings(hp):
     """The optional yaml block `Vocoder.Train` of a `Type: 'HiFiGAN'` block over DEFAULTS, under `pwg_trainer.train_settings`' rules.  A block of another
     `Vocoder.Type` (or none) and a `Vocoder.Train.Discriminator` sub-block raise a ValueError naming the key.  The optional sub-block `Adversarial`
-    (`vocoder.hifigan_disc_settings`) appears in the result only when the yaml has it."""
+    (`vocoder.hifigan_disc_settings`) appears in the result only when the yaml has it, and so does `Mel_Loss` (allowed by `pwg_trainer.train_settings`)."""
     block = getattr(hp, "Vocoder", None)
     kind = getattr(block, "Type", None)
     if kind != "HiFiGAN":

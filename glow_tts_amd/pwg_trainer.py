@@ -16,10 +16,11 @@ import torch
 
 from . import aux_trainer, optim
 from .hparams import get_hp, overlay_settings
-from .vocoder import (STFT_RESOLUTIONS, MultiResolutionSTFTLoss, ParallelWaveGAN, PWGDiscriminator, adversarial_mse, pwg_disc_load, pwg_disc_settings, pwg_geometry,
-                      pwg_load, stft_loss_geometry)
+from .vocoder import (STFT_RESOLUTIONS, MelSpectrogramLoss, MultiResolutionSTFTLoss, ParallelWaveGAN, PWGDiscriminator, adversarial_mse, mel_loss_geometry,
+                      mel_loss_settings, pwg_disc_load, pwg_disc_settings, pwg_geometry, pwg_load, stft_loss_geometry)
 
 TRAIN_KEY = "Vocoder.Train"
+MEL_BLOCK = "Mel_Loss"                                     # the optional sub-block of the mel-L1 term, of every vocoder trainer
 DEFAULTS = {"Batch_Size": 8, "Segment_Frames": 100, "Learning_Rate": 1.0e-4, "Epsilon": 1.0e-6, "Gradient_Norm": 10.0,
             "Learning_Rate_Decay": {"Step": 200000, "Gamma": 0.5}, "STFT_Resolutions": [list(r) for r in STFT_RESOLUTIONS], "Max_Step": 100000,
             "Checkpoint_Save_Interval": 5000, "Evaluation_Interval": 1000, "Checkpoint_Path": "./pwg_results"}
@@ -32,17 +33,21 @@ BUNDLES = (("", "model", "pwg", pwg_load, ("generator", "Optimizer", "Steps")),
 def train_settings(hp, defaults=DEFAULTS, also=("Discriminator",)):
     """The optional yaml block `Vocoder.Train` over `defaults` (`hparams.overlay_settings`), checked: a ValueError names every bad key.  The optional
     sub-block `Discriminator` (`vocoder.pwg_disc_settings`) appears in the result only when the yaml has it.  also: the sub-blocks the caller allows and
-    reads (another trainer's stage two has another key)."""
+    reads (another trainer's stage two has another key).  The optional sub-block `Mel_Loss` (`vocoder.mel_loss_settings`, checked against the segment
+    length by `vocoder.mel_loss_geometry`) is allowed beside them and appears in the result only when the yaml has it."""
     def rules(s, need):
         for k in ("Batch_Size", "Segment_Frames", "Max_Step", "Checkpoint_Save_Interval", "Evaluation_Interval"):
             need(k, lambda v: int(v) >= 1, "at least 1")
         for k in ("Learning_Rate", "Epsilon", "Gradient_Norm"):
             need(k, lambda v: float(v) > 0, "positive")
         need("Learning_Rate_Decay", lambda v: int(v["Step"]) >= 1 and 0 < float(v["Gamma"]) <= 1, "Step >= 1, 0 < Gamma <= 1")
-    s = overlay_settings(getattr(getattr(hp, "Vocoder", None), "Train", None), defaults, TRAIN_KEY, "vocoder", rules, also=also)
+    s = overlay_settings(getattr(getattr(hp, "Vocoder", None), "Train", None), defaults, TRAIN_KEY, "vocoder", rules, also=tuple(also) + (MEL_BLOCK,))
     s["STFT_Resolutions"] = stft_loss_geometry(s["STFT_Resolutions"], int(s["Segment_Frames"]) * int(hp.Sound.Frame_Shift))
     if "Discriminator" in s:
         s["Discriminator"] = pwg_disc_settings(hp)
+    if MEL_BLOCK in s:
+        s[MEL_BLOCK] = mel_loss_settings(hp)
+        mel_loss_geometry(hp, s[MEL_BLOCK], int(s["Segment_Frames"]) * int(hp.Sound.Frame_Shift))
     return s
 
 
@@ -109,6 +114,10 @@ class PWG_Trainer(aux_trainer.Trainer):
         super().__init__(hp, s, steps, device, seed, Sampler, (s["Batch_Size"], s["Segment_Frames"], self.geo["hop"]))
         self.model = self.make_model()
         self.criterion = MultiResolutionSTFTLoss(s["STFT_Resolutions"], self.device)
+        # the mel-L1 term (optional block Vocoder.Train.Mel_Loss; DESIGN.md "Mel loss"): stateless, so no checkpoint knows of it
+        self.mel_set, self.mel_criterion, self.last_evaluation_mel = s.get(MEL_BLOCK), None, None
+        if self.mel_set is not None:
+            self.mel_criterion = MelSpectrogramLoss(hp, self.device, self.mel_set)
         self.params = list(self.model.params.values())
         self.optimizer = optim.RAdam(self.params, lr=float(s["Learning_Rate"]), eps=float(s["Epsilon"]))
         # stage two (optional block Vocoder.Train.Discriminator): initialised from the seed at construction, untouched before Start_Step
@@ -158,11 +167,14 @@ class PWG_Trainer(aux_trainer.Trainer):
 
     def forward(self, mel, target, step, adversarial=False):
         """-> L_stft, or with `adversarial` (L_G = L_stft + Lambda_Adversarial L_adv, L_D, the unscaled (L_adv, real term, fake term) [3]): one discriminator
-        forward over [target; wav]; L_G's backward reaches the generator alone, L_D's the discriminator alone."""
+        forward over [target; wav]; L_G's backward reaches the generator alone, L_D's the discriminator alone.  With the block Vocoder.Train.Mel_Loss,
+        L_stft + Lambda L_mel stands wherever L_stft does (L_D is unchanged); the unscaled L_mel is `self.mel_criterion.term`."""
         mel, target = mel.to(self.device, non_blocking=True), target.to(self.device, non_blocking=True)
         B, _, L = mel.shape
         wav = self.generate(mel, [L] * B, step)
         stft = self.criterion(wav, target)
+        if self.mel_criterion is not None:
+            stft = stft + float(self.mel_set["Lambda"]) * self.mel_criterion(wav, target)
         if not adversarial:
             return stft
         return self.adversarial_losses(target, wav, stft)
@@ -194,6 +206,7 @@ class PWG_Trainer(aux_trainer.Trainer):
         loss = self.forward(mel, target, self.steps)
         norm, = self.update(self.BUNDLES[:1], [loss])
         self.last = {"Loss": loss.detach(), "Terms": self.criterion.terms, "Gradient_Norm": norm}
+        self.note_mel()
         return loss.detach()
 
     def Adversarial_Step(self, mel, target):
@@ -203,15 +216,22 @@ class PWG_Trainer(aux_trainer.Trainer):
         norm, d_norm = self.update(self.BUNDLES, [loss, d_loss])
         self.last = {"Loss": loss.detach(), "Terms": self.criterion.terms, "Gradient_Norm": norm, "STFT_Loss": stft.detach(), "Discriminator_Loss": d_loss.detach(),
                      "L_adv": adv_terms[0], "Real_Term": adv_terms[1], "Fake_Term": adv_terms[2], "Discriminator_Gradient_Norm": d_norm}
+        self.note_mel()
         return loss.detach()
+
+    def note_mel(self):
+        """`last` gains the unscaled mel term of the step when the block Vocoder.Train.Mel_Loss is there"""
+        if self.mel_criterion is not None:
+            self.last["Mel_Loss"] = self.mel_criterion.term
 
     @torch.no_grad()
     def Evaluation(self, batches=4):
         """-> (mean loss, mean (L_sc, L_mag) per resolution [n, 2]) over `batches` batches of the evaluation set; with the discriminator block, a third
-        element: the mean (L_adv, real term, fake term) [3] of the current discriminator on the generated and the target segments."""
+        element: the mean (L_adv, real term, fake term) [3] of the current discriminator on the generated and the target segments.  With the block
+        Vocoder.Train.Mel_Loss the loss is L_stft + Lambda L_mel and the mean unscaled L_mel goes to `self.last_evaluation_mel`."""
         if "Eval" not in self.sampler:
             return None
-        losses, terms, adv = [], [], []
+        losses, terms, adv, mel = [], [], [], []
         for b in range(batches):
             if self.discriminator is None:
                 losses.append(float(self.forward(*self.sampler["Eval"].batch(b), step=-1 - b)))
@@ -220,6 +240,9 @@ class PWG_Trainer(aux_trainer.Trainer):
                 losses.append(float(out[3]))
                 adv.append(out[2].cpu().double())
             terms.append(self.criterion.terms.cpu().double())
+            if self.mel_criterion is not None:
+                mel.append(float(self.mel_criterion.term))
+        self.last_evaluation_mel = float(np.mean(mel)) if mel else None
         ev = float(np.mean(losses)), torch.stack(terms).mean(0)
         return ev if self.discriminator is None else ev + (torch.stack(adv).mean(0),)
 
@@ -249,6 +272,9 @@ class PWG_Trainer(aux_trainer.Trainer):
         logging.info("Step %d: loss %.4f%s", self.steps, float(loss), "" if ev is None else ", evaluation loss {:.4f}, terms {}".format(ev[0], ev[1].tolist()))
         if ev is not None and len(ev) > 2:
             logging.info("Step %d: evaluation L_adv %.4f, real term %.4f, fake term %.4f", self.steps, *ev[2].tolist())
+        if "Mel_Loss" in self.last:
+            logging.info("Step %d: mel loss %.4f%s", self.steps, float(self.last["Mel_Loss"]),
+                         "" if self.last_evaluation_mel is None else ", evaluation mel loss {:.4f}".format(self.last_evaluation_mel))
         if "L_adv" in self.last:
             logging.info("Step %d: L_adv %.4f, real term %.4f, fake term %.4f, discriminator loss %.4f", self.steps, float(self.last["L_adv"]),
                          float(self.last["Real_Term"]), float(self.last["Fake_Term"]), float(self.last["Discriminator_Loss"]))

@@ -765,6 +765,154 @@ class MultiResolutionSTFTLoss:
 
 
 # ================================================================================================================================================
+# Mel-spectrogram L1 loss (Kong et al. 2020, eq. 5; the 45 L_mel of the HiFi-GAN generator loss) on the kernels of csrc/mel_loss_ops.hip.  The contract
+# is this project's own, in DESIGN.md ("Mel loss"); tests/mel_loss_ref.py restates it with the library STFT.  The class is Lambda-free: the trainer scales.
+# ================================================================================================================================================
+MEL_KEY = "Vocoder.Train.Mel_Loss"
+MEL_LAMBDA, MEL_FLOOR = 45.0, 1.0e-5
+MEL_MIN_FILTERS, MEL_MAX_FILTERS = 4, 256
+
+
+def mel_loss_settings(hp):
+    """The optional yaml block `Vocoder.Train.Mel_Loss` over its defaults {Lambda: 45.0, Floor: 1.0e-5, Mel_F_Min / Mel_F_Max: Sound's}, checked: a
+    ValueError names every unknown or bad key as Vocoder.Train.Mel_Loss.<key>.  An absent block gives the defaults: whether the term is trained with is
+    the caller's decision (`pwg_trainer.train_settings` keeps the key only when the yaml has it)."""
+    block = getattr(getattr(getattr(hp, "Vocoder", None), "Train", None), "Mel_Loss", None)
+    defaults = {"Lambda": MEL_LAMBDA, "Floor": MEL_FLOOR, "Mel_F_Min": hp.Sound.Mel_F_Min, "Mel_F_Max": hp.Sound.Mel_F_Max}
+
+    def rules(s, need):
+        for k in ("Lambda", "Floor"):
+            need(k, lambda v: not isinstance(v, bool) and 0 < float(v) < float("inf"), "positive")
+        need("Mel_F_Min", lambda v: not isinstance(v, bool) and 0 <= float(v) < float("inf"), "at least 0")
+        need("Mel_F_Max", lambda v: not isinstance(v, bool) and float(v) > float(s["Mel_F_Min"]), "above Mel_F_Min")
+    return overlay_settings(block, defaults, MEL_KEY, "vocoder", rules)
+
+
+def mel_loss_geometry(hp, block=None, T=None):
+    """The analysis geometry of the mel loss: {n_fft, hop, win, mel, sample_rate, f_min, f_max, floor} from hp.Sound and the settings `block`
+    (`mel_loss_settings`' result; None: that of hp).  Raises ValueError naming the yaml key when the kernels do not support a size, when a filter of the
+    filterbank is empty or, with `T` given, when the segment of T samples is too short for the reflect padding.  Touches no device."""
+    s = hp.Sound
+    block = mel_loss_settings(hp) if block is None else block
+    n_fft, win, hop, mel = (int(s.Spectrogram_Dim) - 1) * 2, int(s.Frame_Length), int(s.Frame_Shift), int(s.Mel_Dim)
+    if n_fft < 256 or n_fft > 4096 or n_fft & (n_fft - 1):
+        raise ValueError(f"Sound.Spectrogram_Dim = {s.Spectrogram_Dim}: the mel loss needs n_fft = 2 * (Spectrogram_Dim - 1) to be a power of two in [256, 4096], "
+                         f"got {n_fft}")
+    if win < 1 or win > n_fft:
+        raise ValueError(f"Sound.Frame_Length = {win} must lie in [1, n_fft = {n_fft}] (Sound.Spectrogram_Dim = {s.Spectrogram_Dim})")
+    if hop < 1 or hop > win:
+        raise ValueError(f"Sound.Frame_Shift = {hop} must lie in [1, Sound.Frame_Length = {win}] (every sample is covered by a frame)")
+    if mel < MEL_MIN_FILTERS or mel > MEL_MAX_FILTERS:
+        raise ValueError(f"Sound.Mel_Dim = {mel} must lie in [{MEL_MIN_FILTERS}, {MEL_MAX_FILTERS}] (one thread of the mel loss's workgroup per filter)")
+    floor, f_min, f_max, rate = float(block["Floor"]), float(block["Mel_F_Min"]), float(block["Mel_F_Max"]), int(s.Sample_Rate)
+    if not floor > 0:
+        raise ValueError(f"{MEL_KEY}.Floor = {block['Floor']} must be positive")
+    if not 0 <= f_min < f_max <= rate / 2:
+        raise ValueError(f"{MEL_KEY}.Mel_F_Min = {f_min:g} and {MEL_KEY}.Mel_F_Max = {f_max:g} (absent: Sound's) must satisfy 0 <= Mel_F_Min < Mel_F_Max <= "
+                         f"Sound.Sample_Rate / 2 = {rate / 2:g}")
+    empty = np.flatnonzero(~audio.mel_filterbank(rate, n_fft, mel, f_min, f_max).any(axis=1))
+    if empty.size:
+        raise ValueError(f"Sound.Mel_Dim = {mel} filters between {MEL_KEY}.Mel_F_Min = {f_min:g} and {MEL_KEY}.Mel_F_Max = {f_max:g} (absent: Sound's) leave filter "
+                         f"{int(empty[0])} without a bin at n_fft = {n_fft} (Sound.Spectrogram_Dim): fewer filters or a wider band")
+    if T is not None and T <= n_fft // 2:
+        raise ValueError(f"{MEL_KEY}: n_fft = {n_fft} (Sound.Spectrogram_Dim) needs segments longer than n_fft / 2 = {n_fft // 2} samples for its reflect "
+                         f"padding, got {T} (Vocoder.Train.Segment_Frames * Sound.Frame_Shift)")
+    return {"n_fft": n_fft, "hop": hop, "win": win, "mel": mel, "sample_rate": rate, "f_min": f_min, "f_max": f_max, "floor": floor}
+
+
+def transposed_filterbank(index, weights, n_freq):
+    """The sparse filterbank of `frontend.sparse_filterbank` read by bin (CSR): (start [n_freq + 1] int32, filter [n] int32, weights [n]) - bin k's
+    entries are start[k] .. start[k + 1], its filters in ascending order.  Every entry of `weights` appears once (zeros inside a run included)."""
+    count = index[:, 1].astype(np.int64)
+    filt = np.repeat(np.arange(index.shape[0], dtype=np.int64), count)
+    bins = np.concatenate([np.arange(f, f + c) for f, c in zip(index[:, 0].astype(np.int64), count)] or [np.zeros(0, np.int64)])
+    order = np.lexsort((filt, bins))                                   # by bin, then by filter
+    start = np.zeros(n_freq + 1, np.int32)
+    start[1:] = np.cumsum(np.bincount(bins, minlength=n_freq))
+    return start, filt[order].astype(np.int32), np.ascontiguousarray(np.asarray(weights)[:filt.size][order])
+
+
+def mel_loss_forward(loss_fn, pred, target):
+    """The forward launches -> (loss [1] = L_mel, terms [1], keep [B frames Mel]): the entry point's own outputs, for `_MelLoss` and the tests."""
+    B, T = pred.shape
+    g, L, dev = loss_fn.geo, _lib.api(), pred.device
+    loss, terms = torch.empty(1, dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.float32, device=dev)
+    keep = torch.empty(L.glowtts_mel_loss_keep_floats(B, T, g["hop"], g["mel"]), dtype=torch.float32, device=dev)
+    work = loss_fn._work(L.glowtts_mel_loss_work_floats(B, T, g["win"], g["hop"]))
+    L.glowtts_mel_loss_forward(_lib.ptr(pred), _lib.ptr(target), _lib.ptr(loss_fn.window), _lib.ptr(loss_fn.twiddle), _lib.ptr(loss_fn.fb_index),
+                               _lib.ptr(loss_fn.fb_weights), _lib.ptr(keep), _lib.ptr(work), _lib.ptr(terms), _lib.ptr(loss), B, T, g["n_fft"], g["win"], g["hop"],
+                               g["mel"], loss_fn.fb_weights.numel(), g["floor"], 1.0, 0, _lib.stream())
+    return loss, terms, keep
+
+
+def mel_loss_backward(loss_fn, pred, keep, grad_out):
+    """The backward launches -> d pred [B, T] = grad_out * dL_mel/dpred (grad_out: one device float; pred: the forward's)."""
+    B, T = pred.shape
+    g, L = loss_fn.geo, _lib.api()
+    dpred = torch.empty(B, T, dtype=torch.float32, device=pred.device)
+    work = loss_fn._work(L.glowtts_mel_loss_work_floats(B, T, g["win"], g["hop"]))
+    L.glowtts_mel_loss_backward(_lib.ptr(pred), _lib.ptr(keep), _lib.ptr(grad_out), _lib.ptr(loss_fn.window), _lib.ptr(loss_fn.twiddle), _lib.ptr(loss_fn.fbt_start),
+                                _lib.ptr(loss_fn.fbt_filter), _lib.ptr(loss_fn.fbt_weights), _lib.ptr(work), _lib.ptr(dpred), B, T, g["n_fft"], g["win"], g["hop"],
+                                g["mel"], loss_fn.fbt_weights.numel(), 1.0, 0, _lib.stream())
+    return dpred
+
+
+class _MelLoss(torch.autograd.Function):
+    """loss = MelSpectrogramLoss(pred, target): forward and backward are the HIP launches of csrc/mel_loss_ops.hip; the target gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, loss_fn, pred, target):
+        loss, terms, keep = mel_loss_forward(loss_fn, pred, target)
+        ctx.loss_fn, ctx.keep, ctx.pred = loss_fn, keep, pred          # (the backward takes the prediction's spectrum again: nothing of it was kept)
+        loss_fn.term = terms[0]
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        dpred = mel_loss_backward(ctx.loss_fn, ctx.pred, ctx.keep, g.to(torch.float32).reshape(1).contiguous())
+        ctx.keep = ctx.pred = None
+        return None, dpred, None
+
+
+class MelSpectrogramLoss:
+    """MelSpectrogramLoss(hp, device, settings=None)(pred [B, T], target [B, T]) -> the scalar L_mel = mean |ln mel(target) - ln mel(pred)| at the analysis
+    geometry of hp.Sound (`mel_loss_geometry`; settings: `mel_loss_settings`' result, None: that of hp), with a backward that yields d pred.  Lambda-free: the
+    trainer scales the term.  `.term` holds the last value.  Every row is of the full length T.  Bit-identical from run to run."""
+
+    def __init__(self, hp, device="cuda:0", settings=None):
+        from .frontend import sparse_filterbank                    # (frontend imports this module)
+        self.settings = mel_loss_settings(hp) if settings is None else settings
+        g = self.geo = mel_loss_geometry(hp, self.settings)        # before anything touches the device
+        self.device = torch.device(device)
+        tw, w = fft_tables(g["n_fft"], g["win"])
+        index, weights = sparse_filterbank(audio.mel_filterbank(g["sample_rate"], g["n_fft"], g["mel"], g["f_min"], g["f_max"]))
+        start, filt, wt = transposed_filterbank(index, weights, g["n_fft"] // 2 + 1)
+        to = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.device)
+        self.twiddle, self.window = to(tw, np.float32), to(w, np.float32)
+        self.fb_index, self.fb_weights = to(index, np.int32), to(weights, np.float32)
+        self.fbt_start, self.fbt_filter, self.fbt_weights = to(start, np.int32), to(filt, np.int32), to(wt, np.float32)
+        self.term, self._scratch = None, None
+
+    _work = MultiResolutionSTFTLoss._work
+
+    def __call__(self, pred, target, lengths=None):
+        if pred.dim() != 2 or tuple(pred.shape) != tuple(target.shape):
+            raise ValueError(f"MelSpectrogramLoss: expected pred and target [B, T] of one shape, got {list(pred.shape)} and {list(target.shape)}")
+        if pred.dtype != torch.float32 or target.dtype != torch.float32 or not pred.is_cuda or not target.is_cuda:
+            raise _lib.GlowTTSHipError("MelSpectrogramLoss: expected fp32 device tensors (the HIP path has no CPU fallback)")
+        B, T = pred.shape
+        if lengths is not None and any(int(n) != T for n in torch.as_tensor(lengths).reshape(-1).tolist()):
+            raise ValueError(f"MelSpectrogramLoss: ragged input (lengths {torch.as_tensor(lengths).reshape(-1).tolist()} of T = {T}): every row must be of "
+                             "the full length, training segments are of one length (Vocoder.Train.Segment_Frames)")
+        if T <= self.geo["n_fft"] // 2:
+            raise ValueError(f"{MEL_KEY}: n_fft = {self.geo['n_fft']} (Sound.Spectrogram_Dim) needs segments longer than n_fft / 2 = {self.geo['n_fft'] // 2} samples "
+                             f"for its reflect padding, got {T} (Vocoder.Train.Segment_Frames * Sound.Frame_Shift)")
+        if B < 1 or B > 65535 or B * T >= 2 ** 31:
+            raise ValueError(f"MelSpectrogramLoss: batch of {B} x {T} samples is outside 1 <= B <= 65535, B T < 2^31 (Vocoder.Train.Batch_Size)")
+        return _MelLoss.apply(self, pred.contiguous(), target.detach().contiguous())
+
+
+# ================================================================================================================================================
 # The Parallel WaveGAN discriminator and the least-squares adversarial loss on the kernels of csrc/pwg_disc_ops.hip: stage two of the recipe.  The
 # contract (DESIGN.md "Training the Parallel WaveGAN discriminator") restates the most widely used implementation from memory and is UNPINNED.
 # ================================================================================================================================================

@@ -1123,6 +1123,37 @@ int glowtts_stft_loss_forward(const float *pred, const float *target, const floa
 int glowtts_stft_loss_backward(const float *keep, const float *terms, const float *grad_out, const float *window, const float *twiddle, float *work,
                                float *dpred, int B, int T, int n_fft, int win_length, int hop, float weight, int accumulate, void *stream);
 
+/* ---- Mel-spectrogram L1 loss of vocoder training (csrc/mel_loss_ops.hip; f32 signals, float64 sums; additions, the ABI version stays) ----
+ * ONE analysis geometry per call.  pred, target [B][T], every row of the full length T, framed exactly as the STFT loss above frames them (NF = 1 + T / hop
+ * frames, F = n_fft / 2 + 1 bins, the same window and twiddle tables).  Per frame and filter j:  |X|[k] = sqrt(re^2 + im^2 + 1e-9);
+ * mel[j] = sum_k fb[j, k] |X|[k] in ascending bin order;  m[j] = ln(max(mel[j], floor));  L_mel = mean over (B, NF, n_mel) of |m_target - m_pred|.
+ * No atomics, fixed summation orders: bit-identical from run to run.
+ * The filterbank is sparse, one run of bins per filter: fb_index [n_mel][3] = (first bin, bin count, offset into fb_weights), fb_weights [n_weights]
+ * (frontend.sparse_filterbank); the backward reads its transpose in CSR form, bin k's entries fbt_start[k] .. fbt_start[k + 1] (fbt_start [F + 1]) with
+ * their filters fbt_filter [n_weights] in ascending order and weights fbt_weights [n_weights].  The kernels hold every table index to the tables' sizes; a
+ * filter without bins contributes ln(floor) on both sides, the callers refuse it.
+ * Supported (glowtts_mel_loss_supported, else GLOWTTS_E_ARG): what glowtts_stft_loss_supported takes and 4 <= n_mel <= 256; also 1 <= B <= 65535,
+ * B T < 2^31, B NF <= 2^24, 1 <= n_weights <= n_mel F, floor > 0.  None of these functions allocates.
+ *   keep   glowtts_mel_loss_keep_floats() = B NF n_mel floats: c[j] = sign(m_pred - m_target) / mel_pred, 0 at equality and where mel_pred <= floor
+ *   work   glowtts_mel_loss_work_floats() = B NF (2 + win_length) floats (8-byte aligned): per-frame sums [B NF] f64 | the backward's windowed frame
+ *          gradients [B NF][win_length]
+ *   terms  [1]: L_mel
+ * glowtts_mel_loss_forward   `mel_loss_fwd` (per frame: both signals through the LDS FFT, magnitudes and filter sums in LDS, c into keep, the frame's sum)
+ *                            and `mel_loss_reduce` (one workgroup): fills terms and loss[0] = weight L_mel, added to loss[0] when accumulate.
+ * glowtts_mel_loss_backward  `mel_loss_bwd_frames` (per frame: pred's spectrum again, G[k] = grad_out[0] weight / (B NF n_mel) (sum_j fb[j, k] c[j])
+ *                            X[k] / |X|[k], the transposed real DFT in LDS, the window) and `mel_loss_bwd_fold` (the STFT loss's fold):
+ *                            dpred [B][T] = grad_out[0] weight dL_mel/dpred (grad_out: one device float), added to dpred when accumulate.  pred is the
+ *                            forward's, unchanged. */
+int glowtts_mel_loss_supported(int n_fft, int win_length, int hop, int T, int n_mel);
+int64_t glowtts_mel_loss_keep_floats(int B, int T, int hop, int n_mel);
+int64_t glowtts_mel_loss_work_floats(int B, int T, int win_length, int hop);
+int glowtts_mel_loss_forward(const float *pred, const float *target, const float *window, const float *twiddle, const int32_t *fb_index,
+                             const float *fb_weights, float *keep, float *work, float *terms, float *loss, int B, int T, int n_fft, int win_length,
+                             int hop, int n_mel, int n_weights, float floor, float weight, int accumulate, void *stream);
+int glowtts_mel_loss_backward(const float *pred, const float *keep, const float *grad_out, const float *window, const float *twiddle,
+                              const int32_t *fbt_start, const int32_t *fbt_filter, const float *fbt_weights, float *work, float *dpred, int B, int T,
+                              int n_fft, int win_length, int hop, int n_mel, int n_weights, float weight, int accumulate, void *stream);
+
 /* ---- The Parallel WaveGAN discriminator and the adversarial loss (csrc/pwg_disc_ops.hip; f32; additions, the ABI version stays) ----
  * `layers` 1-D convolutions of kernel size 3 over wav [B][T], "same" zero padding, bias, LeakyReLU(slope) after all but the last: 1 -> C (dilation 1),
  * C -> C with dilation i for i = 1 .. layers - 2, C -> 1 (dilation 1).  Activations are rows [B][T][C]; EVERY batch row is of the full length T, tiles are
