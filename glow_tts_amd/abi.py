@@ -335,6 +335,21 @@ SIGNATURES = {
     "glowtts_hifigan_disc_conv_bwd": (I, [P] * 6 + [I] * 6 + [F, P]),
     "glowtts_hifigan_disc_first_bwd": (I, [P] * 3 + [I] * 6 + [P]),
     "glowtts_hifigan_disc_wgrad": (I, [P] * 5 + [I] * 8 + [F, P]),
+    "glowtts_hifigan_msd_supported": (I, [I] * 5),
+    "glowtts_hifigan_msd_work_floats": (L, [I] * 6),
+    "glowtts_hifigan_msd_pool": (I, [P] * 2 + [I] * 2 + [P]),
+    "glowtts_hifigan_msd_pool_bwd": (I, [P] * 2 + [I] * 3 + [P]),
+    "glowtts_hifigan_msd_first": (I, [P] * 4 + [I] * 4 + [P]),
+    "glowtts_hifigan_msd_conv": (I, [P] * 4 + [I] * 7 + [F, P]),
+    "glowtts_hifigan_msd_dense": (I, [P] * 4 + [I] * 4 + [F, P]),
+    "glowtts_hifigan_msd_post": (I, [P] * 4 + [I] * 3 + [F, P]),
+    "glowtts_hifigan_msd_post_bwd": (I, [P] * 7 + [I] * 3 + [F, P]),
+    "glowtts_hifigan_msd_dense_bwd": (I, [P] * 6 + [I] * 4 + [F, P]),
+    "glowtts_hifigan_msd_conv_bwd": (I, [P] * 6 + [I] * 7 + [F, P]),
+    "glowtts_hifigan_msd_first_bwd": (I, [P] * 3 + [I] * 5 + [P]),
+    "glowtts_hifigan_msd_wgrad": (I, [P] * 5 + [I] * 7 + [F, P]),
+    "glowtts_hifigan_msd_first_wgrad": (I, [P] * 5 + [I] * 4 + [P]),
+    "glowtts_hifigan_msd_dense_wgrad": (I, [P] * 5 + [I] * 5 + [F, P]),
     "glowtts_mel_cepstrum_supported": (I, [I] * 2),
     "glowtts_mel_cepstrum": (I, [P] * 4 + [I] * 4 + [L] * 3 + [F, P]),
     "glowtts_dtw_supported": (I, [I] * 3),
@@ -355,5 +370,5 @@ VALUE_RETURNING = frozenset({
     "glowtts_cond_linear_supported", "glowtts_gst_supported", "glowtts_conv3x3s2_supported", "glowtts_dur_proj_supported", "glowtts_vocoder_supported",
     "glowtts_pwg_supported", "glowtts_pwg_supported_bf16", "glowtts_hifigan_supported", "glowtts_hifigan_train_supported", "glowtts_ge2e_supported", "glowtts_pwg_train_supported", "glowtts_stft_loss_supported",
     "glowtts_mel_loss_supported",
-    "glowtts_pwg_disc_supported", "glowtts_hifigan_disc_supported", "glowtts_mel_cepstrum_supported", "glowtts_dtw_supported", "glowtts_tsne_supported",
+    "glowtts_pwg_disc_supported", "glowtts_hifigan_disc_supported", "glowtts_hifigan_msd_supported", "glowtts_mel_cepstrum_supported", "glowtts_dtw_supported", "glowtts_tsne_supported",
 })

@@ -6,6 +6,11 @@
 //   folded  (the discriminator) rows are (h, c) of a waveform folded by the period p, flat row h p + c, and the convolution runs over h with stride s: the tile
 //           stages the 64 rows of EVERY tap, [taps][64] rows, through `hd_source_row` - the forward map, or with BWD its inverse - and tap m's rows sit at
 //           m * 64.  Taps that leave [0, Hsrc), and in the inverse map taps that the stride does not divide, are zero rows.
+//   strided span  (the multi-scale discriminator's grouped, strided convolutions, `GRP`) the span mode with a row stride rs: tap m of position s reads
+//           source row s rs + o0 + m ts, so the tile stages ONE contiguous span of 63 rs + 1 + reach rows and position i's tap m sits at LDS row
+//           i rs + m.  The source's row pitch is not the K extent (a group's channels of a wider slab; the caller's pointers carry the channel offset), and
+//           the output's pitch and valid columns are not the weight image's column count.  With rs = 1 and the output phase (os, oph) it is one phase of
+//           the transposed convolution: hifigan_msd_ops.hip.
 // Everything after the staging - the k loop, the chains, the epilogue - is one text.  The comment at the head of hifigan_ops.hip describes the tile.
 #pragma once
 #include <algorithm>
@@ -46,7 +51,7 @@ __device__ __forceinline__ bool hd_source_row(int n, int m, int half, int p, int
 __device__ __forceinline__ float hd_padded(const float* __restrict__ x, int n, int T) { return x[n < T ? n : 2 * T - 2 - n]; }
 
 // How a launch walks its taps: the weight rows of tap m start at (w0 + m wstep) Cin.  Span: the input row of (position s, tap m) is s + o0 + m ts.
-// Folded: period p and row stride s of `hd_source_row` (o0, ts unused).
+// Folded: period p and row stride s of `hd_source_row` (o0, ts unused).  Strided span (GRP): p is the source's row pitch in floats, s the row stride rs.
 struct HgTaps {
     int nt, o0, ts, w0, wstep, p, s;
 };
@@ -61,18 +66,23 @@ struct HgTaps {
 // kernels, whose register figures the discriminator's kernels then share (DESIGN.md has both tables).  Unrolled over a constant five taps the body took 233
 // VGPRs at (4, 2), one wave per SIMD; with run-time taps no launch got slower and the discriminator's launches of a training step went from 64.0 to 47.3 ms
 // on an MI355X, so the template variant was not needed.
-template <int RT, int NT, bool BWD = false, bool FOLD = false>
+// GRP (never with FOLD; channels-last sources alone): Cin is the K extent and the weight image's rows per tap, Cout the image's columns; the source rows are
+// tp.p floats apart, the output rows (and maskb's, resb's) opitch floats, and columns from ovalid on are computed (against zero columns of the image) but
+// never written.  Every GRP term below is a compile-time branch: the other instantiations are the code they were.
+template <int RT, int NT, bool BWD = false, bool FOLD = false, bool GRP = false>
 __device__ __forceinline__ void hg_tile(const float* __restrict__ inb, const float* __restrict__ w, const float* __restrict__ bias, const float* resb,
                                         float* outb, float* Xs, int Tsrc, int Tdst, int tin_max, int s0, int Cin, int Cout, int colgroup, HgTaps tp, float slope,
                                         int cf, int os, int oph, int accumulate, float divisor, const float* maskb = nullptr, float mslope = 1.f,
-                                        float res_scale = 1.f)
+                                        float res_scale = 1.f, int opitch = 0, int ovalid = 0)
 {
+    static_assert(!(GRP && FOLD), "the strided span is a span mode");
     constexpr int WR = WAVES / RT, WC = WAVES / WR;        // the waves as WR row groups x WC column groups
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
     const int wr = wave % WR, wc = wave / WR;
     const int col0 = (colgroup * WC + wc) * NT * 16;
     const int last = tp.o0 + (tp.nt - 1) * tp.ts;
-    const int lo = FOLD ? 0 : min(tp.o0, last), span = FOLD ? tp.nt * TM : TM + max(tp.o0, last) - lo;
+    const int rs = GRP ? tp.s : 1;                         // rows of the source between two positions
+    const int lo = FOLD ? 0 : min(tp.o0, last), span = FOLD ? tp.nt * TM : (GRP ? (TM - 1) * rs + 1 : TM) + max(tp.o0, last) - lo;
     const int xs = lds_stride_of(min(Cin, HG_CK));
 
     f32x4 acc[RT][NT];
@@ -87,7 +97,7 @@ __device__ __forceinline__ void hg_tile(const float* __restrict__ inb, const flo
     for (int c0 = 0; c0 < Cin; c0 += HG_CK) {
         const int ck = min(HG_CK, Cin - c0);
         if (c0) __syncthreads();                           // every wave is done with the previous chunk
-        if (!FOLD && cf) {                                 // channels-first source (the mel): consecutive threads along the rows
+        if (!FOLD && !GRP && cf) {                               // channels-first source (the mel): consecutive threads along the rows
             for (int e = tid; e < span * ck; e += THREADS) {
                 const int c = e / span, row = e - c * span, t = s0 + lo + row;
                 Xs[row * xs + c] = (t >= 0 && t < Tsrc) ? lrelu(inb[(size_t)(c0 + c) * tin_max + t], slope) : 0.f;
@@ -102,12 +112,12 @@ __device__ __forceinline__ void hg_tile(const float* __restrict__ inb, const flo
                     const int m = row / TM, n = s0 + row - m * TM;
                     live = n < Tdst && hd_source_row<BWD>(n, m, (tp.nt - 1) / 2, tp.p, tp.s, Tsrc, &t);
                 } else {
-                    t = s0 + lo + row;
+                    t = s0 * rs + lo + row;
                     live = t >= 0 && t < Tsrc;
                 }
                 float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (live) {
-                    v = *reinterpret_cast<const float4*>(inb + (size_t)t * Cin + c0 + k4);
+                    v = *reinterpret_cast<const float4*>(inb + (size_t)t * (GRP ? tp.p : Cin) + c0 + k4);
                     v.x = lrelu(v.x, slope); v.y = lrelu(v.y, slope); v.z = lrelu(v.z, slope); v.w = lrelu(v.w, slope);
                 }
                 *reinterpret_cast<float4*>(Xs + row * xs + k4) = v;
@@ -115,7 +125,7 @@ __device__ __forceinline__ void hg_tile(const float* __restrict__ inb, const flo
         }
         __syncthreads();
         for (int m = 0; m < tp.nt; ++m) {
-            const float* xa = Xs + (wr * RT * 16 + r + (FOLD ? m * TM : tp.o0 + m * tp.ts - lo)) * xs + q;
+            const float* xa = Xs + ((wr * RT * 16 + r) * rs + (FOLD ? m * TM : tp.o0 + m * tp.ts - lo)) * xs + q;
             const float* wp = w + ((size_t)(tp.w0 + m * tp.wstep) * Cin + c0 + q) * Cout + col0 + r;
             f32x4 part[RT][NT];                            // this (chunk, tap)'s chain
 #pragma unroll
@@ -128,7 +138,7 @@ __device__ __forceinline__ void hg_tile(const float* __restrict__ inb, const flo
                 for (int n = 0; n < NT; ++n) bw[n] = wp[(size_t)k0 * Cout + n * 16];
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) {
-                    const float a = xa[rt * 16 * xs + k0];
+                    const float a = xa[rt * 16 * rs * xs + k0];
 #pragma unroll
                     for (int n = 0; n < NT; ++n) part[rt][n] = mfma4(a, bw[n], part[rt][n]);
                 }
@@ -154,7 +164,8 @@ __device__ __forceinline__ void hg_tile(const float* __restrict__ inb, const flo
             if (s >= Tdst) continue;                       // padded rows are never written
 #pragma unroll
             for (int n = 0; n < NT; ++n) {
-                const size_t idx = ((size_t)s * os + oph) * Cout + col0 + n * 16 + r;
+                if (GRP && col0 + n * 16 + r >= ovalid) continue;
+                const size_t idx = ((size_t)s * os + oph) * (GRP ? opitch : Cout) + col0 + n * 16 + r;
                 float y = acc[rt][n][i];
                 if constexpr (BWD) {
                     y = y * (maskb[idx] > 0.f ? 1.f : mslope) * divisor;

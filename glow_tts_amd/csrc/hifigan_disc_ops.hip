@@ -30,6 +30,9 @@
 //                           written, or added to what d wav holds (the periods add up in period order).
 //   hifigan_disc_wgrad      the generator's weight-gradient kernel and launch sequence (hifigan_wgrad.h: `hw_launch`) with the same row map; +
 //                           `hifigan_disc_wgrad_sum`.
+// The multi-scale discriminator (hifigan_msd_ops.hip) runs its dense last layer and its conv_post on these kernels at period 1, where `hd_source_row` is a
+// zero-padded convolution over time: the entry points glowtts_hifigan_msd_dense* / _post* at the end, launch-log classes `hifigan_msd_dense*` / `_post*`.
+// Period 1 stays refused by the multi-period entry points.
 #include "hifigan_common.h"
 #include "hifigan_wgrad.h"
 
@@ -317,4 +320,57 @@ extern "C" int glowtts_hifigan_disc_wgrad(const float* x, const float* dy, float
         return GLOWTTS_E_ARG;
     const HwArgs a = {x, dy, nullptr, work, B, hd_rows_out(H, stride) * period, 1, Cin, Cout, taps, 0, 0, 0, 0, 0, slope, period, stride, H, wav_samples};
     return hw_launch<true>(a, dw, dbias, 0, taps, 1.f, static_cast<hipStream_t>(stream));
+}
+
+// ---- the multi-scale discriminator's dense layers: the kernels above at period 1 (activations [B][L][C], stride 1) ----
+namespace {
+bool hd_bad_length(int B, int L) { return B < 1 || B > 65535 || L < 1 || (int64_t)B * L > ((int64_t)1 << 30); }
+}  // namespace
+
+extern "C" int glowtts_hifigan_msd_dense(const float* x, const float* w, const float* bias, float* out, int B, int L, int Cin, int Cout, float slope, void* stream)
+{
+    if (!x || !w || !bias || !out || x == out || hd_bad_length(B, L) || !hd_width(Cin) || !hd_width(Cout) || hd_lds_bytes(Cin) > MAX_LDS) return GLOWTTS_E_ARG;
+    if (hd_conv<false>(x, w, bias, nullptr, nullptr, nullptr, out, B, L, L, 1, 1, Cin, Cout, slope, 1.f, stream) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;
+    GLOWTTS_NOTE_STATIC("hifigan_msd_dense");
+    RET_LAUNCH();
+}
+
+extern "C" int glowtts_hifigan_msd_dense_bwd(const float* dy, const float* wt, const float* x, const float* inj, const float* inj_scale, float* dx, int B, int L,
+                                             int Cin, int Cout, float slope, void* stream)
+{
+    if (!dy || !wt || !x || !dx || dx == dy || dx == x || (inj && !inj_scale) || hd_bad_length(B, L) || !hd_width(Cin) || !hd_width(Cout) ||
+        hd_lds_bytes(Cout) > MAX_LDS)
+        return GLOWTTS_E_ARG;
+    if (hd_conv<true>(dy, wt, nullptr, x, inj, inj_scale, dx, B, L, L, 1, 1, Cout, Cin, 1.f, slope, stream) != GLOWTTS_OK) return GLOWTTS_E_LAUNCH;
+    GLOWTTS_NOTE_STATIC("hifigan_msd_dense_bwd");
+    RET_LAUNCH();
+}
+
+extern "C" int glowtts_hifigan_msd_post(const float* x, const float* w, const float* bias, float* scores, int B, int L, int C, float slope, void* stream)
+{
+    if (!x || !w || !bias || !scores || hd_bad_length(B, L) || !hd_width(C)) return GLOWTTS_E_ARG;
+    GLOWTTS_NOTE_STATIC("hifigan_msd_post");
+    hipLaunchKernelGGL(hifigan_disc_post_kernel, dim3((L + WAVES - 1) / WAVES, B), dim3(THREADS), 0, static_cast<hipStream_t>(stream), x, w, bias, scores, L, 1, C,
+                       slope);
+    RET_LAUNCH();
+}
+
+extern "C" int glowtts_hifigan_msd_post_bwd(const float* dscores, const float* dscores2, const float* x, const float* w, const float* inj, const float* inj_scale,
+                                            float* dx, int B, int L, int C, float slope, void* stream)
+{
+    if (!dscores || !x || !w || !dx || dx == x || ((inj || dscores2) && !inj_scale) || hd_bad_length(B, L) || !hd_width(C)) return GLOWTTS_E_ARG;
+    GLOWTTS_NOTE_STATIC("hifigan_msd_post_bwd");
+    hipLaunchKernelGGL(hifigan_disc_post_bwd_kernel, dim3(hd_quads(L, C), B), dim3(THREADS), 0, static_cast<hipStream_t>(stream), dscores, dscores2, x, w, inj,
+                       inj_scale, dx, L, 1, C, slope);
+    RET_LAUNCH();
+}
+
+extern "C" int glowtts_hifigan_msd_dense_wgrad(const float* x, const float* dy, float* work, float* dw, float* dbias, int B, int L, int Cin, int Cout, int taps,
+                                               float slope, void* stream)
+{
+    if (!x || !dy || !work || !dw || !dbias || hd_bad_length(B, L) || !hd_width(Cin) || !(Cout == 1 || hd_width(Cout)) ||
+        !((taps == HD_TAPS && Cout != 1) || (taps == HD_POST_TAPS && Cout == 1)))
+        return GLOWTTS_E_ARG;
+    const HwArgs a = {x, dy, nullptr, work, B, L, 1, Cin, Cout, taps, 0, 0, 0, 0, 0, slope, 1, 1, L, 0};
+    return hw_launch<true, true>(a, dw, dbias, 0, taps, 1.f, static_cast<hipStream_t>(stream));
 }

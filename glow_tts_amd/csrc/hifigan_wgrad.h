@@ -192,8 +192,9 @@ HwSizes hw_sizes(int B, int Tmax, int Ca, int Cd, int taps)
 
 // The launch pair of a weight gradient.  a: everything but nchunk and group, which follow from the rows; dw, dbias, rate, k, scale: the sum kernel's
 // layout arguments (rate 0, k = taps: a convolution).  The kernel's accumulators come in buckets of taps: 3 / 7 / 11 for the generator's kernel sizes (and its
-// views' few offsets), 3 / 5 under MAP, whose callers have no other.  Notes `hifigan_wgrad` + `hifigan_wgrad_sum`, MAP: `hifigan_disc_wgrad` + `.._sum`.
-template <bool MAP>
+// views' few offsets), 3 / 5 under MAP, whose callers have no other.  Notes `hifigan_wgrad` + `hifigan_wgrad_sum`, MAP: `hifigan_disc_wgrad` + `.._sum`, MSD
+// (the multi-scale discriminator's dense layers: MAP at period 1): `hifigan_msd_dense_wgrad` + `.._sum`.
+template <bool MAP, bool MSD = false>
 int hw_launch(HwArgs a, float* dw, float* dbias, int rate, int k, float scale, hipStream_t st)
 {
     const int Tmax = a.Lmax * a.mult;
@@ -209,10 +210,10 @@ int hw_launch(HwArgs a, float* dw, float* dbias, int rate, int k, float scale, h
     else if (a.taps <= 7) status = hg_launch<&hifigan_wgrad_kernel<7>>(grid, lds, st, a);
     else status = hg_launch<&hifigan_wgrad_kernel<HW_MAX_TAPS>>(grid, lds, st, a);
     if (status != GLOWTTS_OK) return status;
-    GLOWTTS_NOTE_STATIC("%s", MAP ? "hifigan_disc_wgrad" : "hifigan_wgrad");
+    GLOWTTS_NOTE_STATIC("%s", MSD ? "hifigan_msd_dense_wgrad" : MAP ? "hifigan_disc_wgrad" : "hifigan_wgrad");
     hipLaunchKernelGGL(hifigan_wgrad_sum_kernel, dim3((unsigned)((z.per_split + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, a.partial, dw, dbias, z.splits, a.taps,
                        a.Ca, a.Cd, z.CiP, z.CoP, a.o0, rate, k, scale);
-    GLOWTTS_NOTE_STATIC("%s", MAP ? "hifigan_disc_wgrad_sum" : "hifigan_wgrad_sum");
+    GLOWTTS_NOTE_STATIC("%s", MSD ? "hifigan_msd_dense_wgrad_sum" : MAP ? "hifigan_disc_wgrad_sum" : "hifigan_wgrad_sum");
     RET_LAUNCH();
 }
 

@@ -12,20 +12,29 @@ L_G = L_stft + Lambda_Adversarial sum_p mean((D_p(G) - 1)^2) + Lambda_Feature_Ma
 both updates from the state before the step, the discriminator with a clipping, a RAdam and a step decay over its own update count; the checkpoint also
 carries `discriminator`, `Discriminator_Optimizer`, `Discriminator_Steps`.  A stage-one checkpoint (no `discriminator`) whose `Steps <= Start_Step` resumes
 with the seeded-init discriminator.  Without the sub-block nothing differs from stage one alone.  The optional sub-block
-`Vocoder.Train.Mel_Loss` (DESIGN.md "Mel loss") adds Lambda L_mel to L_stft in both stages, through `PWG_Trainer.forward`.  The multi-scale discriminator
-is out of scope; a `Vocoder.Train.Discriminator` block - the Parallel WaveGAN discriminator's - is refused."""
+`Vocoder.Train.Mel_Loss` (DESIGN.md "Mel loss") adds Lambda L_mel to L_stft in both stages, through `PWG_Trainer.forward`.  The optional sub-block
+`Vocoder.Train.Adversarial.Multi_Scale` (DESIGN.md "The multi-scale discriminator") adds the multi-scale discriminator: the discriminator is then
+`vocoder.HiFiGANDiscriminators`, the sums over p above run over the periods and then the scales, L_fm is the periods' sum plus the scales', and the one
+discriminator optimizer, clipping and step decay cover the union of the parameters (the scales' under `scale_discriminators.`), which is what the
+checkpoint's `discriminator` then holds.  A checkpoint whose `discriminator` lacks the scales' names resumes such a run only under the stage-one rule
+(`Steps <= Start_Step`: both seeded inits are untouched).  Without the sub-block nothing differs.  A `Vocoder.Train.Discriminator` block - the Parallel
+WaveGAN discriminator's - is refused."""
 import logging
 
 import torch
 
 from . import aux_trainer, pwg_trainer
 from .hparams import plain_block
-from .vocoder import HiFiGAN, HiFiGANPeriodDiscriminator, adversarial_mse, hifigan_disc_load, hifigan_disc_settings, hifigan_geometry, hifigan_load
+from .vocoder import (MSD_BLOCK, MSD_KEY, MSD_PREFIX, HiFiGAN, HiFiGANDiscriminators, HiFiGANPeriodDiscriminator, adversarial_mse, hifigan_disc_load,
+                      hifigan_disc_settings, hifigan_discs_load, hifigan_geometry, hifigan_load)
 
 TRAIN_KEY = pwg_trainer.TRAIN_KEY
 DEFAULTS = dict(pwg_trainer.DEFAULTS, Batch_Size=16, Segment_Frames=32, Learning_Rate=2.0e-4, Checkpoint_Path="./hifigan_results")
 BUNDLES = (("", "model", "hifigan", hifigan_load, ("generator", "Optimizer", "Steps")),
            ("disc_", "discriminator", "hifigan_disc", hifigan_disc_load, ("discriminator", "Discriminator_Optimizer", "Discriminator_Steps")))
+# with the sub-block Multi_Scale the discriminator bundle is the union of both discriminators, under the same checkpoint keys
+BUNDLES_MULTI_SCALE = (BUNDLES[0], BUNDLES[1][:3] + (hifigan_discs_load,) + BUNDLES[1][4:])
+DISC_KEYS = BUNDLES[1][4]
 ADV_KEY = "Adversarial"
 
 
@@ -60,12 +69,19 @@ class HiFiGAN_Trainer(pwg_trainer.PWG_Trainer):
         return self.model.generate(mel, lengths)[0]
 
     def make_discriminator(self):
-        return HiFiGANPeriodDiscriminator(self.hp, self.device, trainable=True, seed=self.seed)
+        """The multi-period discriminator; with the sub-block Multi_Scale, both discriminators as one (and the bundle that loads their union)"""
+        self.multi_scale = MSD_BLOCK in self.disc_set
+        if not self.multi_scale:
+            return HiFiGANPeriodDiscriminator(self.hp, self.device, trainable=True, seed=self.seed)
+        self.BUNDLES = BUNDLES_MULTI_SCALE
+        return HiFiGANDiscriminators(self.hp, self.device, trainable=True, seed=self.seed)
 
     def adversarial_losses(self, target, wav, stft):
-        """-> (L_G, L_D, the unscaled (sum_p L_adv_p, sum_p real term, sum_p fake term) [3], L_stft) from one discriminator forward per period over
-        [target; wav]; `self.fm`: the unscaled L_fm and its terms [periods, widths + 1]."""
-        both, p_fake, l_fm, fm_terms = self.discriminator.score_pair(target, wav)
+        """-> (L_G, L_D, the unscaled (sum_p L_adv_p, sum_p real term, sum_p fake term) [3], L_stft) from one discriminator forward per period (then per
+        scale) over [target; wav]; `self.fm`: the unscaled L_fm and its terms [periods, widths + 1]; `self.fm_scale`: the scales' terms [scales, layers + 1]
+        or None."""
+        both, p_fake, l_fm, fm_terms, *scale_terms = self.discriminator.score_pair(target, wav)
+        self.fm_scale = scale_terms[0] if scale_terms else None
         adv, d_loss, d_terms = 0.0, 0.0, 0.0
         for b, p in zip(both, p_fake):                                      # period order
             a, _ = adversarial_mse(p, 1.0)
@@ -78,7 +94,19 @@ class HiFiGAN_Trainer(pwg_trainer.PWG_Trainer):
     def Adversarial_Step(self, mel, target):
         loss = super().Adversarial_Step(mel, target)
         self.last["L_fm"], self.last["FM_Terms"] = self.fm
+        if self.fm_scale is not None:
+            self.last["FM_Terms_Scale"] = self.fm_scale
         return loss
+
+    def load_state_dict(self, state):
+        """With the sub-block Multi_Scale, a checkpoint whose discriminator lacks the scales' names is a stage-one checkpoint for this run when its
+        `Steps <= Start_Step` (no discriminator has been touched: both seeded inits are their state); later it cannot be resumed: ValueError naming the key."""
+        if getattr(self, "multi_scale", False) and DISC_KEYS[0] in state and not any(str(k).startswith(MSD_PREFIX) for k in state[DISC_KEYS[0]]):
+            if int(state["Steps"]) > int(self.disc_set["Start_Step"]):
+                raise ValueError("{} holds no multi-scale discriminator (no key {}discriminators.0.convs.0.weight): it was written without the block {} and is "
+                                 "past its Start_Step".format(self.checkpoint_file(self.steps), MSD_PREFIX, MSD_KEY))
+            state = {k: v for k, v in state.items() if k not in DISC_KEYS}
+        super().load_state_dict(state)
 
     def without_discriminator(self, state):
         """A stage-one checkpoint: up to Start_Step the discriminator has not been touched, so the seeded init of the constructor IS its state"""

@@ -1658,16 +1658,19 @@ class HiFiGAN:
 # ================================================================================================================================================
 # The HiFi-GAN multi-period discriminator on the kernels of csrc/hifigan_disc_ops.hip: forward, backward, feature matching, f32.  The network is written
 # down in DESIGN.md ("Training the HiFi-GAN discriminator"); it and the checkpoint layout restate the most widely used implementation from memory and are
-# UNPINNED, like the other vocoder contracts.  Kernel sizes 5 / 3 and stride 3 are constants of the architecture, not yaml keys.
+# UNPINNED, like the other vocoder contracts.  Kernel sizes 5 / 3 and stride 3 are constants of the architecture, not yaml keys.  The multi-scale
+# discriminator (the optional sub-block `Multi_Scale`) follows it below.
 # ================================================================================================================================================
 MPD_KEY = "Vocoder.Train.Adversarial"
 MPD_DEFAULTS = {"Start_Step": 0, "Lambda_Adversarial": 1.0, "Lambda_Feature_Matching": 2.0, "Learning_Rate": 2.0e-4, "Epsilon": 1.0e-6, "Gradient_Norm": 10.0,
                 "Learning_Rate_Decay": {"Step": 200000, "Gamma": 0.5}, "Periods": [2, 3, 5, 7, 11], "Channels": [32, 128, 512, 1024, 1024], "Negative_Slope": 0.1}
 MPD_TAPS, MPD_POST_TAPS, MPD_STRIDE, MPD_MAX_PERIOD, MPD_MAX_PERIODS, MPD_MAX_CHANNELS, MPD_MAX_WIDTHS = 5, 3, 3, 16, 8, 1024, 6
+MSD_BLOCK = "Multi_Scale"                                           # the optional sub-block of the multi-scale discriminator (below)
 
 
 def hifigan_disc_settings(hp):
-    """The optional yaml block `Vocoder.Train.Adversarial` over MPD_DEFAULTS (absent block: None), checked: a ValueError names every unknown or bad key."""
+    """The optional yaml block `Vocoder.Train.Adversarial` over MPD_DEFAULTS (absent block: None), checked: a ValueError names every unknown or bad key.
+    The optional sub-block `Multi_Scale` (`hifigan_msd_settings`) appears in the result only when the yaml has it."""
     block = getattr(getattr(getattr(hp, "Vocoder", None), "Train", None), "Adversarial", None)
     if block is None:
         return None
@@ -1685,8 +1688,12 @@ def hifigan_disc_settings(hp):
         need("Channels", lambda v: 2 <= len(v) <= MPD_MAX_WIDTHS and all(whole(c) and 16 <= int(c) <= MPD_MAX_CHANNELS and int(c) % 16 == 0 for c in v),
              "2 to {} widths, each a multiple of 16 in [16, {}]".format(MPD_MAX_WIDTHS, MPD_MAX_CHANNELS))
         need("Negative_Slope", lambda v: 0 <= float(v) < 1, "in [0, 1)")
-    s = overlay_settings(block, MPD_DEFAULTS, MPD_KEY, "vocoder", rules)
+    s = overlay_settings(block, MPD_DEFAULTS, MPD_KEY, "vocoder", rules, also=(MSD_BLOCK,))
     s["Periods"], s["Channels"] = [int(p) for p in s["Periods"]], [int(c) for c in s["Channels"]]
+    if MSD_BLOCK in s:
+        s[MSD_BLOCK] = hifigan_msd_settings(hp)
+        if s[MSD_BLOCK] is None:
+            del s[MSD_BLOCK]
     return s
 
 
@@ -1843,19 +1850,20 @@ def hifigan_disc_backward(disc, fwd, dscores, freeze=False, inj=None, inj_scale=
 
 class _PeriodScore(torch.autograd.Function):
     """scores = HiFiGANPeriodDiscriminator.score(wav): forward and backward are the HIP launches of csrc/hifigan_disc_ops.hip.  `shared`: a forward that was
-    already run on this waveform with these parameters (`score_pair`) - no forward launch is made then.  freeze: no parameter gradients."""
+    already run on this waveform with these parameters (`score_pair`) - no forward launch is made then.  freeze: no parameter gradients.  The discriminator
+    names its forward and backward (`OPS`) and the key of its sub-networks in what the forward returns (`NETS`): the multi-scale discriminator shares this node."""
 
     @staticmethod
     def forward(ctx, disc, wav, freeze, shared, *params):
         if shared is None:
             disc._build_images({k: t.detach() for k, t in zip(disc.params, params)})
-            shared = hifigan_disc_forward(disc, wav.detach())
+            shared = disc.OPS[0](disc, wav.detach())
         ctx.disc, ctx.fwd, ctx.freeze, ctx.n = disc, shared, bool(freeze), len(params)
-        return tuple(per["scores"].clone() for per in shared["periods"])
+        return tuple(per["scores"].clone() for per in shared[disc.NETS])
 
     @staticmethod
     def backward(ctx, *dscores):
-        dwav, grads = hifigan_disc_backward(ctx.disc, ctx.fwd, dscores, ctx.freeze, need_dwav=ctx.needs_input_grad[1])
+        dwav, grads = ctx.disc.OPS[1](ctx.disc, ctx.fwd, dscores, ctx.freeze, need_dwav=ctx.needs_input_grad[1])
         ctx.fwd = None
         return (None, dwav, None, None) + (tuple(grads[k] for k in ctx.disc.params) if not ctx.freeze else (None,) * ctx.n)
 
@@ -1867,12 +1875,12 @@ class _FakeTerms(torch.autograd.Function):
     @staticmethod
     def forward(ctx, disc, fake, half, l_fm, inj):
         ctx.disc, ctx.fwd, ctx.inj = disc, half, inj
-        return tuple(per["scores"].clone() for per in half["periods"]) + (l_fm.reshape(()).clone(),)
+        return tuple(per["scores"].clone() for per in half[disc.NETS]) + (l_fm.reshape(()).clone(),)
 
     @staticmethod
     def backward(ctx, *g):
         scale = g[-1].to(torch.float32).reshape(1).contiguous()
-        dwav, _ = hifigan_disc_backward(ctx.disc, ctx.fwd, g[:-1], True, inj=ctx.inj, inj_scale=scale)
+        dwav, _ = ctx.disc.OPS[1](ctx.disc, ctx.fwd, g[:-1], True, inj=ctx.inj, inj_scale=scale)
         ctx.fwd = ctx.inj = None
         return None, dwav, None, None, None
 
@@ -1882,6 +1890,7 @@ class HiFiGANPeriodDiscriminator:
     `Vocoder.Train.Adversarial` (absent: the defaults).  `params` holds float32 device leaves in `hifigan_disc_expected_shapes`' names - from `state_dict`
     (`hifigan_disc_load`) or, without one, `hifigan_disc_init(geo, seed)`; the weight images are rebuilt from them at every call (an optimizer step writes
     the leaves in place).  A row's scores, feature maps and d wav are bit-identical alone, in any batch and from run to run."""
+    OPS, NETS = (hifigan_disc_forward, hifigan_disc_backward), "periods"
 
     def __init__(self, hp, device="cuda:0", state_dict=None, trainable=True, seed=0):
         self.geo = geo = hifigan_disc_geometry(hp)                  # before anything touches the device
@@ -1941,6 +1950,355 @@ class HiFiGANPeriodDiscriminator:
                                              for per in fwd["periods"]]}
         out = _FakeTerms.apply(self, fake.contiguous(), half, l_fm, inj)
         return list(_PeriodScore.apply(self, both, False, fwd, *self.params.values())), list(out[:-1]), out[-1], terms.detach()
+
+# ================================================================================================================================================
+# The HiFi-GAN multi-scale discriminator on the kernels of csrc/hifigan_msd_ops.hip (the dense last layer and conv_post: the multi-period discriminator's
+# kernels at period 1): forward, backward, feature matching, f32.  The network is written down in DESIGN.md ("The multi-scale discriminator"); it and the
+# checkpoint layout restate the most widely used implementation from memory and are UNPINNED, like the other vocoder contracts.  The block is the optional
+# `Vocoder.Train.Adversarial.Multi_Scale`; conv_post's 3 taps and the pool (4 taps, stride 2, padding 2) are constants of the architecture, not yaml keys.
+# ================================================================================================================================================
+MSD_KEY = MPD_KEY + "." + MSD_BLOCK
+MSD_DEFAULTS = {"Scales": 3, "Channels": [128, 128, 256, 512, 1024, 1024, 1024], "Groups": [1, 4, 16, 16, 16, 16, 1], "Strides": [1, 2, 2, 4, 4, 1, 1],
+                "Kernel_Sizes": [15, 41, 41, 41, 41, 41, 5]}
+MSD_PREFIX = "scale_discriminators."                                # of the multi-scale discriminator's names among the parameters of `HiFiGANDiscriminators`
+MSD_POST_TAPS, MSD_LAST_TAPS, MSD_FIRST_MAX_TAPS, MSD_MAX_TAPS, MSD_MAX_SCALES, MSD_MAX_CHANNELS, MSD_MAX_GROUP_IN = 3, 5, 15, 41, 4, 1024, 64
+MSD_MIN_LAYERS, MSD_MAX_LAYERS, MSD_STRIDES = 3, 8, (1, 2, 4)
+MSD_MIN_SAMPLES = 16            # the shortest waveform: one more than the first layer's 15 taps; at 4 scales its coarsest copy still has 3 samples
+
+
+def hifigan_msd_settings(hp):
+    """The optional yaml block `Vocoder.Train.Adversarial.Multi_Scale` over MSD_DEFAULTS (absent block: None; `{}`: the defaults), checked: a ValueError
+    names every unknown or bad key."""
+    adv = getattr(getattr(getattr(hp, "Vocoder", None), "Train", None), "Adversarial", None)
+    block = getattr(adv, MSD_BLOCK, None)
+    if block is None:
+        return None
+    whole = lambda v: int(v) == v
+    ints = lambda v: all(whole(x) for x in v)
+
+    def rules(s, need):
+        need("Scales", lambda v: whole(v) and 1 <= int(v) <= MSD_MAX_SCALES, f"an integer in [1, {MSD_MAX_SCALES}]")
+        need("Channels", lambda v: MSD_MIN_LAYERS <= len(v) <= MSD_MAX_LAYERS and all(whole(c) and 16 <= int(c) <= MSD_MAX_CHANNELS and int(c) % 16 == 0 for c in v),
+             f"{MSD_MIN_LAYERS} to {MSD_MAX_LAYERS} widths, each a multiple of 16 in [16, {MSD_MAX_CHANNELS}]")
+        n = len(s["Channels"]) if isinstance(s["Channels"], (list, tuple)) else -1
+        mid = lambda v: list(v)[1:-1]
+        need("Kernel_Sizes", lambda v: ints(v) and len(v) == n >= 1 and v[0] % 2 == 1 and 1 <= v[0] <= MSD_FIRST_MAX_TAPS and v[-1] == MSD_LAST_TAPS and
+             all(k % 2 == 1 and 1 <= k <= MSD_MAX_TAPS for k in mid(v)),
+             f"as many as Channels: the first odd and at most {MSD_FIRST_MAX_TAPS}, the last {MSD_LAST_TAPS}, the others odd and at most {MSD_MAX_TAPS}")
+        need("Strides", lambda v: ints(v) and len(v) == n >= 1 and v[0] == 1 and v[-1] == 1 and all(x in MSD_STRIDES for x in mid(v)),
+             "as many as Channels: the first and the last 1, the others 1, 2 or 4")
+
+        def groups(v):
+            ch = [int(c) for c in s["Channels"]]
+            if not (ints(v) and len(v) == n >= 1 and v[0] == 1 and v[-1] == 1):
+                return False
+            return all(g >= 1 and ch[j] % g == 0 and ch[j - 1] % g == 0 and (ch[j] // g) % 16 == 0 and (ch[j - 1] // g) % 4 == 0 and
+                       ch[j - 1] // g <= MSD_MAX_GROUP_IN for j, g in list(enumerate(v))[1:-1])
+        need("Groups", groups, "as many as Channels: the first and the last 1; for the others Channels[j] / Groups[j] a multiple of 16 and "
+             f"Channels[j - 1] / Groups[j] a multiple of 4, at most {MSD_MAX_GROUP_IN}")
+    s = overlay_settings(block, MSD_DEFAULTS, MSD_KEY, "vocoder", rules)
+    s["Scales"] = int(s["Scales"])
+    for k in ("Channels", "Groups", "Strides", "Kernel_Sizes"):
+        s[k] = [int(v) for v in s[k]]
+    return s
+
+
+def hifigan_msd_geometry(hp):
+    """The multi-scale discriminator's sizes as a dict (scales, channels, groups, strides, kernels, slope) from the block
+    `Vocoder.Train.Adversarial.Multi_Scale` (absent: the defaults) and `Negative_Slope` of the block around it; raises ValueError naming the offending yaml
+    keys (`hifigan_disc_settings`)."""
+    adv = hifigan_disc_settings(hp) or MPD_DEFAULTS
+    s = adv.get(MSD_BLOCK) or MSD_DEFAULTS
+    return {"scales": int(s["Scales"]), "channels": list(s["Channels"]), "groups": list(s["Groups"]), "strides": list(s["Strides"]),
+            "kernels": list(s["Kernel_Sizes"]), "slope": float(adv["Negative_Slope"])}
+
+
+def hifigan_msd_rows(geo, T):
+    """Per scale the rows of its waveform and of every layer's output: [[T_i, L_1, ..., L_n]] with T_0 = T, T_{i+1} = T_i // 2 + 1 (the pool) and
+    L' = (L - 1) // stride + 1 (conv_post keeps L_n).  T below MSD_MIN_SAMPLES raises a ValueError naming the key."""
+    if T < MSD_MIN_SAMPLES:
+        raise ValueError(f"{MSD_KEY}: a waveform of {T} samples is shorter than the {MSD_MIN_SAMPLES} samples the multi-scale discriminator supports")
+    rows = []
+    for _ in range(geo["scales"]):
+        L = [T]
+        for s in geo["strides"]:
+            L.append((L[-1] - 1) // s + 1)
+        rows.append(L)
+        T = T // 2 + 1
+    return rows
+
+
+def hifigan_msd_expected_shapes(geo):
+    """state-dict key -> shape of the multi-scale discriminator with the sizes `geo` (Conv1d weights [Cout, Cin / groups, k])"""
+    e = {}
+    for i in range(geo["scales"]):
+        cin = 1
+        for j, (c, g, k) in enumerate(zip(geo["channels"], geo["groups"], geo["kernels"])):
+            e[f"discriminators.{i}.convs.{j}.weight"], e[f"discriminators.{i}.convs.{j}.bias"] = (c, cin // g, k), (c,)
+            cin = c
+        e[f"discriminators.{i}.conv_post.weight"], e[f"discriminators.{i}.conv_post.bias"] = (1, cin, MSD_POST_TAPS), (1,)
+    return e
+
+
+def hifigan_msd_init(geo, seed=0):
+    """A fresh multi-scale discriminator's state dict: torch's default rule per tensor (`conv_default_init`, fan_in = (Cin / groups) k)."""
+    return conv_default_init(hifigan_msd_expected_shapes(geo), seed)
+
+
+def hifigan_msd_find_state_dict(obj):
+    """The multi-scale discriminator's state dict inside what torch.load returned: at the top level, under `scale_discriminator` / `msd`, or inside `model`.
+    It is told by its 3-d Conv1d weights: the multi-period discriminator's state dict has the same names with 4-d Conv2d weights and is not taken for it."""
+    names = ("scale_discriminator", "msd")
+
+    def mine(d):
+        first = [v for k, v in d.items() if str(k).startswith("discriminators.0.convs.0.weight") and torch.is_tensor(v)]
+        return bool(first) and any(v.dim() == 3 for v in first) and not any(v.dim() == 4 for v in first)
+    return find_state_dict(obj, ((),) + tuple((n,) for n in names) + (("model",),) + tuple(("model", n) for n in names), mine,
+                           "no HiFi-GAN multi-scale discriminator state dict found (looked for a 3-d `discriminators.0.convs.0.weight*` at the top level, under "
+                           "scale_discriminator / msd and inside model)")
+
+
+def hifigan_msd_load(obj, geo):
+    """-> {key: float32 host tensor} with exactly the keys of `hifigan_msd_expected_shapes` (`checked_load`: weight-norm pairs are folded once).  A
+    spectral-norm triple (`weight_orig`, `weight_u`, `weight_v`) is refused by name: that parametrisation is out of scope."""
+    found = hifigan_msd_find_state_dict(obj)
+    spectral = sorted(k for k in found if str(k).endswith(".weight_orig"))
+    if spectral:
+        raise ValueError(f"multi-scale discriminator checkpoint: {spectral[0]} is a spectral-norm parametrisation, which this project does not load "
+                         "(fold it into a plain `weight` first)")
+    return checked_load(found, hifigan_msd_expected_shapes(geo), "multi-scale discriminator", "multi-scale discriminator", MSD_KEY)
+
+
+def hifigan_msd_forward(disc, wav, alloc=None):
+    """The forward launches on wav [B, T] (fp32, contiguous, on the device) -> dict(wav, scales: per scale dict(i, L, x, keep, scores)).  x [B, L[0]] is the
+    scale's waveform (scale i: i pools), keep[j] [B, L[j + 1], C_j] layer j's PRE-activation output, scores [B, L[-1]] conv_post's.  alloc(*shape): the
+    caller's buffers (tests)."""
+    g, lib, P, st = disc.geo, _lib.api(), _lib.ptr, _lib.stream()
+    B, T = wav.shape
+    ch, groups, strides, ks, slope, n = g["channels"], g["groups"], g["strides"], g["kernels"], g["slope"], len(g["channels"])
+    f = alloc or (lambda *shape: torch.empty(*shape, dtype=torch.float32, device=wav.device))
+    out, x = [], wav
+    for i, (L, im) in enumerate(zip(hifigan_msd_rows(g, T), disc.images)):
+        if i:
+            y = f(B, L[0])
+            lib.glowtts_hifigan_msd_pool(P(x), P(y), B, x.shape[1], st)
+            x = y
+        keep = [f(B, L[j + 1], c) for j, c in enumerate(ch)]
+        scores = f(B, L[-1])
+        lib.glowtts_hifigan_msd_first(P(x), P(im["first"][0]), P(im["first"][1]), P(keep[0]), B, L[0], ks[0], ch[0], st)
+        for j in range(1, n - 1):
+            w, b, _ = im["convs"][j - 1]
+            lib.glowtts_hifigan_msd_conv(P(keep[j - 1]), P(w), P(b), P(keep[j]), B, L[j], ks[j], strides[j], groups[j], ch[j - 1], ch[j], slope, st)
+        w, b, _ = im["last"]
+        lib.glowtts_hifigan_msd_dense(P(keep[n - 2]), P(w), P(b), P(keep[n - 1]), B, L[n - 1], ch[n - 2], ch[n - 1], slope, st)
+        lib.glowtts_hifigan_msd_post(P(keep[-1]), P(im["post"][0]), P(im["post"][1]), P(scores), B, L[-1], ch[-1], slope, st)
+        out.append({"i": i, "L": L, "x": x, "keep": keep, "scores": scores})
+    return {"wav": wav, "scales": out, "images": disc.images}       # the images this forward ran with: its backward must not see a later rebuild
+
+
+def hifigan_msd_feature_maps(disc, scale_fwd):
+    """The feature maps of one scale of `hifigan_msd_forward` in torch's layout: the activated outputs [B, C_j, L], then conv_post's [B, 1, L]."""
+    return [torch.nn.functional.leaky_relu(k, disc.geo["slope"]).permute(0, 2, 1) for k in scale_fwd["keep"]] + [scale_fwd["scores"][:, None, :]]
+
+
+def hifigan_msd_work(disc, B, T, device, alloc=None):
+    """The work buffer of the backward and of the feature-matching loss on a batch of B x T: the largest layer's `glowtts_hifigan_msd_work_floats` (the
+    dense layers: `glowtts_hifigan_disc_work_floats`)."""
+    g, lib = disc.geo, _lib.api()
+    ch, n, floats = g["channels"], len(g["channels"]), 0
+    for L in hifigan_msd_rows(g, T):
+        cin = 1
+        for j in range(n - 1):
+            floats, cin = max(floats, lib.glowtts_hifigan_msd_work_floats(B, L[j + 1], cin, ch[j], g["kernels"][j], g["groups"][j])), ch[j]
+        floats = max(floats, lib.glowtts_hifigan_disc_work_floats(B, L[n], cin, ch[-1], MSD_LAST_TAPS), lib.glowtts_hifigan_disc_work_floats(B, L[n], ch[-1], 1, MSD_POST_TAPS))
+    f = alloc or (lambda *shape: torch.empty(*shape, dtype=torch.float32, device=device))
+    return f(floats)
+
+
+def hifigan_msd_feature_matching(disc, fwd, alloc=None):
+    """The feature-matching terms of a forward over [real; fake] (2 B rows) -> (terms [scales, layers + 1], l_fm [1], inj), as `hifigan_disc_feature_matching`
+    gives them for the periods: `glowtts_hifigan_disc_fm` per map, added up by the kernels in launch order (scale, then map)."""
+    g, lib, P, st = disc.geo, _lib.api(), _lib.ptr, _lib.stream()
+    B2, T = fwd["wav"].shape
+    B, dev = B2 // 2, fwd["wav"].device
+    f = alloc or (lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev))
+    work, terms, total, inj = hifigan_msd_work(disc, B, T, dev, alloc), f(g["scales"], len(g["channels"]) + 1), f(1), []
+    for i, sc in enumerate(fwd["scales"]):
+        maps = [(k, g["slope"]) for k in sc["keep"]] + [(sc["scores"], 1.0)]
+        inj.append([f(B, *k.shape[1:]) for k, _ in maps])
+        for j, (k, slope) in enumerate(maps):
+            lib.glowtts_hifigan_disc_fm(P(k), P(inj[i][j]), P(work), P(terms[i, j:]), P(total), k.numel() // 2, slope, 1 if i or j else 0, st)
+    return terms, total, inj
+
+
+def hifigan_msd_backward(disc, fwd, dscores, freeze=False, inj=None, inj_scale=None, need_dwav=True, alloc=None):
+    """d scores (one [B, L_last] per scale) -> (d wav [B, T], or None unless `need_dwav`; {name: gradient in torch's layout} or None when `freeze`) from what
+    `hifigan_msd_forward` kept (or the views of some of its batch rows).  d wav: every scale's d of its own waveform, then from the coarsest scale down each is
+    sent through the pool's gradient and added to the next finer one.  inj (`hifigan_msd_feature_matching`) times the device scalar inj_scale is added to
+    every d pre and to d scores on the way down.  freeze: the data chain alone, no weight-gradient launch."""
+    g, lib, P, st = disc.geo, _lib.api(), _lib.ptr, _lib.stream()
+    wav = fwd["wav"]
+    B, T = wav.shape
+    ch, groups, strides, ks, slope, dev, n = g["channels"], g["groups"], g["strides"], g["kernels"], g["slope"], wav.device, len(g["channels"])
+    f = alloc or (lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev))
+    grads = work = None
+    if not freeze:
+        grads, work = {k: f(*shape) for k, shape in hifigan_msd_expected_shapes(g).items()}, hifigan_msd_work(disc, B, T, dev, alloc)
+    scale = P(inj_scale) if inj is not None else None
+    opt = lambda t: P(t) if t is not None else None
+    dxs = []
+    for i, (sc, im, ds) in enumerate(zip(fwd["scales"], fwd["images"], dscores)):
+        L, keep, q = sc["L"], sc["keep"], f"discriminators.{i}."
+        ds, ij = ds.to(torch.float32).contiguous(), inj[i] if inj is not None else [None] * (n + 1)
+        gw = lambda name: (P(grads[q + name + ".weight"]), P(grads[q + name + ".bias"]))
+        d = f(B, L[n], ch[-1])
+        lib.glowtts_hifigan_msd_post_bwd(P(ds), opt(ij[n]), P(keep[-1]), P(im["post"][0]), opt(ij[n - 1]), scale, P(d), B, L[n], ch[-1], slope, st)
+        if not freeze:
+            lib.glowtts_hifigan_msd_dense_wgrad(P(keep[-1]), P(ds), P(work), *gw("conv_post"), B, L[n], ch[-1], 1, MSD_POST_TAPS, slope, st)
+            lib.glowtts_hifigan_msd_dense_wgrad(P(keep[n - 2]), P(d), P(work), *gw(f"convs.{n - 1}"), B, L[n - 1], ch[n - 2], ch[n - 1], MSD_LAST_TAPS, slope, st)
+        dx = f(B, L[n - 1], ch[n - 2])
+        lib.glowtts_hifigan_msd_dense_bwd(P(d), P(im["last"][2]), P(keep[n - 2]), opt(ij[n - 2]), scale, P(dx), B, L[n - 1], ch[n - 2], ch[n - 1], slope, st)
+        d = dx
+        for j in reversed(range(1, n - 1)):
+            if not freeze:
+                lib.glowtts_hifigan_msd_wgrad(P(keep[j - 1]), P(d), P(work), *gw(f"convs.{j}"), B, L[j], ks[j], strides[j], groups[j], ch[j - 1], ch[j], slope, st)
+            dx = f(B, L[j], ch[j - 1])
+            lib.glowtts_hifigan_msd_conv_bwd(P(d), P(im["convs"][j - 1][2]), P(keep[j - 1]), opt(ij[j - 1]), scale, P(dx), B, L[j], ks[j], strides[j], groups[j],
+                                             ch[j - 1], ch[j], slope, st)
+            d = dx
+        if not freeze:
+            lib.glowtts_hifigan_msd_first_wgrad(P(sc["x"]), P(d), P(work), *gw("convs.0"), B, L[0], ks[0], ch[0], st)
+        if need_dwav:
+            dxs.append(f(B, L[0]))
+            lib.glowtts_hifigan_msd_first_bwd(P(d), P(im["first"][0]), P(dxs[-1]), B, L[0], ks[0], ch[0], 0, st)
+    if not need_dwav:
+        return None, grads
+    for i in reversed(range(1, len(dxs))):                          # the scales add up through the pools, from the coarsest to the finest
+        lib.glowtts_hifigan_msd_pool_bwd(P(dxs[i]), P(dxs[i - 1]), B, dxs[i - 1].shape[1], 1, st)
+    return dxs[0], grads
+
+
+class HiFiGANScaleDiscriminator:
+    """HiFiGANScaleDiscriminator(hp, device, state_dict=None, trainable=True, seed=0): the multi-scale discriminator.  The sizes come from the yaml block
+    `Vocoder.Train.Adversarial.Multi_Scale` (absent: the defaults).  `params` holds float32 device leaves in `hifigan_msd_expected_shapes`' names - from
+    `state_dict` (`hifigan_msd_load`) or, without one, `hifigan_msd_init(geo, seed)`; the weight images are rebuilt from them at every call.  A row's scores,
+    feature maps and d wav are bit-identical alone, in any batch and from run to run."""
+    OPS, NETS = (hifigan_msd_forward, hifigan_msd_backward), "scales"
+
+    def __init__(self, hp, device="cuda:0", state_dict=None, trainable=True, seed=0):
+        self.geo = geo = hifigan_msd_geometry(hp)                   # before anything touches the device
+        self.trainable = bool(trainable)
+        w = hifigan_msd_load(state_dict, geo) if state_dict is not None else hifigan_msd_init(geo, seed)
+        lib, widths = _lib.api(), [1] + geo["channels"] + [1]
+        layers = zip(widths, widths[1:], geo["kernels"] + [MSD_POST_TAPS], geo["strides"] + [1], geo["groups"] + [1])
+        if not all(lib.glowtts_hifigan_msd_supported(*layer) for layer in layers):
+            raise ValueError(f"the {MSD_KEY} block's sizes {geo} are not supported by the kernels")
+        self.device = torch.device(device)
+        self.params = {k: t.to(self.device).requires_grad_(self.trainable) for k, t in w.items()}
+        self._build_images({k: t.detach() for k, t in self.params.items()})
+
+    def _build_images(self, w):
+        """Per scale the weight images in the kernels' layouts: first [k][C0] and post [3][C] (row = tap); a grouped layer's forward image
+        [groups][k Cin_g][Cout_g] (row = tap Cin_g + input channel of the group) and its backward image [groups][k][Cout_g][Cin_g rounded up to 16, the
+        new columns zero]; the dense last layer's [5 Cin][Cout] and [5 Cout][Cin]."""
+        dev, g = (lambda t: t.contiguous().to(self.device)), self.geo
+        n = len(g["channels"])
+        self.images = []
+        for i in range(g["scales"]):
+            q = f"discriminators.{i}."
+            convs = []
+            for j in range(1, n - 1):
+                wj, G = w[f"{q}convs.{j}.weight"], g["groups"][j]
+                v = wj.reshape(G, wj.shape[0] // G, wj.shape[1], wj.shape[2])                      # [G, Cout_g, Cin_g, k]
+                back = torch.nn.functional.pad(v.permute(0, 3, 1, 2), (0, -wj.shape[1] % 16))
+                convs.append((dev(v.permute(0, 3, 2, 1).reshape(G, -1, v.shape[1])), dev(w[f"{q}convs.{j}.bias"]), dev(back)))
+            last = w[f"{q}convs.{n - 1}.weight"]
+            self.images.append({"first": (dev(w[f"{q}convs.0.weight"][:, 0, :].t()), dev(w[f"{q}convs.0.bias"])), "convs": convs,
+                                "last": (dev(last.permute(2, 1, 0).reshape(-1, last.shape[0])), dev(w[f"{q}convs.{n - 1}.bias"]),
+                                         dev(last.permute(2, 0, 1).reshape(-1, last.shape[1]))),
+                                "post": (dev(w[f"{q}conv_post.weight"][0].t()), dev(w[f"{q}conv_post.bias"]))})
+
+    def _check(self, wav):
+        if wav.dim() != 2 or wav.dtype != torch.float32 or not wav.is_cuda:
+            raise _lib.GlowTTSHipError("HiFiGANScaleDiscriminator: expected an fp32 device tensor [B, T] (the HIP path has no CPU fallback), got "
+                                       f"{list(wav.shape)} {wav.dtype}")
+        B, T = wav.shape
+        hifigan_msd_rows(self.geo, T)
+        if B < 1 or B > 65535 or B * T > 2 ** 30:
+            raise ValueError(f"HiFiGANScaleDiscriminator: a batch of {B} x {T} samples is outside 1 <= B <= 65535, B T <= 2^30")
+
+    def score(self, wav, freeze=False):
+        """wav [B, T] -> a list of scores [B, L_last], one per scale, with a backward: d wav summed over the scales and, unless `freeze`, the parameter
+        gradients."""
+        self._check(wav)
+        return list(_PeriodScore.apply(self, wav.contiguous(), freeze, None, *self.params.values()))
+
+    def score_pair(self, real, fake):
+        """`HiFiGANPeriodDiscriminator.score_pair` for the scales: ONE forward over [real; fake] (2 B rows) -> (both: scores [2 B, L_last] per scale whose
+        backward yields the parameter gradients alone; p_fake: the fake rows' scores per scale, and l_fm: the 0-d sum over scales and maps of
+        mean |lrelu(real map) - lrelu(fake map)| - their backward is ONE frozen data chain per scale over the fake rows, with no weight-gradient launch;
+        fm_terms [scales, layers + 1])."""
+        self._check(fake)
+        if tuple(real.shape) != tuple(fake.shape):
+            raise ValueError(f"HiFiGANScaleDiscriminator.score_pair: real {list(real.shape)} and fake {list(fake.shape)} differ in shape")
+        B = fake.shape[0]
+        both = torch.cat([real.detach().to(device=self.device, dtype=torch.float32), fake.detach()]).contiguous()
+        self._check(both)
+        self._build_images({k: t.detach() for k, t in self.params.items()})
+        fwd = hifigan_msd_forward(self, both)
+        terms, l_fm, inj = hifigan_msd_feature_matching(self, fwd)
+        half = {"wav": both[B:], "images": fwd["images"], "scales": [{"i": sc["i"], "L": sc["L"], "x": sc["x"][B:], "keep": [k[B:] for k in sc["keep"]],
+                                                                     "scores": sc["scores"][B:]} for sc in fwd["scales"]]}
+        out = _FakeTerms.apply(self, fake.contiguous(), half, l_fm, inj)
+        return list(_PeriodScore.apply(self, both, False, fwd, *self.params.values())), list(out[:-1]), out[-1], terms.detach()
+
+
+def hifigan_discs_split(sd):
+    """The parameters of `HiFiGANDiscriminators` -> (the multi-period discriminator's, the multi-scale discriminator's under its own names)"""
+    return ({k: v for k, v in sd.items() if not str(k).startswith(MSD_PREFIX)}, {str(k)[len(MSD_PREFIX):]: v for k, v in sd.items() if str(k).startswith(MSD_PREFIX)})
+
+
+def hifigan_discs_load(obj, geo):
+    """-> {key: float32 host tensor} of both discriminators (geo: dict(periods, scales) of their sizes) from the union `HiFiGANDiscriminators.params` names:
+    found at the top level, under `discriminator` or inside `model`; each half goes through its own loader's checks.  A union without the scales' names
+    raises a ValueError naming the first of them."""
+    found = find_state_dict(obj, ((), ("discriminator",), ("model",), ("model", "discriminator")),
+                            lambda d: any(str(k).startswith("discriminators.0.convs.0.weight") for k in d),
+                            "no HiFi-GAN discriminator state dict found (looked for `discriminators.0.convs.0.weight*` at the top level, under discriminator and "
+                            "inside model)")
+    mpd, msd = hifigan_discs_split(found)
+    if not msd:
+        raise ValueError(f"discriminator checkpoint: missing key {MSD_PREFIX}discriminators.0.convs.0.weight (it was written without the block {MSD_KEY})")
+    out = hifigan_disc_load(mpd, geo["periods"])
+    out.update({MSD_PREFIX + k: v for k, v in hifigan_msd_load(msd, geo["scales"]).items()})
+    return out
+
+
+class HiFiGANDiscriminators:
+    """HiFiGANDiscriminators(hp, device, state_dict=None, trainable=True, seed=0): the multi-period and the multi-scale discriminator as the ONE discriminator
+    of the adversarial stage.  `params`: the multi-period discriminator's names unchanged, then the multi-scale discriminator's under `scale_discriminators.`.
+    state_dict: what `hifigan_discs_load` reads."""
+
+    def __init__(self, hp, device="cuda:0", state_dict=None, trainable=True, seed=0):
+        self.geo = {"periods": hifigan_disc_geometry(hp), "scales": hifigan_msd_geometry(hp)}                  # before anything touches the device
+        mpd = msd = None
+        if state_dict is not None:
+            mpd, msd = hifigan_discs_split(hifigan_discs_load(state_dict, self.geo))
+        self.periods = HiFiGANPeriodDiscriminator(hp, device, mpd, trainable, seed)
+        self.scales = HiFiGANScaleDiscriminator(hp, device, msd, trainable, seed)
+        self.device, self.trainable = self.periods.device, bool(trainable)
+        self.params = dict(self.periods.params)
+        self.params.update({MSD_PREFIX + k: t for k, t in self.scales.params.items()})
+
+    def score(self, wav, freeze=False):
+        """-> the periods' scores, then the scales'"""
+        return self.periods.score(wav, freeze) + self.scales.score(wav, freeze)
+
+    def score_pair(self, real, fake):
+        """-> (both, p_fake: the periods' lists with the scales' appended; l_fm: the periods' sum + the scales' sum; the periods' terms; the scales' terms)"""
+        both, p_fake, l_fm, terms = self.periods.score_pair(real, fake)
+        both_s, p_fake_s, l_fm_s, terms_s = self.scales.score_pair(real, fake)
+        return both + both_s, p_fake + p_fake_s, l_fm + l_fm_s, terms, terms_s
 
 
 VOCODER_KINDS = ("griffin_lim", "pwg", "hifigan")

@@ -1236,6 +1236,63 @@ int glowtts_hifigan_disc_first_bwd(const float *dpre, const float *w, float *dwa
 int glowtts_hifigan_disc_wgrad(const float *x, const float *dy, float *work, float *dw, float *dbias, int B, int H, int period, int stride, int Cin, int Cout,
                                int taps, int wav_samples, float slope, void *stream);
 
+/* ---- The HiFi-GAN multi-scale discriminator (csrc/hifigan_msd_ops.hip, the dense layers in csrc/hifigan_disc_ops.hip; f32; additions, the ABI version stays) ----
+ * One sub-network per scale: scale 0 sees wav [B][T], scale i the waveform after i average pools (4 taps, stride 2, zero padding 2, always divided by 4:
+ * T' = T / 2 + 1).  A sub-network is a stack of Conv1d over time with zero padding taps / 2 and L' = (L - 1) / stride + 1: a first layer 1 -> C0 (stride 1), grouped
+ * strided middle layers, a dense last layer (5 taps, stride 1) and conv_post (3 taps, width -> 1).  Activations are channels-last [B][L][C] and hold
+ * PRE-activations: the LeakyReLU is the consumer's prologue and the backward recomputes its mask (1 where pre > 0, the slope elsewhere).  Every batch row is of
+ * the full length; a row's result does not depend on the batch around it and nothing beyond the B L rows is read or written.  Matrix products:
+ * v_mfma_f32_16x16x4_f32.  No float atomics, fixed partitions and orders: bit-identical from run to run.  None of these functions allocates.  The feature-matching
+ * loss of a map is glowtts_hifigan_disc_fm, which knows no layout.
+ * Supported (glowtts_hifigan_msd_supported(Cin, Cout, taps, stride, groups), else GLOWTTS_E_ARG): widths multiples of 16 in [16, 1024]; Cin = 1 (the first
+ * layer): odd taps <= 15, stride 1, groups 1; Cout = 1 (conv_post): 3 taps, stride 1, groups 1; the dense layer: 5 taps, stride 1, groups 1; a grouped layer: odd
+ * taps <= 41, stride 1, 2 or 4, Cout / groups a multiple of 16, Cin / groups a multiple of 4 and at most 64.  1 <= B <= 65535, B L <= 2^30.
+ *   work   glowtts_hifigan_msd_work_floats(B, rows_out, Cin, Cout, taps, groups) floats, 8-byte aligned: the weight gradient's splits of a first or grouped
+ *          layer with rows_out output rows per batch row, and at least the block sums of glowtts_hifigan_disc_fm on that layer's output (the dense layers:
+ *          glowtts_hifigan_disc_work_floats).
+ * glowtts_hifigan_msd_pool         `hifigan_msd_pool`: x [B][T] -> y [B][T / 2 + 1], y[j] = (x[2 j - 2] + .. + x[2 j + 1]) / 4, zero outside [0, T).
+ * glowtts_hifigan_msd_pool_bwd     `hifigan_msd_pool_bwd`: dy [B][T / 2 + 1] -> dx [B][T], a gather over the at most 2 outputs that read a sample; accumulate 1:
+ *                                  added to what dx holds.
+ * glowtts_hifigan_msd_first        `hifigan_msd_first`: wav [B][T] -> out [B][T][C]; w [taps][C] (row = tap), bias [C].
+ * glowtts_hifigan_msd_conv         `hifigan_msd_conv`: x [B][L][Cin] -> out [B][L'][Cout] = bias + grouped conv(lrelu(x, slope)); w [groups][taps Cin_g][Cout_g]:
+ *                                  row = tap Cin_g + input channel of the group.
+ * glowtts_hifigan_msd_dense        `hifigan_msd_dense`: x [B][L][Cin] -> out [B][L][Cout], 5 taps; w [5 Cin][Cout] (glowtts_hifigan_disc_conv at period 1).
+ * glowtts_hifigan_msd_post         `hifigan_msd_post`: x [B][L][C] -> scores [B][L] = bias + conv(lrelu(x, slope)); w [3][C] (row = tap), bias [1].
+ * glowtts_hifigan_msd_post_bwd     `hifigan_msd_post_bwd`: glowtts_hifigan_disc_post_bwd at period 1.
+ * glowtts_hifigan_msd_dense_bwd    `hifigan_msd_dense_bwd`: dy [B][L][Cout], x [B][L][Cin] (kept) -> dx [B][L][Cin] = lrelu'(x) times the transposed convolution of
+ *                                  dy, + inj *inj_scale; wt [5 Cout][Cin]: row = tap Cout + output channel.
+ * glowtts_hifigan_msd_conv_bwd     `hifigan_msd_conv_bwd`: dy [B][L'][Cout], x [B][L][Cin] (kept) -> dx [B][L][Cin], the transposed convolution in polyphase form
+ *                                  (input row n takes only the taps m with (n + taps / 2 - m) % stride == 0), times lrelu'(x), + inj *inj_scale (inj [B][L][Cin]
+ *                                  or NULL; inj_scale: ONE float on the device); wt [groups][taps][Cout_g][Cin_g rounded up to 16]: the columns from Cin_g on zero.
+ * glowtts_hifigan_msd_first_bwd    `hifigan_msd_first_bwd`: dpre [B][T][C] of the first layer -> dwav [B][T]; accumulate 1: added to what dwav holds.
+ * glowtts_hifigan_msd_wgrad        `hifigan_msd_wgrad` + `hifigan_msd_wgrad_sum` for ONE grouped layer with L input rows: x its input (lrelu(x, slope) is formed
+ *                                  on the way in), dy [B][L'][Cout] -> dw [Cout][Cin_g][taps], dbias [Cout] in torch's layouts; overwritten.  One split per batch
+ *                                  row and 1024 output rows, added in ascending order.
+ * glowtts_hifigan_msd_first_wgrad  `hifigan_msd_first_wgrad` + `hifigan_msd_first_wgrad_sum`: wav [B][T], dy [B][T][C] -> dw [C][1][taps], dbias [C].
+ * glowtts_hifigan_msd_dense_wgrad  `hifigan_msd_dense_wgrad` + `hifigan_msd_dense_wgrad_sum` (glowtts_hifigan_disc_wgrad at period 1): the dense layer (taps 5) or
+ *                                  conv_post (taps 3, Cout 1, dy = d scores [B][L]); work: glowtts_hifigan_disc_work_floats. */
+int glowtts_hifigan_msd_supported(int Cin, int Cout, int taps, int stride, int groups);
+int64_t glowtts_hifigan_msd_work_floats(int B, int rows_out, int Cin, int Cout, int taps, int groups);
+int glowtts_hifigan_msd_pool(const float *x, float *y, int B, int T, void *stream);
+int glowtts_hifigan_msd_pool_bwd(const float *dy, float *dx, int B, int T, int accumulate, void *stream);
+int glowtts_hifigan_msd_first(const float *wav, const float *w, const float *bias, float *out, int B, int T, int taps, int C, void *stream);
+int glowtts_hifigan_msd_conv(const float *x, const float *w, const float *bias, float *out, int B, int L, int taps, int stride, int groups, int Cin, int Cout,
+                             float slope, void *stream);
+int glowtts_hifigan_msd_dense(const float *x, const float *w, const float *bias, float *out, int B, int L, int Cin, int Cout, float slope, void *stream);
+int glowtts_hifigan_msd_post(const float *x, const float *w, const float *bias, float *scores, int B, int L, int C, float slope, void *stream);
+int glowtts_hifigan_msd_post_bwd(const float *dscores, const float *dscores2, const float *x, const float *w, const float *inj, const float *inj_scale, float *dx,
+                                 int B, int L, int C, float slope, void *stream);
+int glowtts_hifigan_msd_dense_bwd(const float *dy, const float *wt, const float *x, const float *inj, const float *inj_scale, float *dx, int B, int L, int Cin,
+                                  int Cout, float slope, void *stream);
+int glowtts_hifigan_msd_conv_bwd(const float *dy, const float *wt, const float *x, const float *inj, const float *inj_scale, float *dx, int B, int L, int taps,
+                                 int stride, int groups, int Cin, int Cout, float slope, void *stream);
+int glowtts_hifigan_msd_first_bwd(const float *dpre, const float *w, float *dwav, int B, int T, int taps, int C, int accumulate, void *stream);
+int glowtts_hifigan_msd_wgrad(const float *x, const float *dy, float *work, float *dw, float *dbias, int B, int L, int taps, int stride, int groups, int Cin,
+                              int Cout, float slope, void *stream);
+int glowtts_hifigan_msd_first_wgrad(const float *wav, const float *dy, float *work, float *dw, float *dbias, int B, int T, int taps, int C, void *stream);
+int glowtts_hifigan_msd_dense_wgrad(const float *x, const float *dy, float *work, float *dw, float *dbias, int B, int L, int Cin, int Cout, int taps, float slope,
+                                    void *stream);
+
 /* ---- Objective evaluation: mel cepstra and dynamic time warping (csrc/eval_ops.hip; f32; additions, the ABI version stays) ----
  * glowtts_mel_cepstrum   `eval_mel_cepstrum`: mels in this project's normalisation m = 2A (db + 100) / 100 - A (A = max_abs; values at the clip +- A taken
  *   as they are), read through the element strides (stride_b, stride_t, stride_m) - [B][T][Mel] or the models' [B][Mel][T] - with lengths [B] int64 (device)
