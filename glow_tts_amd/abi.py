@@ -276,6 +276,9 @@ SIGNATURES = {
     "glowtts_hifigan_conv": (I, [P] * 6 + [I] * 7 + [F, I, F, I, P]),
     "glowtts_hifigan_upsample": (I, [P] * 5 + [I] * 7 + [F, P]),
     "glowtts_hifigan_post": (I, [P] * 5 + [I] * 5 + [F, P]),
+    "glowtts_hifigan_supported_f16": (I, [I] * 5),
+    "glowtts_hifigan_conv_f16": (I, [P] * 6 + [I] * 7 + [F, I, F, I, P]),
+    "glowtts_hifigan_upsample_f16": (I, [P] * 5 + [I] * 7 + [F, P]),
     "glowtts_hifigan_train_supported": (I, [I] * 5),
     "glowtts_hifigan_wgrad_work_floats": (L, [I] * 7),
     "glowtts_hifigan_conv_bwd": (I, [P] * 6 + [I] * 7 + [F, F, F, I, P]),
@@ -368,7 +371,7 @@ SIGNATURES = {
 VALUE_RETURNING = frozenset({
     "glowtts_abi_version", "glowtts_opt_chunk",
     "glowtts_cond_linear_supported", "glowtts_gst_supported", "glowtts_conv3x3s2_supported", "glowtts_dur_proj_supported", "glowtts_vocoder_supported",
-    "glowtts_pwg_supported", "glowtts_pwg_supported_bf16", "glowtts_hifigan_supported", "glowtts_hifigan_train_supported", "glowtts_ge2e_supported", "glowtts_pwg_train_supported", "glowtts_stft_loss_supported",
+    "glowtts_pwg_supported", "glowtts_pwg_supported_bf16", "glowtts_hifigan_supported", "glowtts_hifigan_supported_f16", "glowtts_hifigan_train_supported", "glowtts_ge2e_supported", "glowtts_pwg_train_supported", "glowtts_stft_loss_supported",
     "glowtts_mel_loss_supported",
     "glowtts_pwg_disc_supported", "glowtts_hifigan_disc_supported", "glowtts_hifigan_msd_supported", "glowtts_mel_cepstrum_supported", "glowtts_dtw_supported", "glowtts_tsne_supported",
 })

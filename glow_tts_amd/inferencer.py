@@ -36,8 +36,9 @@ class Inferencer:
         vocoder: 'pwg' or 'hifigan' (the neural vocoders), 'griffin_lim' (forces the baseline) or None: 'hifigan' when the yaml's `Vocoder` block has
         `Type: 'HiFiGAN'`, 'pwg' for any other `Vocoder` block or when `vocoder_checkpoint` (overrides `Vocoder.Checkpoint_Path`) is given, Griffin-Lim
         otherwise (`vocoder.vocoder_kind`; `vocoder.make_vocoder` builds it).
-        vocoder_precision: 'f32', 'bf16' or None (the yaml's `Vocoder.Precision`, default 'f32') - the Parallel WaveGAN's layer arithmetic
-        (`vocoder.ParallelWaveGAN`); the HiFi-GAN generator is f32 only and refuses 'bf16'; Griffin-Lim ignores it.
+        vocoder_precision: 'f32', 'bf16', 'f16' or None (the yaml's `Vocoder.Precision`, default 'f32') - 'bf16' is the Parallel WaveGAN's layer arithmetic
+        (`vocoder.ParallelWaveGAN`), 'f16' the HiFi-GAN generator's convolution arithmetic (`vocoder.HiFiGAN`); each generator refuses the other's mode
+        naming `Vocoder.Precision`; Griffin-Lim ignores it.
         speaker_encoder: GE2E mode only - a callable mapping a slice stack [B * Samples, Mel, Slice] to unit d-vectors [B, Embedding_Size].  None: the
         `speaker_encoder.GE2E` of `Speaker_Embedding.GE2E.Checkpoint_Path`, else the one the GlowTTS checkpoint carries under `layer_Dict.GE2E.*` (keys of
         another layout: a warning, and they are dropped), else none - then only ready d-vectors can be given."""
@@ -45,8 +46,8 @@ class Inferencer:
         from .vocoder import vocoder_kind
         self.vocoder_kind = vocoder_kind(self.hp, vocoder, vocoder_checkpoint)
         self.vocoder_checkpoint = vocoder_checkpoint
-        if vocoder_precision not in (None, "f32", "bf16"):
-            raise ValueError("vocoder_precision must be 'f32', 'bf16' or None, got {!r}".format(vocoder_precision))
+        if vocoder_precision not in (None, "f32", "bf16", "f16"):
+            raise ValueError("vocoder_precision must be 'f32', 'bf16', 'f16' or None, got {!r}".format(vocoder_precision))
         self.vocoder_precision = vocoder_precision
         self.device = torch.device(device)
         self.device_frontend, self._analyzer = bool(device_frontend), None
@@ -470,9 +471,10 @@ def build_parser():
                          "griffin_lim = the baseline; default: hifigan when the yaml's `Vocoder` block has Type: 'HiFiGAN', pwg for any other `Vocoder` block or when "
                          "--vocoder-checkpoint is given, else griffin_lim")
     ap.add_argument("--vocoder-checkpoint", default=None, metavar="PATH", help="generator checkpoint of the neural vocoder (overrides Vocoder.Checkpoint_Path of the yaml)")
-    ap.add_argument("--vocoder-precision", choices=["f32", "bf16"], default=None,
-                    help="arithmetic of the neural vocoder's layers (overrides Vocoder.Precision of the yaml; default f32): bf16 rounds the layers' operands, "
-                         "weights and gate to bf16 - faster, and with --seed its own reproducible wav, not the f32 one")
+    ap.add_argument("--vocoder-precision", choices=["f32", "bf16", "f16"], default=None,
+                    help="arithmetic of the neural vocoder's layers (overrides Vocoder.Precision of the yaml; default f32): bf16 (--vocoder pwg) rounds the layers' "
+                         "operands, weights and gate to bf16, f16 (--vocoder hifigan) the convolutions' rows and weights to fp16 - faster, and with --seed its own "
+                         "reproducible wav, not the f32 one")
     ap.add_argument("--vocode", default=None, metavar="LIST", help="vocode existing mels instead of synthesising: one label<TAB>mel.npy ([T, Mel]) per line")
     ap.add_argument("--device-frontend", action="store_true", help="analyse wav references / conversion sources on the device instead of the host")
     ap.add_argument("--seed", type=int, default=None, help="reproducible sampling: an utterance's mel depends on this seed, its label and the sample number only")

@@ -213,6 +213,28 @@ def hifigan_post(x, w, bias, wav, frame_lengths, Lmax, mult, taps, slope):
                                     int(taps), float(slope), _lib.stream())
 
 
+# ---- fp16 inference mode (csrc/hifigan_f16_ops.hip): the same arguments; w: the packed fp16 images of vocoder.hifigan_pack_f16 ([taps, Cp / 8, Cout, 8]) ----
+def _hifigan_f16_image(name, w, Cin, Cout, taps):
+    if w.dtype != torch.float16 or tuple(w.shape) != (int(taps), (Cin + 31) // 32 * 4, Cout, 8) or not w.is_contiguous():
+        raise _lib.GlowTTSHipError(f"{name} needs the packed fp16 weight image of vocoder.hifigan_pack_f16 for these sizes")
+
+
+def hifigan_conv_f16(x, w, bias, out, frame_lengths, Lmax, mult, taps, dilation, slope=1.0, residual=None, accumulate=0, divisor=1.0, channels_first=False):
+    """`hifigan_conv` with fp16 operands and fp32 sums (glowtts_hifigan_conv_f16)."""
+    Cin = x.shape[1] if channels_first else x.shape[2]
+    _hifigan_f16_image("glowtts_hifigan_conv_f16", w, Cin, out.shape[2], taps)
+    _lib.api().glowtts_hifigan_conv_f16(_lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(residual), _lib.ptr(out), _lib.ptr(frame_lengths), x.shape[0], int(Lmax),
+                                        int(mult), Cin, out.shape[2], int(taps), int(dilation), float(slope), int(accumulate), float(divisor),
+                                        int(bool(channels_first)), _lib.stream())
+
+
+def hifigan_upsample_f16(x, w, bias, out, frame_lengths, Lmax, mult, taps, rate, slope):
+    """`hifigan_upsample` with fp16 operands and fp32 sums (glowtts_hifigan_upsample_f16)."""
+    _hifigan_f16_image("glowtts_hifigan_upsample_f16", w, x.shape[2], out.shape[2], taps)
+    _lib.api().glowtts_hifigan_upsample_f16(_lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(out), _lib.ptr(frame_lengths), x.shape[0], int(Lmax), int(mult),
+                                            x.shape[2], out.shape[2], int(taps), int(rate), float(slope), _lib.stream())
+
+
 # ---- training the HiFi-GAN generator (csrc/hifigan_train_ops.hip).  x: the forward's input before its LeakyReLU; wt: the transposed images of vocoder.py ----
 def hifigan_conv_bwd(dy, wt, x, out, frame_lengths, Lmax, mult, taps, dilation, mask_slope, residual=None, scale=1.0, res_scale=1.0, accumulate=False):
     """dy [B, Lmax * mult, Cout] -> out [B, Lmax * mult, Cin]: the data gradient of `hifigan_conv` with the mask / residual / accumulate epilogue

@@ -1144,7 +1144,8 @@ def adversarial_mse(scores, value, factor=1.0):
 
 
 # ================================================================================================================================================
-# Neural vocoder: the HiFi-GAN generator (Kong et al. 2020) on the kernels of csrc/hifigan_ops.hip: inference, f32.  The network, the launch plan and the
+# Neural vocoder: the HiFi-GAN generator (Kong et al. 2020) on the kernels of csrc/hifigan_ops.hip: inference, f32 - or, with precision 'f16', on those of
+# csrc/hifigan_f16_ops.hip (fp16 operands, fp32 sums; DESIGN.md "HiFi-GAN generator: fp16 inference mode").  The network, the launch plan and the
 # boundary rule are written down in DESIGN.md ("HiFi-GAN generator"); the checkpoint layout restates the most widely used implementation's names from
 # memory and is UNPINNED, like the Parallel WaveGAN's.  The state-dict finder, the weight-norm fold, the checked load and the initialiser are the shared ones.
 # ================================================================================================================================================
@@ -1153,6 +1154,8 @@ HIFIGAN_DEFAULTS = {"Type": "HiFiGAN", "Checkpoint_Path": None, "Initial_Channel
 HIFIGAN_MAX_CHANNELS, HIFIGAN_MAX_TAPS, HIFIGAN_MAX_DILATION, HIFIGAN_MAX_RATE, HIFIGAN_MAX_UP_TAPS, HIFIGAN_MAX_PHASE_TAPS = 512, 11, 16, 16, 64, 8
 HIFIGAN_PRE_TAPS = HIFIGAN_POST_TAPS = 7
 HIFIGAN_SLOPE, HIFIGAN_LAST_SLOPE = 0.1, 0.01                       # LeakyReLU: 0.1 everywhere but before conv_post, which has torch's default
+HIFIGAN_PRECISIONS = ("f32", "f16")
+F16_MAX = 65504.0                                                   # the largest finite fp16: the f16 mode clamps to it before it rounds
 
 
 def hifigan_settings(hp):
@@ -1167,8 +1170,9 @@ def hifigan_geometry(hp):
     v = hifigan_settings(hp)
     if v["Type"] != "HiFiGAN":
         raise ValueError(f"Vocoder.Type = {v['Type']!r}: the HiFi-GAN generator needs Vocoder.Type: 'HiFiGAN' (a 'PWG' block describes the Parallel WaveGAN generator)")
-    if v["Precision"] != "f32":
-        raise ValueError(f"Vocoder.Precision = {v['Precision']!r}: the HiFi-GAN generator runs in 'f32' only (bf16 is the Parallel WaveGAN layers' mode)")
+    if v["Precision"] not in HIFIGAN_PRECISIONS:
+        raise ValueError(f"Vocoder.Precision = {v['Precision']!r}: the HiFi-GAN generator runs in 'f32' or 'f16' (f16: the convolutions' operands only, inference "
+                         "only; bf16 is the Parallel WaveGAN layers' mode)")
     resblock = str(v["Resblock"])
     if resblock not in ("1", "2"):
         raise ValueError(f"Vocoder.Resblock = {v['Resblock']!r} must be '1' (two convolutions per dilation) or '2' (one)")
@@ -1204,7 +1208,7 @@ def hifigan_geometry(hp):
     if any(d < 1 or d > HIFIGAN_MAX_DILATION for ds in rd for d in ds):
         raise ValueError(f"Vocoder.Resblock_Dilations = {rd} must lie in [1, {HIFIGAN_MAX_DILATION}]")
     return {"A": A, "hop": hop, "C0": C0, "rates": rates, "kernels": kernels, "channels": [C0 >> (i + 1) for i in range(len(rates))], "resblock": resblock,
-            "rk": rk, "rd": rd, "nk": len(rk), "precision": "f32"}
+            "rk": rk, "rd": rd, "nk": len(rk), "precision": v["Precision"]}
 
 
 def hifigan_expected_shapes(geo):
@@ -1256,6 +1260,23 @@ def hifigan_conv_image(weight):
 def hifigan_up_image(weight):
     """ConvTranspose1d weight [Cin, Cout, taps] -> the K-major image [taps * Cin, Cout] (row = tap * Cin + input channel)"""
     return weight.permute(2, 0, 1).reshape(-1, weight.shape[1]).contiguous()
+
+
+def hifigan_pack_f16(image, taps):
+    """The K-major f32 image [taps * Cin, Cout] of `hifigan_conv_image` / `hifigan_up_image` -> the fp16 image [taps, Cp / 8, Cout, 8] of
+    csrc/hifigan_f16_ops.hip: clamped to +-65504 and rounded to nearest even, per tap zero rows from Cin to Cp = pad32(Cin); element (tap, k, n) lies at
+    [tap, k // 8, n, k % 8], so a lane's eight k values of one column are 16 consecutive bytes."""
+    K, N = image.shape
+    Cin = K // taps
+    p = torch.zeros(taps, pad32(Cin), N, dtype=torch.float16, device=image.device)
+    p[:, :Cin] = image.to(torch.float32).clamp(-F16_MAX, F16_MAX).to(torch.float16).view(taps, Cin, N)
+    return p.view(taps, -1, 8, N).permute(0, 1, 3, 2).contiguous()
+
+
+def hifigan_unpack_f16(packed):
+    """The inverse of `hifigan_pack_f16`: [taps, Cp / 8, Cout, 8] fp16 -> [taps, Cp, Cout] float32 (per tap the rounded weights, then the zero rows)"""
+    taps, g, N, _ = packed.shape
+    return packed.permute(0, 1, 3, 2).reshape(taps, g * 8, N).to(torch.float32)
 
 
 # ---- training (csrc/hifigan_train_ops.hip; DESIGN.md "Training the HiFi-GAN generator") ----
@@ -1464,18 +1485,28 @@ class HiFiGAN:
     """HiFiGAN(hp, device, state_dict=None)(mels [B, Mel, T], mel_lengths) -> (wav [B, T * hop] fp32 on the device, wav_lengths [B] int64).
     state_dict None: `Vocoder.Checkpoint_Path` is loaded.  The generator has no noise input: `seeds` / `noises` are accepted (the call signature of
     `ParallelWaveGAN`) and ignored, a waveform repeats bit for bit.  An utterance's waveform is bit-identical alone, in any batch, at any padding and from
-    run to run.  precision: 'f32' or None; 'bf16' raises (f32 only).  `.last_rows` holds the rows entering conv_post of the last call ([B, T * hop,
+    run to run.  precision 'f32' / 'f16' / None (the yaml's `Vocoder.Precision`, default 'f32'), readable as `.precision` and `geo["precision"]`: 'f16' runs
+    the `hifigan_conv` and `hifigan_upsample` launches, conv_pre included, with fp16 operands and fp32 sums (csrc/hifigan_f16_ops.hip; DESIGN.md "fp16
+    inference mode" of the HiFi-GAN generator has the contract) - its own reproducible waveform, not the f32 one; inference only: with trainable=True an
+    explicit 'f16' raises and the yaml's key is ignored (training stays f32).  'bf16' raises (the Parallel WaveGAN layers' mode).
+    `.last_rows` holds the rows entering conv_post of the last call ([B, T * hop,
     channels[-1]], a view of the work buffers: the next call overwrites it; `return_rows=True` returns a copy as a third result).
     `.conv`, `.upsample` and `.stage` run single operators (tests).
     trainable=True (DESIGN.md "Training the HiFi-GAN generator"): `params` holds float32 device leaves in `hifigan_expected_shapes`' names - plain weights,
     from `state_dict` or, without one, `hifigan_init(geo, seed)` - and `generate` returns the same waveform with a backward (csrc/hifigan_train_ops.hip)."""
 
     def __init__(self, hp, device="cuda:0", state_dict=None, precision=None, trainable=False, seed=0):
-        if precision not in (None, "f32"):
-            raise ValueError(f"precision = {precision!r}: the HiFi-GAN generator runs in 'f32' only (Vocoder.Precision: 'bf16' is the Parallel WaveGAN layers' mode)")
-        self.geo = geo = hifigan_geometry(hp)                       # before anything touches the device or the disk
-        self.precision = "f32"
+        if precision is not None and precision not in HIFIGAN_PRECISIONS:
+            raise ValueError(f"precision = {precision!r}: the HiFi-GAN generator runs in 'f32' or 'f16' (None: Vocoder.Precision of the yaml; 'bf16' is the "
+                             "Parallel WaveGAN layers' mode)")
         self.trainable = bool(trainable)
+        if self.trainable and precision == "f16":
+            raise ValueError("precision = 'f16' with trainable=True: the fp16 mode is inference only, training stays f32")
+        geo = hifigan_geometry(hp)                                  # before anything touches the device or the disk
+        self.precision = "f32" if self.trainable else precision or geo["precision"]
+        self.geo = geo = dict(geo, precision=self.precision)        # the precision that runs
+        f16 = self.precision == "f16"
+        self._conv_op, self._up_op = (ops.hifigan_conv_f16, ops.hifigan_upsample_f16) if f16 else (ops.hifigan_conv, ops.hifigan_upsample)
         if self.trainable:
             hifigan_train_geometry(geo)
             if state_dict is None:
@@ -1486,13 +1517,15 @@ class HiFiGAN:
                 raise ValueError("Vocoder.Checkpoint_Path is not set: the neural vocoder needs a HiFi-GAN generator checkpoint")
             state_dict = torch.load(path, map_location="cpu")
         w = hifigan_load(state_dict, geo)
-        supported = _lib.api().glowtts_hifigan_supported
+        supported = _lib.api().glowtts_hifigan_supported_f16 if f16 else _lib.api().glowtts_hifigan_supported
         cin, ok = geo["C0"], supported(geo["A"], geo["C0"], HIFIGAN_PRE_TAPS, 1, 0)
         for u, k, c in zip(geo["rates"], geo["kernels"], geo["channels"]):
             ok = ok and supported(cin, c, k, 1, u) and all(supported(c, c, rk, d, 0) for rk, ds in zip(geo["rk"], geo["rd"]) for d in ds + [1])
             cin = c
         if not (ok and supported(cin, 1, HIFIGAN_POST_TAPS, 1, 0)):
-            raise ValueError(f"the Vocoder block's sizes {geo} are not supported by the kernels")
+            keys = (" of Vocoder.Precision = 'f16' (Vocoder.Initial_Channels, Vocoder.Upsample_Rates, Vocoder.Upsample_Kernel_Sizes, "
+                    "Vocoder.Resblock_Kernel_Sizes, Vocoder.Resblock_Dilations, Sound.Mel_Dim)") if f16 else ""
+            raise ValueError(f"the Vocoder block's sizes {geo} are not supported by the kernels{keys}")
         self.device = torch.device(device)
         self.sample_rate, self.n_mel, self.hop = int(hp.Sound.Sample_Rate), geo["A"], geo["hop"]
         self._capacity, self._buffers, self.last_rows = 0, None, None
@@ -1504,10 +1537,12 @@ class HiFiGAN:
 
     def _build_images(self, w):
         """The K-major weight images (the MFMA B operand reads 16 consecutive output channels of one input row) from the tensors `w` (host or device): built
-        once for a frozen generator; a trainable one rebuilds them on the device at every `generate`, with the transposed images of the backward."""
+        once for a frozen generator; a trainable one rebuilds them on the device at every `generate`, with the transposed images of the backward.
+        precision 'f16': the convolutions' images are the packed fp16 images of `hifigan_pack_f16` instead (biases and conv_post stay float32)."""
         geo = self.geo
         dev = lambda t: t.contiguous().to(self.device)
-        pair = lambda q, image: (dev(image(w[q + ".weight"])), dev(w[q + ".bias"]))
+        packed = (lambda im, weight: hifigan_pack_f16(im, weight.shape[2])) if self.precision == "f16" else (lambda im, weight: im)
+        pair = lambda q, image: (dev(packed(image(w[q + ".weight"]), w[q + ".weight"])), dev(w[q + ".bias"]))
         self.pre = pair("conv_pre", hifigan_conv_image)
         self.ups = [pair(f"ups.{i}", hifigan_up_image) for i in range(len(geo["rates"]))]
         self.blocks = []                                            # per resblock: per dilation (d, convs1 pair, convs2 pair or None)
@@ -1547,20 +1582,31 @@ class HiFiGAN:
             raise _lib.GlowTTSHipError("expected a device tensor (the HIP path has no CPU fallback)")
         return x.to(device=self.device, dtype=torch.float32).contiguous()
 
-    def conv(self, x, frame_lengths, key=None, weight=None, bias=None, dilation=1, slope=1.0, residual=None, out=None, accumulate=0, divisor=1.0):
+    def _image(self, image, weight):
+        """A torch weight -> the image this generator's launches take, on the device (f32: K-major; f16: packed)"""
+        weight = weight.to(device=self.device, dtype=torch.float32)
+        return hifigan_pack_f16(image(weight), weight.shape[2]) if self.precision == "f16" else image(weight)
+
+    def _image_sizes(self, image, cin):
+        """(taps, Cout) of an image over `cin` input channels"""
+        return (image.shape[0], image.shape[2]) if self.precision == "f16" else (image.shape[0] // cin, image.shape[1])
+
+    def conv(self, x, frame_lengths, key=None, weight=None, bias=None, dilation=1, slope=1.0, residual=None, out=None, accumulate=0, divisor=1.0,
+             channels_first=False):
         """One `hifigan_conv` launch on rows x [B, T, Cin] whose utterances own `frame_lengths` rows each -> out [B, T, Cout] (given, or a new tensor).  The
         weights are the generator's own under the state-dict prefix `key` ('conv_pre', 'resblocks.0.convs1.1', ...) or a Conv1d `weight` [Cout, Cin, taps] and
-        `bias`.  accumulate: 0 out = y, 1 out = out + y, 2 out = (out + y) / divisor; residual: added first (may be `out`)."""
+        `bias`.  accumulate: 0 out = y, 1 out = out + y, 2 out = (out + y) / divisor; residual: added first (may be `out`).  channels_first: x is
+        [B, Cin, T], as conv_pre takes the mel."""
         x = self._rows(x)
-        B, T, _ = x.shape
+        B, T, cin = (x.shape[0], x.shape[2], x.shape[1]) if channels_first else x.shape
         if key is not None:
             n, m = (int(s) for s in key.split(".")[1::2]) if key.startswith("resblocks.") else (0, 0)
             image, bias = self.pre if key == "conv_pre" else self.blocks[n][m][1 if ".convs1." in key else 2]
         else:
-            image, bias = hifigan_conv_image(weight.to(device=self.device, dtype=torch.float32)), bias.to(device=self.device, dtype=torch.float32).contiguous()
-        taps = image.shape[0] // x.shape[2]
-        out = out if out is not None else torch.empty(B, T, image.shape[1], dtype=torch.float32, device=self.device)
-        ops.hifigan_conv(x, image, bias, out, self._lengths(frame_lengths, B, T), T, 1, taps, dilation, slope, residual, accumulate, divisor)
+            image, bias = self._image(hifigan_conv_image, weight), bias.to(device=self.device, dtype=torch.float32).contiguous()
+        taps, cout = self._image_sizes(image, cin)
+        out = out if out is not None else torch.empty(B, T, cout, dtype=torch.float32, device=self.device)
+        self._conv_op(x, image, bias, out, self._lengths(frame_lengths, B, T), T, 1, taps, dilation, slope, residual, accumulate, divisor, channels_first)
         return out
 
     def upsample(self, i, x, frame_lengths, out=None, weight=None, bias=None, rate=None):
@@ -1571,9 +1617,10 @@ class HiFiGAN:
         if i is not None:
             (image, bias), rate = self.ups[i], self.geo["rates"][i]
         else:
-            image, bias = hifigan_up_image(weight.to(device=self.device, dtype=torch.float32)), bias.to(device=self.device, dtype=torch.float32).contiguous()
-        out = out if out is not None else torch.empty(B, T * rate, image.shape[1], dtype=torch.float32, device=self.device)
-        ops.hifigan_upsample(x, image, bias, out, self._lengths(frame_lengths, B, T), T, 1, image.shape[0] // x.shape[2], rate, HIFIGAN_SLOPE)
+            image, bias = self._image(hifigan_up_image, weight), bias.to(device=self.device, dtype=torch.float32).contiguous()
+        taps, cout = self._image_sizes(image, x.shape[2])
+        out = out if out is not None else torch.empty(B, T * rate, cout, dtype=torch.float32, device=self.device)
+        self._up_op(x, image, bias, out, self._lengths(frame_lengths, B, T), T, 1, taps, rate, HIFIGAN_SLOPE)
         return out
 
     def _stage(self, i, x, lengths, Lmax, mult, U, X, T, acc):
@@ -1581,7 +1628,8 @@ class HiFiGAN:
         of every block adds into `acc` in its epilogue - the first block writes, the last divides by nk - so the MRF mean costs no launch."""
         g = self.geo
         u, nk = g["rates"][i], g["nk"]
-        ops.hifigan_upsample(x, *self.ups[i], U, lengths, Lmax, mult, g["kernels"][i], u, HIFIGAN_SLOPE)
+        conv = self._conv_op
+        self._up_op(x, *self.ups[i], U, lengths, Lmax, mult, g["kernels"][i], u, HIFIGAN_SLOPE)
         mult *= u
         for j in range(nk):
             rk, steps, cur = g["rk"][j], self.blocks[i * nk + j], U
@@ -1589,12 +1637,12 @@ class HiFiGAN:
             for m, (d, c1, c2) in enumerate(steps):
                 last = m == len(steps) - 1
                 if c2 is not None:                                  # type '1': t = conv1(lrelu(x)), x = conv2(lrelu(t)) + x
-                    ops.hifigan_conv(cur, *c1, T, lengths, Lmax, mult, rk, d, HIFIGAN_SLOPE)
-                    ops.hifigan_conv(T, *c2, acc if last else X, lengths, Lmax, mult, rk, 1, HIFIGAN_SLOPE, residual=cur, accumulate=mode if last else 0, divisor=nk)
+                    conv(cur, *c1, T, lengths, Lmax, mult, rk, d, HIFIGAN_SLOPE)
+                    conv(T, *c2, acc if last else X, lengths, Lmax, mult, rk, 1, HIFIGAN_SLOPE, residual=cur, accumulate=mode if last else 0, divisor=nk)
                     cur = X
                 else:                                               # type '2': x = conv1(lrelu(x)) + x
                     dst = acc if last else (T if cur is X else X)
-                    ops.hifigan_conv(cur, *c1, dst, lengths, Lmax, mult, rk, d, HIFIGAN_SLOPE, residual=cur, accumulate=mode if last else 0, divisor=nk)
+                    conv(cur, *c1, dst, lengths, Lmax, mult, rk, d, HIFIGAN_SLOPE, residual=cur, accumulate=mode if last else 0, divisor=nk)
                     cur = dst
 
     def stage(self, i, x, frame_lengths):
@@ -1621,7 +1669,7 @@ class HiFiGAN:
         p0, p1, U, X, T = self._work(B, L)
         view = lambda buf, rows, c: buf[:B * rows * c].view(B, rows, c)
         x, mult = view(p0, L, g["C0"]), 1
-        ops.hifigan_conv(mels, *self.pre, x, lengths, L, 1, HIFIGAN_PRE_TAPS, 1, channels_first=True)     # the mel as the caller holds it: [B, Mel, L]
+        self._conv_op(mels, *self.pre, x, lengths, L, 1, HIFIGAN_PRE_TAPS, 1, channels_first=True)       # the mel as the caller holds it: [B, Mel, L]
         for i, (u, c) in enumerate(zip(g["rates"], g["channels"])):
             rows = L * mult * u
             acc = view(p1 if i % 2 == 0 else p0, rows, c)
@@ -2317,7 +2365,7 @@ def vocoder_kind(hp, kind=None, checkpoint=None):
 
 def make_vocoder(hp, device, kind=None, checkpoint=None, precision=None):
     """The one place that chooses a vocoder: `kind` as `vocoder_kind` resolves it; `checkpoint` overrides `Vocoder.Checkpoint_Path` of the yaml; `precision`
-    is the neural vocoders' (Griffin-Lim ignores it; HiFi-GAN takes 'f32' only)."""
+    is the neural vocoders' (Griffin-Lim ignores it; Parallel WaveGAN takes 'f32' / 'bf16', HiFi-GAN 'f32' / 'f16')."""
     import argparse
     import copy
     kind = vocoder_kind(hp, kind, checkpoint)

@@ -958,6 +958,22 @@ int glowtts_hifigan_upsample(const float *in, const float *w, const float *bias,
 int glowtts_hifigan_post(const float *in, const float *w, const float *bias, float *wav, const int32_t *frame_lengths, int B, int Lmax, int mult, int Cin,
                          int taps, float slope, void *stream);
 
+/* ---- neural vocoder: HiFi-GAN generator, fp16 inference mode (csrc/hifigan_f16_ops.hip; additions, the ABI version stays) ----
+ * glowtts_hifigan_conv_f16 / glowtts_hifigan_upsample_f16 are glowtts_hifigan_conv / glowtts_hifigan_upsample with fp16 operands on
+ * v_mfma_f32_16x16x32_f16, logged as `hifigan_conv_f16` / `hifigan_upsample_f16`: the staged rows after the LeakyReLU and the weights are clamped to +-65504
+ * and rounded to fp16 (nearest even); the sums (which start at the fp32 bias), the residual (which adds the unrounded row), the accumulate epilogues and
+ * every tensor in memory stay f32.  Arguments, rows, lengths, ownership and bit-identity as for the f32 entries; conv_post stays glowtts_hifigan_post.
+ * The weights come as packed fp16 images [taps][Cp / 8][Cout][8] - element (tap, k, n) at ((tap Cp / 8 + k / 8) Cout + n) 8 + k % 8, Cp = Cin rounded up to
+ * a multiple of 32, zero rows from Cin to Cp; tap and k as the rows tap * Cin + k of the f32 image.
+ * Supported (glowtts_hifigan_supported_f16, else GLOWTTS_E_ARG before any launch): glowtts_hifigan_supported with the fp16 tile
+ * (64 + reach) (min(Cp, 64) + 8) 2 bytes of LDS in place of the f32 tile (Cout == 1: the f32 answer, conv_post has no fp16 form). */
+int glowtts_hifigan_supported_f16(int Cin, int Cout, int taps, int dilation, int rate);
+int glowtts_hifigan_conv_f16(const float *in, const uint16_t *w, const float *bias, const float *residual, float *out, const int32_t *frame_lengths, int B,
+                             int Lmax, int mult, int Cin, int Cout, int taps, int dilation, float slope, int accumulate, float divisor, int channels_first,
+                             void *stream);
+int glowtts_hifigan_upsample_f16(const float *in, const uint16_t *w, const float *bias, float *out, const int32_t *frame_lengths, int B, int Lmax, int mult,
+                                 int Cin, int Cout, int taps, int rate, float slope, void *stream);
+
 /* ---- training the HiFi-GAN generator (csrc/hifigan_train_ops.hip; f32; additions, the ABI version stays) ----
  * Layouts, lengths and ownership as above: nothing is read beyond an utterance's rows [0, L mult) and nothing is written there.  Every product runs on
  * v_mfma_f32_16x16x4_f32, every sum has a fixed order that depends on the sizes alone (no float atomics): every gradient is bit-identical from run to run.
