@@ -285,6 +285,11 @@ SIGNATURES = {
     "glowtts_hifigan_upsample_bwd": (I, [P] * 5 + [I] * 7 + [F, P]),
     "glowtts_hifigan_post_bwd": (I, [P] * 7 + [I] * 5 + [F, P]),
     "glowtts_hifigan_wgrad": (I, [P] * 6 + [I] * 8 + [F, F, I, P]),
+    "glowtts_hifigan_train_supported_mixed": (I, [I] * 5),
+    "glowtts_hifigan_conv_bwd_bf16": (I, [P] * 6 + [I] * 7 + [F, F, F, I, P]),
+    "glowtts_hifigan_upsample_bwd_bf16": (I, [P] * 5 + [I] * 7 + [F, P]),
+    "glowtts_hifigan_wgrad_bf16": (I, [P] * 6 + [I] * 8 + [F, F, I, P]),
+    "glowtts_hifigan_pack_images": (I, [P, I, I, P]),
     "glowtts_ge2e_supported": (I, [I] * 4),
     "glowtts_ge2e_image_floats": (L, [I] * 3),
     "glowtts_ge2e_work_floats": (L, [L] + [I] * 3),
@@ -371,7 +376,7 @@ SIGNATURES = {
 VALUE_RETURNING = frozenset({
     "glowtts_abi_version", "glowtts_opt_chunk",
     "glowtts_cond_linear_supported", "glowtts_gst_supported", "glowtts_conv3x3s2_supported", "glowtts_dur_proj_supported", "glowtts_vocoder_supported",
-    "glowtts_pwg_supported", "glowtts_pwg_supported_bf16", "glowtts_hifigan_supported", "glowtts_hifigan_supported_f16", "glowtts_hifigan_train_supported", "glowtts_ge2e_supported", "glowtts_pwg_train_supported", "glowtts_stft_loss_supported",
+    "glowtts_pwg_supported", "glowtts_pwg_supported_bf16", "glowtts_hifigan_supported", "glowtts_hifigan_supported_f16", "glowtts_hifigan_train_supported", "glowtts_hifigan_train_supported_mixed", "glowtts_ge2e_supported", "glowtts_pwg_train_supported", "glowtts_stft_loss_supported",
     "glowtts_mel_loss_supported",
     "glowtts_pwg_disc_supported", "glowtts_hifigan_disc_supported", "glowtts_hifigan_msd_supported", "glowtts_mel_cepstrum_supported", "glowtts_dtw_supported", "glowtts_tsne_supported",
 })

@@ -4,7 +4,9 @@ host-side step decay.  The sampler, the update, the evaluation and the checkpoin
 trainer's (mel segments with the final audio under them, from the same pattern directories, so the `DIR/GTA` tree of `Align.py --gta` works unchanged).
 The generator has no noise input: the seed fixes the initialisation and the batches.  The checkpoints `HIFIGAN_<steps>.pt` (`generator`, `Optimizer`, `Steps`)
 load unchanged through `Vocoder.Checkpoint_Path` of a `Type: 'HiFiGAN'` block.  The settings are the optional block `Vocoder.Train` of such a block, with
-`pwg_trainer`'s keys and rules; the defaults of an absent block are this project's contract, not a pinned recipe.
+`pwg_trainer`'s keys and rules; the defaults of an absent block are this project's contract, not a pinned recipe.  `Vocoder.Train.Precision: 'mixed'` trains the generator in mixed precision
+(f16 forward, bf16 backward, fp32 master weights, optimizer and checkpoints; DESIGN.md "Training the HiFi-GAN generator: mixed precision") in both stages; the
+discriminators, the losses and d wav stay f32, and a run may resume in either precision.
 
 Stage two (DESIGN.md "Training the HiFi-GAN discriminator"), with the optional sub-block `Vocoder.Train.Adversarial` (`vocoder.hifigan_disc_settings`): from
 `Start_Step` on every step is `PWG_Trainer.Adversarial_Step` with the multi-period discriminator `vocoder.HiFiGANPeriodDiscriminator` -
@@ -25,11 +27,15 @@ import torch
 
 from . import aux_trainer, pwg_trainer
 from .hparams import plain_block
-from .vocoder import (MSD_BLOCK, MSD_KEY, MSD_PREFIX, HiFiGAN, HiFiGANDiscriminators, HiFiGANPeriodDiscriminator, adversarial_mse, hifigan_disc_load,
-                      hifigan_disc_settings, hifigan_discs_load, hifigan_geometry, hifigan_load)
+from .vocoder import (HIFIGAN_TRAIN_PRECISIONS, MSD_BLOCK, MSD_KEY, MSD_PREFIX, HiFiGAN, HiFiGANDiscriminators, HiFiGANPeriodDiscriminator, adversarial_mse,
+                      hifigan_disc_load, hifigan_disc_settings, hifigan_discs_load, hifigan_geometry, hifigan_load)
 
 TRAIN_KEY = pwg_trainer.TRAIN_KEY
 DEFAULTS = dict(pwg_trainer.DEFAULTS, Batch_Size=16, Segment_Frames=32, Learning_Rate=2.0e-4, Checkpoint_Path="./hifigan_results")
+# The optional key `Vocoder.Train.Precision`: 'f32' (absent: f32), or 'mixed' - the generator's f16 forward and bf16 backward over fp32 master weights (DESIGN.md
+# "... mixed precision").  It appears in the settings only when the yaml has it, and is a key of this trainer alone: Train_PWG.py refuses it by name like any
+# other unknown key.
+PRECISION_KEY = "Precision"
 BUNDLES = (("", "model", "hifigan", hifigan_load, ("generator", "Optimizer", "Steps")),
            ("disc_", "discriminator", "hifigan_disc", hifigan_disc_load, ("discriminator", "Discriminator_Optimizer", "Discriminator_Steps")))
 # with the sub-block Multi_Scale the discriminator bundle is the union of both discriminators, under the same checkpoint keys
@@ -50,7 +56,9 @@ def train_settings(hp):
     if isinstance(train, dict) and "Discriminator" in train:
         raise ValueError(f"{TRAIN_KEY}.Discriminator is the Parallel WaveGAN discriminator's block, which does not train this generator: the HiFi-GAN "
                          f"adversarial stage (multi-period discriminator, feature matching) is the block {TRAIN_KEY}.{ADV_KEY}")
-    s = pwg_trainer.train_settings(hp, DEFAULTS, also=(ADV_KEY,))
+    s = pwg_trainer.train_settings(hp, DEFAULTS, also=(ADV_KEY, PRECISION_KEY))
+    if s.get(PRECISION_KEY, "f32") not in HIFIGAN_TRAIN_PRECISIONS:
+        raise ValueError(f"{TRAIN_KEY}.{PRECISION_KEY} = {s[PRECISION_KEY]!r}: the HiFi-GAN generator trains in 'f32' or 'mixed'")
     if ADV_KEY in s:
         s[ADV_KEY] = hifigan_disc_settings(hp)
     return s
@@ -63,7 +71,7 @@ class HiFiGAN_Trainer(pwg_trainer.PWG_Trainer):
     geometry, settings = staticmethod(hifigan_geometry), staticmethod(train_settings)
 
     def make_model(self):
-        return HiFiGAN(self.hp, self.device, trainable=True, seed=self.seed)
+        return HiFiGAN(self.hp, self.device, trainable=True, seed=self.seed)     # the training precision: the yaml's Vocoder.Train.Precision
 
     def generate(self, mel, lengths, step):
         return self.model.generate(mel, lengths)[0]

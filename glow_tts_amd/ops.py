@@ -266,3 +266,43 @@ def hifigan_wgrad(x, dy, frame_lengths, work, dw, dbias, Lmax, mult, taps, dilat
     Cin = x.shape[1] if channels_first else x.shape[2]
     _lib.api().glowtts_hifigan_wgrad(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(frame_lengths), _lib.ptr(work), _lib.ptr(dw), _lib.ptr(dbias), x.shape[0], int(Lmax), int(mult),
                                      Cin, dbias.shape[0], int(taps), int(dilation), int(rate), float(slope), float(scale), int(bool(channels_first)), _lib.stream())
+
+
+# ---- mixed-precision training of the HiFi-GAN generator (csrc/hifigan_mixed_ops.hip): the same arguments; wt: the packed bf16 images [T', Kp / 8, Cin, 8] ----
+def _hifigan_bf16_image(name, wt, offsets, K, N):
+    if wt.dtype != torch.bfloat16 or tuple(wt.shape) != (int(offsets), (K + 31) // 32 * 4, N, 8) or not wt.is_contiguous():
+        raise _lib.GlowTTSHipError(f"{name} needs the packed bf16 data-gradient image of vocoder.hifigan_pack_bf16 for these sizes")
+
+
+def hifigan_conv_bwd_bf16(dy, wt, x, out, frame_lengths, Lmax, mult, taps, dilation, mask_slope, residual=None, scale=1.0, res_scale=1.0, accumulate=False):
+    """`hifigan_conv_bwd` with bf16 operands and fp32 sums (glowtts_hifigan_conv_bwd_bf16)."""
+    _hifigan_bf16_image("glowtts_hifigan_conv_bwd_bf16", wt, taps, dy.shape[2], out.shape[2])
+    _lib.api().glowtts_hifigan_conv_bwd_bf16(_lib.ptr(dy), _lib.ptr(wt), _lib.ptr(x), _lib.ptr(residual), _lib.ptr(out), _lib.ptr(frame_lengths), dy.shape[0],
+                                             int(Lmax), int(mult), out.shape[2], dy.shape[2], int(taps), int(dilation), float(mask_slope), float(scale),
+                                             float(res_scale), int(bool(accumulate)), _lib.stream())
+
+
+def hifigan_upsample_bwd_bf16(dy, wt, x, out, frame_lengths, Lmax, mult, taps, rate, mask_slope):
+    """`hifigan_upsample_bwd` with bf16 operands and fp32 sums (glowtts_hifigan_upsample_bwd_bf16)."""
+    if wt.dim() != 4:
+        raise _lib.GlowTTSHipError("glowtts_hifigan_upsample_bwd_bf16 needs the packed bf16 data-gradient image of vocoder.hifigan_pack_bf16")
+    _hifigan_bf16_image("glowtts_hifigan_upsample_bwd_bf16", wt, wt.shape[0], int(rate) * dy.shape[2], out.shape[2])
+    _lib.api().glowtts_hifigan_upsample_bwd_bf16(_lib.ptr(dy), _lib.ptr(wt), _lib.ptr(x), _lib.ptr(out), _lib.ptr(frame_lengths), dy.shape[0], int(Lmax), int(mult),
+                                                 out.shape[2], dy.shape[2], int(taps), int(rate), float(mask_slope), _lib.stream())
+
+
+def hifigan_wgrad_bf16(x, dy, frame_lengths, work, dw, dbias, Lmax, mult, taps, dilation=1, rate=0, slope=1.0, scale=1.0, channels_first=False):
+    """`hifigan_wgrad` with lrelu(x) and dy rounded to bf16, fp32 sums; the bias gradient from the unrounded dy (glowtts_hifigan_wgrad_bf16).  A single output
+    channel (conv_post) runs the f32 launches."""
+    Cin = x.shape[1] if channels_first else x.shape[2]
+    _lib.api().glowtts_hifigan_wgrad_bf16(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(frame_lengths), _lib.ptr(work), _lib.ptr(dw), _lib.ptr(dbias), x.shape[0], int(Lmax),
+                                          int(mult), Cin, dbias.shape[0], int(taps), int(dilation), int(rate), float(slope), float(scale),
+                                          int(bool(channels_first)), _lib.stream())
+
+
+def hifigan_pack_images(jobs, total_blocks):
+    """Every weight image of a mixed-precision step from the fp32 master weights in ONE launch; jobs: the int64 device table [njobs, 8] of
+    vocoder.hifigan_pack_jobs (glowtts_hifigan_pack_images)."""
+    if jobs.dtype != torch.int64 or jobs.dim() != 2 or jobs.shape[1] != 8 or not jobs.is_contiguous() or not jobs.is_cuda:
+        raise _lib.GlowTTSHipError("glowtts_hifigan_pack_images needs the int64 device job table [njobs, 8] of vocoder.hifigan_pack_jobs")
+    _lib.api().glowtts_hifigan_pack_images(_lib.ptr(jobs), jobs.shape[0], int(total_blocks), _lib.stream())

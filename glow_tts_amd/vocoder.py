@@ -1281,6 +1281,8 @@ def hifigan_unpack_f16(packed):
 
 # ---- training (csrc/hifigan_train_ops.hip; DESIGN.md "Training the HiFi-GAN generator") ----
 HIFIGAN_TRAIN_MAX_OFFSETS, HIFIGAN_TRAIN_MAX_VIEW = 11, 4096
+HIFIGAN_TRAIN_PRECISIONS = ("f32", "mixed")                         # mixed: f16 forward, bf16 backward (DESIGN.md "... mixed precision")
+HIFIGAN_TRAIN_PRECISION_KEY = "Vocoder.Train.Precision"
 
 
 def hifigan_conv_image_t(weight):
@@ -1359,11 +1361,89 @@ def hifigan_train_geometry(geo):
                              "Vocoder.Resblock_Dilations)")
 
 
-def hifigan_train_launches(geo):
+def hifigan_train_precision(hp):
+    """The yaml's `Vocoder.Train.Precision` (absent: 'f32'), unchecked"""
+    train = plain_block(getattr(getattr(hp, "Vocoder", None), "Train", None))
+    return train.get("Precision", "f32") if isinstance(train, dict) else "f32"
+
+
+def hifigan_train_geometry_mixed(geo):
+    """Raises ValueError naming the yaml keys for sizes that train in f32 but not in the mixed mode (`glowtts_hifigan_train_supported_mixed`: the 16-bit tiles'
+    LDS terms).  Construction with train_precision='mixed' only, before the device is touched."""
+    supported = _lib.api().glowtts_hifigan_train_supported_mixed
+    for name, ci, co, taps, d, rate, _ in hifigan_convs(geo):
+        if not supported(ci, co, taps, d, rate):
+            raise ValueError(f"the Vocoder block's sizes do not train with {HIFIGAN_TRAIN_PRECISION_KEY} = 'mixed': {name} ({ci} -> {co} channels, {taps} taps, "
+                             f"dilation {d}, rate {rate}) is beyond the 16-bit kernels (Vocoder.Initial_Channels, Vocoder.Upsample_Rates, "
+                             "Vocoder.Upsample_Kernel_Sizes, Vocoder.Resblock_Kernel_Sizes, Vocoder.Resblock_Dilations, Sound.Mel_Dim)")
+
+
+def hifigan_pack_bf16(image, taps):
+    """The data gradient's f32 image [taps * K, N] of `hifigan_conv_image_t` / `hifigan_up_image_t` -> the bf16 image [taps, Kp / 8, N, 8] of
+    csrc/hifigan_mixed_ops.hip: `hifigan_pack_f16`'s layout, rounded to bf16 (nearest even) without a clamp."""
+    K, N = image.shape
+    K //= taps
+    p = torch.zeros(taps, pad32(K), N, dtype=torch.bfloat16, device=image.device)
+    p[:, :K] = image.to(torch.float32).to(torch.bfloat16).view(taps, K, N)
+    return p.view(taps, -1, 8, N).permute(0, 1, 3, 2).contiguous()
+
+
+HIFIGAN_PACK_KINDS = {"conv_f16": 0, "up_f16": 1, "conv_t_bf16": 2, "up_t_bf16": 3, "post_f32": 4}
+
+
+def hifigan_pack_plan(geo):
+    """The images of a mixed-precision step, one job of `hifigan_pack_images` each: [(state-dict key of the source, kind, Cin, Cout, taps, rate, shape, dtype)] -
+    per convolution the fp16 forward image and (conv_pre has none) the bf16 data-gradient image; conv_post's f32 [taps * Cin] rows."""
+    plan = []
+    for name, ci, co, taps, _, rate, _ in hifigan_convs(geo):
+        key = name + ".weight"
+        if co == 1:
+            plan.append((key, "post_f32", ci, co, taps, rate, (taps * ci,), torch.float32))
+            continue
+        plan.append((key, "up_f16" if rate else "conv_f16", ci, co, taps, rate, (taps, pad32(ci) // 8, co, 8), torch.float16))
+        if name == "conv_pre":
+            continue
+        if rate:
+            lo, hi = hifigan_up_reach(rate, taps)
+            plan.append((key, "up_t_bf16", ci, co, taps, rate, (hi - lo + 1, pad32(rate * co) // 8, ci, 8), torch.bfloat16))
+        else:
+            plan.append((key, "conv_t_bf16", ci, co, taps, rate, (taps, pad32(co) // 8, ci, 8), torch.bfloat16))
+    return plan
+
+
+def hifigan_pack_jobs(plan, params, device):
+    """-> (images, jobs, total_blocks): one flat device buffer cut into the plan's images (16-byte aligned views, in plan order) and the int64 job table
+    [njobs, 8] of `ops.hifigan_pack_images` - source pointer (the parameter's LIVE storage), destination pointer, kind, Cin, Cout, taps, rate, first block.
+    A job has one thread per 16-byte group of its image (conv_post: per float), 256 per block."""
+    sizes = [math.prod(shape) * torch.empty(0, dtype=dtype).element_size() for *_, shape, dtype in plan]
+    offsets = [0]
+    for n in sizes:
+        offsets.append(offsets[-1] + (n + 15) // 16 * 16)
+    flat = torch.zeros(offsets[-1], dtype=torch.uint8, device=device)
+    images, rows, block = [], [], 0
+    for (key, kind, ci, co, taps, rate, shape, dtype), off, n in zip(plan, offsets, sizes):
+        src = params[key]
+        if src.dtype != torch.float32 or not src.is_contiguous() or src.device != flat.device:
+            raise _lib.GlowTTSHipError(f"hifigan_pack_jobs needs contiguous float32 device parameters, got {key}: {src.dtype}, {src.device}")
+        image = flat[off:off + n].view(dtype).view(shape)
+        images.append(image)
+        rows.append([src.data_ptr(), image.data_ptr(), HIFIGAN_PACK_KINDS[kind], ci, co, taps, rate, block])
+        block += -(-(n // (4 if kind == "post_f32" else 16)) // 256)
+    return images, torch.tensor(rows, dtype=torch.int64).to(device), block
+
+
+def hifigan_train_launches(geo, train_precision="f32"):
     """Launches of one training forward + backward by their names in the launch log: the forward is the inference launches (`hifigan_launches`); the backward is
-    conv_post's, then per convolution one data gradient (conv_pre has none: the mel gets no gradient) and the weight gradient's two launches."""
+    conv_post's, then per convolution one data gradient (conv_pre has none: the mel gets no gradient) and the weight gradient's two launches.  'mixed': the
+    f16 forward's names, the bf16 backward's, `hifigan_wgrad` once (conv_post) and the one `hifigan_pack_images` that builds the step's images."""
     convs = hifigan_launches(geo) - 2 - len(geo["rates"])           # the resblock convolutions
     n = hifigan_launches(geo)
+    if train_precision == "mixed":
+        return {"hifigan_pack_images": 1, "hifigan_conv_f16": 1 + convs, "hifigan_upsample_f16": len(geo["rates"]), "hifigan_conv,post": 1, "hifigan_post_bwd": 1,
+                "hifigan_conv_bwd_bf16": convs, "hifigan_upsample_bwd_bf16": len(geo["rates"]), "hifigan_wgrad_bf16": n - 1, "hifigan_wgrad": 1,
+                "hifigan_wgrad_sum": n}
+    if train_precision != "f32":
+        raise ValueError(f"train_precision = {train_precision!r}: 'f32' or 'mixed'")
     return {"hifigan_conv": 1 + convs, "hifigan_upsample": len(geo["rates"]), "hifigan_conv,post": 1, "hifigan_post_bwd": 1, "hifigan_conv_bwd": convs,
             "hifigan_upsample_bwd": len(geo["rates"]), "hifigan_wgrad": n, "hifigan_wgrad_sum": n}
 
@@ -1387,11 +1467,12 @@ def hifigan_train_forward(voc, mels, lengths):
     B, _, L = mels.shape
     f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=mels.device)
     x, mult, nk, stages = f(B, L, g["C0"]), 1, g["nk"], []
-    ops.hifigan_conv(mels, *voc.pre, x, lengths, L, 1, HIFIGAN_PRE_TAPS, 1, channels_first=True)
+    conv, up = (ops.hifigan_conv_f16, ops.hifigan_upsample_f16) if voc.train_precision == "mixed" else (ops.hifigan_conv, ops.hifigan_upsample)
+    conv(mels, *voc.pre, x, lengths, L, 1, HIFIGAN_PRE_TAPS, 1, channels_first=True)
     fwd = {"x0": x, "stages": stages}
     for i, (u, c) in enumerate(zip(g["rates"], g["channels"])):
         U, acc = f(B, L * mult * u, c), f(B, L * mult * u, c)
-        ops.hifigan_upsample(x, *voc.ups[i], U, lengths, L, mult, g["kernels"][i], u, HIFIGAN_SLOPE)
+        up(x, *voc.ups[i], U, lengths, L, mult, g["kernels"][i], u, HIFIGAN_SLOPE)
         mult *= u
         blocks = []
         for j in range(nk):
@@ -1402,11 +1483,11 @@ def hifigan_train_forward(voc, mels, lengths):
                 dst = acc if last else torch.empty_like(U)
                 if c2 is not None:
                     t = torch.empty_like(U)
-                    ops.hifigan_conv(cur, *c1, t, lengths, L, mult, rk, d, HIFIGAN_SLOPE)
-                    ops.hifigan_conv(t, *c2, dst, lengths, L, mult, rk, 1, HIFIGAN_SLOPE, residual=cur, accumulate=mode if last else 0, divisor=nk)
+                    conv(cur, *c1, t, lengths, L, mult, rk, d, HIFIGAN_SLOPE)
+                    conv(t, *c2, dst, lengths, L, mult, rk, 1, HIFIGAN_SLOPE, residual=cur, accumulate=mode if last else 0, divisor=nk)
                 else:
                     t = None
-                    ops.hifigan_conv(cur, *c1, dst, lengths, L, mult, rk, d, HIFIGAN_SLOPE, residual=cur, accumulate=mode if last else 0, divisor=nk)
+                    conv(cur, *c1, dst, lengths, L, mult, rk, d, HIFIGAN_SLOPE, residual=cur, accumulate=mode if last else 0, divisor=nk)
                 kept.append((cur, t))
                 cur = dst
             blocks.append(kept)
@@ -1428,7 +1509,10 @@ def hifigan_train_backward(voc, mels, lengths, fwd, dwav):
     f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=mels.device)
     grads = {k: f(*shape) for k, shape in hifigan_expected_shapes(g).items()}
     work = f(max(ops.hifigan_wgrad_work_floats(B, L, mult, ci, co, taps, rate) for _, ci, co, taps, _, rate, mult in hifigan_convs(g)))
-    wg = lambda key, x, dy, mult, taps, **kw: ops.hifigan_wgrad(x, dy, lengths, work, grads[key + ".weight"], grads[key + ".bias"], L, mult, taps, **kw)
+    mixed = voc.train_precision == "mixed"                         # the bf16 op set; conv_post's single output column stays on the f32 launches
+    wgrad, conv_bwd, up_bwd = ((ops.hifigan_wgrad_bf16, ops.hifigan_conv_bwd_bf16, ops.hifigan_upsample_bwd_bf16) if mixed else
+                               (ops.hifigan_wgrad, ops.hifigan_conv_bwd, ops.hifigan_upsample_bwd))
+    wg = lambda key, x, dy, mult, taps, **kw: wgrad(x, dy, lengths, work, grads[key + ".weight"], grads[key + ".bias"], L, mult, taps, **kw)
     dwav = dwav.to(torch.float32).contiguous()
     mult, x = g["hop"], fwd["stages"][-1]["acc"]
     dpre, dA = f(B, L * mult), torch.empty_like(x)
@@ -1446,20 +1530,19 @@ def hifigan_train_backward(voc, mels, lengths, fwd, dwav):
                 first = m == 0
                 if type1:                                           # x' = conv2(lrelu(t)) + x, t = conv1(lrelu(x))
                     dst = dU if first else G2
-                    ops.hifigan_conv_bwd(dout, w2t, t_m, G1, lengths, L, mult, rk, 1, HIFIGAN_SLOPE, scale=sc)
+                    conv_bwd(dout, w2t, t_m, G1, lengths, L, mult, rk, 1, HIFIGAN_SLOPE, scale=sc)
                     wg(q + f"convs2.{m}", t_m, dout, mult, rk, slope=HIFIGAN_SLOPE, scale=sc)
-                    ops.hifigan_conv_bwd(G1, w1t, x_m, dst, lengths, L, mult, rk, d, HIFIGAN_SLOPE, residual=dout, res_scale=sc, accumulate=first and j > 0)
+                    conv_bwd(G1, w1t, x_m, dst, lengths, L, mult, rk, d, HIFIGAN_SLOPE, residual=dout, res_scale=sc, accumulate=first and j > 0)
                     wg(q + f"convs1.{m}", x_m, G1, mult, rk, dilation=d, slope=HIFIGAN_SLOPE)
                 else:                                               # x' = conv1(lrelu(x)) + x
                     dst = dU if first else (G1 if dout is G2 else G2)
-                    ops.hifigan_conv_bwd(dout, w1t, x_m, dst, lengths, L, mult, rk, d, HIFIGAN_SLOPE, residual=dout, scale=sc, res_scale=sc,
-                                         accumulate=first and j > 0)
+                    conv_bwd(dout, w1t, x_m, dst, lengths, L, mult, rk, d, HIFIGAN_SLOPE, residual=dout, scale=sc, res_scale=sc, accumulate=first and j > 0)
                     wg(q + f"convs1.{m}", x_m, dout, mult, rk, dilation=d, slope=HIFIGAN_SLOPE, scale=sc)
                 dout, sc = dst, 1.0
         mult //= u
         wg(f"ups.{i}", x_in, dU, mult, k, rate=u, slope=HIFIGAN_SLOPE)
         dA = torch.empty_like(x_in)
-        ops.hifigan_upsample_bwd(dU, voc.ups_t[i], x_in, dA, lengths, L, mult, k, u, HIFIGAN_SLOPE)
+        up_bwd(dU, voc.ups_t[i], x_in, dA, lengths, L, mult, k, u, HIFIGAN_SLOPE)
     wg("conv_pre", mels, dA, 1, HIFIGAN_PRE_TAPS, channels_first=True)
     return grads
 
@@ -1493,22 +1576,39 @@ class HiFiGAN:
     channels[-1]], a view of the work buffers: the next call overwrites it; `return_rows=True` returns a copy as a third result).
     `.conv`, `.upsample` and `.stage` run single operators (tests).
     trainable=True (DESIGN.md "Training the HiFi-GAN generator"): `params` holds float32 device leaves in `hifigan_expected_shapes`' names - plain weights,
-    from `state_dict` or, without one, `hifigan_init(geo, seed)` - and `generate` returns the same waveform with a backward (csrc/hifigan_train_ops.hip)."""
+    from `state_dict` or, without one, `hifigan_init(geo, seed)` - and `generate` returns the same waveform with a backward (csrc/hifigan_train_ops.hip).
+    train_precision 'f32' / 'mixed' / None (the yaml's `Vocoder.Train.Precision`, default 'f32'), readable as `.train_precision` (None on a frozen generator, where
+    the argument raises): 'mixed' (DESIGN.md "Training the HiFi-GAN generator: mixed precision") runs `generate`'s forward - and `__call__` - on the 'f16' mode's
+    launches, bit-identical to a frozen `precision='f16'` generator of the same weights, and the backward's matrix products on bf16 operands
+    (csrc/hifigan_mixed_ops.hip); the parameters, every tensor in memory, every sum and conv_post stay fp32, `.precision` still says 'f32', and ONE
+    `hifigan_pack_images` launch per step builds the 16-bit images from the parameters."""
 
-    def __init__(self, hp, device="cuda:0", state_dict=None, precision=None, trainable=False, seed=0):
+    def __init__(self, hp, device="cuda:0", state_dict=None, precision=None, trainable=False, seed=0, train_precision=None):
         if precision is not None and precision not in HIFIGAN_PRECISIONS:
             raise ValueError(f"precision = {precision!r}: the HiFi-GAN generator runs in 'f32' or 'f16' (None: Vocoder.Precision of the yaml; 'bf16' is the "
                              "Parallel WaveGAN layers' mode)")
         self.trainable = bool(trainable)
         if self.trainable and precision == "f16":
             raise ValueError("precision = 'f16' with trainable=True: the fp16 mode is inference only, training stays f32")
+        if train_precision is not None and not self.trainable:
+            raise ValueError(f"train_precision = {train_precision!r} on a frozen generator: the training precision needs trainable=True (a frozen generator's "
+                             "arithmetic is `precision` / Vocoder.Precision)")
         geo = hifigan_geometry(hp)                                  # before anything touches the device or the disk
+        self.train_precision = None
+        if self.trainable:
+            named = "train_precision" if train_precision is not None else HIFIGAN_TRAIN_PRECISION_KEY
+            self.train_precision = train_precision if train_precision is not None else hifigan_train_precision(hp)
+            if self.train_precision not in HIFIGAN_TRAIN_PRECISIONS:
+                raise ValueError(f"{named} = {self.train_precision!r}: the HiFi-GAN generator trains in 'f32' or 'mixed' (f16 forward, bf16 backward, fp32 master "
+                                 "weights)")
         self.precision = "f32" if self.trainable else precision or geo["precision"]
         self.geo = geo = dict(geo, precision=self.precision)        # the precision that runs
-        f16 = self.precision == "f16"
+        f16 = self._f16 = self.precision == "f16" or self.train_precision == "mixed"      # the arithmetic of `__call__` and of the single operators
         self._conv_op, self._up_op = (ops.hifigan_conv_f16, ops.hifigan_upsample_f16) if f16 else (ops.hifigan_conv, ops.hifigan_upsample)
         if self.trainable:
             hifigan_train_geometry(geo)
+            if self.train_precision == "mixed":
+                hifigan_train_geometry_mixed(geo)
             if state_dict is None:
                 state_dict = hifigan_init(geo, seed)
         if state_dict is None:
@@ -1533,6 +1633,7 @@ class HiFiGAN:
             self.params = {k: t.to(self.device).requires_grad_(True) for k, t in w.items()}
             w = {k: t.detach() for k, t in self.params.items()}
             self._up_taps = [hifigan_up_taps(u, k).to(self.device) for u, k in zip(geo["rates"], geo["kernels"])]
+            self._pack = None                                       # 'mixed': (source pointers, images, job table, blocks) of hifigan_pack_images
         self._build_images(w)
 
     def _build_images(self, w):
@@ -1540,6 +1641,8 @@ class HiFiGAN:
         once for a frozen generator; a trainable one rebuilds them on the device at every `generate`, with the transposed images of the backward.
         precision 'f16': the convolutions' images are the packed fp16 images of `hifigan_pack_f16` instead (biases and conv_post stay float32)."""
         geo = self.geo
+        if self.trainable and self.train_precision == "mixed":
+            return self._pack_images(w)
         dev = lambda t: t.contiguous().to(self.device)
         packed = (lambda im, weight: hifigan_pack_f16(im, weight.shape[2])) if self.precision == "f16" else (lambda im, weight: im)
         pair = lambda q, image: (dev(packed(image(w[q + ".weight"]), w[q + ".weight"])), dev(w[q + ".bias"]))
@@ -1556,6 +1659,36 @@ class HiFiGAN:
             self.ups_t = [dev(hifigan_up_image_t(w[f"ups.{i}.weight"], u, self._up_taps[i])) for i, u in enumerate(geo["rates"])]
             self.blocks_t = [[(image_t(f"resblocks.{n}.convs1.{m}"), image_t(f"resblocks.{n}.convs2.{m}") if geo["resblock"] == "1" else None)
                               for m in range(len(geo["rd"][n % geo["nk"]]))] for n in range(len(self.blocks))]
+
+    def _pack_images(self, w):
+        """train_precision 'mixed': ONE `hifigan_pack_images` launch builds every image of the step - the fp16 forward images, the bf16 data-gradient images
+        and conv_post's rows - from the parameters' live storage.  The destinations and the job table are built once; they are rebuilt only when a parameter's
+        storage has moved.  The biases are the parameters themselves."""
+        geo = self.geo
+        plan = self._plan = getattr(self, "_plan", None) or hifigan_pack_plan(geo)
+        ptrs = tuple(w[key].data_ptr() for key, *_ in plan)
+        if self._pack is None or self._pack[0] != ptrs:
+            src = {key: w[key] for key, *_ in plan}
+            images, jobs, blocks = hifigan_pack_jobs(plan, src, self.device)
+            self._pack = (ptrs, images, jobs, blocks)
+            by = {}
+            for (key, kind, *_), image in zip(plan, images):
+                by[(key[:-len(".weight")], kind)] = image
+            self._pack_by = by
+        img = self._pack_by
+        ops.hifigan_pack_images(self._pack[2], self._pack[3])
+        pair = lambda q, kind: (img[(q, kind)], w[q + ".bias"])
+        self.pre = pair("conv_pre", "conv_f16")
+        self.ups = [pair(f"ups.{i}", "up_f16") for i in range(len(geo["rates"]))]
+        self.ups_t = [img[(f"ups.{i}", "up_t_bf16")] for i in range(len(geo["rates"]))]
+        type1 = geo["resblock"] == "1"
+        self.blocks, self.blocks_t = [], []
+        for n in range(len(geo["rates"]) * geo["nk"]):
+            ds = geo["rd"][n % geo["nk"]]
+            q1, q2 = f"resblocks.{n}.convs1.", f"resblocks.{n}.convs2."
+            self.blocks.append([(d, pair(q1 + str(m), "conv_f16"), pair(q2 + str(m), "conv_f16") if type1 else None) for m, d in enumerate(ds)])
+            self.blocks_t.append([(img[(q1 + str(m), "conv_t_bf16")], img[(q2 + str(m), "conv_t_bf16")] if type1 else None) for m in range(len(ds))])
+        self.post = (img[("conv_post", "post_f32")], w["conv_post.bias"])
 
     def _work(self, B, L):
         """Work buffers of a call (two stage outputs that alternate, the transposed convolution's output and two resblock buffers): views of ONE set sized for
@@ -1585,11 +1718,11 @@ class HiFiGAN:
     def _image(self, image, weight):
         """A torch weight -> the image this generator's launches take, on the device (f32: K-major; f16: packed)"""
         weight = weight.to(device=self.device, dtype=torch.float32)
-        return hifigan_pack_f16(image(weight), weight.shape[2]) if self.precision == "f16" else image(weight)
+        return hifigan_pack_f16(image(weight), weight.shape[2]) if self._f16 else image(weight)
 
     def _image_sizes(self, image, cin):
         """(taps, Cout) of an image over `cin` input channels"""
-        return (image.shape[0], image.shape[2]) if self.precision == "f16" else (image.shape[0] // cin, image.shape[1])
+        return (image.shape[0], image.shape[2]) if self._f16 else (image.shape[0] // cin, image.shape[1])
 
     def conv(self, x, frame_lengths, key=None, weight=None, bias=None, dilation=1, slope=1.0, residual=None, out=None, accumulate=0, divisor=1.0,
              channels_first=False):

@@ -1006,6 +1006,33 @@ int glowtts_hifigan_post_bwd(const float *dwav, const float *wav, const float *x
 int glowtts_hifigan_wgrad(const float *x, const float *dy, const int32_t *frame_lengths, float *work, float *dw, float *dbias, int B, int Lmax, int mult,
                           int Cin, int Cout, int taps, int dilation, int rate, float slope, float scale, int channels_first, void *stream);
 
+/* ---- training the HiFi-GAN generator in mixed precision (csrc/hifigan_mixed_ops.hip; additions, the ABI version stays) ----
+ * The forward of the mode is the fp16 inference forward (glowtts_hifigan_conv_f16 / _upsample_f16 / glowtts_hifigan_post); these are the backward's matrix
+ * products on v_mfma_f32_16x16x32_bf16 with fp32 sums.  Every tensor in memory stays f32; arguments, rows, lengths, ownership, epilogues, the partition of the
+ * weight gradient and its work buffer (glowtts_hifigan_wgrad_work_floats) are those of the f32 entries above.  Operands are rounded to bf16, nearest even, no
+ * clamp; run-to-run and batch-independent bit-identity as for the f32 entries.
+ * Supported (glowtts_hifigan_train_supported_mixed, else GLOWTTS_E_ARG before any launch): glowtts_hifigan_train_supported and glowtts_hifigan_supported_f16
+ * with the 16-bit tiles' LDS terms; Cout == 1 (conv_post) answers for the f32 launches that serve it.
+ * glowtts_hifigan_conv_bwd_bf16: glowtts_hifigan_conv_bwd, logged as `hifigan_conv_bwd_bf16`; dy is rounded as it lies in memory (before `scale`); wt is the
+ *   bf16 image [taps][pad32(Cout) / 8][Cin][8] of the tap-reversed, channel-transposed weights (element (tap, k, n) at ((tap Kp / 8 + k / 8) Cin + n) 8 + k % 8).
+ * glowtts_hifigan_upsample_bwd_bf16: glowtts_hifigan_upsample_bwd, logged as `hifigan_upsample_bwd_bf16`; wt is the bf16 image
+ *   [offsets][pad32(rate Cout) / 8][Cin][8] of the view's image with its zero rows.
+ * glowtts_hifigan_wgrad_bf16: glowtts_hifigan_wgrad with lrelu(x) and dy rounded to bf16, logged as `hifigan_wgrad_bf16` and `hifigan_wgrad_sum`; the bias
+ *   gradient is the column sum of the unrounded dy, in double.  Cout == 1 runs glowtts_hifigan_wgrad itself (logged as `hifigan_wgrad`).
+ * glowtts_hifigan_pack_images: ONE launch, logged as `hifigan_pack_images`, builds weight images from fp32 master weights through a DEVICE job table of
+ *   njobs x 8 int64: source, destination, kind, Cin, Cout, taps, rate (of the forward convolution), first block; total_blocks = the jobs' blocks of 256
+ *   16-byte groups (kind 4: floats), first blocks ascending from 0.  Kinds: 0 / 1 the fp16 forward image of a Conv1d / ConvTranspose1d weight
+ *   ([taps][pad32(Cin) / 8][Cout][8], clamped to +-65504), 2 / 3 the bf16 data-gradient images above, 4 conv_post's f32 [taps][Cin] rows. */
+int glowtts_hifigan_train_supported_mixed(int Cin, int Cout, int taps, int dilation, int rate);
+int glowtts_hifigan_conv_bwd_bf16(const float *dy, const uint16_t *wt, const float *x, const float *residual, float *out, const int32_t *frame_lengths, int B,
+                                  int Lmax, int mult, int Cin, int Cout, int taps, int dilation, float mask_slope, float scale, float res_scale, int accumulate,
+                                  void *stream);
+int glowtts_hifigan_upsample_bwd_bf16(const float *dy, const uint16_t *wt, const float *x, float *out, const int32_t *frame_lengths, int B, int Lmax, int mult,
+                                      int Cin, int Cout, int taps, int rate, float mask_slope, void *stream);
+int glowtts_hifigan_wgrad_bf16(const float *x, const float *dy, const int32_t *frame_lengths, float *work, float *dw, float *dbias, int B, int Lmax, int mult,
+                               int Cin, int Cout, int taps, int dilation, int rate, float slope, float scale, int channels_first, void *stream);
+int glowtts_hifigan_pack_images(const int64_t *jobs, int njobs, int total_blocks, void *stream);
+
 /* ---- GE2E speaker encoder: stacked LSTM -> linear -> d-vector (csrc/ge2e_ops.hip; inference, f32; additions, the ABI version stays) ----
  * torch.nn.LSTM's definition (gates i, f, g, o; bias b_ih + b_hh; h0 = c0 = 0), then e = W h_{T-1}^{top} + b per slice, w = e / max(|e|, 1e-12),
  * d = normalize(mean over an utterance's Samples consecutive slices of w).  Every product runs on v_mfma_f32_16x16x4_f32; a sequence's values depend on
