@@ -343,6 +343,10 @@ SIGNATURES = {
     "glowtts_hifigan_disc_conv_bwd": (I, [P] * 6 + [I] * 6 + [F, P]),
     "glowtts_hifigan_disc_first_bwd": (I, [P] * 3 + [I] * 6 + [P]),
     "glowtts_hifigan_disc_wgrad": (I, [P] * 5 + [I] * 8 + [F, P]),
+    "glowtts_hifigan_disc_supported_bf16": (I, [I] * 3),
+    "glowtts_hifigan_disc_conv_bf16": (I, [P] * 4 + [I] * 6 + [F, P]),
+    "glowtts_hifigan_disc_conv_bwd_bf16": (I, [P] * 6 + [I] * 6 + [F, P]),
+    "glowtts_hifigan_disc_wgrad_bf16": (I, [P] * 5 + [I] * 8 + [F, P]),
     "glowtts_hifigan_msd_supported": (I, [I] * 5),
     "glowtts_hifigan_msd_work_floats": (L, [I] * 6),
     "glowtts_hifigan_msd_pool": (I, [P] * 2 + [I] * 2 + [P]),
@@ -378,5 +382,5 @@ VALUE_RETURNING = frozenset({
     "glowtts_cond_linear_supported", "glowtts_gst_supported", "glowtts_conv3x3s2_supported", "glowtts_dur_proj_supported", "glowtts_vocoder_supported",
     "glowtts_pwg_supported", "glowtts_pwg_supported_bf16", "glowtts_hifigan_supported", "glowtts_hifigan_supported_f16", "glowtts_hifigan_train_supported", "glowtts_hifigan_train_supported_mixed", "glowtts_ge2e_supported", "glowtts_pwg_train_supported", "glowtts_stft_loss_supported",
     "glowtts_mel_loss_supported",
-    "glowtts_pwg_disc_supported", "glowtts_hifigan_disc_supported", "glowtts_hifigan_msd_supported", "glowtts_mel_cepstrum_supported", "glowtts_dtw_supported", "glowtts_tsne_supported",
+    "glowtts_pwg_disc_supported", "glowtts_hifigan_disc_supported", "glowtts_hifigan_disc_supported_bf16", "glowtts_hifigan_msd_supported", "glowtts_mel_cepstrum_supported", "glowtts_dtw_supported", "glowtts_tsne_supported",
 })

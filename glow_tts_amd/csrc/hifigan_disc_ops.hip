@@ -32,13 +32,12 @@
 //                           `hifigan_disc_wgrad_sum`.
 // The multi-scale discriminator (hifigan_msd_ops.hip) runs its dense last layer and its conv_post on these kernels at period 1, where `hd_source_row` is a
 // zero-padded convolution over time: the entry points glowtts_hifigan_msd_dense* / _post* at the end, launch-log classes `hifigan_msd_dense*` / `_post*`.
-// Period 1 stays refused by the multi-period entry points.
-#include "hifigan_common.h"
+// Period 1 stays refused by the multi-period entry points.  The bf16 mode of the middle convolutions is hifigan_disc_bf16_ops.hip.
+#include "hifigan_disc_common.h"
 #include "hifigan_wgrad.h"
 
 namespace {
 
-constexpr int HD_TAPS = 5, HD_POST_TAPS = 3, HD_MAX_PERIOD = 16, HD_MAX_CHANNELS = 1024;
 constexpr int HD_FM_ELEMS = 4096;                          // elements of one block of the feature-matching sum
 
 // grid (ceil(Ndst / 64), Cdst / (RT NT 16), B); src [B][Hsrc p][Csrc] -> out [B][Ndst][Cdst]; dynamic LDS [taps][64] rows of lds_stride_of(min(Csrc, 64)) floats.
@@ -199,12 +198,7 @@ __global__ __launch_bounds__(THREADS) void hifigan_disc_first_bwd_kernel(const f
 }
 
 // ---- host side ----
-bool hd_period(int p) { return p >= 2 && p <= HD_MAX_PERIOD; }
-bool hd_width(int C) { return C >= 16 && C <= HD_MAX_CHANNELS && C % 16 == 0; }
-bool hd_stride(int s) { return s == 1 || s == 3; }
-int hd_rows_out(int H, int s) { return (H - 1) / s + 1; }
-// every batch row of the full length: B H p <= 2^30 rows (a grid of one thread per row and four channels stays below 2^31 workgroups at 1024 channels)
-bool hd_bad_rows(int B, int H, int p) { return B < 1 || B > 65535 || H < 1 || !hd_period(p) || (int64_t)B * H * p > ((int64_t)1 << 30); }
+// (the limits and the argument checks: hifigan_disc_common.h)
 int hd_lds_bytes(int Csrc) { return hg_lds_bytes((HD_TAPS - 1) * TM, Csrc); }         // [5][64] rows
 unsigned hd_quads(int64_t rows, int C) { return (unsigned)((rows * (C / 4) + THREADS - 1) / THREADS); }
 

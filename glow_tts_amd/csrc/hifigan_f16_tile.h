@@ -6,7 +6,11 @@
 //   BWD  a data gradient (`hg_tile<.., true>`'s epilogue): the sums start at zero and y = sum * (maskb > 0 ? 1 : mslope) * divisor + resb * res_scale, then
 //        out = y or (accumulate) out = out + y; maskb: the kept fp32 input of the forward's LeakyReLU, laid out as outb.  The staged rows (dy) are taken as they
 //        lie in memory (slope 1).
-// Every BWD / OP term is a compile-time branch: the <RT, NT, HfF16, false> instantiations are the code they were.
+//   FOLD the folded row source of `hg_tile` (hifigan_common.h), for the multi-period discriminator (hifigan_disc_bf16_ops.hip): the tile stages the 64 rows
+//        of EVERY tap, [taps][64] rows through `hd_source_row<BWD>` - tap m's rows at LDS row m * 64, zero rows where the map gives none - with the span
+//        mode's loads (unconditional, from an address clamped into the slab, zeroed afterwards) and its K padding to 32 per chunk.  T is then the count of
+//        flat OUTPUT rows and Hsrc the source's rows h; tp.p, tp.s are the period and the row stride.  Channels-last sources alone.
+// Every BWD / OP / FOLD term is a compile-time branch: the <RT, NT, HfF16, false> instantiations are the code they were.
 #pragma once
 #include "hifigan_common.h"
 
@@ -52,18 +56,20 @@ struct HfBf16 {
 };
 
 // The tile body.  inb: the utterance's slab (channels-last [..][Cin], or channels-first [Cin][tin_max] with cf); position s0 + i writes output row
-// (s0 + i) os + oph of outb ([..][Cout]) when it is below T, the utterance's rows at the input's rate.  Xs: LDS, (64 + reach) rows of min(Cp, 64) + 8 elements.
-template <int RT, int NT, typename OP = HfF16, bool BWD = false>
+// (s0 + i) os + oph of outb ([..][Cout]) when it is below T, the utterance's rows at the input's rate.  Xs: LDS, (64 + reach) rows of min(Cp, 64) + 8 elements
+// (FOLD: taps 64 rows).
+template <int RT, int NT, typename OP = HfF16, bool BWD = false, bool FOLD = false>
 __device__ __forceinline__ void hf_tile(const float* __restrict__ inb, const uint16_t* __restrict__ w, const float* __restrict__ bias, const float* resb,
                                         float* outb, uint16_t* Xs, int T, int tin_max, int s0, int Cin, int Cout, int colgroup, HgTaps tp, float slope, int cf,
-                                        int os, int oph, int accumulate, float divisor, const float* maskb = nullptr, float mslope = 1.f, float res_scale = 1.f)
+                                        int os, int oph, int accumulate, float divisor, const float* maskb = nullptr, float mslope = 1.f, float res_scale = 1.f,
+                                        int Hsrc = 0)
 {
     constexpr int WR = WAVES / RT, WC = WAVES / WR;        // the waves as WR row groups x WC column groups
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
     const int wr = wave % WR, wc = wave / WR;
     const int col0 = (colgroup * WC + wc) * NT * 16;
     const int last = tp.o0 + (tp.nt - 1) * tp.ts;
-    const int lo = min(tp.o0, last), span = TM + max(tp.o0, last) - lo;
+    const int lo = FOLD ? 0 : min(tp.o0, last), span = FOLD ? tp.nt * TM : TM + max(tp.o0, last) - lo;
     const int Cp = hf_pad32(Cin), xs = min(Cp, HG_CK) + 8; // the image's rows per tap; the LDS row stride in elements
     const Chunk16* wv = reinterpret_cast<const Chunk16*>(w);
 
@@ -93,7 +99,7 @@ __device__ __forceinline__ void hf_tile(const float* __restrict__ inb, const uin
         load_tap(0, cur);                                  // in flight while the chunk is staged
 
         if (c0) __syncthreads();                           // every wave is done with the previous chunk
-        if (cf) {                                          // channels-first source (the mel): consecutive threads along the rows
+        if (!FOLD && cf) {                                 // channels-first source (the mel): consecutive threads along the rows
             for (int e = tid; e < span * ckp; e += THREADS) {
                 const int c = e / span, row = e - c * span, t = s0 + lo + row;
                 Xs[row * xs + c] = (c < ck && t >= 0 && t < T) ? OP::bits(lrelu(inb[(size_t)(c0 + c) * tin_max + t], slope)) : (uint16_t)0;
@@ -107,9 +113,19 @@ __device__ __forceinline__ void hf_tile(const float* __restrict__ inb, const uin
                 bool ok[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    const int e = e0 + u * THREADS, row = e >> ksh, k4 = (e & (kq - 1)) * 4, t = s0 + lo + row;
-                    ok[u] = e < total && t >= 0 && t < T && k4 < ck;
-                    v[u] = *reinterpret_cast<const float4*>(inb + (size_t)min(max(t, 0), T - 1) * Cin + c0 + min(k4, ck - 4));
+                    const int e = e0 + u * THREADS, row = e >> ksh, k4 = (e & (kq - 1)) * 4;
+                    int t;
+                    if constexpr (FOLD) {                  // the source row of (output row, tap); row 0 of the slab where there is none
+                        const int m = row / TM, n = s0 + row - m * TM;
+                        int from = 0;
+                        ok[u] = e < total && n < T && hd_source_row<BWD>(n, m, (tp.nt - 1) / 2, tp.p, tp.s, Hsrc, &from) && k4 < ck;
+                        t = ok[u] ? from : 0;
+                    } else {
+                        t = s0 + lo + row;
+                        ok[u] = e < total && t >= 0 && t < T && k4 < ck;
+                        t = min(max(t, 0), T - 1);
+                    }
+                    v[u] = *reinterpret_cast<const float4*>(inb + (size_t)t * Cin + c0 + min(k4, ck - 4));
                 }
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
@@ -126,7 +142,7 @@ __device__ __forceinline__ void hf_tile(const float* __restrict__ inb, const uin
         for (int m = 0; m < tp.nt; ++m) {
             Chunk16 nxt[2][NT];
             if (m + 1 < tp.nt) load_tap(m + 1, nxt);
-            const uint16_t* xa = Xs + (wr * RT * 16 + r + tp.o0 + m * tp.ts - lo) * xs + q * 8;
+            const uint16_t* xa = Xs + (wr * RT * 16 + r + (FOLD ? m * TM : tp.o0 + m * tp.ts - lo)) * xs + q * 8;
             f32x4 part[RT][NT];                            // this (chunk, tap)'s chain
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt)
@@ -179,6 +195,6 @@ __device__ __forceinline__ void hf_tile(const float* __restrict__ inb, const uin
         }
 }
 
-int hf_lds_bytes(int reach, int Cin) { return (TM + reach) * (std::min(hf_pad32(Cin), HG_CK) + 8) * 2; }
+int hf_lds_bytes(int reach, int Cin) { return (TM + reach) * (std::min(hf_pad32(Cin), HG_CK) + 8) * 2; }         // FOLD: reach = (taps - 1) 64
 
 }  // namespace

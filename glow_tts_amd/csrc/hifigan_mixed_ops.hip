@@ -7,7 +7,7 @@
 //                              scale - and the tap-reversed, channel-transposed image are bf16 (nearest even, no clamp), the sums fp32 from zero in the f32
 //                              kernel's chunk and tap order, the epilogue the f32 kernel's: * lrelu'(x) * scale + residual * res_scale, then accumulate.
 //   hifigan_upsample_bwd_bf16  the same kernel over dy read as [T][u Cout] against the view's image with its zero rows.
-//   hifigan_wgrad_bf16         dW[tap][ci][co] = sum over rows of bf16(lrelu(x)[t + off(tap)][ci]) bf16(dy[t][co]), fp32 sums, on the f32 kernel's fixed partition
+//   hifigan_wgrad_bf16         (the kernel is hifigan_wgrad_bf16.h's, shared with the discriminator's bf16 mode)  dW[tap][ci][co] = sum over rows of bf16(lrelu(x)[t + off(tap)][ci]) bf16(dy[t][co]), fp32 sums, on the f32 kernel's fixed partition
 //                              and 32 x 32 workgroup tile, so `hw_sizes`, the partial layout [splits][taps CiP CoP + CoP] and `hifigan_wgrad_sum` serve both
 //                              modes.  K is the ROW index, so a lane needs 8 consecutive rows of one channel: the tile stages lrelu(x) (with the taps' reach)
 //                              and dy as bf16 ROW-major [row][32 channels] (row stride 80 bytes: a multiple of 8, odd in 16-byte slots) and reads both MFMA
@@ -19,17 +19,15 @@
 //   hifigan_pack_images        ONE launch builds every weight image of a step from the fp32 master weights through a device job table (built once by the
 //                              caller): the fp16 forward images (conv / transposed conv: `vocoder.hifigan_pack_f16`'s bytes), the bf16 data-gradient images
 //                              (tap-reversed and channel-transposed; the transposed convolution's view with its zero fill) and conv_post's f32 [taps][Cin]
-//                              rows.  A thread writes one 16-byte group (eight k of one column).
+//                              rows.  A thread writes one 16-byte group (eight k of one column).  Two more kinds serve the multi-period discriminator's
+//                              bf16 mode (hifigan_disc_bf16_ops.hip): a Conv weight's bf16 forward image and its channel-transposed image WITHOUT the
+//                              tap reversal (the discriminator's inverse row map reverses the taps).
 #include "hifigan_f16_tile.h"
-#include "hifigan_wgrad.h"
+#include "hifigan_wgrad_bf16.h"
 
 namespace {
 
 constexpr int HM_MAX_VIEW = 4096;                          // u Cout of the transposed convolution's view (hifigan_train_ops.hip's limit)
-constexpr int HWB_LD = 40;                                 // bf16 per LDS row of the weight gradient: 32 channels + 16 bytes
-constexpr int HWB_BIAS_BYTES = 32 * HW_C * 8;              // the bias gradient's [32 row groups][32 columns] doubles
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 // the row offsets of the transposed convolution in the [T][u Cout] view: [lo, hi] (hifigan_train_ops.hip's hg_up_reach)
 __host__ __device__ __forceinline__ void hm_up_reach(int k, int u, int* lo, int* hi)
@@ -58,107 +56,6 @@ __global__ __launch_bounds__(THREADS) void hifigan_bwd_bf16_kernel(const float* 
                                   1.f, 0, 1, 0, accumulate, scale, x + row0 * Cdx, mslope, res_scale);
 }
 
-// one MFMA operand: rows p .. p + 7 (LDS rows) of 16 channels, transposed; every lane of the wave supplies an address (EXEC all ones)
-__device__ __forceinline__ Chunk16 hwb_frag(const uint16_t* p)
-{
-    s16x4 v[2] = {__builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p)),
-                  __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p + 4 * HWB_LD))};
-    return *reinterpret_cast<Chunk16*>(v);
-}
-
-// grid (ceil(Ca / 32), ceil(Cd / 32), splits); dynamic LDS (64 + reach + 64) rows of 40 bf16, then the bias gradient's doubles
-template <int MAXT>
-__global__ __launch_bounds__(THREADS) void hifigan_wgrad_bf16_kernel(const HwArgs a)
-{
-    extern __shared__ __attribute__((aligned(16))) uint16_t hwb_smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
-    const int wr = wave & 1, wc = wave >> 1;               // the wave's tile: 16 channels of x, 16 of dy
-    const int ci0 = blockIdx.x * HW_C, co0 = blockIdx.y * HW_C;
-    const int last = a.o0 + (a.taps - 1) * a.ts, lo = min(a.o0, last), span = TM + max(a.o0, last) - lo;
-    uint16_t* Xs = hwb_smem;
-    uint16_t* Ds = hwb_smem + span * HWB_LD;
-    const int Tmax = a.Lmax * a.mult;
-    const bool with_bias = blockIdx.x == 0;                // (uniform over the workgroup)
-    const int srow = tid >> 3, sk4 = (tid & 7) * 4;        // the staging thread's rows srow, srow + 32, .. and its four channels
-
-    f32x4 acc[MAXT];
-    double sb[4] = {0.0, 0.0, 0.0, 0.0};                   // the bias gradient: this thread's four columns of the unrounded dy, in double
-#pragma unroll
-    for (int j = 0; j < MAXT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int units = a.B * a.nchunk, u_end = min(((int)blockIdx.z + 1) * a.group, units);
-    for (int unit = blockIdx.z * a.group; unit < u_end; ++unit) {
-        const int b = unit / a.nchunk, chunk = unit - b * a.nchunk;
-        const int T = min(a.lengths[b], a.Lmax) * a.mult, t_end = min((chunk + 1) * HW_ROWS, T);
-        const float* ab = a.a + (size_t)b * Tmax * a.Ca;
-        const float* db = a.dy + (size_t)b * Tmax * a.Cd;
-        for (int t0 = chunk * HW_ROWS; t0 < t_end; t0 += TM) {
-            __syncthreads();                               // every wave is done with the previous tile
-            if (a.cf) {                                    // channels-first source (the mel): consecutive threads along the rows
-                for (int e = tid; e < span * HW_C; e += THREADS) {
-                    const int c = e / span, row = e - c * span, t = t0 + lo + row;
-                    Xs[row * HWB_LD + c] = (t >= 0 && t < T && ci0 + c < a.Ca) ? bf16_bits(lrelu(ab[(size_t)(ci0 + c) * Tmax + t], a.slope)) : (uint16_t)0;
-                }
-            } else {
-                for (int row = srow; row < span; row += THREADS / 8) {
-                    const int t = t0 + lo + row;
-                    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (t >= 0 && t < T && ci0 + sk4 < a.Ca) {
-                        v = *reinterpret_cast<const float4*>(ab + (size_t)t * a.Ca + ci0 + sk4);
-                        v.x = lrelu(v.x, a.slope); v.y = lrelu(v.y, a.slope); v.z = lrelu(v.z, a.slope); v.w = lrelu(v.w, a.slope);
-                    }
-                    *reinterpret_cast<u32x2*>(Xs + row * HWB_LD + sk4) = u32x2{pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w)};
-                }
-            }
-            for (int row = srow; row < TM; row += THREADS / 8) {
-                const int t = t0 + row;
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (t < t_end && co0 + sk4 < a.Cd) v = *reinterpret_cast<const float4*>(db + (size_t)t * a.Cd + co0 + sk4);
-                *reinterpret_cast<u32x2*>(Ds + row * HWB_LD + sk4) = u32x2{pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w)};
-                if (with_bias) {
-                    sb[0] += (double)v.x; sb[1] += (double)v.y; sb[2] += (double)v.z; sb[3] += (double)v.w;
-                }
-            }
-            __syncthreads();
-            const int k_end = min(TM, (t_end - t0 + 31) & ~31);    // rows of dy beyond the chunk are zero (uniform over the workgroup)
-            // lane 4 q' + p of a 16-lane group supplies row q', channels 4 p .. 4 p + 3 of the group's 4 x 16 block; the group l >> 4 takes k = 8 (l >> 4) ..
-            const uint16_t* xa = Xs + (8 * q + (r >> 2) + a.o0 - lo) * HWB_LD + wr * 16 + 4 * (r & 3);
-            const uint16_t* da = Ds + (8 * q + (r >> 2)) * HWB_LD + wc * 16 + 4 * (r & 3);
-            f32x4 part[MAXT];                              // this tile's chains start at zero
-#pragma unroll
-            for (int j = 0; j < MAXT; ++j) part[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-            for (int k0 = 0; k0 < k_end; k0 += 32) {
-                const Chunk16 bv = hwb_frag(da + k0 * HWB_LD);
-#pragma unroll
-                for (int j = 0; j < MAXT; ++j)
-                    if (j < a.taps) part[j] = mfma16_bf16(hwb_frag(xa + (k0 + j * a.ts) * HWB_LD), bv, part[j]);      // (uniform)
-            }
-#pragma unroll
-            for (int j = 0; j < MAXT; ++j) acc[j] += part[j];
-        }
-    }
-
-    const int CiP = gridDim.x * HW_C, CoP = gridDim.y * HW_C;
-    float* out = a.partial + (size_t)blockIdx.z * ((size_t)a.taps * CiP * CoP + CoP);
-#pragma unroll
-    for (int j = 0; j < MAXT; ++j)
-        if (j < a.taps) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) out[((size_t)j * CiP + ci0 + wr * 16 + q * 4 + i) * CoP + co0 + wc * 16 + r] = acc[j][i];
-        }
-    if (with_bias) {                                       // the 32 row groups of a column in ascending order
-        double* Bs = reinterpret_cast<double*>(hwb_smem + (span + TM) * HWB_LD);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) Bs[srow * HW_C + sk4 + i] = sb[i];
-        __syncthreads();
-        if (tid < HW_C) {
-            double s = 0.0;
-            for (int g = 0; g < THREADS / 8; ++g) s += Bs[g * HW_C + tid];
-            out[(size_t)a.taps * CiP * CoP + co0 + tid] = (float)s;
-        }
-    }
-}
-
 // ---- hifigan_pack_images ----
 // A job is HP_WORDS int64: source (fp32 master weight), destination, kind, Cin, Cout, taps, rate, first block.  Cin, Cout, taps, rate name the FORWARD
 // convolution.  Kinds 0 - 3 write [T'][Kp / 8][N][8] 16-bit images, element (tap t', k, n) with zeros for k from K to Kp = pad32(K):
@@ -167,8 +64,10 @@ __global__ __launch_bounds__(THREADS) void hifigan_wgrad_bf16_kernel(const HwArg
 //   2  bf16, the data gradient of 0:             T' = taps, K = Cout, N = Cin, W[k][n][taps - 1 - t']
 //   3  bf16, the data gradient of 1 in the view: T' = hi - lo + 1, K = rate Cout (k = (phase, output channel)), N = Cin, W[n][co][tap of (lo + t', phase)] or zero
 //   4  f32, conv_post [1][Cin][taps] -> [taps][Cin]
+//   5  bf16, Conv [Cout][Cin][taps] (kind 0 in bf16): T' = taps, K = Cin, N = Cout, W[n][k][t']
+//   6  bf16, the channel-transposed image of 5:  T' = taps, K = Cout, N = Cin, W[k][n][t'] (kind 2 without the tap reversal)
 constexpr int HP_WORDS = 8;
-enum { HP_CONV_F16 = 0, HP_UP_F16 = 1, HP_CONV_T_BF16 = 2, HP_UP_T_BF16 = 3, HP_POST_F32 = 4 };
+enum { HP_CONV_F16 = 0, HP_UP_F16 = 1, HP_CONV_T_BF16 = 2, HP_UP_T_BF16 = 3, HP_POST_F32 = 4, HP_CONV_BF16 = 5, HP_CONV_KT_BF16 = 6 };
 
 __global__ __launch_bounds__(THREADS) void hifigan_pack_images_kernel(const int64_t* __restrict__ jobs, int njobs)
 {
@@ -190,7 +89,8 @@ __global__ __launch_bounds__(THREADS) void hifigan_pack_images_kernel(const int6
     int lo = 0, hi = taps - 1;
     if (kind == HP_UP_T_BF16) hm_up_reach(taps, rate, &lo, &hi);
     const int Tw = hi - lo + 1;
-    const int K = kind <= HP_UP_F16 ? Cin : (kind == HP_CONV_T_BF16 ? Cout : rate * Cout), N = kind <= HP_UP_F16 ? Cout : Cin, K8 = hf_pad32(K) >> 3;
+    const bool fwd = kind <= HP_UP_F16 || kind == HP_CONV_BF16;    // K = the forward's input channels
+    const int K = fwd ? Cin : (kind == HP_UP_T_BF16 ? rate * Cout : Cout), N = fwd ? Cout : Cin, K8 = hf_pad32(K) >> 3;
     if (g >= (int64_t)Tw * K8 * N) return;
     const int n = (int)(g % N), kg = (int)((g / N) % K8), tw = (int)(g / ((int64_t)N * K8));
     uint32_t word[4];
@@ -202,9 +102,10 @@ __global__ __launch_bounds__(THREADS) void hifigan_pack_images_kernel(const int6
             const int k = kg * 8 + h * 2 + i;
             v[i] = 0.f;
             if (k < K) {
-                if (kind == HP_CONV_F16) v[i] = src[((size_t)n * Cin + k) * taps + tw];
+                if (kind == HP_CONV_F16 || kind == HP_CONV_BF16) v[i] = src[((size_t)n * Cin + k) * taps + tw];
                 else if (kind == HP_UP_F16) v[i] = src[((size_t)k * Cout + n) * taps + tw];
                 else if (kind == HP_CONV_T_BF16) v[i] = src[((size_t)k * Cin + n) * taps + (taps - 1 - tw)];
+                else if (kind == HP_CONV_KT_BF16) v[i] = src[((size_t)k * Cin + n) * taps + tw];
                 else {
                     const int ph = k / Cout, co = k - ph * Cout;
                     const int shift = ph + (taps - rate) / 2, j0 = shift % rate, m = tw + lo + shift / rate;
@@ -230,8 +131,6 @@ bool hm_walk(int Cd, int taps, int dilation, int rate, int* wt, int* o0, int* ts
     }
     return *wt >= 1 && *wt <= HW_MAX_TAPS;
 }
-
-int hwb_lds_bytes(int reach) { return (TM + reach + TM) * HWB_LD * 2 + HWB_BIAS_BYTES; }
 
 int hm_data_gradient(const float* dy, const uint16_t* wt, const float* x, const float* res, float* out, const int32_t* lengths, int B, int Lmax, int mult, int Cdy,
                      int Cdx, int taps, int o0, int ts, float mslope, float scale, float res_scale, int accumulate, void* stream)

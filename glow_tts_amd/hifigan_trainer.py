@@ -19,7 +19,10 @@ with the seeded-init discriminator.  Without the sub-block nothing differs from 
 `vocoder.HiFiGANDiscriminators`, the sums over p above run over the periods and then the scales, L_fm is the periods' sum plus the scales', and the one
 discriminator optimizer, clipping and step decay cover the union of the parameters (the scales' under `scale_discriminators.`), which is what the
 checkpoint's `discriminator` then holds.  A checkpoint whose `discriminator` lacks the scales' names resumes such a run only under the stage-one rule
-(`Steps <= Start_Step`: both seeded inits are untouched).  Without the sub-block nothing differs.  A `Vocoder.Train.Discriminator` block - the Parallel
+(`Steps <= Start_Step`: both seeded inits are untouched).  Without the sub-block nothing differs.  The optional key
+`Vocoder.Train.Adversarial.Precision: 'bf16'` (DESIGN.md "The multi-period discriminator in bf16") runs the multi-period discriminator's middle convolutions
+on bf16 MFMAs, forward and backward, over fp32 master weights, tensors, optimizer and checkpoints; it governs the period discriminator alone (the
+multi-scale discriminator stays f32), is read by the discriminator's constructor from the yaml, and a run resumes in either precision.  A `Vocoder.Train.Discriminator` block - the Parallel
 WaveGAN discriminator's - is refused."""
 import logging
 

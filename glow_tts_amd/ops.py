@@ -306,3 +306,84 @@ def hifigan_pack_images(jobs, total_blocks):
     if jobs.dtype != torch.int64 or jobs.dim() != 2 or jobs.shape[1] != 8 or not jobs.is_contiguous() or not jobs.is_cuda:
         raise _lib.GlowTTSHipError("glowtts_hifigan_pack_images needs the int64 device job table [njobs, 8] of vocoder.hifigan_pack_jobs")
     _lib.api().glowtts_hifigan_pack_images(_lib.ptr(jobs), jobs.shape[0], int(total_blocks), _lib.stream())
+
+
+# ---- the bf16 mode of the HiFi-GAN multi-period discriminator (csrc/hifigan_disc_bf16_ops.hip): the middle convolutions (5 taps); activations are
+# [B, H * period, C] float32, the images the packed bf16 images of vocoder.hifigan_disc_pack_bf16 ([5, pad32(K) / 8, N, 8]) ----
+def _hifigan_disc_bf16_image(name, w, K, N):
+    if w.dtype != torch.bfloat16 or tuple(w.shape) != (5, (K + 31) // 32 * 4, N, 8) or not w.is_contiguous() or not w.is_cuda:
+        raise _lib.GlowTTSHipError(f"{name} needs the packed bf16 device image [5, {(K + 31) // 32 * 4}, {N}, 8] of vocoder.hifigan_disc_pack_bf16 for these sizes, "
+                                   f"got {w.dtype} {list(w.shape)} on {w.device}")
+
+
+def _hifigan_disc_f32(name, what, t, *shapes):
+    """t: a contiguous float32 device tensor of one of `shapes` - the kernels take every size from the arguments, so a wrong buffer would be read or written
+    out of bounds"""
+    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) not in shapes:
+        raise _lib.GlowTTSHipError(f"{name}: {what} must be a contiguous float32 device tensor {' or '.join(str(list(s)) for s in shapes)}, got {t.dtype} "
+                                   f"{list(t.shape)} on {t.device}")
+
+
+def _hifigan_disc_rows(name, x, H, period, stride):
+    """-> (B, Cin, rows of the layer's output per batch row) of an input x [B, H * period, Cin]"""
+    H, period, stride = int(H), int(period), int(stride)
+    if x.dim() != 3 or H < 1 or period < 1 or stride < 1:
+        raise _lib.GlowTTSHipError(f"{name}: x must be [B, H * period, Cin] with H, period, stride >= 1, got {list(x.shape)}, H = {H}, period = {period}, stride = {stride}")
+    _hifigan_disc_f32(name, "x", x, (x.shape[0], H * period, x.shape[2]))
+    return x.shape[0], x.shape[2], ((H - 1) // stride + 1) * period
+
+
+def hifigan_disc_conv_bf16(x, w, bias, out, H, period, stride, slope):
+    """x [B, H * period, Cin] (pre-activations) -> out [B, H' * period, Cout] = bias + conv(bf16(lrelu(x, slope)), bf16 w), fp32 sums
+    (glowtts_hifigan_disc_conv_bf16); w: the forward image.  H' = (H - 1) // stride + 1."""
+    name = "glowtts_hifigan_disc_conv_bf16"
+    B, Cin, rows = _hifigan_disc_rows(name, x, H, period, stride)
+    if out.dim() != 3:
+        raise _lib.GlowTTSHipError(f"{name}: out must be [B, H' * period, Cout], got {list(out.shape)}")
+    Cout = out.shape[2]
+    _hifigan_disc_f32(name, "out", out, (B, rows, Cout))
+    _hifigan_disc_f32(name, "bias", bias, (Cout,))
+    _hifigan_disc_bf16_image(name, w, Cin, Cout)
+    _lib.api().glowtts_hifigan_disc_conv_bf16(_lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(out), B, int(H), int(period), int(stride), Cin, Cout, float(slope),
+                                              _lib.stream())
+
+
+def hifigan_disc_conv_bwd_bf16(dy, wt, x, dx, H, period, stride, slope, inj=None, inj_scale=None):
+    """dy [B, H' * period, Cout] -> dx [B, H * period, Cin] = lrelu'(x) * (the transposed convolution of bf16(dy) with bf16 wt) + inj * inj_scale[0]
+    (glowtts_hifigan_disc_conv_bwd_bf16); wt: the channel-transposed image, taps not reversed; inj: laid out as dx, inj_scale: a device scalar."""
+    name = "glowtts_hifigan_disc_conv_bwd_bf16"
+    B, Cin, rows = _hifigan_disc_rows(name, x, H, period, stride)
+    if dy.dim() != 3:
+        raise _lib.GlowTTSHipError(f"{name}: dy must be [B, H' * period, Cout], got {list(dy.shape)}")
+    Cout = dy.shape[2]
+    _hifigan_disc_f32(name, "dy", dy, (B, rows, Cout))
+    _hifigan_disc_f32(name, "dx", dx, tuple(x.shape))
+    if inj is not None:
+        if inj_scale is None:
+            raise _lib.GlowTTSHipError(f"{name}: inj needs the device scalar inj_scale")
+        _hifigan_disc_f32(name, "inj", inj, tuple(x.shape))
+        _hifigan_disc_f32(name, "inj_scale", inj_scale, (1,), ())
+    _hifigan_disc_bf16_image(name, wt, Cout, Cin)
+    _lib.api().glowtts_hifigan_disc_conv_bwd_bf16(_lib.ptr(dy), _lib.ptr(wt), _lib.ptr(x), _lib.ptr(inj), _lib.ptr(inj_scale) if inj is not None else None, _lib.ptr(dx),
+                                                  B, int(H), int(period), int(stride), Cin, Cout, float(slope), _lib.stream())
+
+
+def hifigan_disc_wgrad_bf16(x, dy, work, dw, dbias, H, period, stride, slope):
+    """dw [Cout, Cin, 5(, 1)] and dbias [Cout] of one middle convolution from its input x [B, H * period, Cin] before the LeakyReLU and dy
+    [B, H' * period, Cout], both rounded to bf16; the bias gradient from the unrounded dy (glowtts_hifigan_disc_wgrad_bf16).  work: at least
+    glowtts_hifigan_disc_work_floats(B, H' * period, Cin, Cout, 5) floats."""
+    name = "glowtts_hifigan_disc_wgrad_bf16"
+    B, Cin, rows = _hifigan_disc_rows(name, x, H, period, stride)
+    if dy.dim() != 3:
+        raise _lib.GlowTTSHipError(f"{name}: dy must be [B, H' * period, Cout], got {list(dy.shape)}")
+    Cout = dy.shape[2]
+    _hifigan_disc_f32(name, "dy", dy, (B, rows, Cout))
+    _hifigan_disc_f32(name, "dw", dw, (Cout, Cin, 5), (Cout, Cin, 5, 1))
+    _hifigan_disc_f32(name, "dbias", dbias, (Cout,))
+    need = int(_lib.api().glowtts_hifigan_disc_work_floats(B, rows, Cin, Cout, 5))
+    if need < 1 or work.dim() != 1 or work.numel() < need:
+        raise _lib.GlowTTSHipError(f"{name}: work must hold glowtts_hifigan_disc_work_floats(B, rows, Cin, Cout, 5) = {need} floats (0: sizes out of range), got "
+                                   f"{list(work.shape)}")
+    _hifigan_disc_f32(name, "work", work, tuple(work.shape))
+    _lib.api().glowtts_hifigan_disc_wgrad_bf16(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(work), _lib.ptr(dw), _lib.ptr(dbias), B, int(H), int(period), int(stride), Cin, Cout,
+                                               5, 0, float(slope), _lib.stream())

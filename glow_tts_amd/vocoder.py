@@ -1388,7 +1388,7 @@ def hifigan_pack_bf16(image, taps):
     return p.view(taps, -1, 8, N).permute(0, 1, 3, 2).contiguous()
 
 
-HIFIGAN_PACK_KINDS = {"conv_f16": 0, "up_f16": 1, "conv_t_bf16": 2, "up_t_bf16": 3, "post_f32": 4}
+HIFIGAN_PACK_KINDS = {"conv_f16": 0, "up_f16": 1, "conv_t_bf16": 2, "up_t_bf16": 3, "post_f32": 4, "conv_bf16": 5, "conv_kt_bf16": 6}
 
 
 def hifigan_pack_plan(geo):
@@ -1847,11 +1847,31 @@ MPD_DEFAULTS = {"Start_Step": 0, "Lambda_Adversarial": 1.0, "Lambda_Feature_Matc
                 "Learning_Rate_Decay": {"Step": 200000, "Gamma": 0.5}, "Periods": [2, 3, 5, 7, 11], "Channels": [32, 128, 512, 1024, 1024], "Negative_Slope": 0.1}
 MPD_TAPS, MPD_POST_TAPS, MPD_STRIDE, MPD_MAX_PERIOD, MPD_MAX_PERIODS, MPD_MAX_CHANNELS, MPD_MAX_WIDTHS = 5, 3, 3, 16, 8, 1024, 6
 MSD_BLOCK = "Multi_Scale"                                           # the optional sub-block of the multi-scale discriminator (below)
+# The optional key `Vocoder.Train.Adversarial.Precision`: 'f32' (absent: f32) or 'bf16' - the middle convolutions of the multi-period discriminator on bf16
+# MFMAs, forward and backward (DESIGN.md "The multi-period discriminator in bf16").  It governs the period discriminator ALONE: with `Multi_Scale` the
+# multi-scale discriminator stays f32 entirely.  Not a key of MPD_DEFAULTS: it appears in the settings only when the yaml has it.
+MPD_PRECISION, MPD_PRECISIONS = "Precision", ("f32", "bf16")
+
+
+def hifigan_disc_precision(hp, precision=None):
+    """The multi-period discriminator's precision: the argument, else the yaml's `Vocoder.Train.Adversarial.Precision`, else 'f32'; any other value raises a
+    ValueError naming the key (or the argument)."""
+    if precision is None:
+        block = plain_block(getattr(getattr(getattr(hp, "Vocoder", None), "Train", None), "Adversarial", None))
+        given = block.get(MPD_PRECISION, "f32") if isinstance(block, dict) else "f32"
+        name = f"{MPD_KEY}.{MPD_PRECISION}"
+    else:
+        given, name = precision, "precision"
+    if not isinstance(given, str) or given not in MPD_PRECISIONS:
+        raise ValueError(f"{name} = {given!r}: the multi-period discriminator runs in 'f32' or 'bf16' (the key governs the period discriminator alone; the "
+                         "multi-scale discriminator is f32)")
+    return given
 
 
 def hifigan_disc_settings(hp):
     """The optional yaml block `Vocoder.Train.Adversarial` over MPD_DEFAULTS (absent block: None), checked: a ValueError names every unknown or bad key.
-    The optional sub-block `Multi_Scale` (`hifigan_msd_settings`) appears in the result only when the yaml has it."""
+    The optional sub-block `Multi_Scale` (`hifigan_msd_settings`) and the optional key `Precision` ('f32' / 'bf16') appear in the result only when the yaml
+    has them."""
     block = getattr(getattr(getattr(hp, "Vocoder", None), "Train", None), "Adversarial", None)
     if block is None:
         return None
@@ -1869,7 +1889,9 @@ def hifigan_disc_settings(hp):
         need("Channels", lambda v: 2 <= len(v) <= MPD_MAX_WIDTHS and all(whole(c) and 16 <= int(c) <= MPD_MAX_CHANNELS and int(c) % 16 == 0 for c in v),
              "2 to {} widths, each a multiple of 16 in [16, {}]".format(MPD_MAX_WIDTHS, MPD_MAX_CHANNELS))
         need("Negative_Slope", lambda v: 0 <= float(v) < 1, "in [0, 1)")
-    s = overlay_settings(block, MPD_DEFAULTS, MPD_KEY, "vocoder", rules, also=(MSD_BLOCK,))
+    s = overlay_settings(block, MPD_DEFAULTS, MPD_KEY, "vocoder", rules, also=(MSD_BLOCK, MPD_PRECISION))
+    if MPD_PRECISION in s:
+        s[MPD_PRECISION] = hifigan_disc_precision(hp)
     s["Periods"], s["Channels"] = [int(p) for p in s["Periods"]], [int(c) for c in s["Channels"]]
     if MSD_BLOCK in s:
         s[MSD_BLOCK] = hifigan_msd_settings(hp)
@@ -1930,6 +1952,28 @@ def hifigan_disc_load(obj, geo):
     return checked_load(hifigan_disc_find_state_dict(obj), hifigan_disc_expected_shapes(geo), "discriminator", "multi-period discriminator", MPD_KEY)
 
 
+def hifigan_disc_pack_bf16(weight):
+    """The host restatement of the bf16 mode's images of one middle convolution (`hifigan_pack_images` kinds 5 and 6 write these bytes): Conv weight
+    [Cout, Cin, taps(, 1)] -> (the forward image [taps, pad32(Cin) / 8, Cout, 8]: element (tap, k = input channel, n = output channel); the
+    channel-transposed image [taps, pad32(Cout) / 8, Cin, 8]: element (tap, k = output channel, n = input channel), taps NOT reversed), both rounded to
+    bf16 (nearest even) with zero rows from K to pad32(K): `hifigan_pack_bf16`'s layout."""
+    w = weight[..., 0] if weight.dim() == 4 else weight
+    co, ci, taps = w.shape
+    return (hifigan_pack_bf16(w.permute(2, 1, 0).reshape(-1, co), taps), hifigan_pack_bf16(w.permute(2, 0, 1).reshape(-1, ci), taps))
+
+
+def hifigan_disc_pack_plan(geo):
+    """The bf16 images of every period's middle convolutions, one job of `hifigan_pack_images` each, in `hifigan_pack_plan`'s form: per convolution the
+    forward image (kind 5), then the channel-transposed image (kind 6)."""
+    plan, ch = [], geo["channels"]
+    for i in range(len(geo["periods"])):
+        for j in range(1, len(ch)):
+            key, ci, co = f"discriminators.{i}.convs.{j}.weight", ch[j - 1], ch[j]
+            plan.append((key, "conv_bf16", ci, co, MPD_TAPS, 0, (MPD_TAPS, pad32(ci) // 8, co, 8), torch.bfloat16))
+            plan.append((key, "conv_kt_bf16", ci, co, MPD_TAPS, 0, (MPD_TAPS, pad32(co) // 8, ci, 8), torch.bfloat16))
+    return plan
+
+
 def hifigan_disc_forward(disc, wav, alloc=None):
     """The forward launches on wav [B, T] (fp32, contiguous, on the device) -> dict(wav, periods: per period dict(p, H, keep, scores)).  keep[j] [B, H[j + 1] p,
     C_j] is layer j's PRE-activation output with the flat row h p + c, scores [B, H[-1] p] conv_post's.  alloc(*shape): the caller's buffers (tests)."""
@@ -1937,6 +1981,7 @@ def hifigan_disc_forward(disc, wav, alloc=None):
     B, T = wav.shape
     ch, strides, slope = g["channels"], g["strides"], g["slope"]
     f = alloc or (lambda *shape: torch.empty(*shape, dtype=torch.float32, device=wav.device))
+    bf16 = getattr(disc, "precision", "f32") == "bf16"                 # the middle convolutions' op set; everything else is shared
     out = []
     for p, im in zip(g["periods"], disc.images):
         H = hifigan_disc_rows(g, T, p)
@@ -1945,10 +1990,14 @@ def hifigan_disc_forward(disc, wav, alloc=None):
         lib.glowtts_hifigan_disc_first(P(wav), P(im["first"][0]), P(im["first"][1]), P(keep[0]), B, T, p, strides[0], ch[0], st)
         for j in range(1, len(ch)):
             w, b, _ = im["convs"][j - 1]
-            lib.glowtts_hifigan_disc_conv(P(keep[j - 1]), P(w), P(b), P(keep[j]), B, H[j], p, strides[j], ch[j - 1], ch[j], slope, st)
+            if bf16:
+                ops.hifigan_disc_conv_bf16(keep[j - 1], w, b, keep[j], H[j], p, strides[j], slope)
+            else:
+                lib.glowtts_hifigan_disc_conv(P(keep[j - 1]), P(w), P(b), P(keep[j]), B, H[j], p, strides[j], ch[j - 1], ch[j], slope, st)
         lib.glowtts_hifigan_disc_post(P(keep[-1]), P(im["post"][0]), P(im["post"][1]), P(scores), B, H[-1], p, ch[-1], slope, st)
         out.append({"p": p, "H": H, "keep": keep, "scores": scores})
-    return {"wav": wav, "periods": out, "images": disc.images}     # the images this forward ran with: its backward must not see a later rebuild
+    # the images (and the precision) this forward ran with: its backward must not see a later rebuild
+    return {"wav": wav, "periods": out, "images": disc.images, "bf16": bf16}
 
 
 def hifigan_disc_feature_maps(disc, period_fwd):
@@ -2003,6 +2052,7 @@ def hifigan_disc_backward(disc, fwd, dscores, freeze=False, inj=None, inj_scale=
         grads, work = {k: f(*shape) for k, shape in hifigan_disc_expected_shapes(g).items()}, hifigan_disc_work(disc, B, T, dev, alloc)
     scale = P(inj_scale) if inj is not None else None
     dwav = f(B, T) if need_dwav else None
+    bf16 = fwd.get("bf16", False)
     for i, (per, im, ds) in enumerate(zip(fwd["periods"], fwd["images"], dscores)):
         p, H, keep = per["p"], per["H"], per["keep"]
         ds, ij = ds.to(torch.float32).contiguous(), inj[i] if inj is not None else [None] * (n + 1)
@@ -2016,11 +2066,18 @@ def hifigan_disc_backward(disc, fwd, dscores, freeze=False, inj=None, inj_scale=
         if not freeze:
             wgrad("conv_post", keep[-1], ds, H[-1], 1, ch[-1], 1, MPD_POST_TAPS, 0, slope)
         for j in reversed(range(1, n)):
-            if not freeze:
+            if not freeze and bf16:
+                ops.hifigan_disc_wgrad_bf16(keep[j - 1], d, work, grads[f"discriminators.{i}.convs.{j}.weight"], grads[f"discriminators.{i}.convs.{j}.bias"], H[j], p,
+                                            strides[j], slope)
+            elif not freeze:
                 wgrad(f"convs.{j}", keep[j - 1], d, H[j], strides[j], ch[j - 1], ch[j], MPD_TAPS, 0, slope)
             dx = f(B, H[j] * p, ch[j - 1])
-            lib.glowtts_hifigan_disc_conv_bwd(P(d), P(im["convs"][j - 1][2]), P(keep[j - 1]), P(ij[j - 1]) if ij[j - 1] is not None else None, scale, P(dx), B, H[j], p,
-                                              strides[j], ch[j - 1], ch[j], slope, st)
+            if bf16:
+                ops.hifigan_disc_conv_bwd_bf16(d, im["convs"][j - 1][2], keep[j - 1], dx, H[j], p, strides[j], slope, inj=ij[j - 1],
+                                               inj_scale=inj_scale if inj is not None else None)
+            else:
+                lib.glowtts_hifigan_disc_conv_bwd(P(d), P(im["convs"][j - 1][2]), P(keep[j - 1]), P(ij[j - 1]) if ij[j - 1] is not None else None, scale, P(dx), B, H[j],
+                                                  p, strides[j], ch[j - 1], ch[j], slope, st)
             d = dx
         if not freeze:
             wgrad("convs.0", wav, d, H[0], strides[0], 1, ch[0], MPD_TAPS, T, 1.0)
@@ -2067,20 +2124,26 @@ class _FakeTerms(torch.autograd.Function):
 
 
 class HiFiGANPeriodDiscriminator:
-    """HiFiGANPeriodDiscriminator(hp, device, state_dict=None, trainable=True, seed=0): the multi-period discriminator.  The sizes come from the yaml block
+    """HiFiGANPeriodDiscriminator(hp, device, state_dict=None, trainable=True, seed=0, precision=None): the multi-period discriminator.  precision: 'f32',
+    'bf16' (the middle convolutions on bf16 MFMAs, forward and backward; DESIGN.md "The multi-period discriminator in bf16") or None: the yaml's
+    `Vocoder.Train.Adversarial.Precision`, absent 'f32'; readable as `.precision`.  Parameters, checkpoints and every tensor are fp32 in both.  The sizes come from the yaml block
     `Vocoder.Train.Adversarial` (absent: the defaults).  `params` holds float32 device leaves in `hifigan_disc_expected_shapes`' names - from `state_dict`
     (`hifigan_disc_load`) or, without one, `hifigan_disc_init(geo, seed)`; the weight images are rebuilt from them at every call (an optimizer step writes
     the leaves in place).  A row's scores, feature maps and d wav are bit-identical alone, in any batch and from run to run."""
     OPS, NETS = (hifigan_disc_forward, hifigan_disc_backward), "periods"
 
-    def __init__(self, hp, device="cuda:0", state_dict=None, trainable=True, seed=0):
+    def __init__(self, hp, device="cuda:0", state_dict=None, trainable=True, seed=0, precision=None):
         self.geo = geo = hifigan_disc_geometry(hp)                  # before anything touches the device
+        self.precision = hifigan_disc_precision(hp, precision)
         self.trainable = bool(trainable)
         w = hifigan_disc_load(state_dict, geo) if state_dict is not None else hifigan_disc_init(geo, seed)
         lib, widths = _lib.api(), [1] + geo["channels"] + [1]
-        if not all(lib.glowtts_hifigan_disc_supported(p, a, b) for p in geo["periods"] for a, b in zip(widths, widths[1:])):
-            raise ValueError(f"the {MPD_KEY} block's sizes {geo} are not supported by the kernels")
+        supported = lib.glowtts_hifigan_disc_supported_bf16 if self.precision == "bf16" else lib.glowtts_hifigan_disc_supported
+        if not all(supported(p, a, b) for p in geo["periods"] for a, b in zip(widths, widths[1:])):
+            raise ValueError(f"the {MPD_KEY} block's sizes {geo} are not supported by the {self.precision} kernels")
         self.device = torch.device(device)
+        self._plan = hifigan_disc_pack_plan(geo) if self.precision == "bf16" else None
+        self._pack = None                                           # 'bf16': (source pointers, job table, image offsets on the device and here, blocks) of hifigan_pack_images
         self.params = {k: t.to(self.device).requires_grad_(self.trainable) for k, t in w.items()}
         self._build_images({k: t.detach() for k, t in self.params.items()})
 
@@ -2088,14 +2151,44 @@ class HiFiGANPeriodDiscriminator:
         """Per period the weight images in the kernels' layouts: first [5][C0] and post [3][C] (row = tap); a middle layer's forward image [5 Cin][Cout]
         (row = tap Cin + input channel) and its backward image [5 Cout][Cin] (row = tap Cout + output channel)."""
         dev, n = (lambda t: t.contiguous().to(self.device)), len(self.geo["channels"])
+        packed = self._pack_images(w) if self.precision == "bf16" else None
         self.images = []
         for i in range(len(self.geo["periods"])):
             q = f"discriminators.{i}."
             conv = lambda j: w[f"{q}convs.{j}.weight"][..., 0]
-            self.images.append({"first": (dev(conv(0)[:, 0, :].t()), dev(w[f"{q}convs.0.bias"])),
-                                "convs": [(dev(conv(j).permute(2, 1, 0).reshape(-1, conv(j).shape[0])), dev(w[f"{q}convs.{j}.bias"]),
-                                           dev(conv(j).permute(2, 0, 1).reshape(-1, conv(j).shape[1]))) for j in range(1, n)],
+            if packed is not None:                                  # precision 'bf16': (forward image, bias, channel-transposed image) in bf16
+                convs = [(packed[2 * (i * (n - 1) + j - 1)], dev(w[f"{q}convs.{j}.bias"]), packed[2 * (i * (n - 1) + j - 1) + 1]) for j in range(1, n)]
+            else:
+                convs = [(dev(conv(j).permute(2, 1, 0).reshape(-1, conv(j).shape[0])), dev(w[f"{q}convs.{j}.bias"]),
+                          dev(conv(j).permute(2, 0, 1).reshape(-1, conv(j).shape[1]))) for j in range(1, n)]
+            self.images.append({"first": (dev(conv(0)[:, 0, :].t()), dev(w[f"{q}convs.0.bias"])), "convs": convs,
                                 "post": (dev(w[f"{q}conv_post.weight"][0, :, :, 0].t()), dev(w[f"{q}conv_post.bias"]))})
+
+    def _pack_images(self, w):
+        """precision 'bf16': ONE `hifigan_pack_images` launch over a job table covering every period builds the bf16 images of the middle convolutions
+        (`hifigan_disc_pack_plan`: per convolution the forward and the channel-transposed image) from the parameters' live storage -> the images in plan
+        order.  The job table is built once (again only when a parameter's storage has moved); every rebuild writes a FRESH buffer, whose address goes into
+        the table's destination column on the device, so that an earlier forward's backward keeps the images it ran with."""
+        plan = self._plan
+        src = [w[key].to(self.device) for key, *_ in plan]
+        ptrs = tuple(t.data_ptr() for t in src)
+        if self._pack is None or self._pack[0] != ptrs:                 # the table: sources, kinds, sizes and first blocks; the destinations follow per rebuild
+            offsets, rows, block = [0], [], 0
+            for (key, kind, ci, co, taps, rate, shape, _), t in zip(plan, src):
+                if t.dtype != torch.float32 or not t.is_contiguous():
+                    raise _lib.GlowTTSHipError(f"HiFiGANPeriodDiscriminator needs contiguous float32 parameters, got {key}: {t.dtype}")
+                n = math.prod(shape) * 2                                # bytes of the bf16 image: a multiple of 16, one thread per 16-byte group
+                rows.append([t.data_ptr(), 0, HIFIGAN_PACK_KINDS[kind], ci, co, taps, rate, block])
+                block += -(-(n // 16) // 256)
+                offsets.append(offsets[-1] + n)
+            self._pack = (ptrs, torch.tensor(rows, dtype=torch.int64).to(self.device), torch.tensor(offsets[:-1], dtype=torch.int64).to(self.device), offsets, block)
+        _, jobs, offsets_dev, offsets, blocks = self._pack
+        flat = torch.empty(offsets[-1], dtype=torch.uint8, device=self.device)  # the launch writes every group of every image, the zero rows included
+        # Both launches go to the CURRENT stream, like every launch of the discriminator: the table's column is rewritten after the previous pack launch has
+        # read it and before this one does.  Rebuilding on two streams at once is not supported.
+        torch.add(offsets_dev, flat.data_ptr(), out=jobs[:, 1])
+        ops.hifigan_pack_images(jobs, blocks)
+        return [flat[off:end].view(dtype).view(shape) for (*_, shape, dtype), off, end in zip(plan, offsets, offsets[1:])]
 
     def _check(self, wav):
         if wav.dim() != 2 or wav.dtype != torch.float32 or not wav.is_cuda:
@@ -2127,7 +2220,7 @@ class HiFiGANPeriodDiscriminator:
         self._build_images({k: t.detach() for k, t in self.params.items()})
         fwd = hifigan_disc_forward(self, both)
         terms, l_fm, inj = hifigan_disc_feature_matching(self, fwd)
-        half = {"wav": both[B:], "images": fwd["images"], "periods": [{"p": per["p"], "H": per["H"], "keep": [k[B:] for k in per["keep"]], "scores": per["scores"][B:]}
+        half = {"wav": both[B:], "images": fwd["images"], "bf16": fwd["bf16"], "periods": [{"p": per["p"], "H": per["H"], "keep": [k[B:] for k in per["keep"]], "scores": per["scores"][B:]}
                                              for per in fwd["periods"]]}
         out = _FakeTerms.apply(self, fake.contiguous(), half, l_fm, inj)
         return list(_PeriodScore.apply(self, both, False, fwd, *self.params.values())), list(out[:-1]), out[-1], terms.detach()
@@ -2456,16 +2549,18 @@ def hifigan_discs_load(obj, geo):
 
 
 class HiFiGANDiscriminators:
-    """HiFiGANDiscriminators(hp, device, state_dict=None, trainable=True, seed=0): the multi-period and the multi-scale discriminator as the ONE discriminator
-    of the adversarial stage.  `params`: the multi-period discriminator's names unchanged, then the multi-scale discriminator's under `scale_discriminators.`.
+    """HiFiGANDiscriminators(hp, device, state_dict=None, trainable=True, seed=0, precision=None): the multi-period and the multi-scale discriminator as the
+    ONE discriminator of the adversarial stage.  precision ('f32' / 'bf16' / None: the yaml's `Vocoder.Train.Adversarial.Precision`) is handed to the period
+    discriminator and governs it alone: the multi-scale discriminator stays f32 entirely.  `params`: the multi-period discriminator's names unchanged, then the multi-scale discriminator's under `scale_discriminators.`.
     state_dict: what `hifigan_discs_load` reads."""
 
-    def __init__(self, hp, device="cuda:0", state_dict=None, trainable=True, seed=0):
+    def __init__(self, hp, device="cuda:0", state_dict=None, trainable=True, seed=0, precision=None):
         self.geo = {"periods": hifigan_disc_geometry(hp), "scales": hifigan_msd_geometry(hp)}                  # before anything touches the device
+        self.precision = hifigan_disc_precision(hp, precision)                                                 # the period discriminator's; the scales are f32
         mpd = msd = None
         if state_dict is not None:
             mpd, msd = hifigan_discs_split(hifigan_discs_load(state_dict, self.geo))
-        self.periods = HiFiGANPeriodDiscriminator(hp, device, mpd, trainable, seed)
+        self.periods = HiFiGANPeriodDiscriminator(hp, device, mpd, trainable, seed, precision=self.precision)
         self.scales = HiFiGANScaleDiscriminator(hp, device, msd, trainable, seed)
         self.device, self.trainable = self.periods.device, bool(trainable)
         self.params = dict(self.periods.params)

@@ -1279,6 +1279,30 @@ int glowtts_hifigan_disc_first_bwd(const float *dpre, const float *w, float *dwa
 int glowtts_hifigan_disc_wgrad(const float *x, const float *dy, float *work, float *dw, float *dbias, int B, int H, int period, int stride, int Cin, int Cout,
                                int taps, int wav_samples, float slope, void *stream);
 
+/* ---- The bf16 mode of the HiFi-GAN multi-period discriminator (csrc/hifigan_disc_bf16_ops.hip; additions, the ABI version stays) ----
+ * The middle convolutions (5 taps, Cin and Cout multiples of 16) with bf16 operands (nearest even, no clamp) on v_mfma_f32_16x16x32_bf16 and fp32 sums, biases
+ * and epilogues; the arguments are the f32 entries' with 16-bit images.  Every tensor in memory stays fp32; the first layer, conv_post and the
+ * feature-matching loss keep the f32 entries above.  Deterministic; a batch row's results do not depend on the batch.  Bad arguments return GLOWTTS_E_ARG
+ * before any launch.
+ * Supported (glowtts_hifigan_disc_supported_bf16): glowtts_hifigan_disc_supported with the 16-bit tiles' LDS terms; Cin == 1 and Cout == 1 answer for the f32
+ * launches that serve them (the three launches below refuse them).
+ * glowtts_hifigan_disc_conv_bf16      glowtts_hifigan_disc_conv, logged as `hifigan_disc_conv_bf16`; w is the bf16 image [5][pad32(Cin) / 8][Cout][8] of the
+ *                                     weights [Cout][Cin][5] (element (tap, k, n) at ((tap Kp / 8 + k / 8) Cout + n) 8 + k % 8, zero for k from Cin to Kp):
+ *                                     glowtts_hifigan_pack_images kind 5.
+ * glowtts_hifigan_disc_conv_bwd_bf16  glowtts_hifigan_disc_conv_bwd, logged as `hifigan_disc_conv_bwd_bf16`; dy is rounded as it lies in memory; wt is the bf16
+ *                                     image [5][pad32(Cout) / 8][Cin][8] of the channel-transposed weights, taps NOT reversed: kind 6.
+ * glowtts_hifigan_disc_wgrad_bf16     glowtts_hifigan_disc_wgrad with lrelu(x) and dy rounded to bf16, logged as `hifigan_disc_wgrad_bf16` and
+ *                                     `hifigan_disc_wgrad_sum`; the bias gradient is the column sum of the unrounded dy, in double.  taps 5 and
+ *                                     wav_samples 0 alone; work as glowtts_hifigan_disc_wgrad.
+ * glowtts_hifigan_pack_images kinds 5 / 6: the two images above from a Conv weight [Cout][Cin][taps]. */
+int glowtts_hifigan_disc_supported_bf16(int period, int Cin, int Cout);
+int glowtts_hifigan_disc_conv_bf16(const float *x, const uint16_t *w, const float *bias, float *out, int B, int H, int period, int stride, int Cin, int Cout,
+                                   float slope, void *stream);
+int glowtts_hifigan_disc_conv_bwd_bf16(const float *dy, const uint16_t *wt, const float *x, const float *inj, const float *inj_scale, float *dx, int B, int H,
+                                       int period, int stride, int Cin, int Cout, float slope, void *stream);
+int glowtts_hifigan_disc_wgrad_bf16(const float *x, const float *dy, float *work, float *dw, float *dbias, int B, int H, int period, int stride, int Cin, int Cout,
+                                    int taps, int wav_samples, float slope, void *stream);
+
 /* ---- The HiFi-GAN multi-scale discriminator (csrc/hifigan_msd_ops.hip, the dense layers in csrc/hifigan_disc_ops.hip; f32; additions, the ABI version stays) ----
  * One sub-network per scale: scale 0 sees wav [B][T], scale i the waveform after i average pools (4 taps, stride 2, zero padding 2, always divided by 4:
  * T' = T / 2 + 1).  A sub-network is a stack of Conv1d over time with zero padding taps / 2 and L' = (L - 1) / stride + 1: a first layer 1 -> C0 (stride 1), grouped
